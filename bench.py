@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the MPI render hot path on MI355X (one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg3_f32|cfg4|cfg5|video]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg3_f32|cfg4|cfg5|video] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`, `ms_per_step` (wall time of one timed
+step), `roofline` priced on the timed steps themselves.  --full adds every block below that takes work of its own.
+--dump-outputs DIR writes what the last timed step computed (rank 0: the arrays a caller of the timed path receives) as DIR/<name>.npy,
+float32; an array of more than DUMP_MAX_ELEMS elements as a fixed seeded sample of them (dump_outputs()).  The inputs are seeded: the same
+arguments give the same inputs in every run, so two builds can be compared output for output.
 
 Metric (BASELINE.json): Mpix*planes/s = views*H*W*D / t / 1e6 (whole job, all GPUs), plus views/s and
 the fraction of the HBM roofline.  A "step" = ONE pass of the hot path over one batch of views
@@ -24,7 +30,8 @@ launch call on the launch stream; wall time per step).  Algorithmic bytes (SURVE
 cpu_baseline = the CPU oracle (oracle/mpi_oracle.c, OpenMP build, kind "port") timed on this box's
 host cores on a bounded sample of the same workload -- a reported baseline, not the target.
 
-Further blocks of the line, all OUTSIDE the K timed steps (rank 0, N = 1 unless noted):
+Further blocks of the line, with --full only, all OUTSIDE the K timed steps (rank 0, N = 1 unless noted; without --full they are null or
+absent, and so are `roofline.stream_read_gbs` / `frac_of_stream_ceiling` / `range_check_pass_gbs`, which take launches of their own):
     parity      the timed launch itself (same tensors, same variant) rendered once in strict-order mode and once in default mode and
                 compared with the CPU oracle on three 64x64 ray windows per view: strict_bit_exact, max_abs_err_{color,depth,T}, bar 1e-5.
                 A failure makes the process exit non-zero (--no-parity skips it: the PMC passes of tools/prof.sh).
@@ -92,6 +99,23 @@ def footprint_bytes(ray, eye, dhw, S, s_in, want_T):
     h = (iy.max(-1).values.floor() + 1).clamp(0, S - 1) - iy.min(-1).values.floor().clamp(0, S - 1) + 1
     texels = float((w.clamp(min=0) * h.clamp(min=0)).sum())
     return int(texels * 4 * s_in + n * S * S * 12 + n * S * S * 4 * (4 + (1 if want_T else 0)))
+
+
+DUMP_MAX_ELEMS = 1 << 22   # per array: 16 MiB of float32 -- a workload hands out at most three arrays, 48 MiB in all
+
+
+def dump_outputs(dump_dir, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32, whole and in its shape up to DUMP_MAX_ELEMS elements; a larger one flattened and
+    sampled at DUMP_MAX_ELEMS flat indices drawn without replacement by numpy's default_rng(0) and sorted -- they depend on the element count
+    only, so every run and every build with the same arguments samples the same elements."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dump_dir, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(preset, S, D, dtype, budget_s=20.0):
@@ -216,25 +240,31 @@ def run_video(a, dev, rank, world, use_dist):
 
     with torch.no_grad():
         for _ in range(max(a.warmup, 1)):
-            per_call_pass(); batched_pass()
+            per_call_pass()
+            if a.full:
+                batched_pass()
         fence(); t0 = time.perf_counter()
         t_parts[0] = t_parts[1] = 0.0
         for _ in range(a.steps):
-            per_call_pass()
+            frames = per_call_pass()
         fence(); t_call = time.perf_counter() - t0
         in_render, to_host = t_parts[0], t_parts[1]
-        # (the per-call loop keeps the GPU 10 % busy: its clocks have dropped, and a batched pass is only ~7 ms -- untimed passes for
-        #  --prewarm-ms first, as the render workloads do; without them the figure is bimodal, 5 000 or 9 000 views/s from run to run)
-        t_pre = time.perf_counter()
-        while (time.perf_counter() - t_pre) * 1e3 < a.prewarm_ms:
-            batched_pass()
-        n_batch = max(a.steps, 20)
-        fence(); t0 = time.perf_counter()
-        for _ in range(n_batch):
-            batched_pass()
-        fence(); t_batch = (time.perf_counter() - t0) * a.steps / n_batch
-        a_frames, b_frames = per_call_pass(), batched_pass()
-    same = all(np.array_equal(f[0], b_frames[0][i].numpy()) for i, f in enumerate(a_frames))  # the two paths give the same uint8 frames
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"img_u8": np.stack([f[0] for f in frames]), "depth_u8": np.stack([f[1] for f in frames])})
+        t_batch, same = float("nan"), None
+        if a.full:
+            # (the per-call loop keeps the GPU 10 % busy: its clocks have dropped, and a batched pass is only ~7 ms -- untimed passes for
+            #  --prewarm-ms first, as the render workloads do; without them the figure is bimodal, 5 000 or 9 000 views/s from run to run)
+            t_pre = time.perf_counter()
+            while (time.perf_counter() - t_pre) * 1e3 < a.prewarm_ms:
+                batched_pass()
+            n_batch = max(a.steps, 20)
+            fence(); t0 = time.perf_counter()
+            for _ in range(n_batch):
+                batched_pass()
+            fence(); t_batch = (time.perf_counter() - t0) * a.steps / n_batch
+            a_frames, b_frames = per_call_pass(), batched_pass()
+            same = all(np.array_equal(f[0], b_frames[0][i].numpy()) for i, f in enumerate(a_frames))  # the two paths give the same uint8 frames
     t = torch.tensor([t_call, t_batch], device=dev, dtype=torch.float64)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -252,9 +282,10 @@ def run_video(a, dev, rank, world, use_dist):
                                 "script_numpy": round((t_call - in_render - to_host) / (len(angles) * a.steps) * 1e3, 4),
                                 "what": "render(): host time of the call | .cpu() x 2: waits for the kernel, copies 4 MB | the script's own uint8 conversion (numpy)"},
                 "render_and_copy_views_per_s": round(len(angles) * a.steps * world / (in_render + to_host), 1),
-                "batched_driver": {"views_per_s": round(views / t_batch, 1), "ms_per_view": round(t_batch / views * world * 1e3, 4), "batch": 8,
-                                   "what": "ViewBatchDriver.render_path(to_host=True): 8 views per launch, uint8 epilogue on the device per batch, copies into pinned host buffers on a second stream next to the next batch's render"},
-                "frames_identical": bool(same), "roofline": None, "cpu_baseline": None}
+                "batched_driver": None if not a.full else {
+                    "views_per_s": round(views / t_batch, 1), "ms_per_view": round(t_batch / views * world * 1e3, 4), "batch": 8,
+                    "what": "ViewBatchDriver.render_path(to_host=True): 8 views per launch, uint8 epilogue on the device per batch, copies into pinned host buffers on a second stream next to the next batch's render"},
+                "frames_identical": None if same is None else bool(same), "roofline": None, "cpu_baseline": None}
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
@@ -294,6 +325,7 @@ class TrainWorkload:
         self.rgba.grad = None
         color, depth, _, _ = self.r.render(self.rgba, self.S, self.S, given_cam_infos=self.infos, defer_status=True)
         torch.autograd.backward([color, depth], [self.g_color, self.g_depth])
+        self.last = dict(color=color.detach(), depth=depth.detach())   # (--dump-outputs: the frames of the step, next to rgba.grad)
 
     def abi(self):
         """The step's launches through the C ABI (what the bridge enqueues): fwd(), and bwd(g_color, g_depth, grad) on a parameter struct of the forward."""
@@ -451,15 +483,19 @@ def run_train(a, dev, rank, world, use_dist):
     fence()
     elapsed = time.perf_counter() - t0
     kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.steps
-    grad_ref = w.rgba.grad.detach().clone()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(w.last, grad_rgba=w.rgba.grad))
 
-    parts = w.parts()
-    k = w.abi()
-    with torch.no_grad():
-        k["grad"].zero_(); k["bwd"]()
-        torch.cuda.synchronize(dev)
-        same = float((k["grad"] - grad_ref).abs().max() / grad_ref.abs().max())   # (atomics: the order of the adds differs from run to run)
-    del grad_ref
+    parts = same = None
+    if a.full:
+        grad_ref = w.rgba.grad.detach().clone()
+        parts = w.parts()
+        k = w.abi()
+        with torch.no_grad():
+            k["grad"].zero_(); k["bwd"]()
+            torch.cuda.synchronize(dev)
+            same = float((k["grad"] - grad_ref).abs().max() / grad_ref.abs().max())   # (atomics: the order of the adds differs from run to run)
+        del grad_ref
 
     t = torch.tensor([elapsed, kern_ms], device=dev, dtype=torch.float64)
     if use_dist:
@@ -486,7 +522,8 @@ def run_train(a, dev, rank, world, use_dist):
                 "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
                              "priced_on_ms": round(step_ms, 4), "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": ab_fwd + ab_bwd, "traffic": traffic,
                              "parts": parts},
-                "backward_repeatability": {"max_abs_diff_over_max_grad": float(f"{same:.3e}"), "what": "two runs of the backward (atomic adds in a different order)"},
+                "backward_repeatability": None if same is None else {
+                    "max_abs_diff_over_max_grad": float(f"{same:.3e}"), "what": "two runs of the backward (atomic adds in a different order)"},
                 "cpu_baseline": None}
         if not a.no_parity:
             line["parity"] = w.parity()
@@ -890,7 +927,15 @@ def main():
     ap.add_argument("--prewarm-ms", type=float, default=250.0,
                     help="untimed render launches for this long before the W warm-up steps: a GPU coming from idle needs ~0.1 s to reach "
                          "its busy clocks (20 steps are only 23 ms of work); 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything outside the headline (the --no-* options above pick blocks off again): parity, pose sweep, end-to-end "
+                         "render, streaming / range-check ceilings, power, companions, CPU baseline; video: the batched driver; train: the parts, "
+                         "the repeatability and the parity of the backward")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, rank 0; large arrays as a fixed seeded sample)")
     a = ap.parse_args()
+    if not a.full:
+        a.no_parity, a.pose_draws, a.no_cpu_baseline, a.no_companions, a.no_power_probe = True, 0, True, True, True
     if a.profile_clean:
         a.no_parity, a.pose_draws, a.no_cpu_baseline, a.no_companions, a.no_power_probe = True, 0, True, True, True
 
@@ -973,12 +1018,14 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0
         r.mpi.raise_on_status(status)  # asserts of all steps, one read-back
+        if a.dump_outputs and rank == 0:   # (before any block below launches into `out` again)
+            dump_outputs(a.dump_outputs, {("transmittance" if k == "T" else k): v for k, v in out.items()})
         power = None
         if rank == 0 and not a.no_power_probe:
             with torch.no_grad():
                 power = power_probe(step, sync, local_rank)
             r.mpi.raise_on_status(status)
-        if not a.profile_clean:
+        if a.full and not a.profile_clean:
             # end-to-end MPIRenderer.render() as a caller gets it by default: pose sampling on the host + rays + launch + the status read-back
             # in the call (status_mode="sync": the reference's assertion timing)
             r.render(rgba, S, S, views_per_mpi=vpm)  # warm-up of the pose/ray path (first call loads its kernels)
@@ -1110,7 +1157,9 @@ def main():
             torch.cuda.synchronize(dev)
             return vol_bytes / (min(e0.elapsed_time(e1) for e0, e1 in evs[1:]) * 1e-3) / 1e9
 
-        if dry:
+        if not a.full:
+            stream_gbs = range_check_gbs = None
+        elif dry:
             stream_gbs = range_check_gbs = 1.0
         else:
             stream_gbs = timed(probe)
@@ -1132,8 +1181,9 @@ def main():
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "priced_on_ms": round(roof_ms, 4), "traffic": traffic, "traffic_source": traffic_note,
                          # companions: against what a pure streaming read reaches on this box, and the VALU issue floor
-                         "stream_read_gbs": round(stream_gbs, 1), "frac_of_stream_ceiling": round(achieved / stream_gbs, 4),
-                         "range_check_pass_gbs": round(range_check_gbs, 1),
+                         "stream_read_gbs": None if stream_gbs is None else round(stream_gbs, 1),
+                         "frac_of_stream_ceiling": None if stream_gbs is None else round(achieved / stream_gbs, 4),
+                         "range_check_pass_gbs": None if range_check_gbs is None else round(range_check_gbs, 1),
                          "valu_floor_ms": valu_floor_ms,
                          "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": abytes,
                          # conservative companion: only the texel boxes the views actually touch

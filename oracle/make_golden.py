@@ -13,6 +13,8 @@ pin for the oracle (oracle/mpi_oracle.c), for the host-side geometry mirror and 
   geometry.npz   plane depths / dhws / c2w / rays / sampled poses of the reference's host-side
                  helpers (mpi_utils.py:21,787,652; cam_utils.py:734; camera.py:182;
                  mpi_renderer.py:337) for the dataset presets
+  reference_seams.npz  what the reference hands this package at its seams (`python oracle/make_golden.py seams`,
+                 run_seams): replayed by tests/test_install_reference.py without the reference
 """
 import contextlib
 import io
@@ -337,7 +339,138 @@ def run_backward_cases(ns):
     print("wrote backward_forward_ragged_views")
 
 
+def _seam_value(out, meta, key, v):
+    """One keyword argument of a recorded call: tensors (and lists of them, stacked) into the npz, everything else into meta."""
+    if torch.is_tensor(v):
+        out[key] = v.detach().numpy()
+        meta[key] = "tensor"
+    elif isinstance(v, (list, tuple)) and v and all(torch.is_tensor(x) for x in v):
+        out[key] = torch.stack([x.detach() for x in v]).numpy()
+        meta[key] = "tensor_list"
+    elif isinstance(v, (list, tuple)):
+        out[key] = np.asarray(v, dtype=np.float32)
+        meta[key] = "number_list"
+    else:
+        meta[key] = {"value": v}
+
+
+def run_seams(ns):
+    """reference_seams.npz: what the reference hands this package at its seams, replayed without the reference by
+    tests/test_install_reference.py and tests/test_host_geometry.py:
+      rng_after_ctor  torch.rand(3) after torch.manual_seed(77) and the reference's FFHQ renderer with 4 planes (the RNG its constructor draws)
+      cam_dirs_*      its camera's unit directions [3, S*S] (camera.py:117), the right operand of its ray product (camera.py:200)
+      ctor_*          the keyword arguments its MPIRenderer gives `MPI(...)` (mpi_renderer.py:47), and that renderer's plane dhws
+      fwd_*           the keyword arguments its MPIRenderer.render gives `MPI.forward` (mpi_renderer.py:451-461): FFHQ, 6 planes, 3 views of
+                      20^2 over 24^2 textures drawn after torch.manual_seed(5)
+      video_*         the calls its video driver `generate_img` (eval/vis/render_video.py:95-130) makes to MPIRenderer.render for 5 angles
+                      (a fake generator -- seeded torch.rand volumes -- stands in for the network)"""
+    import importlib
+    import types
+    out, meta = {}, {}
+    torch.manual_seed(77)
+    with quiet():
+        ref_import.make_reference_renderer(ns, "FFHQ", 4)
+    out["rng_after_ctor"] = torch.rand(3).numpy()
+    # the camera-space unit directions the reference's ray product multiplies (camera.py:117, 200), for the image sizes of geometry.npz's poses
+    for preset, size in (("FFHQ", 8), ("FFHQ", 16), ("FFHQ", 5), ("AFHQCat", 6)):
+        with quiet():
+            r = ref_import.make_reference_renderer(ns, preset, 4)
+            r.set_cam(r.cam_fov, size, size)
+        out[f"cam_dirs_{preset}_{size}"] = r.cam.ray_dir_torch.numpy()
+
+    ctor, seen = {}, {}
+
+    class SpyMPI(ns.mpi.MPI):
+        def __init__(self, *a, **kw):
+            assert not a, a
+            ctor.update(kw)
+            super().__init__(**kw)
+
+        def forward(self, **kw):
+            seen.update(kw)
+            return super().forward(**kw)
+
+    saved = ns.mpi_renderer.MPI
+    ns.mpi_renderer.MPI = SpyMPI
+    try:
+        with quiet():
+            r = ref_import.make_reference_renderer(ns, "FFHQ", 4)
+        meta["ctor"] = {"kwargs": ctor, "preset": "FFHQ", "D": 4}
+        out["ctor_static_dhws"] = r.static_mpi_plane_dhws.numpy()
+        B, D, S, T = 3, 6, 20, 24
+        with quiet():
+            r = ref_import.make_reference_renderer(ns, "FFHQ", D)
+            r.set_cam(r.cam_fov, S, S)
+        torch.manual_seed(5)
+        rgba = torch.rand(B, D, 4, T, T)
+        with quiet():
+            r.render(rgba, S, S, assert_not_out_of_last_plane=True)
+    finally:
+        ns.mpi_renderer.MPI = saved
+    fwd_meta = {}
+    for k, v in seen.items():
+        _seam_value(out, fwd_meta, "fwd_" + k, v)
+    meta["fwd"] = dict(B=B, D=D, S=S, T=T, seed=5, kwargs=fwd_meta)
+
+    # the video driver: torchvision / imageio / torch_ema are imported by render_video.py but are not on the render path
+    def stub(name, **attrs):
+        m = sys.modules.get(name) or types.ModuleType(name)
+        m.__dict__.update(attrs)
+        sys.modules.setdefault(name, m)
+        return m
+    if importlib.util.find_spec("torchvision") is None:
+        stub("torchvision").utils = stub("torchvision.utils", save_image=lambda *a, **k: None)
+        stub("torchvision.transforms")
+    if importlib.util.find_spec("imageio") is None:
+        stub("imageio", mimwrite=lambda *a, **k: None, imwrite=lambda *a, **k: None)
+    if importlib.util.find_spec("torch_ema") is None:
+        stub("torch_ema", ExponentialMovingAverage=type("ExponentialMovingAverage", (), {"__init__": lambda self, *a, **k: None}))
+    rv = importlib.import_module("gmpi.eval.vis.render_video")
+    D, S, T = 5, 24, 32
+    kw = dict(ref_import.PRESETS["FFHQ"])
+    kw.update(n_mpi_planes=D, plan_spatial_enlarge_factor=1.001, plane_distances_sample_method="inverse",
+              cam_sample_method="truncated_gaussian", mpi_align_corners=True, use_xyz_ztype="depth", use_normalized_xyz=False,
+              normalized_xyz_range="-11", use_confined_volume=True, device=torch.device("cpu"))
+    with quiet():
+        renderer = rv.MPIRenderer(**kw)                           # as render_video.py:168-189
+        ws = renderer.get_xyz_interpolate_ws(D, D)                # :193
+        renderer.set_cam(kw["cam_fov"], S, S)                     # :198
+        xyz, _ = renderer.get_xyz(T, T, ret_single_res=False, only_z=False)   # :200-205
+    calls, gen_calls = [], []
+    ref_render = renderer.render
+
+    def spy_render(*a, **k):
+        calls.append((a, k))
+        return ref_render(*a, **k)
+    renderer.render = spy_render
+    rv.mpi_renderer = renderer                                    # the module global generate_img reads (:104)
+
+    def fake_generator(z, c, xyz_input, only_z, n_planes, z_interpolation_ws=None, truncation_psi=1.0):
+        gen_calls.append(n_planes)
+        return torch.rand((z.shape[0], n_planes, 4, T, T), generator=torch.Generator().manual_seed(11))
+
+    angles = np.linspace(0.5, -0.5, 5).tolist()                   # :236-237 (100 angles there)
+    metadata = dict(img_size=S, h_mean=0.0, v_mean=0.0, h_stddev=0.0, v_stddev=0.0, ray_start=kw["plane_min_d"], ray_end=kw["plane_max_d"])
+    torch.manual_seed(0)
+    z = torch.randn((1, 16))
+    with quiet():
+        rv.generate_img(device=torch.device("cpu"), face_angles=angles, generator=fake_generator, z=z, mpi_xyz_input=xyz, metadata=metadata,
+                        horizontal_cam_move=True, mpi_xyz_only_z=False, z_interpolation_ws=ws, n_planes=D, truncation_psi=1.0,
+                        render_single_image=False, chunk_n_planes=-1, disable_tqdm=True)
+    assert gen_calls == [D, D] and len(calls) == len(angles), (gen_calls, len(calls))
+    vol = calls[0][0][0]
+    assert all(a[0] is vol or torch.equal(a[0], vol) for a, _ in calls)   # one unchanged volume for the whole path
+    out["video_rgba"] = vol.detach().numpy()
+    meta["video"] = dict(D=D, S=S, T=T, angles=angles, renderer_kwargs={k: v for k, v in kw.items() if k != "device"},
+                         generator_calls=gen_calls, calls=[dict(size=[a[1], a[2]], kwargs=k) for a, k in calls])
+    np.savez(os.path.join(OUT, "reference_seams.npz"), meta=json.dumps(meta, default=lambda o: np.asarray(o).tolist()), **out)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "seams":
+        torch.set_num_threads(1)
+        run_seams(ref_import.import_reference())
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "backward":
         torch.set_num_threads(1)
         run_backward_cases(ref_import.import_reference())

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/prof.sh <tag>  -- run on the GPU box (via gpurun): rocprofv3 evidence for the bench workloads.
+# tools/prof.sh <tag> <dir>  -- run on the GPU box: rocprofv3 evidence for the bench workloads, under <dir>/prof_<tag>.
 #   1) kernel trace + stats of the default bench command (cfg3)                      -> $OUT/trace
 #   2) per workload, each in its own rocprofv3 run with --kernel-trace only (MI355X_MICROARCH.md, HBM section):
 #      FETCH_SIZE pass and SQ_INSTS_VALU pass                                          -> $OUT/<workload>/pmc_*
@@ -8,7 +8,7 @@
 #      for matching sources).  Copy both into profiles/ afterwards.
 set -u
 TAG=${1:-r04}
-OUT=gpurun_out/prof_$TAG
+OUT=$(realpath -m "${2:?usage: tools/prof.sh <tag> <output directory>}")/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-.}
@@ -34,9 +34,9 @@ pmc cfg3 tcc TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum
 # the G-step shapes (forward + backward): trace + FETCH / WRITE / issue counters of both kernels
 for wl in ${TRAIN:-train256 train1024}; do
   mkdir -p $OUT/$wl
-  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$wl/trace -o t -- python bench.py --workload $wl --steps 20 --warmup 5 --no-parity > $OUT/$wl/bench_trace.log 2>&1
+  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$wl/trace -o t -- python bench.py --full --workload $wl --steps 20 --warmup 5 --no-parity > $OUT/$wl/bench_trace.log 2>&1
   pmc_t() { local name=$1; shift
-    timeout 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$wl/pmc_$name -o p -- python bench.py --workload $wl --steps 8 --warmup 2 --prewarm-ms 0 --no-parity > $OUT/$wl/bench_$name.log 2>&1
+    timeout 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$wl/pmc_$name -o p -- python bench.py --full --workload $wl --steps 8 --warmup 2 --prewarm-ms 0 --no-parity > $OUT/$wl/bench_$name.log 2>&1
     echo "$wl $name rc=$?"; }
   pmc_t fetch FETCH_SIZE
   pmc_t write WRITE_SIZE

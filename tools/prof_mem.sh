@@ -5,7 +5,7 @@ TAG=$1; PASS=$2; shift; shift
 OUT=gpurun_out/profmem_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline $*"
+ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline $*"
 case $PASS in
   tlb) C="TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum TCP_PENDING_STALL_CYCLES_sum";;
   tcp) C="TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum";;
