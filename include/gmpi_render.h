@@ -114,6 +114,7 @@ enum {
     GMPI_E_ABI = -5,         /* struct_size does not match this library       */
     GMPI_E_VARIANT = -6,     /* requested kernel variant cannot run this shape */
     GMPI_E_FLAGS = -7,       /* a bit outside GMPI_FLAG_ALL is set            */
+    GMPI_E_WORKSPACE = -8,   /* the workspace is missing, too small or not 256-byte aligned */
     GMPI_E_LAUNCH = -100     /* -100 - hipError_t of the failed launch        */
 };
 
@@ -194,6 +195,27 @@ int gmpi_mpi_render_backward_launch(const GmpiRenderParams *params, const float 
                                     float *grad_rgba, const int64_t *grad_rgba_stride, void *stream);
 /* Bytes of caller-owned scratch with which the backward runs without atomics (0: this launch takes the tile kernels). */
 uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams *params);
+
+/*
+ * Gradient of the render w.r.t. the sample POSITIONS (an extension: the reference builds the grid under torch.no_grad(), mpi.py:65):
+ * the rays, the eye positions, the optical axes and the plane geometry.  `params`, grad_rgb, grad_depth and transmittance_out as for
+ * gmpi_mpi_render_backward_launch.  Per view n, pixel, plane k, with s = (d_k - ez)/rz, x = ex + rx s, y = ey + ry s, depth_k = s (r . z_dir),
+ * d_s[c] the gradient w.r.t. sample channel c and G_k = gZ w_k (the volume backward's sweep), and the bilinear derivatives of the four taps
+ * (zeros padding):  g_x = g_ix dix/dx, g_y = g_iy diy/dy, g_s = g_x rx + g_y ry + G_k dot; summed over the planes
+ *     grad_ray_dir[n,:,p] = (g_x s, g_y s, -g_s s / rz) + G_k s z_dir         [N,3,H,W]
+ *     grad_eye_pos[n]     = sum over pixels of (g_x, g_y, -g_s / rz)            [N,3]
+ *     grad_z_dir[n]       = sum over pixels of G_k s r                          [N,3]
+ *     grad_dhw[m,k]       = sum over pixels and every view of MPI m of (g_s / rz, -g_y y / h_k, -g_x x / w_k)   [M,D,3]
+ * Outputs are OVERWRITTEN; NULL = not wanted.  Any view_to_mpi, any ray field.  The per-view and per-plane sums go through slabs in
+ * params->workspace (at least gmpi_render_geometry_backward_workspace_bytes(params, grad_dhw != NULL) bytes, 256-byte aligned; otherwise
+ * GMPI_E_WORKSPACE) and are summed in a fixed order: no atomics, every output bit-reproducible.  The coordinate chain is the forward's for
+ * the launch's flags (GMPI_FLAG_STRICT_ORDER included), so the pass floors to the texels the forward sampled.
+ */
+int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                             float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw,
+                                             void *stream);
+/* Bytes of workspace gmpi_mpi_render_geometry_backward_launch needs for the eye / z_dir sums, and with want_dhw != 0 the plane sums too. */
+uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams *params, int want_dhw);
 
 /*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the

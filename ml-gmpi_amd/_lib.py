@@ -27,6 +27,8 @@ EXPORTS = (
     "gmpi_render_workspace_bytes",
     "gmpi_render_backward_workspace_bytes",
     "gmpi_mpi_render_backward_launch",
+    "gmpi_render_geometry_backward_workspace_bytes",
+    "gmpi_mpi_render_geometry_backward_launch",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -51,6 +53,7 @@ _ERRORS = {
     -5: "GMPI_E_ABI (GmpiRenderParams size mismatch between binding and library)",
     -6: "GMPI_E_VARIANT (requested kernel variant cannot run this shape)",
     -7: "GMPI_E_FLAGS (undefined bit in GmpiRenderParams.flags)",
+    -8: "GMPI_E_WORKSPACE (workspace missing, too small or not 256-byte aligned)",
 }
 
 
@@ -161,6 +164,10 @@ def load_library():
     lib.gmpi_mpi_render_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp,
                                                     ctypes.POINTER(ctypes.c_int64), vp]
+    lib.gmpi_render_geometry_backward_workspace_bytes.restype = ctypes.c_uint64
+    lib.gmpi_render_geometry_backward_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.c_int]
+    lib.gmpi_mpi_render_geometry_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int

@@ -23,6 +23,9 @@ uint64_t band_workspace_bytes(const KParams& p, int dtype);                 // r
 uint32_t* band_gate_words(const KParams& p, int dtype);                     // render_band.hip
 int band_pixels_wide(int dtype);                                            // render_band.hip
 uint64_t backward_gather_workspace_bytes(const KParams& p);                 // render_backward_gather.hip
+uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
+hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, float* g_ray, float* g_eye, float* g_z,
+                                    float* g_dhw, hipStream_t stream);       // render_backward_geometry.hip
 
 // ---- min/max of the normalised grid on the last plane (mpi.py:103-109 diagnostics) --------------
 template <bool AC>
@@ -442,6 +445,29 @@ int gmpi_mpi_render_backward_launch(const GmpiRenderParams* params, const float*
         if (grad_rgba_stride[i] <= 0 && !(i == 0 && params->M == 1)) return GMPI_E_STRIDE;
     return hip_rc(launch_backward(p, params->rgba_dtype, grad_rgb, grad_depth, grad_rgba, grad_rgba_stride,
                                   params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
+}
+
+uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams* params, int want_dhw) {
+    KParams p;
+    if (to_kparams(params, p, false, true) != GMPI_OK || p.N == 0) return 0;
+    return geometry_backward_workspace_bytes(p, want_dhw != 0);
+}
+
+int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, float* grad_ray_dir,
+                                             float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
+    KParams p;
+    const int rc = to_kparams(params, p, false, true);
+    if (rc != GMPI_OK) return rc;
+    if (grad_rgb == nullptr) return GMPI_E_NULL;
+    if (p.N > 65535 || p.M > 65535 || 6 + 3 * static_cast<int64_t>(p.D) > (int64_t(1) << 31) - 1) return GMPI_E_SHAPE;   // grid.y: views / MPIs, grid.x: components
+    if (grad_ray_dir == nullptr && grad_eye_pos == nullptr && grad_z_dir == nullptr && grad_dhw == nullptr) return GMPI_OK;
+    if (grad_eye_pos != nullptr || grad_z_dir != nullptr || grad_dhw != nullptr) {   // the slabs of the per-view / per-plane sums
+        const uint64_t need = geometry_backward_workspace_bytes(p, grad_dhw != nullptr);
+        if (p.ws == nullptr || p.ws_bytes < need || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return GMPI_E_WORKSPACE;
+    }
+    return hip_rc(launch_backward_geometry(p, params->rgba_dtype, grad_rgb, grad_depth, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
+                                           static_cast<hipStream_t>(stream)));
 }
 
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {

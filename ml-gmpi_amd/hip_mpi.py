@@ -300,13 +300,17 @@ class MPI(nn.Module):
                      run to run) | "gather" (round 6: pixel pass + texel gather, render_backward_gather.hip -- no atomics, no zero-fill, every cell
                      written once in a fixed order: bit-reproducible gradients; 3.3 ms and 24 bytes of scratch per pixel and plane;
                      align_corners=True and uniform views per MPI, other launches silently take the atomic path)
+      geometry_grad  False (default: the reference's behaviour -- no gradient reaches the plane geometry or the camera tensors) | True: the
+                     gradient also flows to dhw, ray_dir, eye_pos and z_dir (gmpi_mpi_render_geometry_backward_launch, render_backward_geometry.hip:
+                     an extension, the reference builds its grid under torch.no_grad(), mpi.py:65).  The transmittance output stays non-differentiable.
     """
 
     DEFAULT_RANGE_CHECK = "touched"
 
     def __init__(self, align_corners=True, variant: str = "auto", strict_order: bool = False,
-                 range_check: Optional[str] = None, on_out_of_plane: str = "exit", backward: str = "atomic"):
+                 range_check: Optional[str] = None, on_out_of_plane: str = "exit", backward: str = "atomic", geometry_grad: bool = False):
         super().__init__()
+        self.geometry_grad = bool(geometry_grad)
         self._align_corners = align_corners
         if range_check is None:
             range_check = type(self).DEFAULT_RANGE_CHECK   # (a class attribute: `install()` swaps in a subclass that overrides it)
@@ -416,10 +420,11 @@ class MPI(nn.Module):
         its status travels to pinned host memory behind the kernel and is looked at by a later call on the same stream, by
         `flush_status()` or at interpreter exit (see `_StatusRing`).
         """
-        if torch.is_grad_enabled() and dhw.requires_grad:
+        if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
-                                      "torch.no_grad(), mpi.py:65)")
-        if torch.is_grad_enabled() and rgba.requires_grad and not _in_autograd_fn:
+                                      "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
+        if torch.is_grad_enabled() and not _in_autograd_fn and (
+                rgba.requires_grad or (self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)))):
             # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
             kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                           out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
@@ -610,7 +615,8 @@ class MPI(nn.Module):
 
 
 class _RenderFunction(torch.autograd.Function):
-    """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba).
+    """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba) and, for an MPI with
+    geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir).
 
     Everything the backward reads is kept through `save_for_backward` (so an in-place update of the volume between
     forward and backward raises instead of producing gradients of overwritten memory), the parameter struct is rebuilt
@@ -634,6 +640,8 @@ class _RenderFunction(torch.autograd.Function):
                            H=p.H, W=p.W, views_per_mpi=p.views_per_mpi)
         ctx.backward_mode = mpi.backward
         ctx.in_dtype, ctx.in_shape = rgba.dtype, tuple(rgba.shape)
+        ctx.geometry = mpi.geometry_grad
+        ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
         ctx.mark_non_differentiable(res["status"], T)  # gradient w.r.t. the transmittance output is not provided
         return res["color"], res["depth"], T, res["status"]
 
@@ -644,45 +652,73 @@ class _RenderFunction(torch.autograd.Function):
         vol, dhw, ray_dir, eye_pos, z_dir, T = saved[:6]
         v2m = saved[6] if ctx.has_v2m else None
         dev = vol.device
-        p = _lib.GmpiRenderParams()
-        p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
-        for k, v in ctx.scalars.items():
-            setattr(p, k, v)
-        p.rgba = vol.data_ptr()
-        for i, s in enumerate(vol.stride()):
-            p.rgba_stride[i] = s
-        p.view_to_mpi = v2m.data_ptr() if v2m is not None else None
-        p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
-        p.rgb_out = p.depth_out = p.status = None
-        p.transmittance_out = T.data_ptr()
-        # backward="gather": with a workspace for the sample positions and gradients (N D H W 24 bytes) the launch runs without atomics and WRITES every
-        # element of the gradient: no zero-fill, bit-reproducible (render_backward_gather.hip; align_corners=True, uniform views per MPI).  Default and
-        # everything else: the tile kernels add into a zero-filled volume.
-        need = 0
-        if ctx.backward_mode == "gather" and not getattr(lib, "records_only", False):
-            need = int(lib.gmpi_render_backward_workspace_bytes(ctypes.byref(p)))
-        ws = None
-        if need:
-            try:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)   # (the caching allocator hands out 512-byte aligned blocks; freed with this call)
-            except torch.cuda.OutOfMemoryError:
-                ws = None                                                # (no room for the scratch: the atomics path needs none)
-        if ws is not None:
-            p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-            p.flags |= _lib.FLAG_GRAD_OVERWRITE
-            grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
-        else:
-            grad = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dev)
+
+        def params():   # the forward's launch, rebuilt from the saved tensors
+            p = _lib.GmpiRenderParams()
+            p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
+            for k, v in ctx.scalars.items():
+                setattr(p, k, v)
+            p.rgba = vol.data_ptr()
+            for i, s in enumerate(vol.stride()):
+                p.rgba_stride[i] = s
+            p.view_to_mpi = v2m.data_ptr() if v2m is not None else None
+            p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
+            p.rgb_out = p.depth_out = p.status = None
+            p.transmittance_out = T.data_ptr()
+            return p
+
+        p = params()
         if g_color is None:
             g_color = torch.zeros((p.N, 3, p.H, p.W), dtype=torch.float32, device=dev)
         g_color = g_color.to(torch.float32).contiguous()
         g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
-        gstride = (ctypes.c_int64 * 5)(*grad.stride())
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_mpi_render_backward_launch(
-                ctypes.byref(p), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
-                grad.data_ptr(), gstride, torch.cuda.current_stream(dev).cuda_stream), "gmpi_mpi_render_backward_launch")
-        return grad.to(ctx.in_dtype), None, None, None, None, None, None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        grad = None
+        if ctx.needs_input_grad[0]:
+            # backward="gather": with a workspace for the sample positions and gradients (N D H W 24 bytes) the launch runs without atomics and WRITES every
+            # element of the gradient: no zero-fill, bit-reproducible (render_backward_gather.hip; align_corners=True, uniform views per MPI).  Default and
+            # everything else: the tile kernels add into a zero-filled volume.
+            need = 0
+            if ctx.backward_mode == "gather" and not getattr(lib, "records_only", False):
+                need = int(lib.gmpi_render_backward_workspace_bytes(ctypes.byref(p)))
+            ws = None
+            if need:
+                try:
+                    ws = torch.empty(need, dtype=torch.uint8, device=dev)   # (the caching allocator hands out 512-byte aligned blocks; freed with this call)
+                except torch.cuda.OutOfMemoryError:
+                    ws = None                                                # (no room for the scratch: the atomics path needs none)
+            if ws is not None:
+                p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+                p.flags |= _lib.FLAG_GRAD_OVERWRITE
+                grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
+            else:
+                grad = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dev)
+            gstride = (ctypes.c_int64 * 5)(*grad.stride())
+            with torch.cuda.device(dev):
+                _lib.check(lib.gmpi_mpi_render_backward_launch(
+                    ctypes.byref(p), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
+                    grad.data_ptr(), gstride, stream), "gmpi_mpi_render_backward_launch")
+            grad = grad.to(ctx.in_dtype)
+        geo = [None] * 4   # dhw, ray_dir, eye_pos, z_dir
+        want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
+        if any(want):
+            # gradient w.r.t. the sample positions (render_backward_geometry.hip): every output overwritten, NULL = not wanted; the per-view and
+            # per-plane sums go through slabs in a workspace (no atomics: bit-reproducible)
+            p = params()
+            shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
+            out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+            ws = None
+            if want[0] or want[2] or want[3]:
+                need = int(lib.gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
+                ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+                p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+            ptr = [t.data_ptr() if t is not None else None for t in out]
+            with torch.cuda.device(dev):
+                _lib.check(lib.gmpi_mpi_render_geometry_backward_launch(
+                    ctypes.byref(p), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
+                    ptr[1], ptr[2], ptr[3], ptr[0], stream), "gmpi_mpi_render_geometry_backward_launch")
+            geo = [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
+        return grad, None, geo[0], geo[1], geo[2], geo[3], None
 
 
 HipMPI = MPI

@@ -62,9 +62,9 @@ class MPIRenderer:
                  use_confined_volume=False, device=torch.device("cpu"),
                  # extensions (keyword-only, defaults = reference behaviour)
                  kernel_variant="auto", strict_order=False, range_check=None, on_out_of_plane="exit",
-                 ray_backend="auto", status_mode="sync", backward="atomic"):
+                 ray_backend="auto", status_mode="sync", backward="atomic", geometry_grad=False):
         self.mpi = MPI(align_corners=mpi_align_corners, variant=kernel_variant, strict_order=strict_order,
-                       range_check=range_check, on_out_of_plane=on_out_of_plane, backward=backward)
+                       range_check=range_check, on_out_of_plane=on_out_of_plane, backward=backward, geometry_grad=geometry_grad)
         self.use_confined_volume = use_confined_volume
         self.n_mpi_planes = n_mpi_planes
         self.plane_min_d = plane_min_d
@@ -439,7 +439,7 @@ class MPIRenderer:
             #  backward, and the next render() of this shape would overwrite them through a raw pointer -- no version counter sees that)
             # (nor when the status check lags: the pending entry of this call keeps its camera tensors for the diagnostics of a tripped
             #  assertion -- "pos / dir / min val" of THIS call, printed one or more calls later -- so a later call must not overwrite them)
-            recording = torch.is_grad_enabled() and batch_mpi_rgbas.requires_grad
+            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad))
             ray_t, eye_t, zd_t = self._generate_rays_hip(c2w, reuse=not recording and defer != "lag")
         else:
             if given_cam_infos is None:
@@ -469,3 +469,37 @@ class MPIRenderer:
         if want_T:
             return res["color"], res["depth"], c2w, cam_angles, res["T"]
         return res["color"], res["depth"], c2w, cam_angles
+
+
+class _RaysFromC2W(torch.autograd.Function):
+    """(ray_dir [B,3,H,W], eye_pos [B,3], z_dir [B,3]) of c2w [B,4,4]: forward = gmpi_generate_rays_launch (the rays of the non-differentiable
+    path, bit for bit); backward in torch: ray_dir[b] = R[b] @ dirs, eye_pos[b] = c2w[b][:3,3], z_dir[b] = R[b][:,2] with the camera-frame unit
+    directions dirs [3,HW] constant (no gradient w.r.t. the intrinsics)."""
+
+    @staticmethod
+    def forward(ctx, c2w, renderer):
+        ray, eye, zd = renderer._generate_rays_hip(c2w.detach(), reuse=False)
+        ctx.renderer, ctx.c2w_meta = renderer, (c2w.dtype, c2w.device, tuple(c2w.shape))
+        return ray, eye, zd
+
+    @staticmethod
+    def backward(ctx, g_ray, g_eye, g_zd):
+        dtype, device, shape = ctx.c2w_meta
+        B = shape[0]
+        dev = g_ray.device if g_ray is not None else (g_eye.device if g_eye is not None else g_zd.device)
+        g = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+        if g_ray is not None:
+            dirs = ctx.renderer.cam.unit_dirs(dev)                                          # [3, HW]
+            g[:, :3, :3] = torch.matmul(g_ray.to(torch.float32).reshape(B, 3, -1), dirs.t())
+        if g_zd is not None:
+            g[:, :3, 2] += g_zd.to(torch.float32)
+        if g_eye is not None:
+            g[:, :3, 3] = g_eye.to(torch.float32)
+        return g.to(device=device, dtype=dtype).reshape(shape), None
+
+
+def rays_from_c2w(renderer: MPIRenderer, c2w: torch.Tensor):
+    """Differentiable rays of the renderer's camera for camera-to-world matrices c2w [B,4,4] on the device:
+    (ray_dir [B,3,H,W], eye_pos [B,3], z_dir [B,3]), the same bits as the renderer's own rays; the gradient reaches c2w (pose refinement):
+    feed them to `render(..., given_cam_infos=...)` of a renderer built with geometry_grad=True."""
+    return _RaysFromC2W.apply(c2w, renderer)
