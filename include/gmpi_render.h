@@ -183,8 +183,8 @@ int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
  * w.r.t. the colour the forward wrote (the OUT_PM1 factor 2 is applied inside when that flag is set); grad_depth
  * [N,1,H,W] or NULL; grad_rgba [M,D,4,Ht,Wt] fp32 with the given element strides (innermost 1) is ACCUMULATED into
  * (atomicAdd) -- the caller zero-fills it.
- * Round 6: when params->workspace holds at least gmpi_render_backward_workspace_bytes(params) bytes (256-byte aligned; N D H W 16 bytes for the
- * sample gradients of every pixel and plane), the launch runs WITHOUT atomics: a pixel pass writes the sample gradients, a texel pass gathers them
+ * Round 6: when params->workspace holds at least gmpi_render_backward_workspace_bytes(params) bytes (256-byte aligned; N D H W 24 bytes for the
+ * sample gradients and sample positions of every pixel and plane, plus one homography record per view and plane), the launch runs WITHOUT atomics: a pixel pass writes the sample gradients, a texel pass gathers them
  * through each plane's homography and writes every cell of grad_rgba once (deterministic; += without GMPI_FLAG_GRAD_OVERWRITE, = with it: then no
  * zero-fill is needed).  align_corners = True, uniform views_per_mpi (no view_to_mpi); other launches take the tile kernels whatever the workspace.
  * `ray_dir` must be a pinhole ray field (straight pixel lines map to straight lines on every plane -- what `Camera.generate_rays` /
@@ -193,6 +193,19 @@ int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
  */
 int gmpi_mpi_render_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
                                     float *grad_rgba, const int64_t *grad_rgba_stride, void *stream);
+/*
+ * The same with a gradient w.r.t. the final transmittance as well: grad_transmittance [N,1,H,W] fp32 or NULL (NULL: exactly
+ * gmpi_mpi_render_backward_launch, bit for bit).  With om_k = (1 - a_k) + 1e-10, T_0 = 1, T_{k+1} = T_k om_k, T_out = T_D:
+ *     dT_out/da_k = -T_out / om_k = -T_k prod_{j>k} om_j,    dT_out/drgb_k = 0,
+ * so with q_k = <gC, rgb_k> + gZ depth_k the volume backward's recurrence  dL/da_k = T_k q_k - S_k / om_k  holds unchanged when the suffix sum
+ * starts at gT T_out instead of 0:  S_k = gT T_out + sum_{j>k} w_j q_j  (T_out acts as a background colour every pixel sees through all
+ * planes); dL/drgb_k does not change.  The sweep forms gT T_out from the transmittance it starts from (the forward's value, or the one it
+ * rebuilds in mantissa x 2^exponent form when that value is below 1e-30): when T_out underflows fp32 the term flushes to zero, which loses
+ * contributions below 1e-30 |gT| (four exactly opaque planes give T_out ~ 1e-40).  No scratch of its own: the workspace query is unchanged.
+ */
+int gmpi_mpi_render_backward_ex_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                       const float *grad_transmittance, float *grad_rgba, const int64_t *grad_rgba_stride,
+                                       void *stream);
 /* Bytes of caller-owned scratch with which the backward runs without atomics (0: this launch takes the tile kernels). */
 uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams *params);
 
@@ -214,6 +227,12 @@ uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams *params);
 int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
                                              float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw,
                                              void *stream);
+/* The same with grad_transmittance [N,1,H,W] fp32 or NULL (NULL: exactly gmpi_mpi_render_geometry_backward_launch).  The transmittance
+ * term enters through the alpha sample gradient d_s[3] (the suffix sum starts at gT T_out, as in gmpi_mpi_render_backward_ex_launch) and
+ * reaches the positions through g_ix and g_iy; G_k, the depth term, is untouched. */
+int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                                const float *grad_transmittance, float *grad_ray_dir, float *grad_eye_pos,
+                                                float *grad_z_dir, float *grad_dhw, void *stream);
 /* Bytes of workspace gmpi_mpi_render_geometry_backward_launch needs for the eye / z_dir sums, and with want_dhw != 0 the plane sums too. */
 uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams *params, int want_dhw);
 
@@ -294,6 +313,9 @@ int gmpi_light_apply_launch(const void *rgba, int32_t rgba_dtype, const int64_t 
  *  - gmpi_alpha_depth_backward_launch: gradient of gmpi_alpha_depth_launch w.r.t. alpha, ADDED to grad_alpha (an fp32
  *    [B,D,1,H,W] view with the given element strides, e.g. channel 3 of grad_rgba).  `transmittance` is the forward's
  *    transmittance_out or NULL.
+ *  - gmpi_alpha_depth_backward_ex_launch: the same for both outputs: grad_depth and grad_transmittance ([B,1,H,W] fp32)
+ *    may each be NULL (both NULL: nothing is added).  dL/da_k = T_k q_k - S_k / om_k with q_k = gZ d_k and
+ *    S_k = gT T_out + sum_{j>k} a_j T_j q_j (the derivation of gmpi_mpi_render_backward_ex_launch, same numerics).
  */
 int gmpi_light_apply_backward_launch(const void *rgba, int32_t rgba_dtype, const int64_t *rgba_stride, const float *shading,
                                      const float *grad_out, float *grad_rgba, float *grad_shading, int32_t B, int32_t D,
@@ -302,6 +324,11 @@ int gmpi_alpha_depth_backward_launch(const void *alpha, int32_t alpha_dtype, int
                                      int64_t stride_row, const float *plane_ds, const float *transmittance,
                                      const float *grad_depth, float *grad_alpha, int64_t gstride_b, int64_t gstride_d,
                                      int64_t gstride_row, int32_t B, int32_t D, int32_t H, int32_t W, void *stream);
+int gmpi_alpha_depth_backward_ex_launch(const void *alpha, int32_t alpha_dtype, int64_t stride_b, int64_t stride_d,
+                                        int64_t stride_row, const float *plane_ds, const float *transmittance,
+                                        const float *grad_depth, const float *grad_transmittance, float *grad_alpha,
+                                        int64_t gstride_b, int64_t gstride_d, int64_t gstride_row, int32_t B, int32_t D,
+                                        int32_t H, int32_t W, void *stream);
 
 /*
  * Self-test of the default mode's division: the coordinate chain (mpi.py:76, 89-90) divides through correctly rounded

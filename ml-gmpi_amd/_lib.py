@@ -29,6 +29,8 @@ EXPORTS = (
     "gmpi_mpi_render_backward_launch",
     "gmpi_render_geometry_backward_workspace_bytes",
     "gmpi_mpi_render_geometry_backward_launch",
+    "gmpi_mpi_render_backward_ex_launch",
+    "gmpi_mpi_render_geometry_backward_ex_launch",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -39,6 +41,7 @@ EXPORTS = (
     "gmpi_light_apply_launch",
     "gmpi_light_apply_backward_launch",
     "gmpi_alpha_depth_backward_launch",
+    "gmpi_alpha_depth_backward_ex_launch",
     "gmpi_selftest_division_launch",
     "gmpi_stream_probe_launch",
     "gmpi_query",
@@ -168,6 +171,11 @@ def load_library():
     lib.gmpi_render_geometry_backward_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.c_int]
     lib.gmpi_mpi_render_geometry_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp]
+    lib.gmpi_mpi_render_backward_ex_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_backward_ex_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp,
+                                                       ctypes.POINTER(ctypes.c_int64), vp]
+    lib.gmpi_mpi_render_geometry_backward_ex_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int
@@ -195,6 +203,10 @@ def load_library():
     lib.gmpi_alpha_depth_backward_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                                                      vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
+    lib.gmpi_alpha_depth_backward_ex_launch.restype = ctypes.c_int
+    lib.gmpi_alpha_depth_backward_ex_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
+                                                        vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
     lib.gmpi_stream_probe_launch.restype = ctypes.c_int
     lib.gmpi_stream_probe_launch.argtypes = [vp, ctypes.c_uint64, vp, vp]
     lib.gmpi_selftest_division_launch.restype = ctypes.c_int

@@ -11,7 +11,7 @@ namespace gmpi {
 
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream);  // render_gather.hip
 hipError_t launch_lds(const KParams& p, int dtype, int tune, hipStream_t stream);  // render_lds.hip
-hipError_t launch_backward(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, float* g_rgba,
+hipError_t launch_backward(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
                            const int64_t* gstride, bool tiles, hipStream_t stream);  // render_backward.hip
 bool lds_variant_supports(const KParams& p, int dtype);                     // render_lds.hip
 int lds_variant_query(int what);                                            // render_lds.hip
@@ -24,8 +24,8 @@ uint32_t* band_gate_words(const KParams& p, int dtype);                     // r
 int band_pixels_wide(int dtype);                                            // render_band.hip
 uint64_t backward_gather_workspace_bytes(const KParams& p);                 // render_backward_gather.hip
 uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
-hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, float* g_ray, float* g_eye, float* g_z,
-                                    float* g_dhw, hipStream_t stream);       // render_backward_geometry.hip
+hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
+                                    float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 
 // ---- min/max of the normalised grid on the last plane (mpi.py:103-109 diagnostics) --------------
 template <bool AC>
@@ -434,6 +434,11 @@ uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams* params) {
 
 int gmpi_mpi_render_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
                                     float* grad_rgba, const int64_t* grad_rgba_stride, void* stream) {
+    return gmpi_mpi_render_backward_ex_launch(params, grad_rgb, grad_depth, nullptr, grad_rgba, grad_rgba_stride, stream);
+}
+
+int gmpi_mpi_render_backward_ex_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
+                                       const float* grad_transmittance, float* grad_rgba, const int64_t* grad_rgba_stride, void* stream) {
     if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
     KParams p;
     const int rc = to_kparams(params, p, false, true);
@@ -443,7 +448,7 @@ int gmpi_mpi_render_backward_launch(const GmpiRenderParams* params, const float*
     if (grad_rgba_stride[4] != 1) return GMPI_E_STRIDE;
     for (int i = 0; i < 4; ++i)
         if (grad_rgba_stride[i] <= 0 && !(i == 0 && params->M == 1)) return GMPI_E_STRIDE;
-    return hip_rc(launch_backward(p, params->rgba_dtype, grad_rgb, grad_depth, grad_rgba, grad_rgba_stride,
+    return hip_rc(launch_backward(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, grad_rgba, grad_rgba_stride,
                                   params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
 }
 
@@ -455,6 +460,13 @@ uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams* p
 
 int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, float* grad_ray_dir,
                                              float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, void* stream) {
+    return gmpi_mpi_render_geometry_backward_ex_launch(params, grad_rgb, grad_depth, nullptr, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
+                                                       stream);
+}
+
+int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
+                                                const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
+                                                float* grad_dhw, void* stream) {
     if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
     KParams p;
     const int rc = to_kparams(params, p, false, true);
@@ -466,7 +478,7 @@ int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams* params, con
         const uint64_t need = geometry_backward_workspace_bytes(p, grad_dhw != nullptr);
         if (p.ws == nullptr || p.ws_bytes < need || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return GMPI_E_WORKSPACE;
     }
-    return hip_rc(launch_backward_geometry(p, params->rgba_dtype, grad_rgb, grad_depth, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
+    return hip_rc(launch_backward_geometry(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
                                            static_cast<hipStream_t>(stream)));
 }
 

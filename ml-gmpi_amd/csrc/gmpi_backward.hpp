@@ -8,7 +8,8 @@ namespace gmpi {
 struct BwdParams {
     const float* g_rgb;    // [N,3,H,W] gradient w.r.t. the colour the forward wrote ([0,1] or, with OUT_PM1, [-1,1])
     const float* g_depth;  // [N,1,H,W] or nullptr
-    float* g_rgba;         // [M,D,4,Ht,Wt] fp32, accumulated into (caller zero-fills)
+    const float* g_T;      // [N,1,H,W] gradient w.r.t. the final transmittance, or nullptr: the sweep's S starts at gT * T_out
+    float* g_rgba;        // [M,D,4,Ht,Wt] fp32, accumulated into (caller zero-fills)
     int64_t gs_mpi, gs_plane, gs_chan, gs_row;
 };
 

@@ -150,20 +150,22 @@ __global__ __launch_bounds__(256) void light_apply_backward_kernel(const T* __re
     *reinterpret_cast<FV*>(g_shading + b * plane + pix) = gs;
 }
 
-// (2) depth = sum_k a_k T_k d_k (compute_depth): dL/da_k = g (T_k d_k - S_k / om_k), S_k = sum_{j>k} a_j T_j d_j, back to
-//     front from the forward's final transmittance (same scheme as render_backward.hip: no cancellation behind opaque
-//     planes; T carried as mantissa x 2^exponent).  ADDS into g_alpha (the alpha channel of the volume gradient).
+// (2) depth = sum_k a_k T_k d_k (compute_depth): dL/da_k = T_k q_k - S_k / om_k, q_k = g d_k, S_k = gT T_out + sum_{j>k} a_j T_j q_j,
+//     back to front from the forward's final transmittance (same scheme as render_backward.hip: no cancellation behind opaque
+//     planes; T carried as mantissa x 2^exponent).  g_depth and g_T (the gradient w.r.t. T_out = prod_k om_k: dT_out/da_k =
+//     -T_out / om_k) may each be nullptr.  ADDS into g_alpha (the alpha channel of the volume gradient).
 template <typename T>
 __global__ __launch_bounds__(256) void alpha_depth_backward_kernel(const T* __restrict__ alpha, int64_t sb, int64_t sd, int64_t sr,
                                                                    const float* __restrict__ ds, const float* __restrict__ t_final,
-                                                                   const float* __restrict__ g_depth, float* __restrict__ g_alpha,
-                                                                   int64_t gb, int64_t gd, int64_t gr, int D, int H, int W) {
+                                                                   const float* __restrict__ g_depth, const float* __restrict__ g_T,
+                                                                   float* __restrict__ g_alpha, int64_t gb, int64_t gd, int64_t gr, int D,
+                                                                   int H, int W) {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x >= W) return;
     const T* __restrict__ a = alpha + b * sb + static_cast<int64_t>(y) * sr + x;
     float* __restrict__ ga = g_alpha + b * gb + static_cast<int64_t>(y) * gr + x;
     const int64_t o = (static_cast<int64_t>(b) * H + y) * W + x;
-    const float g = g_depth[o];
+    const float g = g_depth ? g_depth[o] : 0.0f;
     float tm = t_final ? t_final[o] : 0.0f;
     int te = 0;
     if (!(tm >= 1e-30f)) {  // missing or underflowed: rebuild front to back in the extended representation
@@ -175,6 +177,7 @@ __global__ __launch_bounds__(256) void alpha_depth_backward_kernel(const T* __re
         }
     }
     float S = 0.0f;
+    if (g_T) S = g_T[o] * __builtin_amdgcn_ldexpf(tm, te);   // (below 1e-30 * |gT| the term flushes: T_out itself underflows)
     for (int k = D - 1; k >= 0; --k) {
         const float al = to_f32(a[k * sd]);
         const float om = (1.0f - al) + 1e-10f;
@@ -254,21 +257,31 @@ int gmpi_light_apply_backward_launch(const void* rgba, int32_t rgba_dtype, const
     return rc_of(hipGetLastError());
 }
 
+int gmpi_alpha_depth_backward_ex_launch(const void* alpha, int32_t alpha_dtype, int64_t stride_b, int64_t stride_d, int64_t stride_row,
+                                        const float* plane_ds, const float* transmittance, const float* grad_depth,
+                                        const float* grad_transmittance, float* grad_alpha, int64_t gstride_b, int64_t gstride_d,
+                                        int64_t gstride_row, int32_t B, int32_t D, int32_t H, int32_t W, void* stream) {
+    if (B < 0 || D <= 0 || H <= 0 || W <= 0) return GMPI_E_SHAPE;
+    if (B == 0) return GMPI_OK;
+    if (!alpha || !plane_ds || !grad_alpha) return GMPI_E_NULL;
+    if (alpha_dtype < GMPI_DTYPE_F32 || alpha_dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
+    if (stride_b < 0 || stride_d <= 0 || stride_row < W || gstride_b <= 0 || gstride_d <= 0 || gstride_row < W) return GMPI_E_STRIDE;
+    if (!grad_depth && !grad_transmittance) return GMPI_OK;   // (nothing to add)
+    const dim3 grid((W + 255) / 256, H, B), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (alpha_dtype == GMPI_DTYPE_F32) hipLaunchKernelGGL(alpha_depth_backward_kernel<float>, grid, block, 0, st, static_cast<const float*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
+    else if (alpha_dtype == GMPI_DTYPE_BF16) hipLaunchKernelGGL(alpha_depth_backward_kernel<bf16_t>, grid, block, 0, st, static_cast<const bf16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
+    else hipLaunchKernelGGL(alpha_depth_backward_kernel<f16_t>, grid, block, 0, st, static_cast<const f16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
+    return rc_of(hipGetLastError());
+}
+
 int gmpi_alpha_depth_backward_launch(const void* alpha, int32_t alpha_dtype, int64_t stride_b, int64_t stride_d, int64_t stride_row,
                                      const float* plane_ds, const float* transmittance, const float* grad_depth, float* grad_alpha,
                                      int64_t gstride_b, int64_t gstride_d, int64_t gstride_row, int32_t B, int32_t D, int32_t H,
                                      int32_t W, void* stream) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0) return GMPI_E_SHAPE;
-    if (B == 0) return GMPI_OK;
-    if (!alpha || !plane_ds || !grad_depth || !grad_alpha) return GMPI_E_NULL;
-    if (alpha_dtype < GMPI_DTYPE_F32 || alpha_dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
-    if (stride_b < 0 || stride_d <= 0 || stride_row < W || gstride_b <= 0 || gstride_d <= 0 || gstride_row < W) return GMPI_E_STRIDE;
-    const dim3 grid((W + 255) / 256, H, B), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (alpha_dtype == GMPI_DTYPE_F32) hipLaunchKernelGGL(alpha_depth_backward_kernel<float>, grid, block, 0, st, static_cast<const float*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
-    else if (alpha_dtype == GMPI_DTYPE_BF16) hipLaunchKernelGGL(alpha_depth_backward_kernel<bf16_t>, grid, block, 0, st, static_cast<const bf16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
-    else hipLaunchKernelGGL(alpha_depth_backward_kernel<f16_t>, grid, block, 0, st, static_cast<const f16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
-    return rc_of(hipGetLastError());
+    if (B > 0 && D > 0 && H > 0 && W > 0 && !grad_depth) return GMPI_E_NULL;
+    return gmpi_alpha_depth_backward_ex_launch(alpha, alpha_dtype, stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, nullptr,
+                                               grad_alpha, gstride_b, gstride_d, gstride_row, B, D, H, W, stream);
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, c
     // ---- back-to-front sweep: gradients, scattered with the bilinear weights --------------------------------------
     const float t_fwd = p.T_out ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 0.0f;
     BwdPixel bp{gr, gg, gb, gz, dot, total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy), 0.0f};
+    if (b.g_T) bp.S = b.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
     uint32_t unused = 0;
     for (int k = p.D - 1; k >= 0; --k) {
         float ix, iy, s, u, v;
@@ -154,6 +155,7 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
     const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
     BwdPixel bp{gr, gg, gb, gz, dot, XT{1.0f, 0}, 0.0f};
     if (active) bp.T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
+    if (active && b.g_T) bp.S = b.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
     uint32_t unused = 0;
 
     // ---- back-to-front sweep: gradients; scatter through the LDS boxes ------------------------------------------
@@ -401,6 +403,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
         gz = (active && b.g_depth) ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
         const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
         if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
+        if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();
     }
 
     // what a plane keeps between the issue of its taps and their use (Tap), and between its gradients and their scatter (Grad)
@@ -777,7 +780,7 @@ bool backward_gather_supports(const KParams& p);                                
 uint64_t backward_gather_workspace_bytes(const KParams& p);                                                // render_backward_gather.hip
 hipError_t launch_backward_gather(const KParams& p, int dtype, const BwdParams& b, bool overwrite, hipStream_t stream);   // render_backward_gather.hip
 
-hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, const float* g_depth, float* g_rgba,
+hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
                            const int64_t* gstride, bool tiles, hipStream_t stream) {
     KParams p = p0;
 #ifdef GMPI_TUNE  // profiling builds only: 16 = no global atomics in the flush, 32 = no LDS atomics, 64 = the round-1 tile kernel, 128 = no tap loads, 256 = tiles in row-major order over the XCDs
@@ -785,7 +788,7 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
     p.flags |= skip << 16;
 #endif
     BwdParams b;
-    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_rgba = g_rgba;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T, b.g_rgba = g_rgba;
     b.gs_mpi = gstride[0], b.gs_plane = gstride[1], b.gs_chan = gstride[2], b.gs_row = gstride[3];
     if (p.N > 65535) tiles = false;  // grid.y
     // Round 6: with a workspace for the sample gradients (gmpi_render_backward_workspace_bytes) the atomics-free pair -- pixel pass + texel gather,

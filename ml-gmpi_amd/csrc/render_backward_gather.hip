@@ -159,6 +159,7 @@ __global__ __launch_bounds__(kPT, 6) void pixel_pass_kernel(const KParams p, con
     XT T{1.0f, 0};
     if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
     float S = 0.0f;
+    if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
 
     struct Tap { float s, wx1, wy1, ix, iy; int x0, y0; float v[16]; };   // v: per channel (top p0, p1 | bottom p0, p1)
     auto fetch = [&](int t, int k, Tap& q) {   // coordinates of this pixel on plane k (chunk-local t) + its 8 pair loads

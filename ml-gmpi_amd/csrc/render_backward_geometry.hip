@@ -112,6 +112,7 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
     XT T{1.0f, 0};
     if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
     float S = 0.0f;
+    if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
     float sx = 0.0f, sy = 0.0f, ss = 0.0f;      // sum_k g_x, g_y, g_s
     float srx = 0.0f, sry = 0.0f, srz = 0.0f;   // sum_k g_x s, g_y s, g_s s
     float sG = 0.0f;                            // sum_k G_k s
@@ -287,10 +288,10 @@ static void launch_geometry_dtype(const KParams& p, const BwdParams& b, float* g
 
 // g_ray [N,3,H,W], g_eye / g_z [N,3], g_dhw [M,D,3]: overwritten; nullptr = not wanted.  p.ws must hold geometry_backward_workspace_bytes(p,
 // g_dhw != nullptr) bytes when any of g_eye, g_z, g_dhw is wanted (checked by the caller).
-hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, float* g_ray, float* g_eye, float* g_z,
-                                    float* g_dhw, hipStream_t stream) {
+hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
+                                    float* g_z, float* g_dhw, hipStream_t stream) {
     BwdParams b{};
-    b.g_rgb = g_rgb, b.g_depth = g_depth;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T;
     const bool want_dhw = g_dhw != nullptr;
     float* slab = (g_eye || g_z || g_dhw) ? static_cast<float*>(p.ws) : nullptr;
     switch (dtype) {

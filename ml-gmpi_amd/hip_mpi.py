@@ -302,7 +302,10 @@ class MPI(nn.Module):
                      align_corners=True and uniform views per MPI, other launches silently take the atomic path)
       geometry_grad  False (default: the reference's behaviour -- no gradient reaches the plane geometry or the camera tensors) | True: the
                      gradient also flows to dhw, ray_dir, eye_pos and z_dir (gmpi_mpi_render_geometry_backward_launch, render_backward_geometry.hip:
-                     an extension, the reference builds its grid under torch.no_grad(), mpi.py:65).  The transmittance output stays non-differentiable.
+                     an extension, the reference builds its grid under torch.no_grad(), mpi.py:65).
+
+    The transmittance output T (want_transmittance=True) is differentiable like colour and depth: a loss on it (`color + T * bg`, a coverage
+    loss on 1 - T) reaches the volume and, with geometry_grad=True, the geometry (gmpi_mpi_render_backward_ex_launch: dT/da_k = -T / om_k).
     """
 
     DEFAULT_RANGE_CHECK = "touched"
@@ -616,7 +619,8 @@ class MPI(nn.Module):
 
 class _RenderFunction(torch.autograd.Function):
     """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba) and, for an MPI with
-    geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir).
+    geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir); their _ex forms when the loss
+    reaches the transmittance output.
 
     Everything the backward reads is kept through `save_for_backward` (so an in-place update of the volume between
     forward and backward raises instead of producing gradients of overwritten memory), the parameter struct is rebuilt
@@ -642,7 +646,9 @@ class _RenderFunction(torch.autograd.Function):
         ctx.in_dtype, ctx.in_shape = rgba.dtype, tuple(rgba.shape)
         ctx.geometry = mpi.geometry_grad
         ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
-        ctx.mark_non_differentiable(res["status"], T)  # gradient w.r.t. the transmittance output is not provided
+        ctx.mark_non_differentiable(res["status"])
+        # (an output nobody used arrives as None, not as a zero tensor: "T unused" -> today's launch, told apart from gT = 0 without a reduction)
+        ctx.set_materialize_grads(False)
         return res["color"], res["depth"], T, res["status"]
 
     @staticmethod
@@ -672,6 +678,9 @@ class _RenderFunction(torch.autograd.Function):
             g_color = torch.zeros((p.N, 3, p.H, p.W), dtype=torch.float32, device=dev)
         g_color = g_color.to(torch.float32).contiguous()
         g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
+        # gradient w.r.t. the final transmittance (the sweep's suffix sum starts at gT * T_out): the _ex entries; None -> the old ones, NULL.  The
+        # OUT_PM1 factor 2 applies to the colour only (inside the kernels).
+        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
         stream = torch.cuda.current_stream(dev).cuda_stream
         grad = None
         if ctx.needs_input_grad[0]:
@@ -694,10 +703,15 @@ class _RenderFunction(torch.autograd.Function):
             else:
                 grad = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dev)
             gstride = (ctypes.c_int64 * 5)(*grad.stride())
+            gz_ptr = g_depth.data_ptr() if g_depth is not None else None
             with torch.cuda.device(dev):
-                _lib.check(lib.gmpi_mpi_render_backward_launch(
-                    ctypes.byref(p), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
-                    grad.data_ptr(), gstride, stream), "gmpi_mpi_render_backward_launch")
+                if g_T is None:
+                    _lib.check(lib.gmpi_mpi_render_backward_launch(
+                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, grad.data_ptr(), gstride, stream), "gmpi_mpi_render_backward_launch")
+                else:
+                    _lib.check(lib.gmpi_mpi_render_backward_ex_launch(
+                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, g_T.data_ptr(), grad.data_ptr(), gstride, stream),
+                        "gmpi_mpi_render_backward_ex_launch")
             grad = grad.to(ctx.in_dtype)
         geo = [None] * 4   # dhw, ray_dir, eye_pos, z_dir
         want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
@@ -713,10 +727,16 @@ class _RenderFunction(torch.autograd.Function):
                 ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
                 p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
             ptr = [t.data_ptr() if t is not None else None for t in out]
+            gz_ptr = g_depth.data_ptr() if g_depth is not None else None
             with torch.cuda.device(dev):
-                _lib.check(lib.gmpi_mpi_render_geometry_backward_launch(
-                    ctypes.byref(p), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
-                    ptr[1], ptr[2], ptr[3], ptr[0], stream), "gmpi_mpi_render_geometry_backward_launch")
+                if g_T is None:
+                    _lib.check(lib.gmpi_mpi_render_geometry_backward_launch(
+                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, ptr[1], ptr[2], ptr[3], ptr[0], stream),
+                        "gmpi_mpi_render_geometry_backward_launch")
+                else:
+                    _lib.check(lib.gmpi_mpi_render_geometry_backward_ex_launch(
+                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, g_T.data_ptr(), ptr[1], ptr[2], ptr[3], ptr[0], stream),
+                        "gmpi_mpi_render_geometry_backward_ex_launch")
             geo = [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
 

@@ -22,18 +22,38 @@ from .hip_mpi import _DTYPES
 EPS = 1e-8  # light_renderer.py:8
 
 
-@torch.no_grad()
 def compute_depth(mpi_alpha: torch.Tensor, plane_ds: torch.Tensor, want_transmittance: bool = False):
     """mpi_alpha [B, D, 1, H, W] (any float storage dtype; may be the strided view `mpi[:, :, 3:]` of an RGBA volume),
-    plane_ds [D] or [D,1] plane distances -> depth [B, 1, H, W] (float32) [, transmittance [B,1,H,W]]."""
+    plane_ds [D] or [D,1] plane distances -> depth [B, 1, H, W] (float32) [, transmittance [B,1,H,W]].
+
+    Differentiable w.r.t. mpi_alpha (as the reference's plain-torch `LightRenderer.compute_depth`, light_renderer.py:82-100), through both
+    outputs: the backward is gmpi_alpha_depth_backward_ex_launch.  plane_ds gets no gradient."""
     if not mpi_alpha.is_cuda:
         raise _lib.GmpiError("compute_depth needs tensors on a ROCm device (no CPU path)")
     assert mpi_alpha.ndim == 5 and mpi_alpha.shape[2] == 1, f"{mpi_alpha.shape}"
-    lib = _lib.load_library()
+    if torch.is_grad_enabled() and isinstance(plane_ds, torch.Tensor) and plane_ds.requires_grad:
+        raise NotImplementedError("compute_depth provides no gradient w.r.t. plane_ds")
+    if torch.is_grad_enabled() and mpi_alpha.requires_grad:
+        depth, T = _DepthFunction.apply(mpi_alpha, plane_ds)
+    else:
+        with torch.no_grad():
+            depth, T = _alpha_depth(mpi_alpha, plane_ds, want_transmittance)
+    return (depth, T) if want_transmittance else depth
+
+
+def _alpha_operand(mpi_alpha: torch.Tensor) -> torch.Tensor:
+    """The alpha view the kernels read: a storage dtype they take, innermost stride 1, no negative strides."""
     if mpi_alpha.dtype not in _DTYPES:
         mpi_alpha = mpi_alpha.float()
     if mpi_alpha.stride(4) != 1 or any(s < 0 for s in mpi_alpha.stride()):
         mpi_alpha = mpi_alpha.contiguous()
+    return mpi_alpha
+
+
+def _alpha_depth(mpi_alpha: torch.Tensor, plane_ds: torch.Tensor, want_transmittance: bool):
+    """gmpi_alpha_depth_launch -> (depth, T or None), both float32 [B,1,H,W]."""
+    lib = _lib.load_library()
+    mpi_alpha = _alpha_operand(mpi_alpha)
     B, D, _, H, W = mpi_alpha.shape
     ds = plane_ds.reshape(-1).to(mpi_alpha.device, torch.float32).contiguous()
     assert ds.numel() == D, f"{ds.shape}, {D}"
@@ -44,7 +64,42 @@ def compute_depth(mpi_alpha: torch.Tensor, plane_ds: torch.Tensor, want_transmit
             mpi_alpha.data_ptr(), _DTYPES[mpi_alpha.dtype], mpi_alpha.stride(0), mpi_alpha.stride(1), mpi_alpha.stride(3),
             ds.data_ptr(), B, D, H, W, depth.data_ptr(), T.data_ptr() if T is not None else None,
             torch.cuda.current_stream(mpi_alpha.device).cuda_stream), "gmpi_alpha_depth_launch")
-    return (depth, T) if want_transmittance else depth
+    return depth, T
+
+
+class _DepthFunction(torch.autograd.Function):
+    """autograd bridge of compute_depth: forward = gmpi_alpha_depth_launch (T always, into a buffer private to this node: the backward
+    sweeps back to front from it), backward = gmpi_alpha_depth_backward_ex_launch into a zero-filled fp32 gradient.  An output the loss
+    does not use arrives as None (set_materialize_grads(False)) and is passed as NULL."""
+
+    @staticmethod
+    def forward(ctx, mpi_alpha, plane_ds):
+        depth, T = _alpha_depth(mpi_alpha.detach(), plane_ds.detach(), True)
+        ds = plane_ds.detach().reshape(-1).to(mpi_alpha.device, torch.float32).contiguous()
+        ctx.save_for_backward(mpi_alpha, ds, T)
+        ctx.in_dtype = mpi_alpha.dtype
+        ctx.set_materialize_grads(False)
+        return depth, T
+
+    @staticmethod
+    def backward(ctx, g_depth, g_T):
+        mpi_alpha, ds, T = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (g_depth is None and g_T is None):
+            return None, None
+        lib = _lib.load_library()
+        alpha = _alpha_operand(mpi_alpha.detach())
+        B, D, _, H, W = alpha.shape
+        dev = alpha.device
+        g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
+        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
+        grad = torch.zeros((B, D, 1, H, W), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.gmpi_alpha_depth_backward_ex_launch(
+                alpha.data_ptr(), _DTYPES[alpha.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3), ds.data_ptr(), T.data_ptr(),
+                g_depth.data_ptr() if g_depth is not None else None, g_T.data_ptr() if g_T is not None else None, grad.data_ptr(),
+                grad.stride(0), grad.stride(1), grad.stride(3), B, D, H, W, torch.cuda.current_stream(dev).cuda_stream),
+                "gmpi_alpha_depth_backward_ex_launch")
+        return grad.to(ctx.in_dtype), None
 
 
 def gaussian_kernel1d(ksize: int, sigma: float) -> torch.Tensor:
