@@ -237,6 +237,51 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams *params, 
 uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams *params, int want_dhw);
 
 /*
+ * Shared-colour layout: what GMPI's generator produces before it concatenates (networks_cond_on_pos_enc.py:950-975 with gmpi.yml:137-145) -- ONE
+ * colour image per MPI, D alpha planes and, optionally, a separate colour image for the last plane.  By definition the result is the render of the
+ * expanded volume  rgba[m,k,0:3] = rgb[m]  (k = D-1: background[m] when one is given),  rgba[m,k,3] = alpha[m,k,0]  -- per plane and channel the
+ * arithmetic is the one of gmpi_mpi_render_launch (GMPI_FLAG_STRICT_ORDER: bit-identical to it), the volume is never materialised.
+ * All three tensors have the storage type params->rgba_dtype and innermost stride 1.
+ */
+typedef struct GmpiSharedColor {
+    uint32_t struct_size;         /* = sizeof(GmpiSharedColor)                                         */
+    const void *rgb;              /* [M, 3, Ht, Wt] colour of every plane (but the last, with a background) */
+    int64_t rgb_stride[3];        /* element strides: MPI, channel, row; 0 allowed on [0] (expand)     */
+    const void *background;       /* [M, 3, Ht, Wt] colour of plane D-1, or NULL                       */
+    int64_t background_stride[3]; /* MPI, channel, row (ignored without a background)                  */
+} GmpiSharedColor;
+
+/*
+ * The fused render over a shared-colour MPI.  `params` as for gmpi_mpi_render_launch, except: params->rgba points at the ALPHA planes
+ * [M, D, 1, Ht, Wt] -- rgba_stride[0], [1], [3] are its MPI, plane and row strides, rgba_stride[2] is ignored, rgba_stride[4] must be 1 -- so the
+ * strided view rgba[:, :, 3:] of an ordinary volume is a valid alpha tensor.  Every flag, view_to_mpi / views_per_mpi, transmittance_out and the status
+ * bits mean what they mean there; GMPI_FLAG_CHECK_RANGE covers the alpha, colour and background texels the render samples.  D == 1 with a background is
+ * legal (the one plane is the background).  One pixel per lane, taps from global memory (any shape, any ray field); params->variant may be AUTO or
+ * GATHER (the same kernel today), anything else is GMPI_E_VARIANT.  No workspace.  Stream-ordered, allocates nothing, never synchronises.
+ */
+int gmpi_mpi_render_shared_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, void *stream);
+
+/*
+ * Gradient of gmpi_mpi_render_shared_launch w.r.t. the three tensors:  d rgb = sum over the planes that use rgb of d rgba[:, k, 0:3],
+ * d background = d rgba[:, D-1, 0:3],  d alpha = d rgba[:, :, 3:]  of gmpi_mpi_render_backward_ex_launch on the expanded volume.  grad_rgb_out
+ * [N,3,H,W], grad_depth [N,1,H,W] or NULL, grad_transmittance [N,1,H,W] or NULL as there; params->transmittance_out as there.
+ * grad_shared_rgb [M,3,Ht,Wt], grad_alpha [M,D,1,Ht,Wt] and grad_background [M,3,Ht,Wt] are fp32, caller-zeroed and ADDED into (atomicAdd); each has
+ * three element strides (MPI, channel or plane, row; innermost 1); each may be NULL and is then skipped (all three NULL: GMPI_E_NULL; a
+ * grad_background without a background: GMPI_E_NULL).
+ * variant GATHER: one pixel per lane, 16 global atomics per pixel and plane.  Anything else: one workgroup per 32 x 16 pixel tile; the alpha gradient
+ * is staged in LDS and flushed per plane, the colour gradient is summed in LDS ACROSS the planes in a window of 64 x 32 texels, which is flushed
+ * whenever the tile's texel boxes have drifted out of it and at the end of the tile: with the FFHQ geometry and 32 planes 2.8 / 3.9 / 6.1 flushes per
+ * tile on average at 256^2 / 512^2 / 1024^2 (instead of 32 per-plane flushes of the colour channels; up to one per plane for strongly tilted cameras
+ * at 1024^2 -- DESIGN.md 3.3c has the counts).  D > 128 (more planes than the tile kernel's tables hold) takes the one-pixel-per-lane kernel, several
+ * times slower.  The tile kernel's texel boxes assume a pinhole ray field (see ray_dir above); this is NOT checked: a pixel whose taps fall outside its
+ * tile's box adds them straight to global memory, so any ray field gives correct gradients, an irregular one at the one-pixel-per-lane kernel's speed.
+ */
+int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const float *grad_rgb_out,
+                                           const float *grad_depth, const float *grad_transmittance, float *grad_shared_rgb,
+                                           const int64_t *grad_shared_rgb_stride, float *grad_alpha, const int64_t *grad_alpha_stride,
+                                           float *grad_background, const int64_t *grad_background_stride, void *stream);
+
+/*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the
  * normalised grid on the LAST plane per view (what mpi.py:106-109 print).  uv_minmax: [N,4] float.
  * Uses N, M, D, H, W, flags(ALIGN_CORNERS), view_to_mpi/views_per_mpi, dhw, ray_dir, eye_pos.

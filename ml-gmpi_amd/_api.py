@@ -5,10 +5,11 @@ from .renderer import MPIRenderer, PRESETS, make_renderer, rays_from_c2w
 from .driver import ViewBatchDriver, shard_views, render_views_sharded, frames_to_uint8, dump_frames
 from .install import install, uninstall
 from .light import LightRenderer, compute_depth
+from .shared_color import expand_shared_color, split_shared_color
 
 __all__ = [
     "GmpiError", "build_extension", "library_path", "load_library",
     "MPI", "HipMPI", "flush_status", "MPIRenderer", "PRESETS", "make_renderer", "rays_from_c2w",
     "ViewBatchDriver", "shard_views", "render_views_sharded", "frames_to_uint8", "dump_frames",
-    "install", "uninstall", "compute_depth", "LightRenderer",
+    "install", "uninstall", "compute_depth", "LightRenderer", "expand_shared_color", "split_shared_color",
 ]

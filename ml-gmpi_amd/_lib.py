@@ -31,6 +31,8 @@ EXPORTS = (
     "gmpi_mpi_render_geometry_backward_launch",
     "gmpi_mpi_render_backward_ex_launch",
     "gmpi_mpi_render_geometry_backward_ex_launch",
+    "gmpi_mpi_render_shared_launch",
+    "gmpi_mpi_render_shared_backward_launch",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -78,6 +80,15 @@ class GmpiRenderParams(ctypes.Structure):
         ("rgb_out", ctypes.c_void_p), ("depth_out", ctypes.c_void_p), ("transmittance_out", ctypes.c_void_p),
         ("status", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+class GmpiSharedColor(ctypes.Structure):
+    """Field-for-field mirror of `struct GmpiSharedColor` in include/gmpi_render.h."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("rgb", ctypes.c_void_p), ("rgb_stride", ctypes.c_int64 * 3),
+        ("background", ctypes.c_void_p), ("background_stride", ctypes.c_int64 * 3),
     ]
 
 
@@ -176,6 +187,12 @@ def load_library():
                                                        ctypes.POINTER(ctypes.c_int64), vp]
     lib.gmpi_mpi_render_geometry_backward_ex_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gmpi_mpi_render_shared_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shared_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp]
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    lib.gmpi_mpi_render_shared_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shared_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp,
+                                                           vp, i64p, vp, i64p, vp, i64p, vp]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int

@@ -1,6 +1,7 @@
 // gmpi_abi.hip -- the extern "C" entry points declared in include/gmpi_render.h, plus the small
 // auxiliary kernels (diagnostics, exhaustive range check, uint8 frame epilogue).
 #include "gmpi_device.hpp"
+#include "gmpi_shared.hpp"
 
 #include "../../include/gmpi_render.h"
 
@@ -24,6 +25,8 @@ uint32_t* band_gate_words(const KParams& p, int dtype);                     // r
 int band_pixels_wide(int dtype);                                            // render_band.hip
 uint64_t backward_gather_workspace_bytes(const KParams& p);                 // render_backward_gather.hip
 uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
+hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared.hip
+hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream);   // render_shared.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 
@@ -480,6 +483,73 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, 
     }
     return hip_rc(launch_backward_geometry(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
                                            static_cast<hipStream_t>(stream)));
+}
+
+// shared-colour entries: params->rgba = the alpha planes (rgba_stride[2] ignored); checks of to_kparams + the GmpiSharedColor struct
+static int to_shared(const GmpiRenderParams* params, const GmpiSharedColor* shared, bool need_outputs, KParams& p, SharedK& sh) {
+    if (params == nullptr || shared == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams) || shared->struct_size != sizeof(GmpiSharedColor)) return GMPI_E_ABI;
+    GmpiRenderParams q = *params;
+    q.rgba_stride[2] = 1;   // (ignored: the alpha tensor has one channel)
+    const int rc = to_kparams(&q, p, need_outputs, true);
+    if (rc != GMPI_OK) return rc;
+    if (params->variant != GMPI_VARIANT_AUTO && params->variant != GMPI_VARIANT_GATHER) return GMPI_E_VARIANT;
+    if (shared->rgb == nullptr) return GMPI_E_NULL;
+    for (int i = 0; i < 3; ++i)
+        if (shared->rgb_stride[i] < 0 || (shared->background != nullptr && shared->background_stride[i] < 0)) return GMPI_E_STRIDE;
+    if (shared->rgb_stride[2] < q.Wt || shared->rgb_stride[1] == 0) return GMPI_E_STRIDE;
+    if (shared->background != nullptr && (shared->background_stride[2] < q.Wt || shared->background_stride[1] == 0)) return GMPI_E_STRIDE;
+    p.s_chan = 0;   // (render_shared.hip: the 4-channel helpers read the alpha plane four times)
+    sh.rgb = shared->rgb, sh.bg = shared->background;
+    sh.rs_mpi = shared->rgb_stride[0], sh.rs_chan = shared->rgb_stride[1], sh.rs_row = shared->rgb_stride[2];
+    sh.bs_mpi = sh.bg ? shared->background_stride[0] : 0, sh.bs_chan = sh.bg ? shared->background_stride[1] : 0, sh.bs_row = sh.bg ? shared->background_stride[2] : 0;
+    return GMPI_OK;
+}
+
+int gmpi_mpi_render_shared_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, void* stream) {
+    KParams p;
+    SharedK sh;
+    const int rc = to_shared(params, shared, true, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return GMPI_OK;
+    if (p.N > 65535) return GMPI_E_SHAPE;   // the view index is grid.z
+    return hip_rc(launch_shared(p, params->rgba_dtype, sh, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb_out, const float* grad_depth,
+                                           const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride, float* grad_alpha,
+                                           const int64_t* grad_alpha_stride, float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    KParams p;
+    SharedK sh;
+    const int rc = to_shared(params, shared, false, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (grad_rgb_out == nullptr) return GMPI_E_NULL;
+    if (grad_shared_rgb == nullptr && grad_alpha == nullptr && grad_background == nullptr) return GMPI_E_NULL;
+    if (grad_background != nullptr && sh.bg == nullptr) return GMPI_E_NULL;
+    if ((grad_shared_rgb != nullptr && grad_shared_rgb_stride == nullptr) || (grad_alpha != nullptr && grad_alpha_stride == nullptr) ||
+        (grad_background != nullptr && grad_background_stride == nullptr))
+        return GMPI_E_NULL;
+    if (p.N == 0) return GMPI_OK;
+    if (p.N > 65535) return GMPI_E_SHAPE;
+    SharedG g{};
+    g.g_out = grad_rgb_out, g.g_depth = grad_depth, g.g_T = grad_transmittance;
+    g.g_rgb = grad_shared_rgb, g.g_alpha = grad_alpha, g.g_bg = grad_background;
+    auto ok3 = [&](const int64_t* s, int64_t rows_of) {   // MPI stride may be 0 only for one MPI; rows must not overlap
+        return (s[0] > 0 || params->M == 1) && s[0] >= 0 && s[1] > 0 && s[2] >= rows_of;
+    };
+    if (g.g_rgb) {
+        if (!ok3(grad_shared_rgb_stride, p.Wt)) return GMPI_E_STRIDE;
+        g.gr_mpi = grad_shared_rgb_stride[0], g.gr_chan = grad_shared_rgb_stride[1], g.gr_row = grad_shared_rgb_stride[2];
+    }
+    if (g.g_alpha) {
+        if (!ok3(grad_alpha_stride, p.Wt)) return GMPI_E_STRIDE;
+        g.ga_mpi = grad_alpha_stride[0], g.ga_plane = grad_alpha_stride[1], g.ga_row = grad_alpha_stride[2];
+    }
+    if (g.g_bg) {
+        if (!ok3(grad_background_stride, p.Wt)) return GMPI_E_STRIDE;
+        g.gb_mpi = grad_background_stride[0], g.gb_chan = grad_background_stride[1], g.gb_row = grad_background_stride[2];
+    }
+    return hip_rc(launch_shared_backward(p, params->rgba_dtype, sh, g, params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
 }
 
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {

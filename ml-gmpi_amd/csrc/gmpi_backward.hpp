@@ -48,6 +48,26 @@ __device__ __forceinline__ XT total_transmittance(const KParams& p, const float*
     return t;
 }
 
+// One plane of the back-to-front sweep for one pixel: sample, T_k = T_{k+1}/om_k, gradients d_s[4] of the sample
+// (r, g, b, alpha), suffix sum update.
+struct BwdPixel {
+    float gr, gg, gb, gz, dot;
+    XT T;      // T_{k+1} on entry, T_k on exit
+    float S;   // sum_{j>k} w_j q_j on entry, sum_{j>=k} on exit
+    __device__ __forceinline__ void plane(const float (&smp)[4], float s, float (&d_s)[4]) {
+        const float a = smp[3];
+        const float om = (1.0f - a) + 1e-10f;
+        T.m = T.m / om;
+        T.renorm();
+        const float Tk = T.value();
+        const float q = gr * smp[0] + gg * smp[1] + gb * smp[2] + gz * (s * dot);
+        const float w = a * Tk;
+        d_s[0] = gr * w, d_s[1] = gg * w, d_s[2] = gb * w;
+        d_s[3] = Tk * q - S / om;
+        S += w * q;
+    }
+};
+
 template <typename TexT> __device__ __forceinline__ void load_pair(const unsigned char* __restrict__ base, uint32_t byte_off, float& a, float& b) {
     const TexT* __restrict__ q = reinterpret_cast<const TexT*>(base + byte_off);
     a = to_f32(q[0]), b = to_f32(q[1]);

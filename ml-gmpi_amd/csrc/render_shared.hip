@@ -1,0 +1,559 @@
+// render_shared.hip -- the shared-colour layout (gmpi_mpi_render_shared_launch / _backward_launch, include/gmpi_render.h): ONE colour image per MPI,
+// D alpha planes and, optionally, a separate colour image for the last plane -- what GMPI's generator produces before it expands and concatenates
+// (networks_cond_on_pos_enc.py:950-975, gmpi.yml:137-145).  By definition the result is the render of the expanded volume; per plane and channel
+// the arithmetic below IS the volume kernels' (plane_coord, footprint, bilerp, blend; BwdPixel::plane, XT, total_transmittance), so the strict-order
+// forward is bit-identical to render_gather.hip on the expanded volume.
+//
+//   render_shared_kernel           forward, one pixel per lane, any shape / stride / dtype / ray field, every flag
+//   render_shared_backward_kernel  backward, one pixel per lane, 16 global atomics per pixel and plane (the cross-check, and the fall-back for D > 128)
+//   render_shared_tile_kernel      backward, one workgroup per 32 x 16 pixel tile: alpha gradient staged per plane, colour gradient summed in LDS
+//                                  ACROSS the planes (see the kernel)
+//
+// KParams carries the alpha planes in its volume fields: rgba = alpha [M,D,1,Ht,Wt], s_mpi / s_plane / s_row its strides, s_chan = 0 (so that the
+// 4-channel helpers that only want the alpha sample -- total_transmittance -- read the alpha plane four times instead of leaving it).
+#include "gmpi_backward.hpp"
+#include "gmpi_shared.hpp"
+
+namespace gmpi {
+
+// The four taps of one footprint: clamped addresses, weights of taps outside the texture zeroed (gather_sample's rule).
+struct Taps {
+    Footprint f;
+    int xa, xb, ya, yb;
+    bool x0in, x1in, y0in, y1in;
+};
+__device__ __forceinline__ Taps make_taps(float ix, float iy, int Ht, int Wt) {
+    Taps t;
+    t.f = footprint(ix, iy, Ht, Wt);
+    t.x0in = t.f.x0 >= 0 && t.f.x0 <= Wt - 1, t.x1in = t.f.x0 >= -1 && t.f.x0 <= Wt - 2;
+    t.y0in = t.f.y0 >= 0 && t.f.y0 <= Ht - 1, t.y1in = t.f.y0 >= -1 && t.f.y0 <= Ht - 2;
+    if (!(t.x0in && t.y0in)) t.f.nw = 0.0f;
+    if (!(t.x1in && t.y0in)) t.f.ne = 0.0f;
+    if (!(t.x0in && t.y1in)) t.f.sw = 0.0f;
+    if (!(t.x1in && t.y1in)) t.f.se = 0.0f;
+    t.xa = min(max(t.f.x0, 0), Wt - 1), t.xb = min(max(t.f.x0 + 1, 0), Wt - 1);
+    t.ya = min(max(t.f.y0, 0), Ht - 1), t.yb = min(max(t.f.y0 + 1, 0), Ht - 1);
+    return t;
+}
+template <typename TexT, bool STRICT>
+__device__ __forceinline__ float tap_sample(const TexT* __restrict__ ch, int64_t s_row, const Taps& t, bool check_range, uint32_t& bad) {
+    const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
+    const float t_nw = to_f32(ch[oa + t.xa]);
+    const float t_ne = to_f32(ch[oa + t.xb]);
+    const float t_sw = to_f32(ch[ob + t.xa]);
+    const float t_se = to_f32(ch[ob + t.xb]);
+    if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= 2u;
+    return bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, t.f);
+}
+// (r, g, b, alpha) of plane k for one pixel: colour from the shared image (the background on the last plane), alpha from its plane
+template <typename TexT, bool STRICT>
+__device__ __forceinline__ void shared_sample(const TexT* __restrict__ alpha_plane, int64_t a_row, const TexT* __restrict__ col, int64_t c_chan,
+                                              int64_t c_row, const Taps& t, bool check_range, uint32_t& bad, float (&smp)[4]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) smp[c] = tap_sample<TexT, STRICT>(col + c * c_chan, c_row, t, check_range, bad);
+    smp[3] = tap_sample<TexT, STRICT>(alpha_plane, a_row, t, check_range, bad);
+}
+
+// ---- forward: render_gather_kernel with the colour taken from one image -------------------------------------------------------------------------
+template <typename TexT, bool AC, bool STRICT>
+__global__ __launch_bounds__(256) void render_shared_kernel(const KParams p, const SharedK sh) {
+    const int n = blockIdx.z;
+    const int px = blockIdx.x * 64 + threadIdx.x;
+    const int py = blockIdx.y * 4 + threadIdx.y;
+    uint32_t bad = 0;
+    const int m = view_mpi(p, n, bad);
+    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
+    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
+    if (p.status != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {   // mpi.py:70-72, as the gather kernel
+        const float ez0 = p.eye_pos[2];
+        bool behind = false;
+        for (int k = 0; k < p.D; ++k) behind |= !(dhw[3 * k] >= ez0);
+        if (behind) atomicOr(p.status, 4u);
+    }
+    const bool active = px < p.W && py < p.H;
+    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
+    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
+    const float rx = rd[0], ry = rd[HW], rz = rd[2 * HW];
+    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
+    float dot = rx * zx;
+    dot = dot + ry * zy;
+    dot = dot + rz * zz;
+    const int Ht = p.Ht, Wt = p.Wt;
+    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
+    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
+    const bool check_range = (p.flags & (1u << 3)) != 0;
+    const bool check_last = (p.flags & (1u << 2)) != 0;
+    const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
+    const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
+    const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
+
+    Accum A;
+    for (int k = 0; k < p.D; ++k) {
+        const float d = dhw[3 * k + 0], ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
+        float ix, iy, s, u, v;
+        plane_coord<AC>(d - ez, ph, pw, ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
+        if (check_last && k == p.D - 1 && !(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
+        const Taps t = make_taps(ix, iy, Ht, Wt);
+        const bool last_bg = bgi != nullptr && k == p.D - 1;   // uniform
+        float smp[4];
+        shared_sample<TexT, STRICT>(alpha + static_cast<int64_t>(k) * p.s_plane, p.s_row, last_bg ? bgi : rgb, last_bg ? sh.bs_chan : sh.rs_chan,
+                                    last_bg ? sh.bs_row : sh.rs_row, t, check_range, bad, smp);
+        blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
+    }
+    float r = A.r, g = A.g, b = A.b;
+    if (p.flags & (1u << 1)) {
+        r = 2.0f * r - 1.0f;
+        g = 2.0f * g - 1.0f;
+        b = 2.0f * b - 1.0f;
+    }
+    if (active) {
+        float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
+        out[0] = r;
+        out[HW] = g;
+        out[2 * HW] = b;
+        p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
+        if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
+    }
+    report_status(p.status, bad);
+}
+
+// where the colour gradient of plane k goes: the shared image, or the background on the last plane (nullptr: nobody wants it)
+struct ColTarget {
+    float* base;
+    int64_t s_chan, s_row;
+};
+__device__ __forceinline__ ColTarget colour_target(const SharedK& sh, const SharedG& g, int m, int k, int D) {
+    if (sh.bg != nullptr && k == D - 1) return ColTarget{g.g_bg ? g.g_bg + static_cast<int64_t>(m) * g.gb_mpi : nullptr, g.gb_chan, g.gb_row};
+    return ColTarget{g.g_rgb ? g.g_rgb + static_cast<int64_t>(m) * g.gr_mpi : nullptr, g.gr_chan, g.gr_row};
+}
+// one value scattered to the four texels of a footprint (weights of taps outside the texture are zero: those are never written)
+__device__ __forceinline__ void scatter4(float* __restrict__ ch, int64_t s_row, const Footprint& f, float d) {
+    const int64_t oa = static_cast<int64_t>(f.y0) * s_row + f.x0, ob = oa + s_row;
+    if (f.nw != 0.0f) atomicAdd(ch + oa, d * f.nw);
+    if (f.ne != 0.0f) atomicAdd(ch + oa + 1, d * f.ne);
+    if (f.sw != 0.0f) atomicAdd(ch + ob, d * f.sw);
+    if (f.se != 0.0f) atomicAdd(ch + ob + 1, d * f.se);
+}
+
+// what a pixel of the backward starts from
+struct BwdSetup {
+    float rx, ry, rz, dot, gr, gg, gb, gz;
+};
+__device__ __forceinline__ BwdSetup bwd_setup(const KParams& p, const SharedG& g, int n, int64_t pix, bool active) {
+    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
+    BwdSetup q;
+    q.rx = rd[0], q.ry = rd[HW], q.rz = rd[2 * HW];
+    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
+    q.dot = q.rx * zx;
+    q.dot = q.dot + q.ry * zy;
+    q.dot = q.dot + q.rz * zz;
+    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1
+    const float* __restrict__ go = g.g_out + static_cast<int64_t>(n) * 3 * HW + pix;
+    q.gr = active ? scale * go[0] : 0.0f, q.gg = active ? scale * go[HW] : 0.0f, q.gb = active ? scale * go[2 * HW] : 0.0f;
+    q.gz = (active && g.g_depth) ? g.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
+    return q;
+}
+
+// ---- backward, one pixel per lane: render_backward_kernel's sweep, three destinations --------------------------------------------------------
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_shared_backward_kernel(const KParams p, const SharedK sh, const SharedG g) {
+    const int n = blockIdx.z;
+    const int px = blockIdx.x * 64 + threadIdx.x;
+    const int py = blockIdx.y * 4 + threadIdx.y;
+    if (px >= p.W || py >= p.H) return;
+    uint32_t unused = 0;
+    const int m = view_mpi(p, n, unused);
+    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
+    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
+    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const int64_t pix = static_cast<int64_t>(py) * p.W + px;
+    const BwdSetup q = bwd_setup(p, g, n, pix, true);
+    const int Ht = p.Ht, Wt = p.Wt;
+    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
+    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
+    const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
+    const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
+    const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
+    float* __restrict__ ga = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
+
+    const float t_fwd = p.T_out ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 0.0f;
+    BwdPixel bp{q.gr, q.gg, q.gb, q.gz, q.dot,
+                total_transmittance<TexT, AC>(p, dhw, alpha, t_fwd, p.T_out != nullptr, ex, ey, ez, q.rx, q.ry, q.rz, cx, cy), 0.0f};
+    if (g.g_T) bp.S = g.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
+    for (int k = p.D - 1; k >= 0; --k) {
+        float ix, iy, s, u, v;
+        plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, q.rx, q.ry, q.rz, cx, cy, ix, iy, s, u, v);
+        const Taps t = make_taps(ix, iy, Ht, Wt);
+        const bool last_bg = bgi != nullptr && k == p.D - 1;
+        float smp[4], d_s[4];
+        shared_sample<TexT, false>(alpha + static_cast<int64_t>(k) * p.s_plane, p.s_row, last_bg ? bgi : rgb, last_bg ? sh.bs_chan : sh.rs_chan,
+                                   last_bg ? sh.bs_row : sh.rs_row, t, false, unused, smp);
+        bp.plane(smp, s, d_s);
+        const ColTarget ct = colour_target(sh, g, m, k, p.D);
+        if (ct.base != nullptr) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) scatter4(ct.base + c * ct.s_chan, ct.s_row, t.f, d_s[c]);
+        }
+        if (ga != nullptr) scatter4(ga + static_cast<int64_t>(k) * g.ga_plane, g.ga_row, t.f, d_s[3]);
+    }
+}
+
+// ---- backward, one workgroup per pixel tile ------------------------------------------------------------------------------------------------
+// A 32 x 16 pixel tile touches a small texel box on every plane (the corner argument of render_lds.hip / render_backward.hip).
+//
+// ALPHA: as the volume kernels do it -- the 4 adds of a pixel go to a copy of the plane's box in LDS (64-bit fixed point, scaled per plane to the
+// tile's largest |d alpha|: that gradient holds S / om and has no bound known in advance), the box is flushed with one global atomic per texel.
+// Two boxes alternate, so that the flush of plane t + 1 and the scatter of plane t need no barrier between them: ONE barrier per plane, and that
+// barrier orders LDS only (lds_only_barrier); the taps of plane t - 1 are fetched before plane t is scattered.
+//
+// COLOUR, the point of this kernel: every plane's colour gradient belongs to the same image, so it is summed in LDS across ALL planes, in a window of
+// kCW x kCH texels x 3 channels.  The window does NOT hold the union of the tile's per-plane boxes: the boxes drift over the planes by parallax -- with
+// the FFHQ geometry (planes 0.2473 wide) 1.1 / 1.7 / 3.3 texels per plane in x and 0.5 / 1.1 / 2.3 in y on average at 256^2 / 512^2 / 1024^2, 30-100 texels
+// over 32 planes against 29 x 13 texels of slack around a 35 x 19 box; and the last plane is a larger background plane whose box lies elsewhere.  So when the
+// next plane's box leaves the window, the window is flushed and re-anchored with the box at the end it drifts away from, so that the window's whole slack
+// lies ahead (the direction is taken from the boxes of the two ends of the sweep).  Colour flushes per tile (tools/shared_window_replay.py, 32 planes, the
+// poses tools/time_shared_color.py draws): 2.8 / 3.9 / 6.1 on average at 256^2 / 512^2 / 1024^2 (max 4 / 7 / 13) instead of 32 per-plane flushes; at the
+// 2-sigma corner of the pose range 6.6 / 10.8 / 18.1 (max 31 at 1024^2: one per plane).  A plane whose own box does not fit the alpha
+// box (strong minification, degenerate rays) scatters straight to global memory, both gradients, as in render_backward.hip.
+//
+// FIXED POINT of the colour window.  The scale cannot follow the planes; it is fixed per tile before the sweep from M = max over the tile's pixels
+// of max(|gR|, |gG|, |gB|) (OUT_PM1's factor 2 included).  A term is gC w_k weight with w_k = a_k T_k <= 1 (alpha in [0, 1]: T_k <= (1 + 1e-10)^k) and a
+// bilinear weight <= 1, so |term| <= M < 2^(e + 1), e = floor(log2 M).  Scaled by 2^(40 - e) a term is below 2^41.  Terms that can meet in one cell: a pixel
+// adds each plane's sample to four DIFFERENT texels, so at most one term per pixel, plane and channel: 512 D <= 2^9 x 2^7 = 2^16 (D <= 128 here).
+// |sum| < 2^57: 6 bits to spare in a signed 64-bit word.  The spare bits matter: a volume outside [0, 1] (range check off) can have w_k > 1; a lane whose
+// scaled gradient reaches 2^42 -- or is not finite -- therefore scatters that plane's colour straight to global memory, which keeps every staged
+// term below 2^42 and the sum below 2^58 whatever the inputs.  Resolution: 2^-41 M per add (round to nearest) -- finer than one fp32 atomic add's 2^-24 of
+// the running sum.  Integer sums are exact and order-independent; the only fp32 rounding of the staged part is the conversion at the flush.
+// (Plain fp32 LDS adds were not shipped: ds_add_f32 retires ~0.2 T lane-adds/s against ~9 T for ds_add_u64 on this part -- tools/ubench/lds_atomic_rate.hip,
+// render_backward.hip.)
+constexpr int kSTW = 32, kSTH = 16, kSThreads = kSTW * kSTH;
+constexpr int kSAP = 56, kSAR = 27;            // alpha box: pitch, rows (64-bit words; two boxes of 11.8 KB)
+constexpr int kCW = 64, kCH = 32;              // colour window (3 channels of 64-bit words: 48 KB)
+constexpr int kSPlanes = 128;                  // planes a tile kernel launch can take (its tables)
+constexpr int kSAlphaBits = 40, kSColBits = 40;   // largest staged term < 2^41 (to_fix takes |w| < 2^43)
+
+// Workgroup barrier that orders LDS only (render_backward.hip's lds_barrier): `__syncthreads()` is a fence over every address space and drains vmcnt,
+// i.e. every plane would wait for the flush's global atomics and for the next plane's tap loads.  Between the planes only LDS state is shared.
+__device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+__device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {   // every lane enabled
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));
+    return v;
+}
+__device__ __forceinline__ uint32_t abs_bits(float v) { return (v != v) ? 0x7fc00000u : __float_as_uint(fabsf(v)); }   // orders like the magnitude; NaN on top
+// round to nearest (floor(x + 0.5)) in one instruction, as render_backward.hip: the staged sums must not be biased
+__device__ __forceinline__ int cvt_rpi_i32(float x) {
+    int r;
+    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+// fp32 -> 64-bit fixed point without a trip through fp64 (a double conversion and an f64 -> i64 expansion per add were most of the scatter's VALU
+// work): w = v scale (a power of two: exact), |w| < 2^43;  hi = RN(w / 4096) fits 32 bits, lo = w - 4096 hi is exact (one FMA: w has 24 significant
+// bits) and |lo| <= 2048;  the word is 4096 hi + RN(lo) (one v_mad_i64_i32): w rounded to the nearest integer.
+__device__ __forceinline__ unsigned long long to_fix(float v, float scale) {
+    const float w = v * scale;
+    const int hi = cvt_rpi_i32(w * (1.0f / 4096.0f));
+    const int lo = cvt_rpi_i32(__builtin_fmaf(-static_cast<float>(hi), 4096.0f, w));
+    return static_cast<unsigned long long>(static_cast<long long>(hi) * 4096ll + static_cast<long long>(lo));
+}
+
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KParams p, const SharedK sh, const SharedG g, const int tiles_x) {
+    __shared__ int4 box[kSPlanes];        // bx0, by0, nx (<= 0: not staged), ny
+    __shared__ uint32_t gmax[kSPlanes];   // per plane: largest |d alpha| of the tile, fp32 bits
+    __shared__ uint32_t cmax;             // largest |gC| of the tile, fp32 bits
+    __shared__ unsigned long long acc_a[2][kSAP * kSAR];
+    __shared__ unsigned long long acc_c[3 * kCW * kCH];
+    const int tid = threadIdx.x;
+    const int n = blockIdx.y;
+    const int n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
+    const int tile = xcd_item_per_group(static_cast<int>(blockIdx.x), n_tiles, n_tiles);
+    if (tile >= n_tiles) return;   // (whole workgroup: the grid is padded to a multiple of 8)
+    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+    const int px = txi * kSTW + (tid % kSTW), py = tyi * kSTH + (tid / kSTW);
+    const bool active = px < p.W && py < p.H;
+    uint32_t unused = 0;
+    const int m = view_mpi(p, n, unused);
+    const int D = p.D;
+    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * D * 3;
+    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
+    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
+    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
+    const BwdSetup q = bwd_setup(p, g, n, pix, active);
+    const int Ht = p.Ht, Wt = p.Wt;
+    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
+    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
+    const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
+    const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
+    const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
+    float* __restrict__ ga = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
+
+    for (int i = tid; i < 2 * kSAP * kSAR; i += kSThreads) (&acc_a[0][0])[i] = 0ull;
+    for (int i = tid; i < 3 * kCW * kCH; i += kSThreads) acc_c[i] = 0ull;
+    if (tid == 0) cmax = 0u;
+
+    // ---- per-plane texel boxes of the tile (from its four corner pixels) -----------------------------------------------------------------------
+    const int cx0 = txi * kSTW, cx1 = min(cx0 + kSTW - 1, p.W - 1);
+    const int cy0 = tyi * kSTH, cy1 = min(cy0 + kSTH - 1, p.H - 1);
+    for (int k = tid; k < D; k += kSThreads) {
+        const float zdiff = dhw[3 * k] - ez, ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
+        float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
+        bool finite = true;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int64_t qq = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
+            float ix, iy, s, u, v;
+            plane_coord<AC>(zdiff, ph, pw, ex, ey, rdv[qq], rdv[HW + qq], rdv[2 * HW + qq], cx, cy, ix, iy, s, u, v);
+            finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
+            mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
+        }
+        int4 bb = make_int4(0, 0, 0, 0);
+        if (finite) {
+            const float eps = 1.0f / 64;
+            bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
+            bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
+            if (bb.z > kSAP || bb.w > kSAR) bb.z = 0;
+        }
+        box[k] = bb;
+        gmax[k] = 0u;
+    }
+    __syncthreads();   // zero fills, tables, cmax = 0
+    {   // the tile's largest |gC|: one LDS atomic per wave
+        const uint32_t wm = wave_max_bits(max(abs_bits(q.gr), max(abs_bits(q.gg), abs_bits(q.gb))));
+        if ((tid & 63) == 0 && wm != 0u) atomicMax(&cmax, wm);
+    }
+
+    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
+    BwdPixel bp{q.gr, q.gg, q.gb, q.gz, q.dot, XT{1.0f, 0}, 0.0f};
+    if (active) bp.T = total_transmittance<TexT, AC>(p, dhw, alpha, t_fwd, p.T_out != nullptr, ex, ey, ez, q.rx, q.ry, q.rz, cx, cy);
+    if (active && g.g_T) bp.S = g.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
+
+    struct Grad { float d[4]; Footprint f; };
+    struct Tap { float s; Footprint f; float v[16]; };   // v: per channel (r, g, b, alpha) the taps nw, ne, sw, se
+    // plane k for this pixel, first half: coordinates and the 16 tap loads (issued one plane ahead of their use: the scatter of the plane before
+    // runs while they are in flight)
+    auto fetch = [&](int k, Tap& tp) {
+        tp.s = 0.0f;
+        tp.f = Footprint{-2, -2, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tp.v[i] = 0.0f;
+        if (active) {
+            float ix, iy, u, v;
+            plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, q.rx, q.ry, q.rz, cx, cy, ix, iy, tp.s, u, v);
+            const Taps t = make_taps(ix, iy, Ht, Wt);
+            tp.f = t.f;
+            const bool last_bg = bgi != nullptr && k == D - 1;
+            const TexT* __restrict__ col = last_bg ? bgi : rgb;
+            const int64_t c_chan = last_bg ? sh.bs_chan : sh.rs_chan, c_row = last_bg ? sh.bs_row : sh.rs_row;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const TexT* __restrict__ ch = c < 3 ? col + c * c_chan : alpha + static_cast<int64_t>(k) * p.s_plane;
+                const int64_t s_row = c < 3 ? c_row : p.s_row;
+                const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
+                tp.v[4 * c + 0] = to_f32(ch[oa + t.xa]), tp.v[4 * c + 1] = to_f32(ch[oa + t.xb]);
+                tp.v[4 * c + 2] = to_f32(ch[ob + t.xa]), tp.v[4 * c + 3] = to_f32(ch[ob + t.xb]);
+            }
+        }
+    };
+    // second half: bilinear samples (tap_sample's arithmetic), BwdPixel::plane, the tile maximum of |d alpha|
+    auto grads = [&](int k, const Tap& tp, Grad& G) {
+        G.d[0] = G.d[1] = G.d[2] = G.d[3] = 0.0f;
+        G.f = tp.f;
+        if (active) {
+            float smp[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) smp[c] = bilerp<false>(tp.v[4 * c + 0], tp.v[4 * c + 1], tp.v[4 * c + 2], tp.v[4 * c + 3], tp.f);
+            bp.plane(smp, tp.s, G.d);
+        }
+        const uint32_t wm = wave_max_bits(abs_bits(G.d[3]));
+        if ((tid & 63) == 0 && wm != 0u) atomicMax(&gmax[k], wm);
+    };
+
+    // the colour window: anchor (texel of cell 0,0), the rows in use since the last flush.  All workgroup-uniform.
+    int wx0 = 0, wy0 = 0, wrow0 = kCH, wrow1 = 0;
+    bool w_open = false;
+    float cscale = 0.0f, cinv = 0.0f;
+    bool cstage = false;
+    // window -> global memory (one atomic per texel and channel, a wave = 64 consecutive texels of one row) and reset
+    auto flush_colour = [&](const ColTarget& ct) {
+        if (wrow1 > wrow0 && ct.base != nullptr) {
+            const int rows = wrow1 - wrow0;
+            for (int i = tid; i < rows * 3 * kCW; i += kSThreads) {
+                const int line = i / kCW, x = i - line * kCW;      // line = (row, channel)
+                const int row = wrow0 + line / 3, c = line - (line / 3) * 3;
+                unsigned long long* __restrict__ src = acc_c + (c * kCH + row) * kCW + x;
+                const long long v = static_cast<long long>(*src);
+                const int gx = wx0 + x, gy = wy0 + row;
+                if (v != 0) {
+                    *src = 0ull;
+                    if (gx >= 0 && gx < Wt && gy >= 0 && gy < Ht)   // (a cell outside the texture only ever receives zero weights: belt and braces)
+                        atomicAdd(ct.base + c * ct.s_chan + static_cast<int64_t>(gy) * ct.s_row + gx, static_cast<float>(static_cast<double>(v)) * cinv);
+                }
+            }
+        }
+        wrow0 = kCH, wrow1 = 0;
+    };
+    // scatter of one plane: alpha into its box (per-plane scale), colour into the window (tile scale); what is not staged goes straight to global memory
+    auto scatter = [&](int k, const Grad& G, const ColTarget& ct, bool col_staged) {
+        const int4 bb = box[k];
+        const uint32_t mb = gmax[k];
+        const Footprint& f = G.f;
+        const bool any_w = f.nw != 0.0f || f.ne != 0.0f || f.sw != 0.0f || f.se != 0.0f;
+        const int lx = f.x0 - bb.x, ly = f.y0 - bb.y;
+        const bool in_box = bb.z > 0 && lx >= 0 && ly >= 0 && lx + 1 < bb.z && ly + 1 < bb.w;
+        if (ga != nullptr && mb != 0u && any_w) {
+            const bool staged = in_box && mb < 0x7f800000u;
+            if (staged) {
+                const int shf = min(kSAlphaBits - (static_cast<int>(mb >> 23) - 127), 126);
+                const float sc = __builtin_amdgcn_ldexpf(1.0f, shf);
+                unsigned long long* __restrict__ l0 = &acc_a[k & 1][ly * kSAP + lx];
+                const float d = G.d[3];
+                if (f.nw != 0.0f) atomicAdd(l0, to_fix(d * f.nw, sc));
+                if (f.ne != 0.0f) atomicAdd(l0 + 1, to_fix(d * f.ne, sc));
+                if (f.sw != 0.0f) atomicAdd(l0 + kSAP, to_fix(d * f.sw, sc));
+                if (f.se != 0.0f) atomicAdd(l0 + kSAP + 1, to_fix(d * f.se, sc));
+            } else {
+                scatter4(ga + static_cast<int64_t>(k) * g.ga_plane, g.ga_row, f, G.d[3]);
+            }
+        }
+        if (ct.base != nullptr && any_w) {
+            const int wx = f.x0 - wx0, wy = f.y0 - wy0;
+            const float dm = fmaxf(fmaxf(fabsf(G.d[0]), fabsf(G.d[1])), fabsf(G.d[2]));
+            // (dm * cscale < 2^42 is false for NaN; in_box implies the footprint lies inside the window, the second test keeps wild coordinates out)
+            const bool staged = col_staged && in_box && wx >= 0 && wy >= 0 && wx + 1 < kCW && wy + 1 < kCH && (dm * cscale < 4398046511104.0f);
+            if (staged) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    unsigned long long* __restrict__ l0 = acc_c + (c * kCH + wy) * kCW + wx;
+                    const float d = G.d[c];
+                    if (f.nw != 0.0f) atomicAdd(l0, to_fix(d * f.nw, cscale));
+                    if (f.ne != 0.0f) atomicAdd(l0 + 1, to_fix(d * f.ne, cscale));
+                    if (f.sw != 0.0f) atomicAdd(l0 + kCW, to_fix(d * f.sw, cscale));
+                    if (f.se != 0.0f) atomicAdd(l0 + kCW + 1, to_fix(d * f.se, cscale));
+                }
+            } else if (dm != 0.0f) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) scatter4(ct.base + c * ct.s_chan, ct.s_row, f, G.d[c]);
+            }
+        }
+    };
+    // box of plane k -> global memory and reset (the plane's own scale)
+    auto flush_alpha = [&](int k) {
+        const int4 bb = box[k];
+        const uint32_t mb = gmax[k];
+        if (!(ga != nullptr && bb.z > 0 && mb != 0u && mb < 0x7f800000u)) return;
+        const int shf = min(kSAlphaBits - (static_cast<int>(mb >> 23) - 127), 126);
+        const float inv = __builtin_amdgcn_ldexpf(1.0f, -shf);
+        float* __restrict__ gp = ga + static_cast<int64_t>(k) * g.ga_plane;
+        for (int i = tid; i < bb.w * kSAP; i += kSThreads) {
+            const int row = i / kSAP, x = i - row * kSAP;
+            unsigned long long* __restrict__ src = &acc_a[k & 1][i];
+            const long long v = static_cast<long long>(*src);
+            const int gx = bb.x + x, gy = bb.y + row;
+            if (v != 0) {
+                *src = 0ull;
+                if (gx >= 0 && gx < Wt && gy >= 0 && gy < Ht)
+                    atomicAdd(gp + static_cast<int64_t>(gy) * g.ga_row + gx, static_cast<float>(static_cast<double>(v)) * inv);
+            }
+        }
+    };
+
+    // ---- back-to-front sweep, software-pipelined by one plane -----------------------------------------------------------------------------------
+    Grad G;
+    Tap tp;
+    fetch(D - 1, tp);
+    grads(D - 1, tp, G);
+    __syncthreads();   // cmax, gmax[D - 1] complete
+    {
+        const uint32_t cm = cmax;
+        cstage = cm != 0u && cm < 0x7f800000u;
+        const int shf = min(kSColBits - (static_cast<int>(cm >> 23) - 127), 126);
+        cscale = cstage ? __builtin_amdgcn_ldexpf(1.0f, shf) : 0.0f, cinv = cstage ? __builtin_amdgcn_ldexpf(1.0f, -shf) : 0.0f;
+    }
+    const int4 box_front = box[0];
+    for (int k = D - 1; k >= 0; --k) {
+        const ColTarget ct = colour_target(sh, g, m, k, D);
+        const int4 bb = box[k];
+        const bool want_window = cstage && ct.base != nullptr && bb.z > 0;   // uniform
+        if (want_window) {
+            const bool inside = w_open && bb.x >= wx0 && bb.y >= wy0 && bb.x + bb.z <= wx0 + kCW && bb.y + bb.w <= wy0 + kCH;
+            if (!inside) {
+                if (w_open) {   // the previous planes' adds are complete (the barrier that ended the last iteration)
+                    flush_colour(colour_target(sh, g, m, k + 1, D));
+                    lds_only_barrier();
+                }
+                // re-anchor: the box at the end of the window it drifts away from (boxes of nearer planes: towards box_front)
+                wx0 = (box_front.z > 0 && box_front.x < bb.x) ? bb.x + bb.z - kCW : bb.x;
+                wy0 = (box_front.z > 0 && box_front.y < bb.y) ? bb.y + bb.w - kCH : bb.y;
+                w_open = true;
+            }
+            wrow0 = min(wrow0, bb.y - wy0), wrow1 = max(wrow1, bb.y + bb.w - wy0);
+        }
+        if (k > 0) fetch(k - 1, tp);   // (in flight across the scatter)
+        scatter(k, G, ct, want_window);
+        if (k > 0) grads(k - 1, tp, G);
+        if (k + 1 < D) flush_alpha(k + 1);
+        lds_only_barrier();   // plane k's adds and gmax[k - 1] complete; box (k + 1) & 1 is clean for plane k - 1
+        // the last plane's colour belongs to the background image: its own flush (the window stays where it is)
+        if (k == D - 1 && bgi != nullptr && w_open && D > 1) {
+            flush_colour(ct);
+            lds_only_barrier();
+        }
+    }
+    flush_alpha(0);
+    if (w_open) flush_colour(colour_target(sh, g, m, 0, D));
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------------------
+template <typename TexT>
+static hipError_t launch_shared_t(const KParams& p, const SharedK& sh, hipStream_t stream) {
+    const dim3 block(64, 4);
+    const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
+    const bool ac = p.flags & 1u, strict = p.flags & (1u << 4);
+    if (ac && strict) hipLaunchKernelGGL((render_shared_kernel<TexT, true, true>), grid, block, 0, stream, p, sh);
+    else if (ac) hipLaunchKernelGGL((render_shared_kernel<TexT, true, false>), grid, block, 0, stream, p, sh);
+    else if (strict) hipLaunchKernelGGL((render_shared_kernel<TexT, false, true>), grid, block, 0, stream, p, sh);
+    else hipLaunchKernelGGL((render_shared_kernel<TexT, false, false>), grid, block, 0, stream, p, sh);
+    return hipGetLastError();
+}
+
+hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream) {
+    switch (dtype) {
+        case 0: return launch_shared_t<float>(p, sh, stream);
+        case 1: return launch_shared_t<bf16_t>(p, sh, stream);
+        default: return launch_shared_t<f16_t>(p, sh, stream);
+    }
+}
+
+bool shared_tile_supports(const KParams& p) { return p.D <= kSPlanes; }
+
+template <typename TexT>
+static hipError_t launch_shared_backward_t(const KParams& p, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream) {
+    const bool ac = p.flags & 1u;
+    if (tiles) {
+        const int tiles_x = (p.W + kSTW - 1) / kSTW, n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
+        const dim3 grid(xcd_grid_per_group(n_tiles, n_tiles), p.N);
+        if (ac) hipLaunchKernelGGL((render_shared_tile_kernel<TexT, true>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x);
+        else hipLaunchKernelGGL((render_shared_tile_kernel<TexT, false>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x);
+    } else {
+        const dim3 block(64, 4);
+        const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
+        if (ac) hipLaunchKernelGGL((render_shared_backward_kernel<TexT, true>), grid, block, 0, stream, p, sh, g);
+        else hipLaunchKernelGGL((render_shared_backward_kernel<TexT, false>), grid, block, 0, stream, p, sh, g);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream) {
+    tiles = tiles && shared_tile_supports(p);
+    switch (dtype) {
+        case 0: return launch_shared_backward_t<float>(p, sh, g, tiles, stream);
+        case 1: return launch_shared_backward_t<bf16_t>(p, sh, g, tiles, stream);
+        default: return launch_shared_backward_t<f16_t>(p, sh, g, tiles, stream);
+    }
+}
+
+}  // namespace gmpi

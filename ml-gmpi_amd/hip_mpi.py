@@ -409,7 +409,8 @@ class MPI(nn.Module):
                      view_to_mpi: Optional[torch.Tensor] = None, check_last_plane: bool = False,
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
-                     _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False):
+                     _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
+                     _shared=None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -426,7 +427,18 @@ class MPI(nn.Module):
         if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
-        if torch.is_grad_enabled() and not _in_autograd_fn and (
+        if _shared is not None and torch.is_grad_enabled() and not _in_autograd_fn:
+            # shared-colour layout (render_views_shared): rgba is the alpha tensor, _shared = (rgb, background or None)
+            if self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
+                raise NotImplementedError("the shared-colour render has no gradient w.r.t. the plane geometry or the camera tensors "
+                                          "(geometry_grad=True): render the expanded volume (expand_shared_color) with render_views for that")
+            if rgba.requires_grad or any(t is not None and t.requires_grad for t in _shared):
+                kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
+                              out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
+                              status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
+                color, depth, T, st = _SharedRenderFunction.apply(_shared[0], rgba, _shared[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
+                return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
+        if _shared is None and torch.is_grad_enabled() and not _in_autograd_fn and (
                 rgba.requires_grad or (self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)))):
             # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
             kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
@@ -448,6 +460,17 @@ class MPI(nn.Module):
         if rgba.stride(4) != 1 or any(s < 0 for s in rgba.stride()):
             rgba = rgba.contiguous()
         M, D, _, Ht, Wt = rgba.shape
+        sh_rgb = sh_bg = None
+        if _shared is not None:   # one storage dtype for the three tensors, innermost stride 1
+            for t in _shared:
+                if t is not None and t.dtype != rgba_in.dtype:   # (no quiet cast: an fp32 colour image next to bf16 alphas would be rounded unseen)
+                    raise TypeError(f"shared-colour render: rgb, alpha and background must have one storage dtype, got {t.dtype} next to alpha in {rgba_in.dtype}")
+
+            def _like_alpha(t):
+                t = t.to(dev, rgba.dtype)   # (a dtype the kernels do not store -- float64 -- becomes fp32 with the alpha tensor)
+                return t.contiguous() if t.stride(3) != 1 or any(s_ < 0 for s_ in t.stride()) else t
+            sh_rgb = _like_alpha(_shared[0])
+            sh_bg = None if _shared[1] is None else _like_alpha(_shared[1])
         ray_dir, eye_pos, z_dir, dhw = (_f32_on(t, dev) for t in (ray_dir, eye_pos, z_dir, dhw))
         N, _, H, W = ray_dir.shape
         assert eye_pos.shape == (N, 3) and z_dir.shape == (N, 3), (eye_pos.shape, z_dir.shape, N)
@@ -520,6 +543,8 @@ class MPI(nn.Module):
             p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
             p.flags = flags
             p.variant = _lib.VARIANTS[self.variant]
+            if _shared is not None:   # (the shared-colour entries know AUTO and GATHER)
+                p.variant = _lib.VARIANT_GATHER if self.variant == "gather" else _lib.VARIANT_AUTO
             p.rgba_dtype = _DTYPES[rgba.dtype]
             p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W = N, M, D, Ht, Wt, H, W
             p.views_per_mpi = max(uniform, 1)
@@ -532,22 +557,42 @@ class MPI(nn.Module):
             p.transmittance_out = T.data_ptr() if T is not None else None
             p.status = status.data_ptr()
             stream = torch.cuda.current_stream(dev).cuda_stream if on_device else 0
-            if on_device:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
+            if on_device and _shared is None:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
                 need = int(lib.gmpi_render_workspace_bytes(ctypes.byref(p)))
                 if need:
                     ws = _workspace(dev, stream, need)
                     p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
             with _on_device(dev if on_device else None):
                 ran_full = False
-                if self.range_check == "full" and self._full_check_needed(rgba_in):
+                if _shared is not None:
+                    sc = _lib.GmpiSharedColor()
+                    sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
+                    sc.rgb = sh_rgb.data_ptr()
+                    for i, s_ in enumerate((sh_rgb.stride(0), sh_rgb.stride(1), sh_rgb.stride(2))):
+                        sc.rgb_stride[i] = s_
+                    if sh_bg is not None:
+                        sc.background = sh_bg.data_ptr()
+                        for i, s_ in enumerate((sh_bg.stride(0), sh_bg.stride(1), sh_bg.stride(2))):
+                            sc.background_stride[i] = s_
+                    if self.range_check == "full":   # the exhaustive pass over the three tensors (never cached: three identities to track)
+                        for t in (rgba, sh_rgb, sh_bg):
+                            if t is not None:
+                                t = t if t.is_contiguous() else t.contiguous()
+                                _lib.check(lib.gmpi_rgba_range_check_launch(t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream),
+                                           "gmpi_rgba_range_check_launch")
+                    _lib.check(lib.gmpi_mpi_render_shared_launch(ctypes.byref(p), ctypes.byref(sc), stream), "gmpi_mpi_render_shared_launch")
+                elif self.range_check == "full" and self._full_check_needed(rgba_in):
                     vol = rgba if rgba.is_contiguous() else rgba.contiguous()
                     _lib.check(lib.gmpi_rgba_range_check_launch(vol.data_ptr(), p.rgba_dtype, vol.numel(),
                                                                 status.data_ptr(), stream), "gmpi_rgba_range_check_launch")
                     ran_full = True
-                _lib.check(lib.gmpi_mpi_render_launch(ctypes.byref(p), stream), "gmpi_mpi_render_launch")
+                if _shared is None:
+                    _lib.check(lib.gmpi_mpi_render_launch(ctypes.byref(p), stream), "gmpi_mpi_render_launch")
             res = dict(color=color, depth=depth, T=T, status=status)
             if _in_autograd_fn:  # what the backward needs to rebuild the launch
                 res["_bwd"] = (p, (rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi))
+                if _shared is not None:
+                    res["_bwd"] += ((sh_rgb, sh_bg),)
             if lag:
                 ring.host_words[slot].copy_(status, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -566,6 +611,25 @@ class MPI(nn.Module):
                 if ran_full:
                     self._full_check_record(rgba_in)   # (read back and clean: the whole volume is in [0, 1])
             return res
+
+    # -- shared-colour layout ----------------------------------------------------------------------------------------------------------
+    def render_views_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
+                            z_dir: torch.Tensor, background: Optional[torch.Tensor] = None, **kwargs):
+        """`render_views` of the volume `expand_shared_color(rgb, alpha, background)` without building it: rgb [M,3,Ht,Wt] colours every plane
+        (all but the last when `background` [M,3,Ht,Wt] is given), alpha [M,D,1,Ht,Wt] may be the view `rgba[:, :, 3:]` of a volume.  Same
+        keyword arguments, returned dict and status handling as `render_views`; under autograd the gradient reaches rgb, alpha and background
+        (gmpi_mpi_render_shared_backward_launch: the colour gradient is summed over the planes on the chip).  variant "gather" forces the
+        one-pixel-per-lane kernels, every other variant lets the library choose.  No gradient w.r.t. the geometry (NotImplementedError with
+        geometry_grad=True and a camera / dhw tensor that requires grad).  The three tensors must have ONE dtype (TypeError otherwise: nothing is
+        cast behind the caller's back).  range_check="full" runs the exhaustive pass over the three tensors in EVERY call (the volume path's
+        "unchanged volume" cache is not kept for three tensors), and that pass reads contiguous memory: a strided alpha view such as
+        `rgba[:, :, 3:]` is copied for it, D planes per call -- use the default "touched" where the no-copy property matters.  The tile
+        backward (every variant but "gather", D <= 128) assumes a pinhole ray field like the other staged kernels; D > 128 takes the
+        one-pixel-per-lane backward, which is several times slower."""
+        from .shared_color import _check
+        _check(rgb, alpha, background)
+        assert "_shared" not in kwargs
+        return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _shared=(rgb, background), **kwargs)
 
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
     def raise_on_status(self, status: torch.Tensor, params=None, keep=None, c2w_mat=None, sphere_c=None):
@@ -739,6 +803,86 @@ class _RenderFunction(torch.autograd.Function):
                         "gmpi_mpi_render_geometry_backward_ex_launch")
             geo = [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
+
+
+class _SharedRenderFunction(torch.autograd.Function):
+    """autograd bridge of the shared-colour render, built like `_RenderFunction`: forward = gmpi_mpi_render_shared_launch, backward =
+    gmpi_mpi_render_shared_backward_launch into zero-filled fp32 gradients of the inputs that need one (the others are passed as NULL and
+    skipped by the kernel).  Saved tensors, private T buffer, unused outputs as None: as there."""
+
+    @staticmethod
+    def forward(ctx, rgb, alpha, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+        kw = dict(kwargs, want_transmittance=True)
+        user_out = kw.get("out") or {}
+        kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # private T
+        res = mpi.render_views(alpha.detach(), dhw, ray_dir, eye_pos, z_dir, _in_autograd_fn=True,
+                               _shared=(rgb.detach(), None if background is None else background.detach()), **kw)
+        p, keep, (rgb_d, bg_d) = res.pop("_bwd")
+        T = res["T"]
+        if kwargs.get("want_transmittance") and user_out.get("T") is not None:
+            user_out["T"].copy_(T)
+        alpha_d, dhw_d, ray_d, eye_d, zd_d, v2m = keep
+        ctx.has_bg, ctx.has_v2m = bg_d is not None, v2m is not None
+        ctx.save_for_backward(alpha_d, rgb_d, dhw_d, ray_d, eye_d, zd_d, T, *([bg_d] if bg_d is not None else []), *([v2m] if v2m is not None else []))
+        ctx.scalars = dict(flags=p.flags, variant=p.variant, rgba_dtype=p.rgba_dtype, N=p.N, M=p.M, D=p.D, Ht=p.Ht, Wt=p.Wt,
+                           H=p.H, W=p.W, views_per_mpi=p.views_per_mpi)
+        ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, alpha, background)]
+        ctx.mark_non_differentiable(res["status"])
+        ctx.set_materialize_grads(False)
+        return res["color"], res["depth"], T, res["status"]
+
+    @staticmethod
+    def backward(ctx, g_color, g_depth, g_T, g_status):
+        lib = _lib.load_library()
+        saved = list(ctx.saved_tensors)
+        alpha, rgb, dhw, ray_dir, eye_pos, z_dir, T = saved[:7]
+        rest = saved[7:]
+        bg = rest.pop(0) if ctx.has_bg else None
+        v2m = rest.pop(0) if ctx.has_v2m else None
+        dev = alpha.device
+        want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
+        if not any(want) or (g_color is None and g_depth is None and g_T is None):
+            return (None,) * 9
+        p = _lib.GmpiRenderParams()
+        p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
+        for k, v in ctx.scalars.items():
+            setattr(p, k, v)
+        p.rgba = alpha.data_ptr()
+        for i, s in enumerate(alpha.stride()):
+            p.rgba_stride[i] = s
+        p.view_to_mpi = v2m.data_ptr() if v2m is not None else None
+        p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
+        p.rgb_out = p.depth_out = p.status = None
+        p.transmittance_out = T.data_ptr()
+        sc = _lib.GmpiSharedColor()
+        sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
+        sc.rgb = rgb.data_ptr()
+        for i in range(3):
+            sc.rgb_stride[i] = rgb.stride(i)
+        if bg is not None:
+            sc.background = bg.data_ptr()
+            for i in range(3):
+                sc.background_stride[i] = bg.stride(i)
+        if g_color is None:
+            g_color = torch.zeros((p.N, 3, p.H, p.W), dtype=torch.float32, device=dev)
+        g_color = g_color.to(torch.float32).contiguous()
+        g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
+        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()   # None: the launch stays on the path without a transmittance gradient
+        shapes = [(p.M, 3, p.Ht, p.Wt), (p.M, p.D, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)]
+        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+
+        def ptr_stride(t, dims):
+            if t is None:
+                return None, None
+            return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
+        (gr, gr_s), (ga, ga_s), (gb, gb_s) = ptr_stride(grads[0], (0, 1, 2)), ptr_stride(grads[1], (0, 1, 3)), ptr_stride(grads[2], (0, 1, 2))
+        with torch.cuda.device(dev):
+            _lib.check(lib.gmpi_mpi_render_shared_backward_launch(
+                ctypes.byref(p), ctypes.byref(sc), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
+                g_T.data_ptr() if g_T is not None else None, gr, gr_s, ga, ga_s, gb, gb_s, torch.cuda.current_stream(dev).cuda_stream),
+                "gmpi_mpi_render_shared_backward_launch")
+        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
+        return out[0], out[1], out[2], None, None, None, None, None, None
 
 
 HipMPI = MPI

@@ -266,18 +266,32 @@ class LightRenderer:
                        "gmpi_light_apply_launch")
         return out, depth, T, shading
 
-    def render(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
-        """batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3] -> shaded MPI [B,D,4,H,W] float32
-        (differentiable w.r.t. batch_mpi)."""
-        if not batch_mpi.is_cuda:
-            raise _lib.GmpiError("LightRenderer.render needs tensors on a ROCm device (no CPU path)")
+    def render_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor,
+                      background: torch.Tensor = None):
+        """`render` for a shared-colour MPI (rgb [B,3,H,W], alpha [B,D,1,H,W], background [B,3,H,W] or None): the shading is one value per
+        texel, the same for every plane, so the shaded MPI is a shared-colour MPI again -- (clip(rgb * shading, 0, 1), alpha, clip(background
+        * shading, 0, 1) or None), colours in float32.  Equal to `render(expand_shared_color(rgb, alpha, background))` split again; the step
+        counter, cur_ka / cur_kd and the torch RNG advance as in `render`.  The depth comes from the differentiable `compute_depth` kernel (one
+        pass over the alpha planes), the rest is image-sized torch: differentiable w.r.t. rgb, alpha and background."""
+        if not alpha.is_cuda:
+            raise _lib.GmpiError("LightRenderer.render_shared needs tensors on a ROCm device (no CPU path)")
+        from .shared_color import _check
+        _check(rgb, alpha, background)
+        dev = alpha.device
+        light_direction = self._next_light(alpha.shape[0])
+        plane_ds = mpi_plane_dhws[:, :1].detach().to(dev)
+        xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach().to(dev, torch.float32)
+        H, W = alpha.shape[-2:]
+        depth = compute_depth(alpha, plane_ds)                                                      # [B,1,H,W] float32
+        blurred = _blur_torch(depth, _blur_matrix(H, self._k1d, dev), _blur_matrix(W, self._k1d, dev))
+        shading = _shading_torch(blurred, xyz_last, light_direction.to(dev, torch.float32), self.cur_ka, self.cur_kd).unsqueeze(1)   # [B,1,H,W]
+        shade = lambda c: torch.clip(c.to(torch.float32) * shading, min=0.0, max=1.0)
+        return shade(rgb), alpha, (None if background is None else shade(background))
+
+    def _next_light(self, B: int) -> torch.Tensor:
+        """One step of the augmentation's schedule: advances `step`, draws the light position on the sphere (consumes the torch RNG exactly as
+        the reference's gen_sphere_path call), sets cur_ka / cur_kd; returns the light direction [B,3] (host tensor)."""
         self.step += 1
-        dev = batch_mpi.device
-        vol = batch_mpi if batch_mpi.dtype in _DTYPES else batch_mpi.float()
-        if vol.stride(4) != 1 or any(s < 0 for s in vol.stride()):
-            vol = vol.contiguous()
-        B = vol.shape[0]
-        # light position on the sphere (consumes the torch RNG exactly as the reference's gen_sphere_path call)
         c2w, _, _ = poses.gen_sphere_path(n_cams=B, sphere_center=self.sphere_center, sphere_r=self.sphere_r,
                                           yaw_mean=self.l_h_mean, yaw_std=self.l_h_std, pitch_mean=self.l_v_mean,
                                           pitch_std=self.l_v_std, n_truncated_stds=2, flag_rnd=True,
@@ -288,6 +302,18 @@ class LightRenderer:
             light_direction = poses._unit(self.sphere_center.reshape(1, 3) - light_pos)  # towards the sphere centre
         cur_ratio = min(1.0, self.step / self.n_grow_iters)
         self.cur_ka, self.cur_kd = cur_ratio * self.ka_max, cur_ratio * self.kd_max
+        return light_direction
+
+    def render(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
+        """batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3] -> shaded MPI [B,D,4,H,W] float32
+        (differentiable w.r.t. batch_mpi)."""
+        if not batch_mpi.is_cuda:
+            raise _lib.GmpiError("LightRenderer.render needs tensors on a ROCm device (no CPU path)")
+        dev = batch_mpi.device
+        vol = batch_mpi if batch_mpi.dtype in _DTYPES else batch_mpi.float()
+        if vol.stride(4) != 1 or any(s < 0 for s in vol.stride()):
+            vol = vol.contiguous()
+        light_direction = self._next_light(vol.shape[0])
         plane_ds = mpi_plane_dhws[:, :1].detach().to(dev)
         xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach()
         if torch.is_grad_enabled() and vol.requires_grad:

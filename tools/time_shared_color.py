@@ -1,0 +1,142 @@
+"""Times the shared-colour layout (one colour image per MPI + D alpha planes + a background image) against the volume path it replaces, through the
+C ABI, with HIP events (medians): at 256^2 x 8, 512^2 x 4 and 1024^2 x 4 with 32 planes in fp32 the whole G-step (forward, zero-fill, backward),
+at 1024^2 x 96 x 4 (fp32, bf16) the forward only.
+
+  baseline  materialise the expanded volume as the generator does (expand + two cat), forward (variant auto), zero-fill of the volume gradient,
+            volume backward (tile kernels), plane sum of the colour gradient (the backward of the generator's expand)
+  shared    forward, zero-fill of the three gradients, shared backward: one-pixel-per-lane kernel ("gather") and tile kernel separately
+
+and the peak device memory of one pass of each (torch.cuda.max_memory_allocated).  Every shape runs in a child process of its own under a time
+limit; the first failure ends the run.  usage: python tools/time_shared_color.py [reps]"""
+import ctypes
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [("256", 8, 32, "f32", 1), ("512", 4, 32, "f32", 1), ("1024", 4, 32, "f32", 1), ("1024", 4, 96, "f32", 0), ("1024", 4, 96, "bf16", 0)]
+
+
+def one(S, B, D, dtype_name, with_backward, reps):
+    import torch
+    sys.path.insert(0, ROOT)
+    import ml_gmpi_amd
+    from ml_gmpi_amd import _lib, expand_shared_color
+    lib = _lib.load_library()
+    dev = torch.device("cuda:0")
+    cs = torch.cuda.current_stream(dev).cuda_stream
+    dtype = {"f32": torch.float32, "bf16": torch.bfloat16}[dtype_name]
+
+    def timed(fn, n=reps):
+        for _ in range(3):
+            fn()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        for e0, e1 in evs:
+            e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return sorted(a.elapsed_time(b) for a, b in evs)[n // 2]   # median
+
+    r = ml_gmpi_amd.make_renderer("FFHQ", n_planes=D, device=dev, on_out_of_plane="raise")
+    r.set_cam(r.cam_fov, S, S)
+    g = torch.Generator(device=dev).manual_seed(7000)
+    rgb = torch.rand((B, 3, S, S), device=dev, generator=g).to(dtype)
+    alpha = torch.rand((B, D, 1, S, S), device=dev, generator=g).to(dtype)
+    bg = torch.rand((B, 3, S, S), device=dev, generator=g).to(dtype)
+    gc = torch.randn((B, 3, S, S), device=dev, generator=g)
+    gd = torch.randn((B, 1, S, S), device=dev, generator=g)
+    torch.manual_seed(3)
+    cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
+    ray, eye, zd = torch.cat(cam[3]), torch.cat(cam[4]), torch.cat(cam[5])
+    dhw = r._dhw_on_device().expand(B, -1, -1).contiguous()
+    kw = dict(views_per_mpi=1, check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True)
+    base_mem = torch.cuda.memory_allocated(dev)
+    row = dict(S=S, B=B, D=D, dtype=dtype_name)
+
+    # ---- baseline: the volume path of the parent commit ------------------------------------------------------------------------------------------
+    torch.cuda.reset_peak_memory_stats(dev)
+    vol = expand_shared_color(rgb, alpha, bg)
+    out = {k: torch.empty(s, device=dev) for k, s in (("color", (B, 3, S, S)), ("depth", (B, 1, S, S)), ("T", (B, 1, S, S)))}
+    with torch.no_grad():
+        res = r.mpi.render_views(vol, dhw, ray, eye, zd, out=out, _in_autograd_fn=True, **kw)
+    p = res.pop("_bwd")[0]   # (the tuple also holds the volume: dropped here, so that `del vol` below frees it)
+    if with_backward:
+        pb = _lib.GmpiRenderParams.from_buffer_copy(p)
+        pb.rgb_out = pb.depth_out = pb.status = None
+        grad = torch.zeros_like(vol, dtype=torch.float32)
+        gs = (ctypes.c_int64 * 5)(*grad.stride())
+        bwd = lambda: _lib.check(lib.gmpi_mpi_render_backward_launch(ctypes.byref(pb), gc.data_ptr(), gd.data_ptr(), grad.data_ptr(), gs, cs), "backward")
+        bwd()
+        plane_sum = lambda: (grad[:, :D - 1, :3].sum(1), grad[:, D - 1, :3].contiguous())
+        plane_sum()
+    torch.cuda.synchronize()
+    row["base_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    row["base_expand"] = timed(lambda: expand_shared_color(rgb, alpha, bg))
+    with torch.no_grad():
+        row["base_fwd"] = timed(lambda: r.mpi.render_views(vol, dhw, ray, eye, zd, out=out, **kw))
+    if with_backward:
+        row["base_fill"] = timed(lambda: grad.zero_())
+        row["base_bwd"] = timed(bwd)
+        row["base_sum"] = timed(plane_sum)
+        del grad, bwd, plane_sum
+    del vol, res, p
+    torch.cuda.empty_cache()
+    assert torch.cuda.memory_allocated(dev) - base_mem <= 4 * out["color"].numel() * 8, "the baseline's volume is still alive"
+
+    # ---- shared --------------------------------------------------------------------------------------------------------------------------------
+    torch.cuda.reset_peak_memory_stats(dev)
+    with torch.no_grad():
+        res = r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, _in_autograd_fn=True, **kw)
+    p = res.pop("_bwd")[0]
+    if with_backward:
+        sc = _lib.GmpiSharedColor()
+        sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
+        sc.rgb, sc.background = rgb.data_ptr(), bg.data_ptr()
+        for i in range(3):
+            sc.rgb_stride[i], sc.background_stride[i] = rgb.stride(i), bg.stride(i)
+        g_rgb, g_alpha, g_bg = torch.zeros_like(rgb, dtype=torch.float32), torch.zeros_like(alpha, dtype=torch.float32), torch.zeros_like(bg, dtype=torch.float32)
+        s3 = lambda t, dims: (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
+        strides = (s3(g_rgb, (0, 1, 2)), s3(g_alpha, (0, 1, 3)), s3(g_bg, (0, 1, 2)))
+
+        def shared_bwd(variant):
+            q = _lib.GmpiRenderParams.from_buffer_copy(p)
+            q.rgb_out = q.depth_out = q.status = None
+            q.variant = variant
+            return lambda: _lib.check(lib.gmpi_mpi_render_shared_backward_launch(
+                ctypes.byref(q), ctypes.byref(sc), gc.data_ptr(), gd.data_ptr(), None, g_rgb.data_ptr(), strides[0], g_alpha.data_ptr(), strides[1],
+                g_bg.data_ptr(), strides[2], cs), "shared backward")
+        tile, gather = shared_bwd(_lib.VARIANT_AUTO), shared_bwd(_lib.VARIANT_GATHER)
+        tile()
+    torch.cuda.synchronize()
+    row["shared_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    with torch.no_grad():
+        row["shared_fwd"] = timed(lambda: r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, **kw))
+    if with_backward:
+        row["shared_fill"] = timed(lambda: (g_rgb.zero_(), g_alpha.zero_(), g_bg.zero_()))
+        row["shared_bwd_tile"] = timed(tile)
+        row["shared_bwd_gather"] = timed(gather)
+        row["base_total"] = row["base_expand"] + row["base_fwd"] + row["base_fill"] + row["base_bwd"] + row["base_sum"]
+        row["shared_total_tile"] = row["shared_fwd"] + row["shared_fill"] + row["shared_bwd_tile"]
+        row["shared_total_gather"] = row["shared_fwd"] + row["shared_fill"] + row["shared_bwd_gather"]
+    try:
+        clock = f"{torch.cuda.clock_rate()} MHz"
+    except Exception:  # noqa: BLE001 -- no SMI binding in this torch
+        clock = "n/a"
+    print("ROW " + " ".join(f"{k}={v:.3f}" if isinstance(v, float) else f"{k}={v}" for k, v in row.items()) + f" device={torch.cuda.get_device_name(0)!r} clock={clock}",
+          flush=True)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--one":
+        S, B, D, dt, bw, reps = sys.argv[2:8]
+        one(int(S), int(B), int(D), dt, int(bw), int(reps))
+        sys.exit(0)
+    reps = sys.argv[1] if len(sys.argv) > 1 else "15"
+    print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape")
+    for S, B, D, dt, bw in SHAPES:
+        try:
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), dt, str(bw), reps], timeout=240).returncode
+        except subprocess.TimeoutExpired:   # (run() has killed the child)
+            rc = "time limit of 240 s"
+        if rc != 0:
+            print(f"shape {S} x {B} x {D} {dt}: exit status {rc}; stopping")
+            sys.exit(1)
