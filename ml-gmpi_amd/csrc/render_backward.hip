@@ -257,7 +257,8 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
 //   * that barrier is `s_waitcnt lgkmcnt(0); s_barrier` -- it orders LDS only.  `__syncthreads()` is a workgroup-scope fence over EVERY
 //     address space: on this part it drains vmcnt, i.e. every plane would wait for its own prefetch and for the flush's global atomics;
 //   * two boxes fit because the staged sums are 32-bit fixed point (v_cvt_i32_f32 + ds_add_u32 instead of a double conversion +
-//     ds_add_u64): per plane and tile the largest |sample gradient| M is scaled to 2^(30 - h), h = the bits of headroom for the taps that
+//     ds_add_u64): per plane and tile the largest |sample gradient| M (of the colour channels | of the alpha channel, each on a grid of
+//     its own: on a thin plane the two differ by a factor 1 / a_k) is scaled to 2^(30 - h), h = the bits of headroom for the taps that
 //     can meet in one texel (from the pixel density of the tile on that plane: 4 bits at one pixel per texel, 11 = every tap of the tile
 //     when the texture is much coarser than the image), i.e. <= 2^-27 M per add (rounded to nearest) at one pixel per texel -- finer than
 //     the rounding of a chain of fp32 atomic adds (2^-24 of the running sum);
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     __shared__ int4 box[kB2Chunk];        // bx0, by0, nx (<= 0: not staged), ny
     __shared__ float4 pcA[kB2Chunk];      // zdiff, w/2, h/2, RN(2/w)
     __shared__ float2 pcB[kB2Chunk];      // RN(2/h), headroom bits (as int bits)
-    __shared__ uint32_t gmax[kB2Chunk];   // per plane: largest |sample gradient| of the tile, as fp32 bits
+    __shared__ uint2 gmax[kB2Chunk];      // per plane: largest |sample gradient| of the tile, as fp32 bits: x colour channels, y alpha channel
     __shared__ uint32_t acc[2][kB2Cap];
 #ifdef GMPI_B2_PAD  // (experiment: LDS nobody uses, to hold the workgroups per CU down)
     __shared__ uint32_t lds_pad[GMPI_B2_PAD / 4];
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
         }
     };
     // the taps have landed: bilinear samples, the plane's gradients (the arithmetic of BwdPixel::plane), the tile maximum
-    auto grads = [&](int t, const Tap& q, Grad& gq) -> uint32_t {
+    auto grads = [&](int t, const Tap& q, Grad& gq) -> uint2 {
         const int x0 = q.x0, y0 = q.y0;
         const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
         const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
@@ -452,34 +453,40 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
             gq.sw = (x0in && y1in) ? ux0 * q.wy1 : 0.0f, gq.se = (x1in && y1in) ? q.wx1 * q.wy1 : 0.0f;
         }
         gq.x0 = x0, gq.y0 = y0;
-        // non-negative floats order like their bit patterns; NaN/Inf end up on top
-        const float mx = fmaxf(fmaxf(fabsf(gq.d[0]), fabsf(gq.d[1])), fmaxf(fabsf(gq.d[2]), fabsf(gq.d[3])));
-        return (mx != mx) ? 0x7fc00000u : __float_as_uint(mx);
+        // non-negative floats order like their bit patterns; NaN/Inf end up on top.  Colour and alpha apart: on a thin plane (a_k of a few
+        // percent) the colour gradients w_k g are a hundred times smaller than dL/da_k, and a fixed-point grid sized for the latter is a hundred
+        // times coarser for them (seen as 6e-4 of a plane's own largest colour gradient where many taps meet in a texel)
+        const float mc = fmaxf(fmaxf(fabsf(gq.d[0]), fabsf(gq.d[1])), fabsf(gq.d[2])), ma = fabsf(gq.d[3]);
+        return make_uint2((mc != mc) ? 0x7fc00000u : __float_as_uint(mc), (ma != ma) ? 0x7fc00000u : __float_as_uint(ma));
     };
-    // the tile maximum of a plane: one LDS atomic per wave (every lane of the wave must call this)
-    auto tile_max = [&](int t, uint32_t lane_bits) {
-        const uint32_t wmax = wave_max_u32(lane_bits);
-        if (wmax != 0u && box[t].z > 0 && (tid & 63) == 0) atomicMax(&gmax[t], wmax);
+    // the tile maxima of a plane: one LDS atomic instruction per wave, lane 0 the colour maximum, lane 1 the alpha maximum (every lane of
+    // the wave must call this)
+    auto tile_max = [&](int t, uint2 lane_bits) {
+        const uint32_t cmax = wave_max_u32(lane_bits.x), amax = wave_max_u32(lane_bits.y);
+        const int lane = tid & 63;
+        const uint32_t wmax = lane == 0 ? cmax : amax;
+        if (lane < 2 && wmax != 0u && box[t].z > 0) atomicMax(&gmax[t].x + lane, wmax);
     };
     // scatter of one plane's gradients: into the LDS box (fixed point) or, for a plane / a pixel that is not staged, straight to global memory
     auto scatter = [&](int t, int k, const Grad& gq, uint32_t* __restrict__ bx_acc) {
         const int4 bb = box[t];
-        const uint32_t mb = gmax[t];
-        const bool staged = bb.z > 0 && mb < 0x7f800000u;  // workgroup-uniform
-        if (mb == 0u && bb.z > 0) return;                   // every gradient of the tile is zero (workgroup-uniform)
+        const uint32_t mbc = gmax[t].x, mba = gmax[t].y;
+        const bool staged = bb.z > 0 && mbc < 0x7f800000u && mba < 0x7f800000u;  // workgroup-uniform
+        if (mbc == 0u && mba == 0u && bb.z > 0) return;     // every gradient of the tile is zero (workgroup-uniform)
         const int x0 = gq.x0, y0 = gq.y0;
         const float nw = gq.nw, ne = gq.ne, sw = gq.sw, se = gq.se;
         const int lx = x0 - bb.x, ly = y0 - bb.y;
         const bool in_box = lx >= 0 && ly >= 0 && lx + 1 < bb.z && ly + 1 < bb.w;
         const bool any_w = nw != 0.0f || ne != 0.0f || sw != 0.0f || se != 0.0f;
         if (staged && in_box && active) {
-            // scale = 2^(29 - h - floor(log2 M)): |d * weight * scale| < 2^(30 - h), and at most 2^h taps meet in one word
+            // scale = 2^(29 - h - floor(log2 M)): |d * weight * scale| < 2^(30 - h), and at most 2^h taps meet in one word; M = the tile's
+            // largest colour gradient for channels 0-2, its largest alpha gradient for channel 3 (a maximum of 0: every d of the group is 0)
             const int hword = __float_as_int(pcB[t].y);
             const int hbits = hword & 0xff;
             const bool wide = (hword & 0x100) != 0;   // workgroup-uniform: two words per cell, |d * weight * scale| < 2^(42 - h)
-            const int shf = min((wide ? 41 : 29) - hbits - (static_cast<int>(mb >> 23) - 127), 126);
-            const float sc = __builtin_amdgcn_ldexpf(1.0f, shf);
-            const float fnw = nw * sc, fne = ne * sc, fsw = sw * sc, fse = se * sc;   // (a power of two: exact)
+            const int shc = min((wide ? 41 : 29) - hbits - (static_cast<int>(mbc >> 23) - 127), 126);
+            const int sha = min((wide ? 41 : 29) - hbits - (static_cast<int>(mba >> 23) - 127), 126);
+            const float scc = __builtin_amdgcn_ldexpf(1.0f, shc), sca = __builtin_amdgcn_ldexpf(1.0f, sha);   // (powers of two: d * scale is exact)
             uint32_t* __restrict__ l0 = bx_acc + ly * (4 * kB2Pitch) + lx;
             if (wide && !abl_nolds) {
                 auto add2 = [&](uint32_t* __restrict__ cell, float v) {   // v = hi * 2^12 + lo exactly (fp32: 24 significant bits), hi rounded to nearest
@@ -490,21 +497,21 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
                 };
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) {
-                    const float d = gq.d[c4];
+                    const float d = gq.d[c4] * (c4 == 3 ? sca : scc);
                     uint32_t* __restrict__ lc = l0 + c4 * kB2Pitch;
-                    add2(lc, d * fnw), add2(lc + 1, d * fne), add2(lc + 4 * kB2Pitch, d * fsw), add2(lc + 4 * kB2Pitch + 1, d * fse);
+                    add2(lc, d * nw), add2(lc + 1, d * ne), add2(lc + 4 * kB2Pitch, d * sw), add2(lc + 4 * kB2Pitch + 1, d * se);
                 }
             } else if (!abl_nolds) {
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) {
-                    const float d = gq.d[c4];
+                    const float d = gq.d[c4] * (c4 == 3 ? sca : scc);
                     uint32_t* __restrict__ lc = l0 + c4 * kB2Pitch;
                     // (a tap outside the texture has weight 0 and adds 0 to a box cell outside the texture, which the flush never writes out;
                     //  round to nearest: at most half a unit of 2^-(30 - h) M per add, in either direction)
-                    atomicAdd(lc, static_cast<uint32_t>(cvt_rpi(d * fnw)));
-                    atomicAdd(lc + 1, static_cast<uint32_t>(cvt_rpi(d * fne)));
-                    atomicAdd(lc + 4 * kB2Pitch, static_cast<uint32_t>(cvt_rpi(d * fsw)));
-                    atomicAdd(lc + 4 * kB2Pitch + 1, static_cast<uint32_t>(cvt_rpi(d * fse)));
+                    atomicAdd(lc, static_cast<uint32_t>(cvt_rpi(d * nw)));
+                    atomicAdd(lc + 1, static_cast<uint32_t>(cvt_rpi(d * ne)));
+                    atomicAdd(lc + 4 * kB2Pitch, static_cast<uint32_t>(cvt_rpi(d * sw)));
+                    atomicAdd(lc + 4 * kB2Pitch + 1, static_cast<uint32_t>(cvt_rpi(d * se)));
                 }
             }
         }
@@ -537,13 +544,16 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     //  machines, and the flush -- the kernel's critical path -- took 38 % longer: profiles/r06_backward.txt.)
     auto flush = [&](int t, int k, uint32_t* __restrict__ bx_acc) {
         const int4 bb = box[t];
-        const uint32_t mb = gmax[t];
-        if (!(bb.z > 0 && mb < 0x7f800000u && mb != 0u)) return;
+        const uint32_t mbc = gmax[t].x, mba = gmax[t].y;
+        if (!(bb.z > 0 && mbc < 0x7f800000u && mba < 0x7f800000u && (mbc | mba) != 0u)) return;
         const int hword = __float_as_int(pcB[t].y);
         const int hbits = hword & 0xff;
         const bool wide = __builtin_amdgcn_readfirstlane(hword & 0x100) != 0;
-        const int shf = min((wide ? 41 : 29) - hbits - (static_cast<int>(mb >> 23) - 127), 126);
-        const float inv = __builtin_amdgcn_ldexpf(1.0f, -shf);
+        const int shc = min((wide ? 41 : 29) - hbits - (static_cast<int>(mbc >> 23) - 127), 126);
+        const int sha = min((wide ? 41 : 29) - hbits - (static_cast<int>(mba >> 23) - 127), 126);
+        // line & 3 = the channel of a box line; a flush wave takes the lines fw, fw + kFW, ...: one channel, fw & 3
+        static_assert(kFW % 4 == 0, "a flush wave's lines are all of one channel");
+        const float inv = __builtin_amdgcn_ldexpf(1.0f, (fw & 3) == 3 ? -sha : -shc);
         const int nx = __builtin_amdgcn_readfirstlane(bb.z), nlines = __builtin_amdgcn_readfirstlane(bb.w) * 4;
         const int bx = __builtin_amdgcn_readfirstlane(bb.x), by = __builtin_amdgcn_readfirstlane(bb.y);
         float* __restrict__ gp = gvol + static_cast<int64_t>(k) * b.gs_plane + static_cast<int64_t>(by) * b.gs_row + bx;
@@ -643,7 +653,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
                 }
             }
             box[t] = bb;
-            gmax[t] = 0u;
+            gmax[t] = make_uint2(0u, 0u);
             const float hw = pw * 0.5f, hh = ph * 0.5f;
             pcA[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
             pcB[t] = make_float2(1.0f / hh, __int_as_float(hbits));
@@ -679,7 +689,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
             tq.s = tq.wx1 = tq.wy1 = 0.0f, tq.x0 = tq.y0 = -2;
             gq.d[0] = gq.d[1] = gq.d[2] = gq.d[3] = 0.0f, gq.nw = gq.ne = gq.sw = gq.se = 0.0f, gq.x0 = gq.y0 = -2;
             // prologue: gradients of the chunk's last plane, taps of the one in front of it in flight
-            uint32_t mbits = 0u;
+            uint2 mbits = make_uint2(0u, 0u);
             if (active) {
                 fetch(kn - 1, kc + kn - 1, tq);
                 mbits = grads(kn - 1, tq, gq);
@@ -691,7 +701,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
             for (int t = kn - 1; t >= 0; --t) {
                 scatter(t, kc + t, gq, acc[t & 1]);                               // plane t: gradients -> box (gmax[t] complete since the last barrier)
                 B2_STAMP(0);
-                mbits = 0u;
+                mbits = make_uint2(0u, 0u);
                 if (active && t >= 1) mbits = grads(t - 1, tq, gq);               // plane t - 1: taps landed -> gradients
                 if (t >= 1) tile_max(t - 1, mbits);                               //              ... and their tile maximum
                 B2_STAMP(1);

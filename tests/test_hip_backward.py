@@ -21,13 +21,24 @@ def _setup(N, M, D, Ht, Wt, H, W, seed, v2m=None):
     return rgba, dhw, ray, eye, zd, v2m
 
 
-def _ref_grads(rgba, dhw, ray, eye, zd, v2m, gc, gd, ac):
-    t = lambda a: torch.from_numpy(np.asarray(a)).double()
+def _ref_grads(rgba, dhw, ray, eye, zd, v2m, gc, gd, ac, dtype=torch.float64):
+    t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)
     vol = t(rgba).requires_grad_(True)
     color, depth = torch_render(vol, t(dhw), t(ray), t(eye), t(zd), v2m, align_corners=ac)
     loss = (color * t(gc)).sum() + (depth * t(gd)).sum()
     loss.backward()
     return color.detach().numpy(), depth.detach().numpy(), vol.grad.numpy()
+
+
+def _slab_check(got, ref_g, args, ac, label):
+    """On top of the per-tensor assertions: every (MPI, plane, channel) slab of the gradient whose maximum is >= 1e-6 of the tensor's against
+    ITS OWN maximum (tests/_visible.py `slab_compare`: max(5e-5, 4 e_ref), e_ref from the same chain in fp32) -- planes ~8-20 of a white-noise
+    stack, which the per-tensor bar does not see; the number of slabs below that is printed."""
+    from _visible import slab_compare
+    ref32 = _ref_grads(*args, ac, dtype=torch.float32)[2].astype(np.float64)
+    res = slab_compare(got, ref_g, ref32, min_rel_scale=1e-6, label=label)
+    print(f"{label} slabs below 1e-6 of the maximum (left out): {res['skipped']} of {res['slabs']}")
+    assert not res["failures"], (label, len(res["failures"]), res["worst"], res["where"], res["failures"][:5])
 
 
 @pytest.mark.parametrize("cfg", [
@@ -63,6 +74,7 @@ def test_backward_matches_autograd(cfg):
     # relative check on the significant entries
     big = np.abs(ref_g) > 1e-3 * scale
     assert np.max(np.abs(got[big] - ref_g[big]) / np.abs(ref_g[big])) <= cfg.get("rel_tol", 2e-3)
+    _slab_check(got, ref_g, (rgba, dhw, ray, eye, zd, v2m, gc, gd), ac, f"autograd case D={cfg['D']}")
 
 
 def test_backward_behind_opaque_and_nearly_opaque_planes():
@@ -91,6 +103,7 @@ def test_backward_behind_opaque_and_nearly_opaque_planes():
         scale = np.abs(ref_g).max()
         assert np.isfinite(got).all()
         assert np.abs(got - ref_g).max() <= 1e-4 * scale, (variant, np.abs(got - ref_g).max(), scale)
+        _slab_check(got, ref_g, (rgba, dhw, ray, eye, zd, v2m, gc, gd), True, f"opaque planes {variant}")
 
 
 def test_backward_through_renderer_render_pm1_and_expand():
@@ -290,6 +303,8 @@ def test_tile_backward_matches_the_all_atomic_kernel(cfg):
     # (float64 coordinates against fp32 ones on white noise, hundreds of pixels per row: a little looser than the small cases above)
     _, _, ref_g = _ref_grads(rgba, dhw, ray, eye, zd, v2m, gc, gd, True)
     assert np.abs(grads["auto"] - ref_g).max() <= 5e-5 * np.abs(ref_g).max() + 1e-6
+    for variant in ("auto", "gather"):
+        _slab_check(grads[variant], ref_g, (rgba, dhw, ray, eye, zd, v2m, gc, gd), True, f"tile backward case {variant}")
 
 
 @pytest.mark.parametrize("cfg", [
@@ -331,6 +346,7 @@ def test_gather_backward_matches_autograd_and_is_bit_reproducible(cfg):
     assert np.abs(a - b).max() <= 1e-5 * scale, (np.abs(a - b).max(), scale)
     _, _, ref_g = _ref_grads(rgba, dhw, ray, eye, zd, np.repeat(np.arange(M), vpm), gc, gd, True)
     assert np.abs(a - ref_g).max() <= 5e-5 * np.abs(ref_g).max() + 1e-6
+    _slab_check(a, ref_g, (rgba, dhw, ray, eye, zd, np.repeat(np.arange(M), vpm), gc, gd), True, "gather backward case")
 
 
 def test_gather_backward_falls_back_and_accumulates():

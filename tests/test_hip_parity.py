@@ -93,8 +93,9 @@ def test_golden_ragged_views_per_mpi():
         assert np.array_equal(out["color"], out2["color"]) and np.array_equal(out["depth"], out2["depth"])
 
 
-def _random_case(seed, B, D, S, T=None, preset="FFHQ", extreme=False):
-    """Seeded inputs: white-noise volume (torch CPU RNG) + poses/rays from the host mirror on CPU."""
+def _random_case(seed, B, D, S, T=None, preset="FFHQ", extreme=False, alpha="noise"):
+    """Seeded inputs: white-noise volume (torch CPU RNG) + poses/rays from the host mirror on CPU.  `alpha`: "noise" (U[0,1), the stack is
+    opaque after ~25 planes), "thin" or "surface" (tests/_visible.py: every plane counts)."""
     from ml_gmpi_amd.renderer import MPIRenderer, PRESETS
     T = T or S
     kw = dict(PRESETS[preset])
@@ -105,6 +106,9 @@ def _random_case(seed, B, D, S, T=None, preset="FFHQ", extreme=False):
     r.set_cam(r.cam_fov, S, S)
     g = torch.Generator().manual_seed(seed)
     rgba = torch.rand((B, D, 4, T, T), generator=g)
+    if alpha != "noise":
+        from _visible import make_alpha
+        rgba = make_alpha(rgba, alpha)
     torch.manual_seed(seed)
     if extreme:
         n = r.cam_pose_n_truncated_stds

@@ -1,6 +1,7 @@
 """Long randomized parity run on the GPU box (not part of the test suite): random image / texture sizes, plane counts, batch sizes,
 presets, align_corners, storage types and poses (random, 2-sigma, beyond); every kernel variant; strict mode must equal the CPU
-oracle bit for bit, default mode must stay within 1e-5.  usage: python tools/fuzz_gpu.py [n_cases] [seed]"""
+oracle bit for bit, default mode must stay within 1e-5.  The alpha law is drawn per case, one third each (tests/_visible.py): white noise
+(opaque after ~25 planes), thin or surface (every plane of a deep stack reaches the image).  usage: python tools/fuzz_gpu.py [n_cases] [seed]"""
 import os
 import sys
 import time
@@ -12,6 +13,7 @@ import numpy as np
 import torch
 import oracle
 from test_hip_parity import hip_render
+from _visible import ALPHA_LAWS, make_alpha
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -47,8 +49,9 @@ for i in range(n_cases):
         gy = torch.tensor([[(-1) ** b * f * r.horizontal_std * rng.uniform(0.3, 1)] for b in range(B)], dtype=torch.float32)
         gp = torch.tensor([[(-1) ** (b // 2) * f * r.vertical_std * rng.uniform(0.3, 1)] for b in range(B)], dtype=torch.float32)
         cam = r.sample_cam_poses(B, 0, 0, 0, 0, False, given_yaws=gy, given_pitches=gp)
-    rgba = torch.rand((B, D, 4, Ht, Wt))
-    if rng.random() < 0.3:
+    law = ALPHA_LAWS[int(rng.integers(0, 3))]
+    rgba = make_alpha(torch.rand((B, D, 4, Ht, Wt)), law)
+    if law == "noise" and rng.random() < 0.3:
         rgba[:, :, 3] = (rgba[:, :, 3] > 0.6).float()
     dtype = [torch.float32, torch.bfloat16, torch.float16][int(rng.integers(0, 3))]
     vol = rgba.to(dtype)
@@ -62,7 +65,7 @@ for i in range(n_cases):
         out = hip_render(vol, dhw, ray, eye, zd, ac=ac, variant=variant, strict=True, check_last=False)
         for k in ("color", "depth", "T"):
             if not np.array_equal(out[k], orc[k]):
-                print("STRICT MISMATCH", i, dict(H=H, W=W, Ht=Ht, Wt=Wt, D=D, B=B, preset=preset, ac=ac, dtype=str(dtype), mode=mode), variant, k,
+                print("STRICT MISMATCH", i, dict(H=H, W=W, Ht=Ht, Wt=Wt, D=D, B=B, preset=preset, ac=ac, dtype=str(dtype), mode=mode, alpha=law), variant, k,
                       float(np.nanmax(np.abs(out[k] - orc[k]))))
                 sys.exit(1)
         fast = hip_render(vol, dhw, ray, eye, zd, ac=ac, variant=variant, check_last=False)
@@ -70,7 +73,7 @@ for i in range(n_cases):
             err = float(np.abs(fast[k] - orc[k]).max())
             worst[k] = max(worst[k], err)
             if not err <= tol:
-                print("DEFAULT-MODE MISMATCH", i, dict(H=H, W=W, Ht=Ht, Wt=Wt, D=D, B=B, preset=preset, ac=ac, dtype=str(dtype), mode=mode), variant, k, err)
+                print("DEFAULT-MODE MISMATCH", i, dict(H=H, W=W, Ht=Ht, Wt=Wt, D=D, B=B, preset=preset, ac=ac, dtype=str(dtype), mode=mode, alpha=law), variant, k, err)
                 sys.exit(1)
 print(f"fuzz ok: {n_cases} cases, {n_runs} (case, variant) pairs x 2 modes (gather / lds / wave / band / auto) in {time.time() - t0:.0f} s; "
       f"worst default-mode error {worst}")
