@@ -45,7 +45,9 @@ def _alpha_operand(mpi_alpha: torch.Tensor) -> torch.Tensor:
     """The alpha view the kernels read: a storage dtype they take, innermost stride 1, no negative strides."""
     if mpi_alpha.dtype not in _DTYPES:
         mpi_alpha = mpi_alpha.float()
-    if mpi_alpha.stride(4) != 1 or any(s < 0 for s in mpi_alpha.stride()):
+    # (a plane stride of 0 -- one plane expanded over D -- or overlapping rows are legal torch views that the entries refuse with GMPI_E_STRIDE:
+    # tests/test_hip_light_shapes.py::test_render_takes_a_volume_expanded_over_the_planes)
+    if mpi_alpha.stride(4) != 1 or any(s < 0 for s in mpi_alpha.stride()) or mpi_alpha.stride(1) == 0 or mpi_alpha.stride(3) < mpi_alpha.shape[4]:
         mpi_alpha = mpi_alpha.contiguous()
     return mpi_alpha
 
@@ -311,8 +313,8 @@ class LightRenderer:
             raise _lib.GmpiError("LightRenderer.render needs tensors on a ROCm device (no CPU path)")
         dev = batch_mpi.device
         vol = batch_mpi if batch_mpi.dtype in _DTYPES else batch_mpi.float()
-        if vol.stride(4) != 1 or any(s < 0 for s in vol.stride()):
-            vol = vol.contiguous()
+        if vol.stride(4) != 1 or any(s < 0 for s in vol.stride()) or vol.stride(1) == 0 or vol.stride(2) == 0 or vol.stride(3) < vol.shape[4]:
+            vol = vol.contiguous()   # (what the apply entries refuse, see _alpha_operand; a batch stride of 0 they take)
         light_direction = self._next_light(vol.shape[0])
         plane_ds = mpi_plane_dhws[:, :1].detach().to(dev)
         xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach()

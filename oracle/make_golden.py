@@ -13,6 +13,8 @@ pin for the oracle (oracle/mpi_oracle.c), for the host-side geometry mirror and 
   geometry.npz   plane depths / dhws / c2w / rays / sampled poses of the reference's host-side
                  helpers (mpi_utils.py:21,787,652; cam_utils.py:734; camera.py:182;
                  mpi_renderer.py:337) for the dataset presets
+  light_render_nonsquare.npz  LightRenderer.render and its intermediate quantities at two shapes with H != W (`python oracle/make_golden.py
+                 light-nonsquare`, run_light_render_nonsquare)
   reference_seams.npz  what the reference hands this package at its seams (`python oracle/make_golden.py seams`,
                  run_seams): replayed by tests/test_install_reference.py without the reference
 """
@@ -281,6 +283,68 @@ def run_light_render():
     print("wrote light_render", {k: v.shape for k, v in out.items()})
 
 
+NONSQUARE_LIGHT_CASES = (("21x37", 21, 37, 81), ("50x18", 50, 18, 82))   # name, H, W, seed: W % 4 != 0, H < W and H > W
+LIGHT_TEXEL_PITCH = 0.2473 / 32
+
+
+def light_grid(plane_ds, H, W, pitch=LIGHT_TEXEL_PITCH):
+    """A synthetic `mpi_tex_pix_xyz` [D,H,W,3]: texel centres on a grid of constant pitch in x (along W) and y (along H), centred on the
+    axis, z = the plane's distance.  `LightRenderer.render` reads only the last plane's grid."""
+    D = len(plane_ds)
+    xyz = np.empty((D, H, W, 3), np.float32)
+    xyz[..., 0] = ((np.arange(W, dtype=np.float64) - (W - 1) / 2) * pitch).astype(np.float32)[None, None, :]
+    xyz[..., 1] = ((np.arange(H, dtype=np.float64) - (H - 1) / 2) * pitch).astype(np.float32)[None, :, None]
+    xyz[..., 2] = np.asarray(plane_ds, np.float32).reshape(D, 1, 1)
+    return xyz
+
+
+def run_light_render_nonsquare():
+    """tests/golden/light_render_nonsquare.npz: the reference's `LightRenderer.render` (and its `compute_depth`, `blurrer_func`, `compute_pcl`,
+    `get_normal`, for the intermediate quantities) at two shapes with H != W, on a synthetic texel grid; same torchvision stand-in as
+    run_light_render.  ka + kd > 1: some rgb * shading clip at 1."""
+    import importlib
+    sys.modules["torchvision"] = _torchvision_stand_in()
+    sys.modules.pop("gmpi.core.light_renderer", None)
+    if ref_import.REFERENCE_ROOT not in sys.path:
+        sys.path.insert(0, ref_import.REFERENCE_ROOT)
+    ns = ref_import.import_reference()
+    lr = importlib.import_module("gmpi.core.light_renderer")
+    B, D = 2, 5
+    with quiet():
+        dhw = ref_import.make_reference_renderer(ns, "FFHQ", D).static_mpi_plane_dhws
+    out = {"dhw": dhw.numpy()}
+    for name, H, W, seed in NONSQUARE_LIGHT_CASES:
+        xyz = torch.from_numpy(light_grid(dhw[:, 0].numpy(), H, W))
+        rgba = oracle.synth_rgba(seed, (B, D, 4, H, W), last_alpha_one=True)
+        a = torch.from_numpy(rgba[:, :, 3:4].reshape(B * D, 1, H, W))
+        for _ in range(3):   # (one pass, as run_light_render, leaves the fp32 chain 1.1e-5 from float64 at this pitch: above the 1e-5 the tests ask)
+            a = torch.nn.functional.avg_pool2d(torch.nn.functional.pad(a, (3, 3, 3, 3), mode="replicate"), 7, stride=1)
+        rgba[:, :, 3] = a.reshape(B, D, H, W).numpy()
+        rgba[:, -1, 3] = 1.0
+        vol = torch.from_numpy(rgba)
+        L = lr.LightRenderer(sphere_center_z=1.0, sphere_r=1.0, ka_max=0.6, kd_max=0.9, n_grow_iters=2)
+        torch.manual_seed(321)
+        for _ in range(3):   # the third call renders with the full ka, kd
+            res = L.render(vol, dhw, xyz)
+        torch.manual_seed(321)
+        for _ in range(3):
+            c2w, _, _ = ns.cam_utils.gen_sphere_path(n_cams=B, sphere_center=L.sphere_center, sphere_r=L.sphere_r,
+                                                     yaw_mean=L.l_h_mean, yaw_std=L.l_h_std, pitch_mean=L.l_v_mean,
+                                                     pitch_std=L.l_v_std, n_truncated_stds=2, flag_rnd=True,
+                                                     sample_method="truncated_gaussian", given_yaws=None, given_pitches=None)
+        pos = torch.as_tensor(c2w[:, :3, 3], dtype=torch.float32)
+        depth = L.compute_depth(vol[:, :, 3:], dhw[:, :1])
+        pcl = L.compute_pcl(vol[:, :, 3:], dhw, xyz)
+        out.update({f"rgba_{name}": rgba, f"xyz_last_{name}": xyz[-1].numpy(), f"ref_{name}": res.numpy(),
+                    f"light_dir_{name}": ns.torch_utils.normalize_vecs(torch.FloatTensor(L.sphere_center).reshape(1, 3) - pos).numpy(),
+                    f"ka_kd_{name}": np.array([L.cur_ka, L.cur_kd], dtype=np.float64),
+                    f"ref_depth_{name}": depth.numpy(), f"ref_blurred_{name}": L.blurrer_func(depth).numpy(),
+                    f"ref_normal_{name}": L.get_normal(pcl).numpy()})
+    np.savez(os.path.join(OUT, "light_render_nonsquare.npz"),
+             meta=json.dumps(dict(B=B, D=D, pitch=LIGHT_TEXEL_PITCH, cases=[list(c) for c in NONSQUARE_LIGHT_CASES])), **out)
+    print("wrote light_render_nonsquare", {k: v.shape for k, v in out.items()})
+
+
 def run_backward_cases(ns):
     """Gradient of the reference w.r.t. the RGBA volume: autograd through the reference's own MPIRenderer.render /
     MPI.forward (mpi.py:308-436), exactly what the G-step back-propagates (train.py:740-779), fp32 on the CPU.
@@ -480,6 +544,12 @@ def main():
         torch.set_num_threads(1)
         run_light_depth()
         run_light_render()
+        run_light_render_nonsquare()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "light-nonsquare":
+        os.makedirs(OUT, exist_ok=True)
+        torch.set_num_threads(1)
+        run_light_render_nonsquare()
         return
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(1)
@@ -491,6 +561,7 @@ def main():
     run_geometry(ns)
     run_light_depth()
     run_light_render()
+    run_light_render_nonsquare()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:
         f.write("Generated by oracle/make_golden.py from the reference at /root/reference "
                 "(apple/ml-gmpi @ 2024_08_07), CPU fp32, torch %s, numpy %s.\n" % (torch.__version__, np.__version__))
