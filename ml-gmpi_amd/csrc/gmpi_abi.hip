@@ -578,16 +578,18 @@ int gmpi_rgba_range_check_launch(const void* rgba, int32_t rgba_dtype, int64_t c
     if (nvec > 0) {
         const int blocks = static_cast<int>(std::min<int64_t>((nvec + 255) / 256, 256 * 8));
         const uint4* v = static_cast<const uint4*>(rgba);
-        if (rgba_dtype == GMPI_DTYPE_F32) hipLaunchKernelGGL((range_check_vec_kernel<float, 4>), dim3(blocks), dim3(256), 0, st, v, nvec, status);
-        else if (rgba_dtype == GMPI_DTYPE_BF16) hipLaunchKernelGGL((range_check_vec_kernel<bf16_t, 8>), dim3(blocks), dim3(256), 0, st, v, nvec, status);
-        else hipLaunchKernelGGL((range_check_vec_kernel<f16_t, 8>), dim3(blocks), dim3(256), 0, st, v, nvec, status);
+        dispatch_dtype(rgba_dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((range_check_vec_kernel<T, 16 / static_cast<int>(sizeof(T))>), dim3(blocks), dim3(256), 0, st, v, nvec, status);
+        });
     }
     if (tail > 0) {
         const char* base = static_cast<const char*>(rgba) + nvec * 16;
         const int blocks = static_cast<int>(std::min<int64_t>((tail + 255) / 256, 256 * 8));
-        if (rgba_dtype == GMPI_DTYPE_F32) hipLaunchKernelGGL(range_check_kernel<float>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float*>(base), tail, status);
-        else if (rgba_dtype == GMPI_DTYPE_BF16) hipLaunchKernelGGL(range_check_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(base), tail, status);
-        else hipLaunchKernelGGL(range_check_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const f16_t*>(base), tail, status);
+        dispatch_dtype(rgba_dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(range_check_kernel<T>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const T*>(base), tail, status);
+        });
     }
     return hip_rc(hipGetLastError());
 }
@@ -627,12 +629,11 @@ int gmpi_alpha_depth_launch(const void* alpha, int32_t alpha_dtype, int64_t stri
     if (stride_b < 0 || stride_d <= 0 || stride_row < W) return GMPI_E_STRIDE;
     const dim3 grid((W + 255) / 256, H, B), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (alpha_dtype == GMPI_DTYPE_F32)
-        hipLaunchKernelGGL(alpha_depth_kernel<float>, grid, block, 0, st, static_cast<const float*>(alpha), stride_b, stride_d, stride_row, plane_ds, D, H, W, depth_out, transmittance_out);
-    else if (alpha_dtype == GMPI_DTYPE_BF16)
-        hipLaunchKernelGGL(alpha_depth_kernel<bf16_t>, grid, block, 0, st, static_cast<const bf16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, D, H, W, depth_out, transmittance_out);
-    else
-        hipLaunchKernelGGL(alpha_depth_kernel<f16_t>, grid, block, 0, st, static_cast<const f16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, D, H, W, depth_out, transmittance_out);
+    dispatch_dtype(alpha_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(alpha_depth_kernel<T>, grid, block, 0, st, static_cast<const T*>(alpha), stride_b, stride_d, stride_row, plane_ds, D, H, W, depth_out,
+                           transmittance_out);
+    });
     return hip_rc(hipGetLastError());
 }
 

@@ -1,7 +1,18 @@
-// gmpi_backward.hpp -- what the backward kernels of the render share (render_backward.hip: the tile kernels with their atomics;
-// render_backward_gather.hip: the atomics-free pair of round 6).
+// gmpi_backward.hpp -- the ONE home of what the backward kernels of the render share.  Seven kernels run the same back-to-front sweep
+// (render_backward.hip: one pixel per lane, tile, tile2; render_backward_gather.hip: pixel_pass; render_backward_geometry.hip: geometry_pixel;
+// render_shared.hip: shared_backward, shared_tile), and the claims of DESIGN.md section 3.3 -- the forward's quotients and texels, bit-reproducible
+// gather and geometry passes, gT entering S in every sweep -- hold because they all run THIS code:
+//   BwdView / bwd_view              what is uniform over a view: MPI, plane table, eye, texture centre
+//   BwdPixel / bwd_pixel_setup      the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
+//   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
+//   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
+//   tile_box                        texel box of a pixel tile on one plane, from its four corner pixels
+//   cvt_rpi_i32, fix_split, to_fix, abs_bits, lds_barrier, wave_max_u32, wave_max_bits     the fixed-point and wave primitives of the staged scatters
+// A change to the sweep is made here, never in a kernel.
 #pragma once
 #include "gmpi_device.hpp"
+
+#include <type_traits>
 
 namespace gmpi {
 
@@ -48,25 +59,102 @@ __device__ __forceinline__ XT total_transmittance(const KParams& p, const float*
     return t;
 }
 
-// One plane of the back-to-front sweep for one pixel: sample, T_k = T_{k+1}/om_k, gradients d_s[4] of the sample
-// (r, g, b, alpha), suffix sum update.
+// What is uniform over view n: the MPI it samples (a bad index is only clamped here; the forward reports it), that MPI's plane table, the eye,
+// the image size and the texture centre of the coordinate chain (plane_coord's cx, cy).
+struct BwdView {
+    int m;
+    const float* __restrict__ dhw;
+    float ex, ey, ez;
+    int64_t HW;
+    float cx, cy;
+};
+template <bool AC>
+__device__ __forceinline__ BwdView bwd_view(const KParams& p, int n) {
+    uint32_t bad_index = 0;
+    BwdView vw;
+    vw.m = view_mpi(p, n, bad_index);
+    vw.dhw = p.dhw + static_cast<int64_t>(vw.m) * p.D * 3;
+    vw.ex = p.eye_pos[3 * n + 0], vw.ey = p.eye_pos[3 * n + 1], vw.ez = p.eye_pos[3 * n + 2];
+    vw.HW = static_cast<int64_t>(p.H) * p.W;
+    vw.cx = AC ? static_cast<float>(p.Wt - 1) * 0.5f : static_cast<float>(p.Wt);
+    vw.cy = AC ? static_cast<float>(p.Ht - 1) * 0.5f : static_cast<float>(p.Ht);
+    return vw;
+}
+
+// The state of one pixel through the back-to-front sweep.  A default-constructed one is a pixel that contributes nothing (a lane outside the
+// image, a wave with another role).
 struct BwdPixel {
-    float gr, gg, gb, gz, dot;
-    XT T;      // T_{k+1} on entry, T_k on exit
-    float S;   // sum_{j>k} w_j q_j on entry, sum_{j>=k} on exit
-    __device__ __forceinline__ void plane(const float (&smp)[4], float s, float (&d_s)[4]) {
-        const float a = smp[3];
-        const float om = (1.0f - a) + 1e-10f;
-        T.m = T.m / om;
+    int64_t pix = 0;                                  // py W + px (clamped into the image)
+    float rx = 0.0f, ry = 0.0f, rz = 1.0f;            // the ray
+    float rrz = 1.0f;                                 // RN(1 / rz), for plane_coord_recip (a kernel that divides never reads it)
+    float zx = 0.0f, zy = 0.0f, zz = 0.0f;            // the view's optical axis
+    float dot = 0.0f;                                 // ray . z_dir: depth_k = s_k dot
+    float gr = 0.0f, gg = 0.0f, gb = 0.0f, gz = 0.0f;   // upstream gradients (colour: w.r.t. C in [0, 1])
+    XT T{1.0f, 0};                                    // T_{k+1} on entry of a plane, T_k on exit
+    float S = 0.0f;                                   // sum_{j>k} w_j q_j on entry, sum_{j>=k} on exit
+
+    // One plane: T_k = T_{k+1} / om_k, gradients d_s[4] of the sample (r, g, b, alpha), suffix sum update.  t_over_om = T.m / om, s_over_om = S / om.
+    // Returns the plane's weight w_k = a_k T_k.
+    __device__ __forceinline__ float step(const float (&smp)[4], float s, float t_over_om, float s_over_om, float (&d_s)[4]) {
+        T.m = t_over_om;
         T.renorm();
         const float Tk = T.value();
         const float q = gr * smp[0] + gg * smp[1] + gb * smp[2] + gz * (s * dot);
-        const float w = a * Tk;
+        const float w = smp[3] * Tk;
         d_s[0] = gr * w, d_s[1] = gg * w, d_s[2] = gb * w;
-        d_s[3] = Tk * q - S / om;
+        d_s[3] = Tk * q - s_over_om;
         S += w * q;
+        return w;
+    }
+    // Division form.  plane_recip below gives the same quotients (div_by_recip is correctly rounded), hence the same gradients bit for bit.
+    __device__ __forceinline__ float plane(const float (&smp)[4], float s, float (&d_s)[4]) {
+        const float om = (1.0f - smp[3]) + 1e-10f;
+        return step(smp, s, T.m / om, S / om, d_s);
+    }
+    // Both quotients through ONE reciprocal: v_rcp_f32, a Newton step (r = RN(1 / om) up to the last bit), Markstein's correction.
+    __device__ __forceinline__ float plane_recip(const float (&smp)[4], float s, float (&d_s)[4]) {
+        const float om = (1.0f - smp[3]) + 1e-10f;
+        float r = __builtin_amdgcn_rcpf(om);
+        r = __builtin_fmaf(__builtin_fmaf(-om, r, 1.0f), r, r);
+        return step(smp, s, div_by_recip(T.m, om, r), div_by_recip(S, om, r), d_s);
     }
 };
+
+// The start of the sweep for pixel (px, py) of view n.  g_rgb / g_depth / g_T: the upstream gradients (g_depth, g_T may be nullptr); vol: channel 0 of
+// the view's MPI -- the RGBA volume, or the alpha planes of the shared-colour layout (s_chan = 0).
+// MASKED: the workgroup keeps lanes outside the image (they pass its barriers): the pixel index is clamped, an inactive lane loads its ray but
+// contributes nothing, and t_fwd defaults to 1.  Not MASKED: the lane is known to be inside the image (`active` is ignored), t_fwd defaults to 0.
+template <typename TexT, bool AC, bool MASKED>
+__device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
+                                                const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
+                                                const TexT* __restrict__ vol) {
+    if (!MASKED) active = true;
+    const int64_t HW = vw.HW;
+    const int64_t pix = MASKED ? static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1) : static_cast<int64_t>(py) * p.W + px;
+    bp.pix = pix;
+    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
+    bp.rx = rd[0], bp.ry = rd[HW], bp.rz = rd[2 * HW];
+    bp.rrz = 1.0f / bp.rz;
+    bp.zx = p.z_dir[3 * n + 0], bp.zy = p.z_dir[3 * n + 1], bp.zz = p.z_dir[3 * n + 2];
+    float dot = bp.rx * bp.zx;   // (this association: the forward's)
+    dot = dot + bp.ry * bp.zy;
+    dot = dot + bp.rz * bp.zz;
+    bp.dot = dot;
+    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
+    const float* __restrict__ g = g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
+    bp.gr = active ? scale * g[0] : 0.f, bp.gg = active ? scale * g[HW] : 0.f, bp.gb = active ? scale * g[2 * HW] : 0.f;
+    bp.gz = (active && g_depth) ? g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
+    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : (MASKED ? 1.0f : 0.0f);
+    if (active) bp.T = total_transmittance<TexT, AC>(p, vw.dhw, vol, t_fwd, p.T_out != nullptr, vw.ex, vw.ey, vw.ez, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy);
+    if (active && g_T) bp.S = g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
+}
+
+// Where the pixel's ray meets plane k of its view's MPI, by the forward's strict-order chain (compiler divisions).
+template <bool AC>
+__device__ __forceinline__ void pixel_plane_coord(const BwdView& vw, const BwdPixel& bp, int k, float& ix, float& iy, float& s) {
+    float u, v;
+    plane_coord<AC>(vw.dhw[3 * k] - vw.ez, vw.dhw[3 * k + 1], vw.dhw[3 * k + 2], vw.ex, vw.ey, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy, ix, iy, s, u, v);
+}
 
 template <typename TexT> __device__ __forceinline__ void load_pair(const unsigned char* __restrict__ base, uint32_t byte_off, float& a, float& b) {
     const TexT* __restrict__ q = reinterpret_cast<const TexT*>(base + byte_off);
@@ -76,6 +164,142 @@ template <> __device__ __forceinline__ void load_pair<float>(const unsigned char
     float v[2];
     __builtin_memcpy(v, base + byte_off, 8);  // (one global_load_dwordx2 at dword alignment, uniform base + 32-bit lane offset)
     a = v[0], b = v[1];
+}
+
+// ---- taps fetched as (x, x + 1) pairs: 8 loads of 8 bytes instead of 16 of 4 for fp32 volumes, at 32-bit offsets from a uniform base (the launcher
+// checks Wt >= 2 and that a plane's byte offsets fit 32 bits).  What a plane keeps between the issue of its taps and their use:
+struct PairTaps {
+    float s, wx1, wy1;   // depth factor; ix - floor(ix), iy - floor(iy)
+    int x0, y0;          // floor(ix), floor(iy); -2 = out of range (NaN / huge coordinates: all weights 0)
+    float v[16];         // per channel (top p0, p1 | bottom p0, p1)
+};
+// Coordinates of the pixel on a plane (the default mode's chain; pa = zdiff, w/2, h/2, RN(2/w); rh = RN(2/h)): fills q.s .. q.y0, returns (ix, iy).
+template <bool AC>
+__device__ __forceinline__ void pair_tap_coord(PairTaps& q, const BwdPixel& bp, const BwdView& vw, const float4 pa, float rh, int Ht, int Wt, float& ix, float& iy) {
+    plane_coord_recip<AC>(pa.x, pa.y, pa.z, pa.w, rh, vw.ex, vw.ey, bp.rx, bp.ry, bp.rz, bp.rrz, vw.cx, vw.cy, ix, iy, q.s);
+    const float fx = floorf(ix), fy = floorf(iy);
+    q.wx1 = ix - fx, q.wy1 = iy - fy;
+    q.x0 = (fx >= -2.0f && fx <= static_cast<float>(Wt)) ? static_cast<int>(fx) : -2;
+    q.y0 = (fy >= -2.0f && fy <= static_cast<float>(Ht)) ? static_cast<int>(fy) : -2;
+}
+// The 8 pair loads of q's footprint; pl = channel 0 of the plane, strides in bytes.
+template <typename TexT>
+__device__ __forceinline__ void fetch_pair_taps(PairTaps& q, const TexT* __restrict__ plane, uint32_t s_chan_b, uint32_t s_row_b, int Ht, int Wt) {
+    constexpr int kES = static_cast<int>(sizeof(TexT));
+    const int xa = min(max(q.x0, 0), Wt - 2);
+    const int ya = min(max(q.y0, 0), Ht - 1), yb = min(max(q.y0 + 1, 0), Ht - 1);
+    const unsigned char* __restrict__ pl = reinterpret_cast<const unsigned char*>(plane);
+    const uint32_t oa = static_cast<uint32_t>(ya) * s_row_b + static_cast<uint32_t>(xa) * kES;
+    const uint32_t ob = static_cast<uint32_t>(yb) * s_row_b + static_cast<uint32_t>(xa) * kES;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        load_pair<TexT>(pl, oa + c4 * s_chan_b, q.v[4 * c4 + 0], q.v[4 * c4 + 1]);
+        load_pair<TexT>(pl, ob + c4 * s_chan_b, q.v[4 * c4 + 2], q.v[4 * c4 + 3]);
+    }
+}
+// The taps have landed: the bilinear samples (zeros padding: the weight of a tap outside the texture is 0).
+__device__ __forceinline__ void pair_samples(const PairTaps& q, int Ht, int Wt, float (&smp)[4]) {
+    const int x0 = q.x0, y0 = q.y0;
+    const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
+    const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
+    const float wx0 = x0in ? 1.0f - q.wx1 : 0.0f, wx1 = x1in ? q.wx1 : 0.0f;
+    const float wy0 = y0in ? 1.0f - q.wy1 : 0.0f, wy1 = y1in ? q.wy1 : 0.0f;
+    // the pair (p0, p1) sits at columns (xa, xa + 1), xa = clamp(x0, 0, Wt - 2): at the left border (x0 = -1) the tap x0 + 1 is p0, at the
+    // right border (x0 = Wt - 1) the tap x0 is p1
+    const int sh = x0 - min(max(x0, 0), Wt - 2);
+    const float a0 = sh == 0 ? wx0 : (sh < 0 ? wx1 : 0.0f), a1 = sh == 0 ? wx1 : (sh > 0 ? wx0 : 0.0f);
+    const float w00 = a0 * wy0, w01 = a1 * wy0, w10 = a0 * wy1, w11 = a1 * wy1;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        float acc_s = q.v[4 * c4 + 0] * w00;
+        acc_s = __builtin_fmaf(q.v[4 * c4 + 1], w01, acc_s);
+        acc_s = __builtin_fmaf(q.v[4 * c4 + 2], w10, acc_s);
+        smp[c4] = __builtin_fmaf(q.v[4 * c4 + 3], w11, acc_s);
+    }
+}
+
+// ---- texel box of a pixel tile on one plane ---------------------------------------------------------------------------------------------------
+// The tile's corner pixels (cx0, cy0), (cx1, cy0), (cx0, cy1), (cx1, cy1) map to (cix, ciy)[0..3] (the forward's chain; rdv = the view's rays); a
+// pinhole ray field maps pixel lines to lines, so every tap of the tile lies in the box of those images grown by 1/64 texel + the 2 x 2 support.
+// Returns (bx0, by0, nx, ny); nx = 0: not staged -- the images are not finite (all four fields 0) or the box exceeds pitch x rows.
+template <bool AC>
+__device__ __forceinline__ int4 tile_box(const KParams& p, const BwdView& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0,
+                                         int cx1, int cy0, int cy1, int pitch, int rows, float (&cix)[4], float (&ciy)[4]) {
+    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
+    bool finite = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
+        float ix, iy, s, u, v;
+        plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[vw.HW + q], rdv[2 * vw.HW + q], vw.cx, vw.cy, ix, iy, s, u, v);
+        finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
+        mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
+        cix[c] = ix, ciy[c] = iy;
+    }
+    int4 bb = make_int4(0, 0, 0, 0);
+    if (finite) {
+        const float eps = 1.0f / 64;
+        bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
+        bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
+        if (bb.z > pitch || bb.w > rows) bb.z = 0;
+    }
+    return bb;
+}
+template <bool AC>
+__device__ __forceinline__ int4 tile_box(const KParams& p, const BwdView& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0,
+                                         int cx1, int cy0, int cy1, int pitch, int rows) {
+    float cix[4], ciy[4];
+    return tile_box<AC>(p, vw, rdv, zdiff, ph, pw, cx0, cx1, cy0, cy1, pitch, rows, cix, ciy);
+}
+
+// ---- primitives of the staged (fixed-point, LDS) scatters ---------------------------------------------------------------------------------------
+// round to nearest (floor(x + 0.5)) in one instruction: the staged sums must not be biased -- with a texture much coarser than the image a hundred
+// taps meet in one texel, and a truncating conversion adds up to half a unit of the fixed-point grid PER TAP in one direction
+__device__ __forceinline__ int cvt_rpi_i32(float x) {
+    int r;
+    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+// w = hi * 2^12 + lo with integers hi = RN(w / 4096) and lo = RN(w - 4096 hi): the remainder is exact (one FMA: w has 24 significant bits) and
+// |lo| <= 2048, so the pair is w rounded to the nearest integer; hi fits 32 bits for |w| < 2^43.
+__device__ __forceinline__ void fix_split(float w, int& hi, int& lo) {
+    hi = cvt_rpi_i32(w * (1.0f / 4096.0f));
+    lo = cvt_rpi_i32(__builtin_fmaf(-static_cast<float>(hi), 4096.0f, w));
+}
+// fp32 -> 64-bit fixed point without a trip through fp64 (a double conversion and an f64 -> i64 expansion per add were most of the scatter's VALU
+// work): v scale (a power of two: exact) as 4096 hi + lo (one v_mad_i64_i32).
+__device__ __forceinline__ unsigned long long to_fix(float v, float scale) {
+    int hi, lo;
+    fix_split(v * scale, hi, lo);
+    return static_cast<unsigned long long>(static_cast<long long>(hi) * 4096ll + static_cast<long long>(lo));
+}
+// |v| as a word that orders like the magnitude (non-negative floats order like their bit patterns), NaN / Inf on top
+__device__ __forceinline__ uint32_t abs_bits(float v) { return (v != v) ? 0x7fc00000u : __float_as_uint(fabsf(v)); }
+// Workgroup barrier that orders LDS only.  `__syncthreads()` is a workgroup-scope fence over EVERY address space: on this part it drains vmcnt, i.e.
+// every plane would wait for its own tap prefetch and for the flush's global atomics.  Between the planes of a sweep only LDS state is shared.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Maximum of an unsigned word over the 64 lanes of a wave (EVERY lane must be enabled).  Two forms, each kept where it was measured:
+// wave_max_u32 -- a scalar result; four row shifts and two row broadcasts on the DPP path (tile2).  (Left to the compiler, `atomicMax` on a
+// wave-uniform LDS address becomes a SCALAR loop over the lanes -- s_ff1 / v_readlane / s_max, 64 rounds of 7 instructions per wave and plane: it
+// was two thirds of that kernel's pixel phase.)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    auto step = [&](auto ctrl, auto rows) {
+        const uint32_t o = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), decltype(ctrl)::value, decltype(rows)::value, 0xf, true));
+        v = max(v, o);
+    };
+    step(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});   // row_shr:1
+    step(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});   // row_shr:2
+    step(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});   // row_shr:4
+    step(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});   // row_shr:8   -> lane 15 of a row: the row's maximum
+    step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});   // row_bcast:15 into rows 1, 3
+    step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});   // row_bcast:31 into rows 2, 3 -> lane 63: the wave's maximum
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
+}
+// wave_max_bits -- the maximum in every lane, by xor shuffles (the shared-colour tile kernel).
+__device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));
+    return v;
 }
 
 }  // namespace gmpi

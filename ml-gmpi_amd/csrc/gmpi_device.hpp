@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace gmpi {
@@ -89,6 +91,23 @@ struct f16_t { _Float16 v; };
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return __uint_as_float(static_cast<uint32_t>(v.bits) << 16); }
 __device__ __forceinline__ float to_f32(f16_t v) { return static_cast<float>(v.v); }
+
+// Host side: a run-time dtype (GMPI_DTYPE_F32 / _BF16 / _F16 = 0 / 1 / 2, validated by the C ABI) or flag picks the template instance.
+// f is a generic lambda: it gets TypeTag<float | bf16_t | f16_t>{} (storage type: `typename decltype(t)::type`), resp. std::true_type{} /
+// std::false_type{} (`decltype(b)::value`), and its result is passed on.
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+inline auto dispatch_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case 0: return f(TypeTag<float>{});
+        case 1: return f(TypeTag<bf16_t>{});
+        default: return f(TypeTag<f16_t>{});
+    }
+}
+template <typename F>
+inline auto dispatch_bool(bool flag, F&& f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---- ray/plane intersection -> unnormalised texture coordinates --------------------------------
 // One rounding per line, in the reference's order.

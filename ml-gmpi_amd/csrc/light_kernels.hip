@@ -228,9 +228,7 @@ int gmpi_light_apply_launch(const void* rgba, int32_t rgba_dtype, const int64_t*
     if (rgba_dtype < GMPI_DTYPE_F32 || rgba_dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
     if (rgba_stride[4] != 1 || rgba_stride[3] < W || rgba_stride[2] <= 0 || rgba_stride[1] <= 0 || rgba_stride[0] < 0) return GMPI_E_STRIDE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (rgba_dtype == GMPI_DTYPE_F32) launch_light_apply<float>(rgba, rgba_stride, shading, out, B, D, H, W, st);
-    else if (rgba_dtype == GMPI_DTYPE_BF16) launch_light_apply<bf16_t>(rgba, rgba_stride, shading, out, B, D, H, W, st);
-    else launch_light_apply<f16_t>(rgba, rgba_stride, shading, out, B, D, H, W, st);
+    dispatch_dtype(rgba_dtype, [&](auto t) { launch_light_apply<typename decltype(t)::type>(rgba, rgba_stride, shading, out, B, D, H, W, st); });
     return rc_of(hipGetLastError());
 }
 
@@ -249,11 +247,13 @@ int gmpi_light_apply_backward_launch(const void* rgba, int32_t rgba_dtype, const
                      reinterpret_cast<uintptr_t>(shading) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_out) % 16 == 0 &&
                      reinterpret_cast<uintptr_t>(grad_rgba) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_shading) % 16 == 0;
     const dim3 block(256), grid(((vec ? W / 4 : W) + 255) / 256, H, B);
-#define GMPI_LAB(T, V) hipLaunchKernelGGL((light_apply_backward_kernel<T, V>), grid, block, 0, st, static_cast<const T*>(rgba), sb, sd, sc, sr, shading, grad_out, grad_rgba, grad_shading, D, H, W)
-    if (rgba_dtype == GMPI_DTYPE_F32) { if (vec) GMPI_LAB(float, 4); else GMPI_LAB(float, 1); }
-    else if (rgba_dtype == GMPI_DTYPE_BF16) { if (vec) GMPI_LAB(bf16_t, 4); else GMPI_LAB(bf16_t, 1); }
-    else { if (vec) GMPI_LAB(f16_t, 4); else GMPI_LAB(f16_t, 1); }
-#undef GMPI_LAB
+    dispatch_dtype(rgba_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        dispatch_bool(vec, [&](auto VEC) {
+            hipLaunchKernelGGL((light_apply_backward_kernel<T, decltype(VEC)::value ? 4 : 1>), grid, block, 0, st, static_cast<const T*>(rgba), sb, sd, sc, sr, shading,
+                               grad_out, grad_rgba, grad_shading, D, H, W);
+        });
+    });
     return rc_of(hipGetLastError());
 }
 
@@ -269,9 +269,11 @@ int gmpi_alpha_depth_backward_ex_launch(const void* alpha, int32_t alpha_dtype, 
     if (!grad_depth && !grad_transmittance) return GMPI_OK;   // (nothing to add)
     const dim3 grid((W + 255) / 256, H, B), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (alpha_dtype == GMPI_DTYPE_F32) hipLaunchKernelGGL(alpha_depth_backward_kernel<float>, grid, block, 0, st, static_cast<const float*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
-    else if (alpha_dtype == GMPI_DTYPE_BF16) hipLaunchKernelGGL(alpha_depth_backward_kernel<bf16_t>, grid, block, 0, st, static_cast<const bf16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
-    else hipLaunchKernelGGL(alpha_depth_backward_kernel<f16_t>, grid, block, 0, st, static_cast<const f16_t*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
+    dispatch_dtype(alpha_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(alpha_depth_backward_kernel<T>, grid, block, 0, st, static_cast<const T*>(alpha), stride_b, stride_d, stride_row, plane_ds, transmittance,
+                           grad_depth, grad_transmittance, grad_alpha, gstride_b, gstride_d, gstride_row, D, H, W);
+    });
     return rc_of(hipGetLastError());
 }
 

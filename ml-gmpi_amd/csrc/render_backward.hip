@@ -20,7 +20,6 @@
 #include "gmpi_backward.hpp"
 
 #include <cstdlib>
-#include <type_traits>
 
 namespace gmpi {
 
@@ -30,36 +29,18 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, c
     const int px = blockIdx.x * 64 + threadIdx.x;
     const int py = blockIdx.y * 4 + threadIdx.y;
     if (px >= p.W || py >= p.H) return;
-    uint32_t bad_index = 0;  // (the forward reports a bad view index; here it is only clamped)
-    const int m = view_mpi(p, n, bad_index);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(py) * p.W + px;
-    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float rx = rd[0], ry = rd[HW], rz = rd[2 * HW];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    float dot = rx * zx;
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
+    const BwdView vw = bwd_view<AC>(p, n);
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
-    const float* __restrict__ g = b.g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float gr = scale * g[0], gg = scale * g[HW], gb = scale * g[2 * HW];
-    const float gz = b.g_depth ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(m) * b.gs_mpi;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, b.g_rgb, b.g_depth, b.g_T, vol);
 
     // ---- back-to-front sweep: gradients, scattered with the bilinear weights --------------------------------------
-    const float t_fwd = p.T_out ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    BwdPixel bp{gr, gg, gb, gz, dot, total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy), 0.0f};
-    if (b.g_T) bp.S = b.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
     uint32_t unused = 0;
     for (int k = p.D - 1; k >= 0; --k) {
-        float ix, iy, s, u, v;
-        plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
+        float ix, iy, s;
+        pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
         float smp[4], d_s[4];
         gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
         bp.plane(smp, s, d_s);
@@ -108,34 +89,17 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
     const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
     const int px = txi * kBwdTW + (tid % kBwdTW), py = tyi * kBwdTH + (tid / kBwdTW);
     const bool active = px < p.W && py < p.H;
-    uint32_t bad_index = 0;  // (the forward reports a bad view index; here it is only clamped)
-    const int m = view_mpi(p, n, bad_index);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
-    const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    float dot = rx * zx;
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
+    const BwdView vw = bwd_view<AC>(p, n);
+    const float* __restrict__ dhw = vw.dhw;
+    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * vw.HW;
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
-    const float* __restrict__ g = b.g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float gr = active ? scale * g[0] : 0.f, gg = active ? scale * g[HW] : 0.f, gb = active ? scale * g[2 * HW] : 0.f;
-    const float gz = (active && b.g_depth) ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(m) * b.gs_mpi;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
 
     for (int i = tid; i < kBwdCap; i += kBwdThreads) acc[i] = 0ull;
 
-    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
-    BwdPixel bp{gr, gg, gb, gz, dot, XT{1.0f, 0}, 0.0f};
-    if (active) bp.T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
-    if (active && b.g_T) bp.S = b.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
     uint32_t unused = 0;
 
     // ---- back-to-front sweep: gradients; scatter through the LDS boxes ------------------------------------------
@@ -146,25 +110,7 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
         __syncthreads();  // previous chunk's table no longer read; (first pass) the zero fill is complete
         for (int t = tid; t < kn; t += kBwdThreads) {
             const int k = kc + t;
-            const float zdiff = dhw[3 * k] - ez, ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
-            float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-            bool finite = true;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
-                float ix, iy, s, u, v;
-                plane_coord<AC>(zdiff, ph, pw, ex, ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], cx, cy, ix, iy, s, u, v);
-                finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
-                mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-            }
-            int4 bb = make_int4(0, 0, 0, 0);
-            if (finite) {
-                const float eps = 1.0f / 64;
-                bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
-                bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
-                if (bb.z > kBwdPitch || bb.w > kBwdRows) bb.z = 0;
-            }
-            box[t] = bb;
+            box[t] = tile_box<AC>(p, vw, rdv, dhw[3 * k] - vw.ez, dhw[3 * k + 1], dhw[3 * k + 2], cx0, cx1, cy0, cy1, kBwdPitch, kBwdRows);
             gmax[t] = 0u;
         }
         __syncthreads();
@@ -175,16 +121,13 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
             float d_s[4] = {0.f, 0.f, 0.f, 0.f};
             Footprint f{};
             if (active) {
-                float ix, iy, s, u, v;
-                plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
+                float ix, iy, s;
+                pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
                 float smp[4];
                 gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
                 bp.plane(smp, s, d_s);
                 f = footprint(ix, iy, Ht, Wt);
-                if (bb.z > 0) {  // non-negative floats order like their bit patterns; NaN/Inf end up on top
-                    const float m = fmaxf(fmaxf(fabsf(d_s[0]), fabsf(d_s[1])), fmaxf(fabsf(d_s[2]), fabsf(d_s[3])));
-                    atomicMax(&gmax[t], (m != m) ? 0x7fc00000u : __float_as_uint(m));
-                }
+                if (bb.z > 0) atomicMax(&gmax[t], abs_bits(fmaxf(fmaxf(fabsf(d_s[0]), fabsf(d_s[1])), fmaxf(fabsf(d_s[2]), fabsf(d_s[3])))));
             }
             __syncthreads();  // gmax[t] complete; the previous plane's flush is finished
             const uint32_t mb = gmax[t];
@@ -288,31 +231,6 @@ using B2Tall = B2Geo<32, 16, 56, 27>;   // 23.6 KB per box
 using B2Wide = B2Geo<64, 8, 80, 19>;    // 23.8 KB per box
 constexpr int kBwdDefaultGeo = 2;       // 1 = 32 x 16 tiles (round 5) | 2 = 64 x 8 tiles (profiles/r06_backward.txt)
 
-// round to nearest (floor(x + 0.5)) in one instruction: the staged sums must not be biased -- with a texture much coarser than the image a hundred
-// taps meet in one texel, and a truncating conversion adds up to half a unit of the fixed-point grid PER TAP in one direction
-__device__ __forceinline__ int cvt_rpi(float x) {
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// Maximum of an unsigned word over the 64 lanes of a wave (EVERY lane must be enabled), as a scalar: four row shifts and two row broadcasts on
-// the DPP path.  (Left to the compiler, `atomicMax` on a wave-uniform LDS address becomes a SCALAR loop over the lanes -- s_ff1 / v_readlane /
-// s_max, 64 rounds of 7 instructions per wave and plane: it was two thirds of this kernel's pixel phase.)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    auto step = [&](auto ctrl, auto rows) {
-        const uint32_t o = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), decltype(ctrl)::value, decltype(rows)::value, 0xf, true));
-        v = max(v, o);
-    };
-    step(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});   // row_shr:1
-    step(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});   // row_shr:2
-    step(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});   // row_shr:4
-    step(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});   // row_shr:8   -> lane 15 of a row: the row's maximum
-    step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});   // row_bcast:15 into rows 1, 3
-    step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});   // row_bcast:31 into rows 2, 3 -> lane 63: the wave's maximum
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
-}
-
 template <typename TexT, bool AC, typename G>
 __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(const KParams p, const BwdParams b, const int tiles_x) {
     constexpr int kB2TW = G::TW, kB2TH = G::TH, kB2Pitch = G::Pitch, kB2Rows = G::Rows, kB2Cap = G::Cap;
@@ -343,23 +261,17 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
     const int px = txi * kB2TW + (ptid % kB2TW), py = tyi * kB2TH + (ptid / kB2TW);
     const bool active = !flusher && px < p.W && py < p.H;
-    uint32_t bad_index = 0;  // (the forward reports a bad view index; here it is only clamped)
-    const int m = view_mpi(p, n, bad_index);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
+    const BwdView vw = bwd_view<AC>(p, n);
+    const float* __restrict__ dhw = vw.dhw;
+    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * vw.HW;
 #ifdef GMPI_TUNE
     const bool abl_noglobal = (p.flags & (1u << 20)) != 0, abl_nolds = (p.flags & (1u << 21)) != 0, abl_notaps = (p.flags & (1u << 23)) != 0;
 #else
     constexpr bool abl_noglobal = false, abl_nolds = false, abl_notaps = false;
 #endif
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(m) * b.gs_mpi;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
     // (the launcher has checked that a plane's byte offsets fit 32 bits, for the volume and for its gradient)
     const uint32_t s_chan_b = static_cast<uint32_t>(p.s_chan) * kES, s_row_b = static_cast<uint32_t>(p.s_row) * kES;
     const uint32_t gs_chan = static_cast<uint32_t>(b.gs_chan), gs_row = static_cast<uint32_t>(b.gs_row);
@@ -368,96 +280,37 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
 
     // the pixel's own state: loaded by the PIXEL waves only (a load a flush wave issued and never used would stay "pending" for the
     // compiler's wait-count insertion, which then drains vmcnt -- the flush's own atomics -- in front of the first overwrite of its register)
-    float rx = 0.0f, ry = 0.0f, rz = 1.0f, rrz = 1.0f, dot = 0.0f, gr = 0.0f, gg = 0.0f, gb = 0.0f, gz = 0.0f;
-    XT T{1.0f, 0};
-    float S = 0.0f;
-    if (!flusher) {
-        rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
-        rrz = 1.0f / rz;
-        const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-        dot = rx * zx;
-        dot = dot + ry * zy;
-        dot = dot + rz * zz;
-        const float oscale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
-        const float* __restrict__ g = b.g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
-        gr = active ? oscale * g[0] : 0.f, gg = active ? oscale * g[HW] : 0.f, gb = active ? oscale * g[2 * HW] : 0.f;
-        gz = (active && b.g_depth) ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-        const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
-        if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
-        if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();
-    }
+    BwdPixel bp;
+    if (!flusher) bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
 
-    // what a plane keeps between the issue of its taps and their use (Tap), and between its gradients and their scatter (Grad)
-    struct Tap { float s, wx1, wy1; int x0, y0; float v[16]; };   // v: per channel (top p0, p1 | bottom p0, p1)
+    // what a plane keeps between the issue of its taps and their use (PairTaps), and between its gradients and their scatter (Grad)
     struct Grad { float d[4]; float nw, ne, sw, se; int x0, y0; };   // (weights of taps outside the texture are 0)
 
     // coordinates of this pixel on plane (chunk-local index t) + its 8 pair loads
-    auto fetch = [&](int t, int k, Tap& q) {
-        const float4 a = pcA[t];
-        const float2 c = pcB[t];
+    auto fetch = [&](int t, int k, PairTaps& q) {
         float ix, iy;
-        plane_coord_recip<AC>(a.x, a.y, a.z, a.w, c.x, ex, ey, rx, ry, rz, rrz, cx, cy, ix, iy, q.s);
-        const float fx = floorf(ix), fy = floorf(iy);
-        q.wx1 = ix - fx, q.wy1 = iy - fy;
-        q.x0 = (fx >= -2.0f && fx <= static_cast<float>(Wt)) ? static_cast<int>(fx) : -2;   // (NaN / huge coordinates: out of range, all weights 0)
-        q.y0 = (fy >= -2.0f && fy <= static_cast<float>(Ht)) ? static_cast<int>(fy) : -2;
+        pair_tap_coord<AC>(q, bp, vw, pcA[t], pcB[t].x, Ht, Wt, ix, iy);
         if (abl_notaps) return;
-        const int xa = min(max(q.x0, 0), Wt - 2);
-        const int ya = min(max(q.y0, 0), Ht - 1), yb = min(max(q.y0 + 1, 0), Ht - 1);
-        const unsigned char* __restrict__ pl = reinterpret_cast<const unsigned char*>(vol + static_cast<int64_t>(k) * p.s_plane);
-        const uint32_t oa = static_cast<uint32_t>(ya) * s_row_b + static_cast<uint32_t>(xa) * kES;
-        const uint32_t ob = static_cast<uint32_t>(yb) * s_row_b + static_cast<uint32_t>(xa) * kES;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            load_pair<TexT>(pl, oa + c4 * s_chan_b, q.v[4 * c4 + 0], q.v[4 * c4 + 1]);
-            load_pair<TexT>(pl, ob + c4 * s_chan_b, q.v[4 * c4 + 2], q.v[4 * c4 + 3]);
-        }
+        fetch_pair_taps<TexT>(q, vol + static_cast<int64_t>(k) * p.s_plane, s_chan_b, s_row_b, Ht, Wt);
     };
-    // the taps have landed: bilinear samples, the plane's gradients (the arithmetic of BwdPixel::plane), the tile maximum
-    auto grads = [&](int t, const Tap& q, Grad& gq) -> uint2 {
-        const int x0 = q.x0, y0 = q.y0;
-        const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
-        const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
-        const float wx0 = x0in ? 1.0f - q.wx1 : 0.0f, wx1 = x1in ? q.wx1 : 0.0f;
-        const float wy0 = y0in ? 1.0f - q.wy1 : 0.0f, wy1 = y1in ? q.wy1 : 0.0f;
-        // the pair (p0, p1) sits at columns (xa, xa + 1), xa = clamp(x0, 0, Wt - 2): at the left border (x0 = -1) the tap x0 + 1 is p0, at the
-        // right border (x0 = Wt - 1) the tap x0 is p1
-        const int sh = x0 - min(max(x0, 0), Wt - 2);
-        const float a0 = sh == 0 ? wx0 : (sh < 0 ? wx1 : 0.0f), a1 = sh == 0 ? wx1 : (sh > 0 ? wx0 : 0.0f);
-        const float w00 = a0 * wy0, w01 = a1 * wy0, w10 = a0 * wy1, w11 = a1 * wy1;
+    // the taps have landed: bilinear samples, the plane's gradients, the tile maximum
+    auto grads = [&](int t, const PairTaps& q, Grad& gq) -> uint2 {
         float smp[4];
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            float acc_s = q.v[4 * c4 + 0] * w00;
-            acc_s = __builtin_fmaf(q.v[4 * c4 + 1], w01, acc_s);
-            acc_s = __builtin_fmaf(q.v[4 * c4 + 2], w10, acc_s);
-            smp[c4] = __builtin_fmaf(q.v[4 * c4 + 3], w11, acc_s);
-        }
-        {   // T_k = T_{k+1} / om, the gradients, the suffix sum
-            const float alpha = smp[3];
-            const float om = (1.0f - alpha) + 1e-10f;
-            float r = __builtin_amdgcn_rcpf(om);
-            r = __builtin_fmaf(__builtin_fmaf(-om, r, 1.0f), r, r);      // Newton step: r = RN(1 / om) up to the last bit
-            T.m = div_by_recip(T.m, om, r);
-            T.renorm();
-            const float Tk = T.value();
-            const float qv = gr * smp[0] + gg * smp[1] + gb * smp[2] + gz * (q.s * dot);
-            const float w = alpha * Tk;
-            gq.d[0] = gr * w, gq.d[1] = gg * w, gq.d[2] = gb * w;
-            gq.d[3] = Tk * qv - div_by_recip(S, om, r);
-            S += w * qv;
-        }
+        pair_samples(q, Ht, Wt, smp);
+        bp.plane_recip(smp, q.s, gq.d);
         {   // the scatter weights of the true taps (x0, y0) .. (x0 + 1, y0 + 1)
+            const int x0 = q.x0, y0 = q.y0;
+            const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
+            const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
             const float ux0 = 1.0f - q.wx1, uy0 = 1.0f - q.wy1;
             gq.nw = (x0in && y0in) ? ux0 * uy0 : 0.0f, gq.ne = (x1in && y0in) ? q.wx1 * uy0 : 0.0f;
             gq.sw = (x0in && y1in) ? ux0 * q.wy1 : 0.0f, gq.se = (x1in && y1in) ? q.wx1 * q.wy1 : 0.0f;
+            gq.x0 = x0, gq.y0 = y0;
         }
-        gq.x0 = x0, gq.y0 = y0;
-        // non-negative floats order like their bit patterns; NaN/Inf end up on top.  Colour and alpha apart: on a thin plane (a_k of a few
-        // percent) the colour gradients w_k g are a hundred times smaller than dL/da_k, and a fixed-point grid sized for the latter is a hundred
-        // times coarser for them (seen as 6e-4 of a plane's own largest colour gradient where many taps meet in a texel)
-        const float mc = fmaxf(fmaxf(fabsf(gq.d[0]), fabsf(gq.d[1])), fabsf(gq.d[2])), ma = fabsf(gq.d[3]);
-        return make_uint2((mc != mc) ? 0x7fc00000u : __float_as_uint(mc), (ma != ma) ? 0x7fc00000u : __float_as_uint(ma));
+        // Colour and alpha apart: on a thin plane (a_k of a few percent) the colour gradients w_k g are a hundred times smaller than dL/da_k, and
+        // a fixed-point grid sized for the latter is a hundred times coarser for them (seen as 6e-4 of a plane's own largest colour gradient where
+        // many taps meet in a texel)
+        return make_uint2(abs_bits(fmaxf(fmaxf(fabsf(gq.d[0]), fabsf(gq.d[1])), fabsf(gq.d[2]))), abs_bits(gq.d[3]));
     };
     // the tile maxima of a plane: one LDS atomic instruction per wave, lane 0 the colour maximum, lane 1 the alpha maximum (every lane of
     // the wave must call this)
@@ -490,8 +343,8 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
             uint32_t* __restrict__ l0 = bx_acc + ly * (4 * kB2Pitch) + lx;
             if (wide && !abl_nolds) {
                 auto add2 = [&](uint32_t* __restrict__ cell, float v) {   // v = hi * 2^12 + lo exactly (fp32: 24 significant bits), hi rounded to nearest
-                    const int hi = cvt_rpi(v * (1.0f / 4096.0f));
-                    const int lo = cvt_rpi(__builtin_fmaf(-static_cast<float>(hi), 4096.0f, v));
+                    int hi, lo;
+                    fix_split(v, hi, lo);
                     atomicAdd(cell, static_cast<uint32_t>(hi));
                     atomicAdd(cell + kB2Cap / 2, static_cast<uint32_t>(lo));
                 };
@@ -508,10 +361,10 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
                     uint32_t* __restrict__ lc = l0 + c4 * kB2Pitch;
                     // (a tap outside the texture has weight 0 and adds 0 to a box cell outside the texture, which the flush never writes out;
                     //  round to nearest: at most half a unit of 2^-(30 - h) M per add, in either direction)
-                    atomicAdd(lc, static_cast<uint32_t>(cvt_rpi(d * nw)));
-                    atomicAdd(lc + 1, static_cast<uint32_t>(cvt_rpi(d * ne)));
-                    atomicAdd(lc + 4 * kB2Pitch, static_cast<uint32_t>(cvt_rpi(d * sw)));
-                    atomicAdd(lc + 4 * kB2Pitch + 1, static_cast<uint32_t>(cvt_rpi(d * se)));
+                    atomicAdd(lc, static_cast<uint32_t>(cvt_rpi_i32(d * nw)));
+                    atomicAdd(lc + 1, static_cast<uint32_t>(cvt_rpi_i32(d * ne)));
+                    atomicAdd(lc + 4 * kB2Pitch, static_cast<uint32_t>(cvt_rpi_i32(d * sw)));
+                    atomicAdd(lc + 4 * kB2Pitch + 1, static_cast<uint32_t>(cvt_rpi_i32(d * se)));
                 }
             }
         }
@@ -611,46 +464,29 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     auto build_tables = [&](int kc, int kn) {
         for (int t = tid; t < kn; t += kB2Threads) {
             const int k = kc + t;
-            const float zdiff = dhw[3 * k] - ez, ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
-            float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
+            const float zdiff = dhw[3 * k] - vw.ez, ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
             float cix[4], ciy[4];   // images of the tile's corner pixels (cx0, cy0), (cx1, cy0), (cx0, cy1), (cx1, cy1)
-            bool finite = true;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
-                float ix, iy, s, u, v;
-                plane_coord<AC>(zdiff, ph, pw, ex, ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], cx, cy, ix, iy, s, u, v);
-                finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
-                mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-                cix[c] = ix, ciy[c] = iy;
-            }
-            int4 bb = make_int4(0, 0, 0, 0);
+            const int4 bb = tile_box<AC>(p, vw, rdv, zdiff, ph, pw, cx0, cx1, cy0, cy1, kB2Pitch, kB2Rows, cix, ciy);
             int hbits = 11;
-            if (finite) {
-                const float eps = 1.0f / 64;
-                bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
-                bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
-                if (bb.z > kB2Pitch || bb.w > kB2Rows) bb.z = 0;
-                else {
-                    // taps that can meet in one texel: 4 x the tile's pixels per texel on average; 8 x + 8 is the bound used (a homography is
-                    // smooth over a tile), 2^11 = every tap of the tile when the footprint is only a few texels.  The density comes from the AREA of
-                    // the quadrilateral the tile's corner pixels map to (round 6; round 5 took the bounding box, which a rolled or sheared footprint
-                    // fills only partly: its density is then higher than the box average)
-                    const float quad2 = fabsf((cix[0] * ciy[1] - cix[1] * ciy[0]) + (cix[1] * ciy[3] - cix[3] * ciy[1]) + (cix[3] * ciy[2] - cix[2] * ciy[3]) +
-                                              (cix[2] * ciy[0] - cix[0] * ciy[2]));
-                    const int area = max(min(static_cast<int>(0.5f * quad2), (bb.z - 1) * (bb.w - 1)), 1);
-                    const int bound = (8 * npix + area - 1) / area + 8;
-                    hbits = min(11, 32 - __clz(bound - 1));
+            if (bb.z > 0) {   // staged
+                // taps that can meet in one texel: 4 x the tile's pixels per texel on average; 8 x + 8 is the bound used (a homography is
+                // smooth over a tile), 2^11 = every tap of the tile when the footprint is only a few texels.  The density comes from the AREA of
+                // the quadrilateral the tile's corner pixels map to (round 6; round 5 took the bounding box, which a rolled or sheared footprint
+                // fills only partly: its density is then higher than the box average)
+                const float quad2 = fabsf((cix[0] * ciy[1] - cix[1] * ciy[0]) + (cix[1] * ciy[3] - cix[3] * ciy[1]) + (cix[3] * ciy[2] - cix[2] * ciy[3]) +
+                                          (cix[2] * ciy[0] - cix[0] * ciy[2]));
+                const int area = max(min(static_cast<int>(0.5f * quad2), (bb.z - 1) * (bb.w - 1)), 1);
+                const int bound = (8 * npix + area - 1) / area + 8;
+                hbits = min(11, 32 - __clz(bound - 1));
 #ifdef GMPI_B2_HBITS  // (experiment: a fixed headroom)
-                    hbits = GMPI_B2_HBITS;
+                hbits = GMPI_B2_HBITS;
 #endif
-                    // WIDE planes: with 9 and more bits of headroom (a texture several times coarser than the image: a hundred and more taps
-                    // per texel) one 32-bit word leaves less than 2^-21 of the tile's largest gradient per add -- the round-1 kernel's 64-bit sums
-                    // were measurably better there (tools/fuzz_backward_gpu.py: 1.2e-5 against 2.5e-6 of the largest gradient).  Such a box is
-                    // small: when its rows fill at most half of the buffer, every cell gets a second word (the residual of the first, 12 bits
-                    // finer) in the other half.
-                    if (hbits >= 9 && bb.w * 4 * kB2Pitch <= kB2Cap / 2) hbits |= 0x100;
-                }
+                // WIDE planes: with 9 and more bits of headroom (a texture several times coarser than the image: a hundred and more taps
+                // per texel) one 32-bit word leaves less than 2^-21 of the tile's largest gradient per add -- the round-1 kernel's 64-bit sums
+                // were measurably better there (tools/fuzz_backward_gpu.py: 1.2e-5 against 2.5e-6 of the largest gradient).  Such a box is
+                // small: when its rows fill at most half of the buffer, every cell gets a second word (the residual of the first, 12 bits
+                // finer) in the other half.
+                if (hbits >= 9 && bb.w * 4 * kB2Pitch <= kB2Cap / 2) hbits |= 0x100;
             }
             box[t] = bb;
             gmax[t] = make_uint2(0u, 0u);
@@ -682,7 +518,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
             lds_barrier();  // previous chunk's tables and boxes are done with; (first pass) the zero fill is complete
             build_tables(kc, kn);
             lds_barrier();
-            Tap tq;
+            PairTaps tq;
             Grad gq;
 #pragma unroll
             for (int i = 0; i < 16; ++i) tq.v[i] = 0.0f;
@@ -737,8 +573,7 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
         v1 = v1 || (p.flags & (1u << 22)) != 0;  // GMPI_TUNE_SKIP=64: the round-1 tile kernel (A/B)
 #endif
         if (v1) {
-            if (ac) hipLaunchKernelGGL((render_backward_tile_kernel<TexT, true>), grid, block, 0, stream, p, b, tiles_x);
-            else hipLaunchKernelGGL((render_backward_tile_kernel<TexT, false>), grid, block, 0, stream, p, b, tiles_x);
+            dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_tile_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, tiles_x); });
             return hipGetLastError();
         }
         // Round 6: 64 x 8 pixel tiles (32 x 16 in round 5)
@@ -751,16 +586,14 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
             using G = decltype(geo_tag);
             const int tx = (p.W + G::TW - 1) / G::TW, ty = (p.H + G::TH - 1) / G::TH;
             const dim3 grid2(xcd_grid_per_group(tx * ty, tx * ty), p.N);
-            if (ac) hipLaunchKernelGGL((render_backward_tile2_kernel<TexT, true, G>), grid2, block2, 0, stream, p, b, tx);
-            else hipLaunchKernelGGL((render_backward_tile2_kernel<TexT, false, G>), grid2, block2, 0, stream, p, b, tx);
+            dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_tile2_kernel<TexT, decltype(AC)::value, G>), grid2, block2, 0, stream, p, b, tx); });
         };
         if (geo == 1) go(B2Tall{});
         else go(B2Wide{});
         return hipGetLastError();
     }
     const dim3 block(64, 4), grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
-    if (ac) hipLaunchKernelGGL((render_backward_kernel<TexT, true>), grid, block, 0, stream, p, b);
-    else hipLaunchKernelGGL((render_backward_kernel<TexT, false>), grid, block, 0, stream, p, b);
+    dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b); });
     return hipGetLastError();
 }
 
@@ -792,11 +625,7 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
     }
 #endif
     if (gather) return launch_backward_gather(p, dtype, b, (p.flags & (1u << 7)) != 0 /* GMPI_FLAG_GRAD_OVERWRITE */, stream);
-    switch (dtype) {
-        case 0: return launch_backward_t<float>(p, b, tiles, stream);
-        case 1: return launch_backward_t<bf16_t>(p, b, tiles, stream);
-        default: return launch_backward_t<f16_t>(p, b, tiles, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_backward_t<typename decltype(t)::type>(p, b, tiles, stream); });
 }
 
 }  // namespace gmpi

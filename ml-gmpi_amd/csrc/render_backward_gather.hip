@@ -7,7 +7,7 @@
 // 2.12 ms at 1024^2 x 32 x 4 where the launch without its global writes takes 1.27), needs a zero-filled gradient volume (0.32 ms) and, with the
 // write path behind the L2s as the shared resource, cannot be helped by storing what a tile owns (built and measured in round 6).  This file replaces the
 // scatter by a GATHER, so that every gradient cell is written exactly once, by the one workgroup that owns it:
-//   pass 1 (pixel_pass_kernel), pixel-stationary: the back-to-front sweep of render_backward.hip (same taps, same arithmetic), but instead of
+//   pass 1 (pixel_pass_kernel), pixel-stationary: the back-to-front sweep of the tile kernel (gmpi_backward.hpp: the same functions), but instead of
 //           scattering, every pixel WRITES its four sample gradients d_s = dL/d(r, g, b, alpha sample) per plane: G[n][k][py][px], 16 bytes,
 //           coalesced -- no LDS boxes, no barriers in the plane loop, no flush waves;
 //   pass 2 (texel_gather_kernel), texel-stationary: a workgroup owns a 64 x 16 texel tile of one plane of one MPI.  The pixels whose bilinear
@@ -133,85 +133,26 @@ __global__ __launch_bounds__(kPT, 6) void pixel_pass_kernel(const KParams p, con
     const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
     const int px = txi * kPTW + (tid % kPTW), py = tyi * kPTH + (tid / kPTW);
     const bool active = px < p.W && py < p.H;
-    uint32_t bad_index = 0;
-    const int m = view_mpi(p, n, bad_index);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
+    const BwdView vw = bwd_view<AC>(p, n);
+    const float* __restrict__ dhw = vw.dhw;
+    const int64_t HW = vw.HW;
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
     const uint32_t s_chan_b = static_cast<uint32_t>(p.s_chan) * kES, s_row_b = static_cast<uint32_t>(p.s_row) * kES;
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    const int64_t pix = bp.pix;
 
-    const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
-    const float rrz = 1.0f / rz;
-    float dot = rx * p.z_dir[3 * n + 0];
-    dot = dot + ry * p.z_dir[3 * n + 1];
-    dot = dot + rz * p.z_dir[3 * n + 2];
-    const float oscale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
-    const float* __restrict__ g = b.g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float gr = active ? oscale * g[0] : 0.f, gg = active ? oscale * g[HW] : 0.f, gb = active ? oscale * g[2 * HW] : 0.f;
-    const float gz = (active && b.g_depth) ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
-    XT T{1.0f, 0};
-    if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
-    float S = 0.0f;
-    if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
-
-    struct Tap { float s, wx1, wy1, ix, iy; int x0, y0; float v[16]; };   // v: per channel (top p0, p1 | bottom p0, p1)
-    auto fetch = [&](int t, int k, Tap& q) {   // coordinates of this pixel on plane k (chunk-local t) + its 8 pair loads
-        const float4 a = pcA[t];
-        float ix, iy;
-        plane_coord_recip<AC>(a.x, a.y, a.z, a.w, pcB[t], ex, ey, rx, ry, rz, rrz, cx, cy, ix, iy, q.s);
-        const float fx = floorf(ix), fy = floorf(iy);
-        q.wx1 = ix - fx, q.wy1 = iy - fy, q.ix = ix, q.iy = iy;
-        q.x0 = (fx >= -2.0f && fx <= static_cast<float>(Wt)) ? static_cast<int>(fx) : -2;   // (NaN / huge coordinates: out of range, all weights 0)
-        q.y0 = (fy >= -2.0f && fy <= static_cast<float>(Ht)) ? static_cast<int>(fy) : -2;
-        const int xa = min(max(q.x0, 0), Wt - 2);
-        const int ya = min(max(q.y0, 0), Ht - 1), yb = min(max(q.y0 + 1, 0), Ht - 1);
-        const unsigned char* __restrict__ pl = reinterpret_cast<const unsigned char*>(vol + static_cast<int64_t>(k) * p.s_plane);
-        const uint32_t oa = static_cast<uint32_t>(ya) * s_row_b + static_cast<uint32_t>(xa) * kES;
-        const uint32_t ob = static_cast<uint32_t>(yb) * s_row_b + static_cast<uint32_t>(xa) * kES;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            load_pair<TexT>(pl, oa + c4 * s_chan_b, q.v[4 * c4 + 0], q.v[4 * c4 + 1]);
-            load_pair<TexT>(pl, ob + c4 * s_chan_b, q.v[4 * c4 + 2], q.v[4 * c4 + 3]);
-        }
+    struct Tap { PairTaps q; float ix, iy; };   // + the exact sample position (the forward's chain): the texel pass decides membership on it
+    auto fetch = [&](int t, int k, Tap& tp) {   // coordinates of this pixel on plane k (chunk-local t) + its 8 pair loads
+        pair_tap_coord<AC>(tp.q, bp, vw, pcA[t], pcB[t], Ht, Wt, tp.ix, tp.iy);
+        fetch_pair_taps<TexT>(tp.q, vol + static_cast<int64_t>(k) * p.s_plane, s_chan_b, s_row_b, Ht, Wt);
     };
-    auto grads = [&](const Tap& q) -> float4 {   // the taps have landed: bilinear samples, the plane's gradients (the arithmetic of BwdPixel::plane)
-        const int x0 = q.x0, y0 = q.y0;
-        const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
-        const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
-        const float wx0 = x0in ? 1.0f - q.wx1 : 0.0f, wx1 = x1in ? q.wx1 : 0.0f;
-        const float wy0 = y0in ? 1.0f - q.wy1 : 0.0f, wy1 = y1in ? q.wy1 : 0.0f;
-        // the pair (p0, p1) sits at columns (xa, xa + 1), xa = clamp(x0, 0, Wt - 2): at the left border (x0 = -1) the tap x0 + 1 is p0, at the
-        // right border (x0 = Wt - 1) the tap x0 is p1
-        const int sh = x0 - min(max(x0, 0), Wt - 2);
-        const float a0 = sh == 0 ? wx0 : (sh < 0 ? wx1 : 0.0f), a1 = sh == 0 ? wx1 : (sh > 0 ? wx0 : 0.0f);
-        const float w00 = a0 * wy0, w01 = a1 * wy0, w10 = a0 * wy1, w11 = a1 * wy1;
-        float smp[4];
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            float acc_s = q.v[4 * c4 + 0] * w00;
-            acc_s = __builtin_fmaf(q.v[4 * c4 + 1], w01, acc_s);
-            acc_s = __builtin_fmaf(q.v[4 * c4 + 2], w10, acc_s);
-            smp[c4] = __builtin_fmaf(q.v[4 * c4 + 3], w11, acc_s);
-        }
-        const float alpha = smp[3];
-        const float om = (1.0f - alpha) + 1e-10f;
-        float r = __builtin_amdgcn_rcpf(om);
-        r = __builtin_fmaf(__builtin_fmaf(-om, r, 1.0f), r, r);      // Newton step: r = RN(1 / om) up to the last bit
-        T.m = div_by_recip(T.m, om, r);
-        T.renorm();
-        const float Tk = T.value();
-        const float qv = gr * smp[0] + gg * smp[1] + gb * smp[2] + gz * (q.s * dot);
-        const float w = alpha * Tk;
-        const float4 d = make_float4(gr * w, gg * w, gb * w, Tk * qv - div_by_recip(S, om, r));
-        S += w * qv;
-        return d;
+    auto grads = [&](const Tap& tp) -> float4 {   // the taps have landed: bilinear samples, the plane's gradients
+        float smp[4], d[4];
+        pair_samples(tp.q, Ht, Wt, smp);
+        bp.plane_recip(smp, tp.q.s, d);
+        return make_float4(d[0], d[1], d[2], d[3]);
     };
 
     f32x4* __restrict__ Gpix = G + static_cast<int64_t>(n) * p.D * HW + pix;   // + k * HW per plane
@@ -222,7 +163,7 @@ __global__ __launch_bounds__(kPT, 6) void pixel_pass_kernel(const KParams p, con
         for (int t = tid; t < kn; t += kPT) {
             const int k = kc + t;
             const float hw = dhw[3 * k + 2] * 0.5f, hh = dhw[3 * k + 1] * 0.5f;
-            pcA[t] = make_float4(dhw[3 * k] - ez, hw, hh, 1.0f / hw);
+            pcA[t] = make_float4(dhw[3 * k] - vw.ez, hw, hh, 1.0f / hw);
             pcB[t] = 1.0f / hh;
         }
         __syncthreads();
@@ -230,7 +171,7 @@ __global__ __launch_bounds__(kPT, 6) void pixel_pass_kernel(const KParams p, con
             Tap tq;
             fetch(kn - 1, kc + kn - 1, tq);
             for (int t = kn - 1; t >= 0; --t) {
-                const f32x2 pv = {tq.ix, tq.iy};   // the exact sample position (the forward's chain): the texel pass decides membership on it
+                const f32x2 pv = {tq.ix, tq.iy};
                 const float4 d = grads(tq);
                 if (t >= 1) fetch(t - 1, kc + t - 1, tq);
                 const f32x4 dv = {d.x, d.y, d.z, d.w};
@@ -490,8 +431,7 @@ static hipError_t launch_gather_t(const KParams& p, const BwdParams& b, bool ove
         if (env_ppw > 0) ppw = std::min(env_ppw, p.D);
 #endif
         const dim3 grid(xcd_grid_per_group(tx * ty, tx * ty), (p.D + ppw - 1) / ppw, p.M);
-        if (overwrite) hipLaunchKernelGGL((texel_gather_kernel<true>), grid, dim3(kTT), 0, stream, p, b, P, G, recs, tx, ty, ppw);
-        else hipLaunchKernelGGL((texel_gather_kernel<false>), grid, dim3(kTT), 0, stream, p, b, P, G, recs, tx, ty, ppw);
+        dispatch_bool(overwrite, [&](auto OW) { hipLaunchKernelGGL((texel_gather_kernel<decltype(OW)::value>), grid, dim3(kTT), 0, stream, p, b, P, G, recs, tx, ty, ppw); });
     }
     return hipGetLastError();
 }
@@ -499,11 +439,7 @@ static hipError_t launch_gather_t(const KParams& p, const BwdParams& b, bool ove
 // p.ws / p.ws_bytes: the caller's workspace (>= backward_gather_workspace_bytes).  overwrite: the gradient volume's content is not needed (every cell is
 // WRITTEN); otherwise every cell is read, added to and written back -- by its one owner: no atomics either way.
 hipError_t launch_backward_gather(const KParams& p, int dtype, const BwdParams& b, bool overwrite, hipStream_t stream) {
-    switch (dtype) {
-        case 0: return launch_gather_t<float>(p, b, overwrite, stream);
-        case 1: return launch_gather_t<bf16_t>(p, b, overwrite, stream);
-        default: return launch_gather_t<f16_t>(p, b, overwrite, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, b, overwrite, stream); });
 }
 
 }  // namespace gmpi

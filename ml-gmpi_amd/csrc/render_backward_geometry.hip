@@ -4,7 +4,7 @@
 //
 // Per view n, pixel p, plane k (the forward's chain, gmpi_device.hpp):  s = (d_k - ez) / rz,  x = ex + rx s,  y = ey + ry s,  u = 2x / w_k,
 // v = 2y / h_k,  ix / iy the unnormalised texel coordinates (align_corners, or the 0.95 narrowing inside [-1, 1] without it),  depth_k = s dot,
-// dot = r . z_dir.  The back-to-front sweep of the volume backward (pixel_pass_kernel, render_backward_gather.hip) gives d_s[c] = dL/d(sample c)
+// dot = r . z_dir.  The back-to-front sweep of the volume backward (BwdPixel::plane_recip, gmpi_backward.hpp) gives d_s[c] = dL/d(sample c)
 // and the depth term G_k = gZ w_k; the four taps it gathers give the bilinear derivatives (grid_sampler_2d, zeros padding, tx = ix - x0):
 //     g_ix = sum_c d_s[c] ((t_ne - t_nw)(1 - ty) + (t_se - t_sw) ty),   g_iy = sum_c d_s[c] ((t_sw - t_nw)(1 - tx) + (t_se - t_ne) tx)
 //     g_x = g_ix dix/dx,  g_y = g_iy diy/dy,  g_s = g_x rx + g_y ry + G_k dot      (dix/dx = (Wt - 1) / w_k, or c Wt / w_k with c = 0.95 | 1)
@@ -85,34 +85,16 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
     const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
     const int px = txi * kGTW + lane, py = tyi * kGTH + wave;
     const bool active = px < p.W && py < p.H;
-    uint32_t bad_index = 0;
-    const int m = view_mpi(p, n, bad_index);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
+    const BwdView vw = bwd_view<AC>(p, n);
+    const float* __restrict__ dhw = vw.dhw;
+    const float ex = vw.ex, ey = vw.ey, cx = vw.cx, cy = vw.cy;
+    const int64_t HW = vw.HW;
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
     const float rWt = 1.0f / static_cast<float>(Wt), rHt = 1.0f / static_cast<float>(Ht);
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-
-    const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
-    const float rrz = 1.0f / rz;
-    float dot = rx * zx;
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
-    const float oscale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
-    const float* __restrict__ g = b.g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float gr = active ? oscale * g[0] : 0.f, gg = active ? oscale * g[HW] : 0.f, gb = active ? oscale * g[2 * HW] : 0.f;
-    const float gz = (active && b.g_depth) ? b.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
-    XT T{1.0f, 0};
-    if (active) T = total_transmittance<TexT, AC>(p, dhw, vol, t_fwd, p.T_out != nullptr, ex, ey, ez, rx, ry, rz, cx, cy);
-    float S = 0.0f;
-    if (active && b.g_T) S = b.g_T[static_cast<int64_t>(n) * HW + pix] * T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    const float rx = bp.rx, ry = bp.ry, rz = bp.rz, rrz = bp.rrz, dot = bp.dot;
     float sx = 0.0f, sy = 0.0f, ss = 0.0f;      // sum_k g_x, g_y, g_s
     float srx = 0.0f, sry = 0.0f, srz = 0.0f;   // sum_k g_x s, g_y s, g_s s
     float sG = 0.0f;                            // sum_k G_k s
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
         for (int t = tid; t < kn; t += kGT) {
             const int k = kc + t;
             const float pw = dhw[3 * k + 2], ph = dhw[3 * k + 1];
-            pcA[t] = make_float4(dhw[3 * k] - ez, pw, ph, 1.0f / (pw * 0.5f));
+            pcA[t] = make_float4(dhw[3 * k] - vw.ez, pw, ph, 1.0f / (pw * 0.5f));
             pcB[t] = 1.0f / (ph * 0.5f);
         }
         __syncthreads();
@@ -151,18 +133,10 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
                 dix[c] = __builtin_fmaf(q.t[c][3] - q.t[c][2], q.wy1, (q.t[c][1] - q.t[c][0]) * q.wy0);
                 diy[c] = __builtin_fmaf(q.t[c][3] - q.t[c][1], q.wx1, (q.t[c][2] - q.t[c][0]) * q.wx0);
             }
-            // the sweep (the arithmetic of pixel_pass_kernel): T_k = T_{k+1} / om_k, sample gradients d_s
-            const float alpha = smp[3];
-            const float om = (1.0f - alpha) + 1e-10f;
-            float r = __builtin_amdgcn_rcpf(om);
-            r = __builtin_fmaf(__builtin_fmaf(-om, r, 1.0f), r, r);
-            T.m = div_by_recip(T.m, om, r);
-            T.renorm();
-            const float Tk = T.value();
-            const float qv = gr * smp[0] + gg * smp[1] + gb * smp[2] + gz * (s * dot);
-            const float w = alpha * Tk;
-            const float d0 = gr * w, d1 = gg * w, d2 = gb * w, d3 = Tk * qv - div_by_recip(S, om, r);
-            S += w * qv;
+            // the sweep: T_k = T_{k+1} / om_k, sample gradients d_s
+            float d_s[4];
+            const float w = bp.plane_recip(smp, s, d_s);   // w_k = a_k T_k
+            const float d0 = d_s[0], d1 = d_s[1], d2 = d_s[2], d3 = d_s[3];
             // position gradient
             const float g_ix = d0 * dix[0] + d1 * dix[1] + d2 * dix[2] + d3 * dix[3];
             const float g_iy = d0 * diy[0] + d1 * diy[1] + d2 * diy[2] + d3 * diy[3];
@@ -173,7 +147,7 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
                 ky = 0.5f * cy * (fabsf(vv) <= 0.975f ? kNarrowScale : 1.0f);
             }
             const float g_x = g_ix * (kx * rw), g_y = g_iy * (ky * rh);   // du/dx = 2/w = rw
-            const float Gk = gz * w;
+            const float Gk = bp.gz * w;
             const float g_s = g_x * rx + g_y * ry + Gk * dot;
             sx += g_x, sy += g_y, ss += g_s;
             srx += g_x * s, sry += g_y * s, srz += g_s * s;
@@ -201,10 +175,10 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
         }
     }
     if (active && g_ray != nullptr) {
-        float* o = g_ray + static_cast<int64_t>(n) * 3 * HW + pix;
-        o[0] = srx + sG * zx;
-        o[HW] = sry + sG * zy;
-        o[2 * HW] = -srz * rrz + sG * zz;
+        float* o = g_ray + static_cast<int64_t>(n) * 3 * HW + bp.pix;
+        o[0] = srx + sG * bp.zx;
+        o[HW] = sry + sG * bp.zy;
+        o[2 * HW] = -srz * rrz + sG * bp.zz;
     }
     if (slab != nullptr) {
         float v[6] = {sx, sy, -ss * rrz, sG * rx, sG * ry, sG * rz};
@@ -268,24 +242,6 @@ uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw) {
     return (comps * p.N * static_cast<uint64_t>(bwgeo::tiles_of(p)) * sizeof(float) + 255) / 256 * 256;
 }
 
-template <typename TexT, bool AC, bool STRICT>
-static void launch_geometry_t(const KParams& p, const BwdParams& b, float* g_ray, float* slab, bool want_dhw, hipStream_t stream) {
-    using namespace bwgeo;
-    const int tx = tiles_x_of(p), nt = tiles_of(p);
-    const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
-    if (want_dhw) hipLaunchKernelGGL((geometry_pixel_kernel<TexT, AC, STRICT, true>), grid, dim3(kGT), 0, stream, p, b, g_ray, slab, tx, nt);
-    else hipLaunchKernelGGL((geometry_pixel_kernel<TexT, AC, STRICT, false>), grid, dim3(kGT), 0, stream, p, b, g_ray, slab, tx, nt);
-}
-
-template <typename TexT>
-static void launch_geometry_dtype(const KParams& p, const BwdParams& b, float* g_ray, float* slab, bool want_dhw, hipStream_t stream) {
-    const bool ac = p.flags & 1u, strict = p.flags & (1u << 4);
-    if (ac && strict) launch_geometry_t<TexT, true, true>(p, b, g_ray, slab, want_dhw, stream);
-    else if (ac) launch_geometry_t<TexT, true, false>(p, b, g_ray, slab, want_dhw, stream);
-    else if (strict) launch_geometry_t<TexT, false, true>(p, b, g_ray, slab, want_dhw, stream);
-    else launch_geometry_t<TexT, false, false>(p, b, g_ray, slab, want_dhw, stream);
-}
-
 // g_ray [N,3,H,W], g_eye / g_z [N,3], g_dhw [M,D,3]: overwritten; nullptr = not wanted.  p.ws must hold geometry_backward_workspace_bytes(p,
 // g_dhw != nullptr) bytes when any of g_eye, g_z, g_dhw is wanted (checked by the caller).
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
@@ -294,10 +250,20 @@ hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_
     b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T;
     const bool want_dhw = g_dhw != nullptr;
     float* slab = (g_eye || g_z || g_dhw) ? static_cast<float*>(p.ws) : nullptr;
-    switch (dtype) {
-        case 0: launch_geometry_dtype<float>(p, b, g_ray, slab, want_dhw, stream); break;
-        case 1: launch_geometry_dtype<bf16_t>(p, b, g_ray, slab, want_dhw, stream); break;
-        default: launch_geometry_dtype<f16_t>(p, b, g_ray, slab, want_dhw, stream); break;
+    {
+        using namespace bwgeo;
+        const int tx = tiles_x_of(p), nt = tiles_of(p);
+        const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
+        dispatch_dtype(dtype, [&](auto t) {
+            dispatch_bool(p.flags & 1u, [&](auto AC) {
+                dispatch_bool(p.flags & (1u << 4), [&](auto STRICT) {
+                    dispatch_bool(want_dhw, [&](auto DHW) {
+                        hipLaunchKernelGGL((geometry_pixel_kernel<typename decltype(t)::type, decltype(AC)::value, decltype(STRICT)::value, decltype(DHW)::value>),
+                                           grid, dim3(kGT), 0, stream, p, b, g_ray, slab, tx, nt);
+                    });
+                });
+            });
+        });
     }
     if (slab != nullptr) {
         const dim3 grid(6 + (want_dhw ? 3 * p.D : 0), std::max(p.N, p.M));

@@ -136,26 +136,6 @@ __device__ __forceinline__ void scatter4(float* __restrict__ ch, int64_t s_row, 
     if (f.se != 0.0f) atomicAdd(ch + ob + 1, d * f.se);
 }
 
-// what a pixel of the backward starts from
-struct BwdSetup {
-    float rx, ry, rz, dot, gr, gg, gb, gz;
-};
-__device__ __forceinline__ BwdSetup bwd_setup(const KParams& p, const SharedG& g, int n, int64_t pix, bool active) {
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
-    BwdSetup q;
-    q.rx = rd[0], q.ry = rd[HW], q.rz = rd[2 * HW];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    q.dot = q.rx * zx;
-    q.dot = q.dot + q.ry * zy;
-    q.dot = q.dot + q.rz * zz;
-    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1
-    const float* __restrict__ go = g.g_out + static_cast<int64_t>(n) * 3 * HW + pix;
-    q.gr = active ? scale * go[0] : 0.0f, q.gg = active ? scale * go[HW] : 0.0f, q.gb = active ? scale * go[2 * HW] : 0.0f;
-    q.gz = (active && g.g_depth) ? g.g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    return q;
-}
-
 // ---- backward, one pixel per lane: render_backward_kernel's sweep, three destinations --------------------------------------------------------
 template <typename TexT, bool AC>
 __global__ __launch_bounds__(256) void render_shared_backward_kernel(const KParams p, const SharedK sh, const SharedG g) {
@@ -164,27 +144,19 @@ __global__ __launch_bounds__(256) void render_shared_backward_kernel(const KPara
     const int py = blockIdx.y * 4 + threadIdx.y;
     if (px >= p.W || py >= p.H) return;
     uint32_t unused = 0;
-    const int m = view_mpi(p, n, unused);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(py) * p.W + px;
-    const BwdSetup q = bwd_setup(p, g, n, pix, true);
+    const BwdView vw = bwd_view<AC>(p, n);
+    const int m = vw.m;
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
     const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
     float* __restrict__ ga = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
 
-    const float t_fwd = p.T_out ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 0.0f;
-    BwdPixel bp{q.gr, q.gg, q.gb, q.gz, q.dot,
-                total_transmittance<TexT, AC>(p, dhw, alpha, t_fwd, p.T_out != nullptr, ex, ey, ez, q.rx, q.ry, q.rz, cx, cy), 0.0f};
-    if (g.g_T) bp.S = g.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, g.g_out, g.g_depth, g.g_T, alpha);
     for (int k = p.D - 1; k >= 0; --k) {
-        float ix, iy, s, u, v;
-        plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, q.rx, q.ry, q.rz, cx, cy, ix, iy, s, u, v);
+        float ix, iy, s;
+        pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
         const Taps t = make_taps(ix, iy, Ht, Wt);
         const bool last_bg = bgi != nullptr && k == p.D - 1;
         float smp[4], d_s[4];
@@ -201,12 +173,12 @@ __global__ __launch_bounds__(256) void render_shared_backward_kernel(const KPara
 }
 
 // ---- backward, one workgroup per pixel tile ------------------------------------------------------------------------------------------------
-// A 32 x 16 pixel tile touches a small texel box on every plane (the corner argument of render_lds.hip / render_backward.hip).
+// A 32 x 16 pixel tile touches a small texel box on every plane (tile_box, gmpi_backward.hpp).
 //
 // ALPHA: as the volume kernels do it -- the 4 adds of a pixel go to a copy of the plane's box in LDS (64-bit fixed point, scaled per plane to the
 // tile's largest |d alpha|: that gradient holds S / om and has no bound known in advance), the box is flushed with one global atomic per texel.
 // Two boxes alternate, so that the flush of plane t + 1 and the scatter of plane t need no barrier between them: ONE barrier per plane, and that
-// barrier orders LDS only (lds_only_barrier); the taps of plane t - 1 are fetched before plane t is scattered.
+// barrier orders LDS only (lds_barrier); the taps of plane t - 1 are fetched before plane t is scattered.
 //
 // COLOUR, the point of this kernel: every plane's colour gradient belongs to the same image, so it is summed in LDS across ALL planes, in a window of
 // kCW x kCH texels x 3 channels.  The window does NOT hold the union of the tile's per-plane boxes: the boxes drift over the planes by parallax -- with
@@ -234,31 +206,6 @@ constexpr int kCW = 64, kCH = 32;              // colour window (3 channels of 6
 constexpr int kSPlanes = 128;                  // planes a tile kernel launch can take (its tables)
 constexpr int kSAlphaBits = 40, kSColBits = 40;   // largest staged term < 2^41 (to_fix takes |w| < 2^43)
 
-// Workgroup barrier that orders LDS only (render_backward.hip's lds_barrier): `__syncthreads()` is a fence over every address space and drains vmcnt,
-// i.e. every plane would wait for the flush's global atomics and for the next plane's tap loads.  Between the planes only LDS state is shared.
-__device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {   // every lane enabled
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));
-    return v;
-}
-__device__ __forceinline__ uint32_t abs_bits(float v) { return (v != v) ? 0x7fc00000u : __float_as_uint(fabsf(v)); }   // orders like the magnitude; NaN on top
-// round to nearest (floor(x + 0.5)) in one instruction, as render_backward.hip: the staged sums must not be biased
-__device__ __forceinline__ int cvt_rpi_i32(float x) {
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-// fp32 -> 64-bit fixed point without a trip through fp64 (a double conversion and an f64 -> i64 expansion per add were most of the scatter's VALU
-// work): w = v scale (a power of two: exact), |w| < 2^43;  hi = RN(w / 4096) fits 32 bits, lo = w - 4096 hi is exact (one FMA: w has 24 significant
-// bits) and |lo| <= 2048;  the word is 4096 hi + RN(lo) (one v_mad_i64_i32): w rounded to the nearest integer.
-__device__ __forceinline__ unsigned long long to_fix(float v, float scale) {
-    const float w = v * scale;
-    const int hi = cvt_rpi_i32(w * (1.0f / 4096.0f));
-    const int lo = cvt_rpi_i32(__builtin_fmaf(-static_cast<float>(hi), 4096.0f, w));
-    return static_cast<unsigned long long>(static_cast<long long>(hi) * 4096ll + static_cast<long long>(lo));
-}
-
 template <typename TexT, bool AC>
 __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KParams p, const SharedK sh, const SharedG g, const int tiles_x) {
     __shared__ int4 box[kSPlanes];        // bx0, by0, nx (<= 0: not staged), ny
@@ -274,22 +221,17 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
     const int px = txi * kSTW + (tid % kSTW), py = tyi * kSTH + (tid / kSTW);
     const bool active = px < p.W && py < p.H;
-    uint32_t unused = 0;
-    const int m = view_mpi(p, n, unused);
-    const int D = p.D;
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
-    const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
-    const BwdSetup q = bwd_setup(p, g, n, pix, active);
+    const BwdView vw = bwd_view<AC>(p, n);
+    const int m = vw.m, D = p.D;
+    const float* __restrict__ dhw = vw.dhw;
+    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * vw.HW;
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
     const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
     float* __restrict__ ga = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, g.g_out, g.g_depth, g.g_T, alpha);
 
     for (int i = tid; i < 2 * kSAP * kSAR; i += kSThreads) (&acc_a[0][0])[i] = 0ull;
     for (int i = tid; i < 3 * kCW * kCH; i += kSThreads) acc_c[i] = 0ull;
@@ -299,37 +241,14 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     const int cx0 = txi * kSTW, cx1 = min(cx0 + kSTW - 1, p.W - 1);
     const int cy0 = tyi * kSTH, cy1 = min(cy0 + kSTH - 1, p.H - 1);
     for (int k = tid; k < D; k += kSThreads) {
-        const float zdiff = dhw[3 * k] - ez, ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
-        float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-        bool finite = true;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int64_t qq = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
-            float ix, iy, s, u, v;
-            plane_coord<AC>(zdiff, ph, pw, ex, ey, rdv[qq], rdv[HW + qq], rdv[2 * HW + qq], cx, cy, ix, iy, s, u, v);
-            finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
-            mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-        }
-        int4 bb = make_int4(0, 0, 0, 0);
-        if (finite) {
-            const float eps = 1.0f / 64;
-            bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
-            bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
-            if (bb.z > kSAP || bb.w > kSAR) bb.z = 0;
-        }
-        box[k] = bb;
+        box[k] = tile_box<AC>(p, vw, rdv, dhw[3 * k] - vw.ez, dhw[3 * k + 1], dhw[3 * k + 2], cx0, cx1, cy0, cy1, kSAP, kSAR);
         gmax[k] = 0u;
     }
     __syncthreads();   // zero fills, tables, cmax = 0
     {   // the tile's largest |gC|: one LDS atomic per wave
-        const uint32_t wm = wave_max_bits(max(abs_bits(q.gr), max(abs_bits(q.gg), abs_bits(q.gb))));
+        const uint32_t wm = wave_max_bits(max(abs_bits(bp.gr), max(abs_bits(bp.gg), abs_bits(bp.gb))));
         if ((tid & 63) == 0 && wm != 0u) atomicMax(&cmax, wm);
     }
-
-    const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : 1.0f;
-    BwdPixel bp{q.gr, q.gg, q.gb, q.gz, q.dot, XT{1.0f, 0}, 0.0f};
-    if (active) bp.T = total_transmittance<TexT, AC>(p, dhw, alpha, t_fwd, p.T_out != nullptr, ex, ey, ez, q.rx, q.ry, q.rz, cx, cy);
-    if (active && g.g_T) bp.S = g.g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();
 
     struct Grad { float d[4]; Footprint f; };
     struct Tap { float s; Footprint f; float v[16]; };   // v: per channel (r, g, b, alpha) the taps nw, ne, sw, se
@@ -341,8 +260,8 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
 #pragma unroll
         for (int i = 0; i < 16; ++i) tp.v[i] = 0.0f;
         if (active) {
-            float ix, iy, u, v;
-            plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, q.rx, q.ry, q.rz, cx, cy, ix, iy, tp.s, u, v);
+            float ix, iy;
+            pixel_plane_coord<AC>(vw, bp, k, ix, iy, tp.s);
             const Taps t = make_taps(ix, iy, Ht, Wt);
             tp.f = t.f;
             const bool last_bg = bgi != nullptr && k == D - 1;
@@ -483,7 +402,7 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
             if (!inside) {
                 if (w_open) {   // the previous planes' adds are complete (the barrier that ended the last iteration)
                     flush_colour(colour_target(sh, g, m, k + 1, D));
-                    lds_only_barrier();
+                    lds_barrier();
                 }
                 // re-anchor: the box at the end of the window it drifts away from (boxes of nearer planes: towards box_front)
                 wx0 = (box_front.z > 0 && box_front.x < bb.x) ? bb.x + bb.z - kCW : bb.x;
@@ -496,11 +415,11 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
         scatter(k, G, ct, want_window);
         if (k > 0) grads(k - 1, tp, G);
         if (k + 1 < D) flush_alpha(k + 1);
-        lds_only_barrier();   // plane k's adds and gmax[k - 1] complete; box (k + 1) & 1 is clean for plane k - 1
+        lds_barrier();   // plane k's adds and gmax[k - 1] complete; box (k + 1) & 1 is clean for plane k - 1
         // the last plane's colour belongs to the background image: its own flush (the window stays where it is)
         if (k == D - 1 && bgi != nullptr && w_open && D > 1) {
             flush_colour(ct);
-            lds_only_barrier();
+            lds_barrier();
         }
     }
     flush_alpha(0);
@@ -512,20 +431,16 @@ template <typename TexT>
 static hipError_t launch_shared_t(const KParams& p, const SharedK& sh, hipStream_t stream) {
     const dim3 block(64, 4);
     const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
-    const bool ac = p.flags & 1u, strict = p.flags & (1u << 4);
-    if (ac && strict) hipLaunchKernelGGL((render_shared_kernel<TexT, true, true>), grid, block, 0, stream, p, sh);
-    else if (ac) hipLaunchKernelGGL((render_shared_kernel<TexT, true, false>), grid, block, 0, stream, p, sh);
-    else if (strict) hipLaunchKernelGGL((render_shared_kernel<TexT, false, true>), grid, block, 0, stream, p, sh);
-    else hipLaunchKernelGGL((render_shared_kernel<TexT, false, false>), grid, block, 0, stream, p, sh);
+    dispatch_bool(p.flags & 1u, [&](auto AC) {
+        dispatch_bool(p.flags & (1u << 4), [&](auto STRICT) {
+            hipLaunchKernelGGL((render_shared_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, sh);
+        });
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream) {
-    switch (dtype) {
-        case 0: return launch_shared_t<float>(p, sh, stream);
-        case 1: return launch_shared_t<bf16_t>(p, sh, stream);
-        default: return launch_shared_t<f16_t>(p, sh, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_shared_t<typename decltype(t)::type>(p, sh, stream); });
 }
 
 bool shared_tile_supports(const KParams& p) { return p.D <= kSPlanes; }
@@ -536,24 +451,18 @@ static hipError_t launch_shared_backward_t(const KParams& p, const SharedK& sh, 
     if (tiles) {
         const int tiles_x = (p.W + kSTW - 1) / kSTW, n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
         const dim3 grid(xcd_grid_per_group(n_tiles, n_tiles), p.N);
-        if (ac) hipLaunchKernelGGL((render_shared_tile_kernel<TexT, true>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x);
-        else hipLaunchKernelGGL((render_shared_tile_kernel<TexT, false>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x);
+        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_shared_tile_kernel<TexT, decltype(AC)::value>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x); });
     } else {
         const dim3 block(64, 4);
         const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
-        if (ac) hipLaunchKernelGGL((render_shared_backward_kernel<TexT, true>), grid, block, 0, stream, p, sh, g);
-        else hipLaunchKernelGGL((render_shared_backward_kernel<TexT, false>), grid, block, 0, stream, p, sh, g);
+        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_shared_backward_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, sh, g); });
     }
     return hipGetLastError();
 }
 
 hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream) {
     tiles = tiles && shared_tile_supports(p);
-    switch (dtype) {
-        case 0: return launch_shared_backward_t<float>(p, sh, g, tiles, stream);
-        case 1: return launch_shared_backward_t<bf16_t>(p, sh, g, tiles, stream);
-        default: return launch_shared_backward_t<f16_t>(p, sh, g, tiles, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_shared_backward_t<typename decltype(t)::type>(p, sh, g, tiles, stream); });
 }
 
 }  // namespace gmpi

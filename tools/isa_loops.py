@@ -34,6 +34,9 @@ for i, l in enumerate(body):
                 c['VMEM'] += 1
             else:
                 c[x] += 1
+        waits = [x for x in body[st:i + 1] if x.startswith('\ts_waitcnt') and 'vmcnt' in x]
+        c['vmcnt waits'] = len(waits)
+        c['vmcnt(0)'] = sum('vmcnt(0)' in x for x in waits)
         print(f"loop {m.group(1)} lines {st}-{i}: {len(ins)} instr {dict(c)}")
         if len(sys.argv) > 3 and sys.argv[3] == 'hist':
             print(collections.Counter(ins).most_common(40))
