@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void range_check_kernel(const T* __restrict__ 
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride)
         bad |= !in_unit(to_f32(v[i]));
-    report_status(status, bad ? 2u : 0u);
+    report_status(status, bad ? GMPI_STATUS_RGBA_RANGE : 0u);
 }
 
 // 16-byte vectorised body for contiguous, aligned volumes
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void range_check_vec_kernel(const uint4* __res
         test(q0), test(q1), test(q2), test(q3);
     }
     for (; i < nvec; i += stride) test(__builtin_nontemporal_load(vv + i));
-    report_status(status, bad ? 2u : 0u);
+    report_status(status, bad ? GMPI_STATUS_RGBA_RANGE : 0u);
 }
 
 // ---- diagnostic: a pure streaming read (the ceiling bench.py quotes next to the render kernel's rate) -------------------------------

@@ -2,7 +2,7 @@
 // (render_backward.hip: one pixel per lane, tile, tile2; render_backward_gather.hip: pixel_pass; render_backward_geometry.hip: geometry_pixel;
 // render_shared.hip: shared_backward, shared_tile), and the claims of DESIGN.md section 3.3 -- the forward's quotients and texels, bit-reproducible
 // gather and geometry passes, gT entering S in every sweep -- hold because they all run THIS code:
-//   BwdView / bwd_view              what is uniform over a view: MPI, plane table, eye, texture centre
+//   BwdView / bwd_view              what is uniform over a view: the forward's View / view_setup (gmpi_device.hpp)
 //   BwdPixel / bwd_pixel_setup      the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
@@ -59,26 +59,13 @@ __device__ __forceinline__ XT total_transmittance(const KParams& p, const float*
     return t;
 }
 
-// What is uniform over view n: the MPI it samples (a bad index is only clamped here; the forward reports it), that MPI's plane table, the eye,
-// the image size and the texture centre of the coordinate chain (plane_coord's cx, cy).
-struct BwdView {
-    int m;
-    const float* __restrict__ dhw;
-    float ex, ey, ez;
-    int64_t HW;
-    float cx, cy;
-};
+// What is uniform over view n is the forward's View (gmpi_device.hpp): the backward reads the forward's constants.  A bad view index is only
+// clamped here; the forward reports it.
+using BwdView = View;
 template <bool AC>
 __device__ __forceinline__ BwdView bwd_view(const KParams& p, int n) {
     uint32_t bad_index = 0;
-    BwdView vw;
-    vw.m = view_mpi(p, n, bad_index);
-    vw.dhw = p.dhw + static_cast<int64_t>(vw.m) * p.D * 3;
-    vw.ex = p.eye_pos[3 * n + 0], vw.ey = p.eye_pos[3 * n + 1], vw.ez = p.eye_pos[3 * n + 2];
-    vw.HW = static_cast<int64_t>(p.H) * p.W;
-    vw.cx = AC ? static_cast<float>(p.Wt - 1) * 0.5f : static_cast<float>(p.Wt);
-    vw.cy = AC ? static_cast<float>(p.Ht - 1) * 0.5f : static_cast<float>(p.Ht);
-    return vw;
+    return view_setup<AC>(p, n, bad_index);
 }
 
 // The state of one pixel through the back-to-front sweep.  A default-constructed one is a pixel that contributes nothing (a lane outside the
@@ -132,15 +119,11 @@ __device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, 
     const int64_t HW = vw.HW;
     const int64_t pix = MASKED ? static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1) : static_cast<int64_t>(py) * p.W + px;
     bp.pix = pix;
-    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
-    bp.rx = rd[0], bp.ry = rd[HW], bp.rz = rd[2 * HW];
+    bp.rx = vw.rays[pix], bp.ry = vw.rays[HW + pix], bp.rz = vw.rays[2 * HW + pix];
     bp.rrz = 1.0f / bp.rz;
-    bp.zx = p.z_dir[3 * n + 0], bp.zy = p.z_dir[3 * n + 1], bp.zz = p.z_dir[3 * n + 2];
-    float dot = bp.rx * bp.zx;   // (this association: the forward's)
-    dot = dot + bp.ry * bp.zy;
-    dot = dot + bp.rz * bp.zz;
-    bp.dot = dot;
-    const float scale = (p.flags & (1u << 1)) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
+    bp.zx = vw.zx, bp.zy = vw.zy, bp.zz = vw.zz;
+    bp.dot = ray_dot(vw, bp.rx, bp.ry, bp.rz);
+    const float scale = (p.flags & GMPI_FLAG_OUT_PM1) ? 2.0f : 1.0f;  // forward wrote 2*C-1 (mpi_renderer.py:467)
     const float* __restrict__ g = g_rgb + static_cast<int64_t>(n) * 3 * HW + pix;
     bp.gr = active ? scale * g[0] : 0.f, bp.gg = active ? scale * g[HW] : 0.f, bp.gb = active ? scale * g[2 * HW] : 0.f;
     bp.gz = (active && g_depth) ? g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;

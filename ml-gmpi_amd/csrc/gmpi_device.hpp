@@ -15,6 +15,8 @@
 
 #include <type_traits>
 
+#include "../../include/gmpi_render.h"  // GMPI_FLAG_* / GMPI_STATUS_*: device and launcher code names the bits, never writes them out
+
 #pragma clang fp contract(off)
 
 namespace gmpi {
@@ -74,14 +76,30 @@ __device__ __forceinline__ bool view_gated_out(const KParams& p, int n) {
 }
 
 // MPI sampled by view n: view_to_mpi[n], or n / views_per_mpi.  An index outside [0, M) would address dhw and the volume
-// out of bounds: it is clamped and reported (status bit 8 = GMPI_STATUS_BAD_VIEW_INDEX) instead.
+// out of bounds: it is clamped and reported (GMPI_STATUS_BAD_VIEW_INDEX) instead.
 __device__ __forceinline__ int view_mpi(const KParams& p, int n, uint32_t& bad) {
     int m = p.view_to_mpi ? p.view_to_mpi[n] : n / p.views_per_mpi;
     if (m < 0 || m >= p.M) {
-        bad |= 8u;
+        bad |= GMPI_STATUS_BAD_VIEW_INDEX;
         m = min(max(m, 0), p.M - 1);
     }
     return m;
+}
+
+// Work item (pixel tile / strip band / band) -> view n and position `rem` inside the view, `per_view` items per view.  Views that share one MPI
+// (video paths: views_per_mpi > 1) are interleaved per position, so that the workgroups that need (nearly) the same texels of a plane run next to
+// each other in time and on the same XCD: the volume is then read from HBM about once per group of views instead of once per view.
+__device__ __forceinline__ void item_to_view(const KParams& p, int item, int per_view, int& n, int& rem) {
+    if (p.view_to_mpi == nullptr && p.views_per_mpi > 1) {
+        const int group = item / (per_view * p.views_per_mpi);  // full groups come first
+        const int first = group * p.views_per_mpi, size = min(p.views_per_mpi, p.N - first);
+        const int r = item - first * per_view;
+        rem = r / size;
+        n = first + (r - rem * size);
+    } else {
+        n = item / per_view;
+        rem = item - n * per_view;
+    }
 }
 
 // ---- texel fetch: storage type -> fp32 (exact upcast, mpi_renderer.py:446) -----------------------
@@ -107,6 +125,17 @@ inline auto dispatch_dtype(int dtype, F&& f) {
 template <typename F>
 inline auto dispatch_bool(bool flag, F&& f) {
     return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+// The two flags every forward kernel is instantiated over: f(AC, STRICT) for GMPI_FLAG_ALIGN_CORNERS, GMPI_FLAG_STRICT_ORDER.
+template <typename F>
+inline auto dispatch_ac_strict(uint32_t flags, F&& f) {
+    return dispatch_bool(flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) { return dispatch_bool(flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) { return f(AC, STRICT); }); });
+}
+// Host side: the volume can be staged in 16-byte loader items -- items of a box that touches the border do not straddle it, and every item is aligned.
+inline __host__ bool volume_stages_in_items(const KParams& p, int dtype) {
+    const int tpi = 16 / (dtype == GMPI_DTYPE_F32 ? 4 : 2);  // texels per item
+    return p.Wt % tpi == 0 && reinterpret_cast<uintptr_t>(p.rgba) % 16 == 0 && p.s_row % tpi == 0 && p.s_chan % tpi == 0 && p.s_plane % tpi == 0 &&
+           p.s_mpi % tpi == 0;
 }
 
 // ---- ray/plane intersection -> unnormalised texture coordinates --------------------------------
@@ -304,8 +333,106 @@ __device__ __forceinline__ void gather_sample(const TexT* __restrict__ pl, int64
         const float t_ne = to_f32(ch[oa + xb]);
         const float t_sw = to_f32(ch[ob + xa]);
         const float t_se = to_f32(ch[ob + xb]);
-        if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= 2u;
+        if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= GMPI_STATUS_RGBA_RANGE;
         smp[c] = bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, f);
+    }
+}
+
+// ---- the forward's frame: what every render kernel does around its plane loop.  A change here reaches all of them, and
+//      the backward sweeps (gmpi_backward.hpp), which read the same view constants and the same dot product. -----------------------------------
+// What is uniform over view n.  Everything is forced inline: a field a kernel does not read costs it nothing.
+struct View {
+    int m;                          // the MPI the view samples
+    const float* __restrict__ dhw;  // its plane table [D, 3]
+    float ex, ey, ez;               // eye
+    float zx, zy, zz;               // optical axis
+    float cx, cy;                   // plane_coord's texture constants: (Wt - 1) / 2, (Ht - 1) / 2 (align_corners) or Wt, Ht
+    int64_t HW;
+    const float* __restrict__ rays; // ray_dir of the view: [3, H W]
+};
+template <bool AC>
+__device__ __forceinline__ View view_setup(const KParams& p, int n, uint32_t& bad) {
+    View vw;
+    vw.m = view_mpi(p, n, bad);  // (an index outside [0, M) is clamped and reported)
+    vw.dhw = p.dhw + static_cast<int64_t>(vw.m) * p.D * 3;
+    vw.ex = p.eye_pos[3 * n + 0], vw.ey = p.eye_pos[3 * n + 1], vw.ez = p.eye_pos[3 * n + 2];
+    vw.zx = p.z_dir[3 * n + 0], vw.zy = p.z_dir[3 * n + 1], vw.zz = p.z_dir[3 * n + 2];
+    vw.cx = AC ? static_cast<float>(p.Wt - 1) * 0.5f : static_cast<float>(p.Wt);
+    vw.cy = AC ? static_cast<float>(p.Ht - 1) * 0.5f : static_cast<float>(p.Ht);
+    vw.HW = static_cast<int64_t>(p.H) * p.W;
+    vw.rays = p.ray_dir + static_cast<int64_t>(n) * 3 * vw.HW;
+    return vw;
+}
+
+// mpi.py:70-72 compares every plane distance of the view's MPI with eye_z of the FIRST view ("Camera must be placed closer...").  The caller
+// says which one lane of the view runs it (`once`).
+__device__ __forceinline__ void check_camera_behind(const KParams& p, const View& vw, bool once) {
+    if (p.status != nullptr && once) {
+        const float ez0 = p.eye_pos[2];
+        bool behind = false;
+        for (int k = 0; k < p.D; ++k) behind |= !(vw.dhw[3 * k] >= ez0);
+        if (behind) atomicOr(p.status, GMPI_STATUS_CAMERA_BEHIND_PLANE);
+    }
+}
+
+// ray . z_dir in the association of einsum("nchw,nc->nhw") (mpi.py:149): depth_k = s_k dot
+__device__ __forceinline__ float ray_dot(const View& vw, float rx, float ry, float rz) {
+    float dot = rx * vw.zx;
+    dot = dot + ry * vw.zy;
+    dot = dot + rz * vw.zz;
+    return dot;
+}
+
+__device__ __forceinline__ bool outside_pm1(float u, float v) { return !(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f); }
+
+// assert_not_out_of_last_plane (mpi.py:381-395, 103-109), once per pixel in the epilogue: whether the launch asks for it (GMPI_FLAG_CHECK_LAST_PLANE)
+// and plane D - 1, read once per thread; then per pixel whether its u, v on that plane leave [-1, 1].
+struct LastPlane {
+    bool check;
+    float d, ph, pw;
+};
+__device__ __forceinline__ LastPlane last_plane(const KParams& p, const View& vw) {
+    LastPlane lp{(p.flags & GMPI_FLAG_CHECK_LAST_PLANE) != 0, 0.0f, 1.0f, 1.0f};
+    if (lp.check) lp.d = vw.dhw[3 * (p.D - 1) + 0], lp.ph = vw.dhw[3 * (p.D - 1) + 1], lp.pw = vw.dhw[3 * (p.D - 1) + 2];
+    return lp;
+}
+template <bool AC>
+__device__ __forceinline__ bool leaves_last_plane(const View& vw, const LastPlane& lp, float rx, float ry, float rz) {
+    if (!lp.check) return false;
+    float ix, iy, s, u, v;
+    plane_coord<AC>(lp.d - vw.ez, lp.ph, lp.pw, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
+    return outside_pm1(u, v);
+}
+
+// One plane for one pixel straight from global memory: the gather kernel's loop body and the staged kernels' last resort (a box that does not
+// fit).  `vol` points at channel 0 of plane 0 of the view's MPI; (zdiff, ph, pw) = (d - eye_z, height, width) of plane k.  check_range: a bool, or std::bool_constant where
+// the range check is a template parameter of the kernel (the band kernel: as a run-time value it moves that kernel's registers).
+template <typename TexT, bool AC, bool STRICT, typename CheckT>
+__device__ __forceinline__ void gather_plane(const KParams& p, const View& vw, const TexT* vol, int k, float zdiff, float ph, float pw,
+                                             float rx, float ry, float rz, float dot, CheckT check_range, uint32_t& bad, Accum& A) {
+    float ix, iy, s, u, v, smp[4];
+    plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
+    gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
+    blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
+}
+
+// The pixel's results: colour ([0, 1], or 2 c - 1 with GMPI_FLAG_OUT_PM1: mpi_renderer.py:467), depth, transmittance if wanted.  (2 c - 1 is
+// formed before the `active` test on purpose: the 16-bit tile kernels sit at their register cap and the other order moves their spills.)
+template <bool STRICT>
+__device__ __forceinline__ void store_pixel(const KParams& p, int n, int64_t HW, int64_t pix, const Accum& A, float dot, bool active) {
+    float r = A.r, g = A.g, b = A.b;
+    if (p.flags & GMPI_FLAG_OUT_PM1) {
+        r = 2.0f * r - 1.0f;
+        g = 2.0f * g - 1.0f;
+        b = 2.0f * b - 1.0f;
+    }
+    if (active) {
+        float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
+        out[0] = r;
+        out[HW] = g;
+        out[2 * HW] = b;
+        p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
+        if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
     }
 }
 

@@ -561,7 +561,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
 
 template <typename TexT>
 static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool tiles, hipStream_t stream) {
-    const bool ac = p.flags & 1u;
+    const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
     if (tiles) {
         const int tiles_x = (p.W + kBwdTW - 1) / kBwdTW, tiles_y = (p.H + kBwdTH - 1) / kBwdTH;
         const dim3 grid(tiles_x * tiles_y, p.N), block(kBwdThreads), block2(kB2Threads);
@@ -624,7 +624,7 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
         if (env_geo == 1 || env_geo == 2) gather = false;
     }
 #endif
-    if (gather) return launch_backward_gather(p, dtype, b, (p.flags & (1u << 7)) != 0 /* GMPI_FLAG_GRAD_OVERWRITE */, stream);
+    if (gather) return launch_backward_gather(p, dtype, b, (p.flags & GMPI_FLAG_GRAD_OVERWRITE) != 0, stream);
     return dispatch_dtype(dtype, [&](auto t) { return launch_backward_t<typename decltype(t)::type>(p, b, tiles, stream); });
 }
 

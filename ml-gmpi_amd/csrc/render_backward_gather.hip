@@ -395,7 +395,7 @@ static uint64_t recs_bytes(const KParams& p) { return align256(static_cast<uint6
 
 // Can the atomics-free pair run this launch (workspace aside)?
 bool backward_gather_supports(const KParams& p) {
-    if (!(p.flags & 1u)) return false;                                   // align_corners = True only (see the head of this file)
+    if (!(p.flags & GMPI_FLAG_ALIGN_CORNERS)) return false;                                   // align_corners = True only (see the head of this file)
     if (p.view_to_mpi != nullptr) return false;                          // uniform views per MPI
     if (p.N > 65535 || p.M > 65535 || p.D > 65535) return false;         // grid.y / grid.z
     if (p.Wt < 2) return false;                                          // pair loads

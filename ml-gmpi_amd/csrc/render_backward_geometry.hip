@@ -255,8 +255,8 @@ hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_
         const int tx = tiles_x_of(p), nt = tiles_of(p);
         const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
         dispatch_dtype(dtype, [&](auto t) {
-            dispatch_bool(p.flags & 1u, [&](auto AC) {
-                dispatch_bool(p.flags & (1u << 4), [&](auto STRICT) {
+            dispatch_bool(p.flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) {
+                dispatch_bool(p.flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) {
                     dispatch_bool(want_dhw, [&](auto DHW) {
                         hipLaunchKernelGGL((geometry_pixel_kernel<typename decltype(t)::type, decltype(AC)::value, decltype(STRICT)::value, decltype(DHW)::value>),
                                            grid, dim3(kGT), 0, stream, p, b, g_ray, slab, tx, nt);

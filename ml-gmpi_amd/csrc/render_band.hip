@@ -183,21 +183,6 @@ template <int O> __device__ __forceinline__ void tap32x2(uint32_t& t0, uint32_t&
     t0 = v.x, t1 = v.y;
 }
 
-// blockIdx / band index -> view n and band position inside the view.  Views that share one MPI (views_per_mpi > 1) are interleaved per band
-// position, so that the workgroups that need (nearly) the same texels of a plane run next to each other in time and on the same XCD.
-__device__ __forceinline__ void band_to_view(const KParams& p, int band_id, int per_view, int& n, int& brem) {
-    if (p.view_to_mpi == nullptr && p.views_per_mpi > 1) {
-        const int group = band_id / (per_view * p.views_per_mpi);
-        const int first = group * p.views_per_mpi, size = min(p.views_per_mpi, p.N - first);
-        const int r = band_id - first * per_view;
-        brem = r / size;
-        n = first + (r - brem * size);
-    } else {
-        n = band_id / per_view;
-        brem = band_id - n * per_view;
-    }
-}
-
 // band index inside the view -> (column, row) of bands.  The bands of a view are walked in WINDOWS of `wc` band columns: window by window, inside a
 // window row by row (the wc bands of a row next to each other).  XCD x = blockIdx % 8 owns a contiguous run of that walk (xcd_item_per_group), so
 // an XCD's share of a view is wc columns wide and the workgroups that are resident together in one L2 are neighbours in both directions.
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(1024) void band_table_kernel(const KParams p, const
     static_assert(kCols < 32 && kMaxRows < 16, "shape_pack");
     const int band_id = blockIdx.x;
     int n, brem;
-    band_to_view(p, band_id, bands_x * bands_y, n, brem);
+    item_to_view(p, band_id, bands_x * bands_y, n, brem);
     int bxi, byi;
     band_pos(brem, bands_x, bands_y, p.band_cols, bxi, byi);
     uint32_t ignore = 0;
@@ -387,7 +372,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
 #endif
     if (band_id >= n_bands) return;
     int n, brem;
-    band_to_view(p, band_id, bands_x * bands_y, n, brem);
+    item_to_view(p, band_id, bands_x * bands_y, n, brem);
     if (view_gated_out(p, n)) return;  // (AUTO: a view with a box that does not fit is the tile kernel's)
     int bxi, byi;
     band_pos(brem, bands_x, bands_y, p.band_cols, bxi, byi);
@@ -406,26 +391,20 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
     const int lane = tid & 63;
     // status bits: kept wave-uniform (a scalar register) until the epilogue -- a per-lane word would cost a VGPR through the plane loop
     uint32_t bad_w = 0;
-    const int m = view_mpi(p, n, bad_w);
-    const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    // cx, cy: (Wt - 1) / 2, (Ht - 1) / 2 (align_corners) or Wt, Ht -- kernel arguments, i.e. scalar registers: computed here they would sit in
-    // a VGPR each through the plane loop
+    View vw = view_setup<AC>(p, n, bad_w);
+    // cx, cy: (Wt - 1) / 2, (Ht - 1) / 2 (align_corners) or Wt, Ht -- kernel arguments, i.e. scalar registers: the ones view_setup computes would
+    // sit in a VGPR each through the plane loop (overwritten here, they are never formed)
+    vw.cx = cx, vw.cy = cy;
+    const int D = p.D, H = p.H, W = p.W;
+    const float* __restrict__ dhw = vw.dhw;
+    const float ex = vw.ex, ey = vw.ey, ez = vw.ez;  // (the names the plane loop uses)
     constexpr bool check_range = CHECK;  // GMPI_FLAG_CHECK_RANGE (a template parameter: the test would sit in the plane loop)
-    const bool check_last = (p.flags & (1u << 2)) != 0;
-    const int64_t HW = static_cast<int64_t>(H) * W;
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-    const int64_t s_chan = p.s_chan, s_row = p.s_row, s_plane = p.s_plane;
+    const int64_t HW = vw.HW;
+    const float* __restrict__ rdv = vw.rays;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const int64_t s_chan = p.s_chan, s_row = p.s_row;
 
-    if (p.status != nullptr && brem == 0 && tid == 0) {  // mpi.py:70-72, once per view
-        const float ez0 = p.eye_pos[2];
-        bool behind = false;
-        for (int k = 0; k < D; ++k) behind |= !(dhw[3 * k] >= ez0);
-        if (behind) atomicOr(p.status, 4u);
-    }
+    check_camera_behind(p, vw, brem == 0 && tid == 0);  // once per view
 
     // ---- this thread's pixels: column px, rows py0 + WPS q (out-of-image pixels shadow the last row / column) ------------
     const int px = bxi * (NSB * SBW) + sb * SBW + lane;
@@ -439,12 +418,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
         rx[q] = rdv[pix], ry[q] = rdv[HW + pix], rz[q] = rdv[2 * HW + pix];
         rcp_rz[q] = 1.0f / rz[q];  // correctly rounded; hoisted out of the plane loop (div_by_recip)
     }
-    auto ray_dot = [&](int q) {  // einsum("nchw,nc->nhw") mpi.py:149
-        float dot = rx[q] * zx;
-        dot = dot + ry[q] * zy;
-        dot = dot + rz[q] * zz;
-        return dot;
-    };
+    auto ray_dot = [&](int q) { return gmpi::ray_dot(vw, rx[q], ry[q], rz[q]); };
 
     // ---- this thread's loader items: item kPassItems r + (tid % kSubLanes) of its sub-block's box -> (texel row, channel, item column) ----
     auto loader_pos = [&](int& l_col, int& l_line, int& l_row, bool& l_on) {  // pass 0: line = 4 row + channel
@@ -493,14 +467,9 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
         for (int q = 0; q < PPT; ++q) {
             const float dot = ray_dot(q);
             for (int t = 0; t < D; ++t) {
-                const float d = dhw[3 * t + 0], ph = dhw[3 * t + 1], pw = dhw[3 * t + 2];
-                float ix, iy, s, u, v;
-                plane_coord<AC>(d - ez, ph, pw, ex, ey, rx[q], ry[q], rz[q], cx, cy, ix, iy, s, u, v);
-                float smp[4];
                 uint32_t gbad = 0;
-                gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(t) * s_plane, s_chan, s_row, Ht, Wt, ix, iy, check_range, gbad, smp);
-                if (check_range && __any(gbad != 0)) bad_w |= 2u;
-                blend<STRICT>(A[q], smp[0], smp[1], smp[2], smp[3], s, dot);
+                gather_plane<TexT, AC, STRICT>(p, vw, vol, t, dhw[3 * t] - ez, dhw[3 * t + 1], dhw[3 * t + 2], rx[q], ry[q], rz[q], dot, std::bool_constant<CHECK>{}, gbad, A[q]);
+                if (check_range && __any(gbad != 0)) bad_w |= GMPI_STATUS_RGBA_RANGE;
             }
         }
     } else {
@@ -866,7 +835,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
             if (p.status != nullptr && mx > kOne) { atomicMax(p.status + 1, mx); atomicMax(p.status + 2, static_cast<uint32_t>(band_id)); atomicMax(p.status + 3, static_cast<uint32_t>(tid)); }
 #endif
             if (__any(mx > kOne)) {
-                if (__any(mx > kOne && mx != kNegZero)) bad_w |= 2u;
+                if (__any(mx > kOne && mx != kNegZero)) bad_w |= GMPI_STATUS_RGBA_RANGE;
                 else {
                     int l_col, l_line, l_row;
                     bool l_on;
@@ -891,7 +860,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
                             }
                         }
                     }
-                    if (__any(lane_bad)) bad_w |= 2u;
+                    if (__any(lane_bad)) bad_w |= GMPI_STATUS_RGBA_RANGE;
                 }
             }
         }
@@ -899,32 +868,13 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
 
     // ---- epilogue per pixel -------------------------------------------------------------------------------------------------
     uint32_t bad = bad_w;
-    float dl = 0.0f, phl = 1.0f, pwl = 1.0f;
-    if (check_last) dl = dhw[3 * (D - 1) + 0], phl = dhw[3 * (D - 1) + 1], pwl = dhw[3 * (D - 1) + 2];
+    const LastPlane lp = last_plane(p, vw);
     const int px_e = bxi * (NSB * SBW) + sb * SBW + (fresh_tid() & 63);
 #pragma unroll
     for (int q = 0; q < PPT; ++q) {
         const int py = byi * SBH + wj + WPS * q;
-        if (check_last) {  // assert_not_out_of_last_plane (mpi.py:381-395): u,v of the last plane, once per pixel
-            float ix, iy, s, u, v;
-            plane_coord<AC>(dl - ez, phl, pwl, ex, ey, rx[q], ry[q], rz[q], cx, cy, ix, iy, s, u, v);
-            if (!(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
-        }
-        float r = A[q].r, g = A[q].g, b = A[q].b;
-        if (p.flags & (1u << 1)) {  // mpi_renderer.py:467  2*c - 1
-            r = 2.0f * r - 1.0f;
-            g = 2.0f * g - 1.0f;
-            b = 2.0f * b - 1.0f;
-        }
-        if (px_e < W && py < H) {
-            const int64_t pix = static_cast<int64_t>(py) * W + px_e;
-            float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
-            out[0] = r;
-            out[HW] = g;
-            out[2 * HW] = b;
-            p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A[q], ray_dot(q));
-            if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A[q].T;
-        }
+        if (leaves_last_plane<AC>(vw, lp, rx[q], ry[q], rz[q])) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
+        store_pixel<STRICT>(p, n, HW, static_cast<int64_t>(py) * W + px_e, A[q], ray_dot(q), px_e < W && py < H);
     }
     report_status(p.status, bad);
 #ifdef GMPI_TUNE
@@ -969,7 +919,7 @@ static hipError_t launch_t(const KParams& p, hipStream_t stream) {
     const int tail = std::min(p.band_tail, (group_items + 7) / 8);
     const dim3 grid(xcd_grid_per_group(group_items, n_bands) + 8u * static_cast<unsigned>(tail)), block(Geo<TexT>::kThreads);   // (+ the extra blocks that only draw tickets)
     uint32_t* tickets = static_cast<uint32_t*>(p.ws) + n_bands + p.N;
-    const bool acf = p.flags & 1u;
+    const bool acf = p.flags & GMPI_FLAG_ALIGN_CORNERS;
     const float cx = acf ? static_cast<float>(p.Wt - 1) * 0.5f : static_cast<float>(p.Wt), cy = acf ? static_cast<float>(p.Ht - 1) * 0.5f : static_cast<float>(p.Ht);
     uint32_t* hdr = static_cast<uint32_t*>(p.ws);
     uint4* pl = reinterpret_cast<uint4*>(static_cast<unsigned char*>(p.ws) + ws_hdr_bytes(n_bands, p.N));
@@ -977,17 +927,16 @@ static hipError_t launch_t(const KParams& p, hipStream_t stream) {
     // 1. the geometry table (one workgroup per band; writes every word the render kernel reads but the two planes of padding, whose content
     //    is never used)
     const dim3 tgrid(static_cast<unsigned>(n_bands)), tblock(static_cast<unsigned>(std::min(1024, (p.D * NSB + 63) / 64 * 64)));  // one record per thread up to 256 planes
-    if (acf) hipLaunchKernelGGL((band_table_kernel<TexT, true>), tgrid, tblock, 0, stream, p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
-    else hipLaunchKernelGGL((band_table_kernel<TexT, false>), tgrid, tblock, 0, stream, p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
+    dispatch_bool(acf, [&](auto AC) {
+        hipLaunchKernelGGL((band_table_kernel<TexT, decltype(AC)::value>), tgrid, tblock, 0, stream, p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
+    });
     // 2. the render
-    const int sel = (p.flags & 1u ? 4 : 0) | (p.flags & (1u << 4) ? 2 : 0) | (p.flags & (1u << 3) ? 1 : 0);  // align_corners, strict order, range check
-    switch (sel) {
-#define GMPI_BAND_CASE(I, AC_, ST_, CK_) \
-    case I: hipLaunchKernelGGL((render_band_kernel<TexT, AC_, ST_, CK_>), grid, block, 0, stream, p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets); break;
-        GMPI_BAND_CASE(0, false, false, false) GMPI_BAND_CASE(1, false, false, true) GMPI_BAND_CASE(2, false, true, false) GMPI_BAND_CASE(3, false, true, true)
-        GMPI_BAND_CASE(4, true, false, false) GMPI_BAND_CASE(5, true, false, true) GMPI_BAND_CASE(6, true, true, false) GMPI_BAND_CASE(7, true, true, true)
-#undef GMPI_BAND_CASE
-    }
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        dispatch_bool(p.flags & GMPI_FLAG_CHECK_RANGE, [&](auto CHECK) {
+            hipLaunchKernelGGL((render_band_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, decltype(CHECK)::value>), grid, block, 0, stream, p, bands_x,
+                               bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -1009,10 +958,8 @@ bool band_variant_supports(const KParams& p, int dtype) {
     const int nsb = band::nsb_of(dtype), bw = nsb * band::SBW;
     if (p.ws == nullptr || p.ws_bytes < band::ws_bytes(p, nsb) || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return false;  // needs the caller's workspace
     if (static_cast<int64_t>(p.N) * p.D * ((p.W + bw - 1) / bw) * ((p.H + 7) / 8) > (int64_t(1) << 28)) return false;  // record indices stay in 32 bits
-    const int es = dtype == 0 ? 4 : 2, tpi = 16 / es;
-    if (p.Wt % tpi != 0) return false;
-    if (reinterpret_cast<uintptr_t>(p.rgba) % 16 != 0) return false;
-    if (p.s_row % tpi != 0 || p.s_chan % tpi != 0 || p.s_plane % tpi != 0 || p.s_mpi % tpi != 0) return false;
+    const int es = dtype == 0 ? 4 : 2;
+    if (!volume_stages_in_items(p, dtype)) return false;
     if (p.Ht > 8192 || p.Wt > 8192) return false;  // tap addresses are formed in fp32
     const int64_t span = 3 * p.s_chan + 18 * p.s_row + 128;  // the in-plane item offset (row < 6, + 2 passes of 6 rows, 3 channels) is kept in 32 bits
     if (span >= (int64_t(1) << 31) / es) return false;
@@ -1036,10 +983,8 @@ hipError_t launch_band(const KParams& p0, int dtype, int tune, hipStream_t strea
 #else
     (void)tune;
 #endif
-    if (dtype == 1) return band::launch_t<bf16_t>(p, stream);
-    if (dtype == 2) return band::launch_t<f16_t>(p, stream);
-    if (dtype == 0) return band::launch_t<float>(p, stream);
-    return hipErrorInvalidValue;
+    if (dtype < 0 || dtype > 2) return hipErrorInvalidValue;
+    return dispatch_dtype(dtype, [&](auto t) { return band::launch_t<typename decltype(t)::type>(p, stream); });
 }
 
 }  // namespace gmpi

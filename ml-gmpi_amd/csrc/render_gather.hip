@@ -20,66 +20,30 @@ __global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kern
     const int px = blockIdx.x * kGatherTileW + threadIdx.x;
     const int py = blockIdx.y * kGatherTileH + threadIdx.y;
     uint32_t bad = 0;
-    const int m = view_mpi(p, n, bad);  // (an index outside [0, M) is clamped and reported)
-
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-
-    // mpi.py:70-72 compares every plane distance with eye_z of the FIRST view; one lane per view checks it.
-    if (p.status != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
-        const float ez0 = p.eye_pos[2];
-        bool behind = false;
-        for (int k = 0; k < p.D; ++k) behind |= !(dhw[3 * k] >= ez0);
-        if (behind) atomicOr(p.status, 4u);
-    }
+    const View vw = view_setup<AC>(p, n, bad);
+    check_camera_behind(p, vw, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0);  // one lane per view
     // edge tiles: out-of-image lanes shadow the last pixel (keeps the wave converged for the status reduce)
     const bool active = px < p.W && py < p.H;
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const int64_t HW = vw.HW;
     const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float rx = rd[0], ry = rd[HW], rz = rd[2 * HW];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    float dot = rx * zx;  // einsum("nchw,nc->nhw") mpi.py:149
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
-
-    const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const bool check_range = (p.flags & (1u << 3)) != 0;
-    const bool check_last = (p.flags & (1u << 2)) != 0;
-
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
-    const int64_t s_chan = p.s_chan, s_row = p.s_row;
+    const float rx = vw.rays[pix], ry = vw.rays[HW + pix], rz = vw.rays[2 * HW + pix];
+    const float dot = ray_dot(vw, rx, ry, rz);
+    const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
 
     Accum A;
 #pragma unroll 2
-    for (int k = 0; k < p.D; ++k) {
-        const float d = dhw[3 * k + 0], ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
-        const float zdiff = d - ez;
+    for (int k = 0; k < p.D; ++k) {  // gather_plane's body, written out: through the helper one instance (fp16, align_corners, strict) takes 2 VGPRs more
+        const float d = vw.dhw[3 * k + 0], ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
         float ix, iy, s, u, v;
-        plane_coord<AC>(zdiff, ph, pw, ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
-        if (check_last && k == p.D - 1 && !(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
-
+        plane_coord<AC>(d - vw.ez, ph, pw, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
         float smp[4];
-        gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(k) * p.s_plane, s_chan, s_row, Ht, Wt, ix, iy, check_range, bad, smp);
+        gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
         blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
     }
-
-    float r = A.r, g = A.g, b = A.b;
-    if (p.flags & (1u << 1)) {  // mpi_renderer.py:467  2*c - 1
-        r = 2.0f * r - 1.0f;
-        g = 2.0f * g - 1.0f;
-        b = 2.0f * b - 1.0f;
-    }
-    if (active) {
-        float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
-        out[0] = r;
-        out[HW] = g;
-        out[2 * HW] = b;
-        p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
-        if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
-    }
+    const LastPlane lp = last_plane(p, vw);
+    if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
     report_status(p.status, bad);
 }
 
@@ -87,20 +51,14 @@ template <typename TexT>
 static hipError_t launch_gather_t(const KParams& p, hipStream_t stream) {
     const dim3 block(kGatherTileW, kGatherTileH);
     const dim3 grid((p.W + kGatherTileW - 1) / kGatherTileW, (p.H + kGatherTileH - 1) / kGatherTileH, p.N);
-    const bool ac = p.flags & 1u, strict = p.flags & (1u << 4);
-    if (ac && strict) hipLaunchKernelGGL((render_gather_kernel<TexT, true, true>), grid, block, 0, stream, p);
-    else if (ac) hipLaunchKernelGGL((render_gather_kernel<TexT, true, false>), grid, block, 0, stream, p);
-    else if (strict) hipLaunchKernelGGL((render_gather_kernel<TexT, false, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((render_gather_kernel<TexT, false, false>), grid, block, 0, stream, p);
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_gather_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case 0: return launch_gather_t<float>(p, stream);
-        case 1: return launch_gather_t<bf16_t>(p, stream);
-        default: return launch_gather_t<f16_t>(p, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, stream); });
 }
 
 }  // namespace gmpi

@@ -188,54 +188,31 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
     }
 #endif
     if (tile_id >= n_tiles) return;
-    // Views that share one MPI (video paths: views_per_mpi > 1) are interleaved per tile position, so the workgroups
-    // that need (nearly) the same texels of a plane run next to each other in time and on the same XCD: the volume is
-    // then read from HBM about once per group of views instead of once per view (the rest hits in that XCD's L2).
     int n, trem;
-    if (p.view_to_mpi == nullptr && p.views_per_mpi > 1) {
-        const int group = tile_id / (tiles_per_view * p.views_per_mpi);           // full groups come first
-        const int first = group * p.views_per_mpi, size = min(p.views_per_mpi, p.N - first);
-        const int r = tile_id - first * tiles_per_view;
-        trem = r / size;
-        n = first + (r - trem * size);
-    } else {
-        n = tile_id / tiles_per_view;
-        trem = tile_id - n * tiles_per_view;
-    }
+    item_to_view(p, tile_id, tiles_per_view, n, trem);  // (views that share one MPI are interleaved per tile position)
     if (view_bits != nullptr ? ((view_bits[n >> 5] >> (n & 31)) & 1u) == 0u : view_gated_out(p, n)) return;  // (AUTO: this view is the band kernel's)
     const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
 
     const int tid = threadIdx.x;
     uint32_t bad = 0;
-    const int m = view_mpi(p, n, bad);  // (an index outside [0, M) is clamped and reported)
+    const View vw = view_setup<AC>(p, n, bad);
     const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const bool check_range = (p.flags & (1u << 3)) != 0;
-    const bool check_last = (p.flags & (1u << 2)) != 0;
-    const int64_t HW = static_cast<int64_t>(H) * W;
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
+    const float* __restrict__ dhw = vw.dhw;
+    const float ex = vw.ex, ey = vw.ey, ez = vw.ez, cx = vw.cx, cy = vw.cy;  // (the names the plane loop uses)
+    const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
+    const int64_t HW = vw.HW;
+    const float* __restrict__ rdv = vw.rays;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
     const int64_t s_chan = p.s_chan, s_row = p.s_row, s_plane = p.s_plane;
 
-    if (p.status != nullptr && trem == 0 && tid == 0) {  // mpi.py:70-72, once per view
-        const float ez0 = p.eye_pos[2];
-        bool behind = false;
-        for (int k = 0; k < D; ++k) behind |= !(dhw[3 * k] >= ez0);
-        if (behind) atomicOr(p.status, 4u);
-    }
+    check_camera_behind(p, vw, trem == 0 && tid == 0);  // once per view
 
     // ---- this thread's pixel (out-of-image lanes shadow the last row/column) ---------------------------------
     const int px = txi * TW + (tid % TW), py = tyi * TH + (tid / TW);
     const bool active = px < W && py < H;
     const int64_t pix = static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
-    float dot = rx * zx;  // einsum("nchw,nc->nhw") mpi.py:149
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
+    const float dot = ray_dot(vw, rx, ry, rz);
     const float rcp_rz = 1.0f / rz;  // correctly rounded; hoisted out of the plane loop (see div_by_recip)
     Accum A;
 
@@ -331,12 +308,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
             if (!mine) return;
             for (int t = 0; t < kn; ++t) {
                 const float4 rf = tabF[t];
-                float ix, iy, s, u, v;
-                plane_coord<AC>(rf.x, rf.z + rf.z, rf.y + rf.y, ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
-                float smp[4];
-                gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(kc + t) * s_plane, s_chan, s_row, Ht, Wt, ix, iy,
-                                            check_range, bad, smp);
-                blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
+                gather_plane<TexT, AC, STRICT>(p, vw, vol, kc + t, rf.x, rf.z + rf.z, rf.y + rf.y, rx, ry, rz, dot, check_range, bad, A);  // (exact doublings of the table's halves)
             }
         };
 
@@ -408,7 +380,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
                 if (check_range && __builtin_expect(mx > 0x3f800000u, 0)) {
 #pragma unroll
                     for (int r = 0; r < NP; ++r)
-                        if (quad_out_of_unit(make_float4(__uint_as_float(L[r].x), __uint_as_float(L[r].y), __uint_as_float(L[r].z), __uint_as_float(L[r].w)))) bad |= 2u;
+                        if (quad_out_of_unit(make_float4(__uint_as_float(L[r].x), __uint_as_float(L[r].y), __uint_as_float(L[r].z), __uint_as_float(L[r].w)))) bad |= GMPI_STATUS_RGBA_RANGE;
                 }
                 return;
             } else if constexpr (LAYOUT == 1) {
@@ -438,7 +410,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
                         const uint32_t d[4] = {L[r].x, L[r].y, L[r].z, L[r].w};
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
-                            if (!(ok(d[c] & 0xffffu) && ok(d[c] >> 16))) bad |= 2u;
+                            if (!(ok(d[c] & 0xffffu) && ok(d[c] >> 16))) bad |= GMPI_STATUS_RGBA_RANGE;
                     }
                 }
                 return;
@@ -467,7 +439,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
                     Q::cvt(L[r], q);
 #pragma unroll
                     for (int h = 0; h < NQ; ++h)
-                        if (quad_out_of_unit(q[h])) bad |= 2u;
+                        if (quad_out_of_unit(q[h])) bad |= GMPI_STATUS_RGBA_RANGE;
                 }
             }
         };
@@ -602,28 +574,9 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
         }
     }
 
-    // ---- assert_not_out_of_last_plane (mpi.py:381-395): u,v of the last plane, once per pixel ------------------
-    if (check_last) {
-        const float d = dhw[3 * (D - 1) + 0], ph = dhw[3 * (D - 1) + 1], pw = dhw[3 * (D - 1) + 2];
-        float ix, iy, s, u, v;
-        plane_coord<AC>(d - ez, ph, pw, ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
-        if (!(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
-    }
-
-    float r = A.r, g = A.g, b = A.b;
-    if (p.flags & (1u << 1)) {  // mpi_renderer.py:467  2*c - 1
-        r = 2.0f * r - 1.0f;
-        g = 2.0f * g - 1.0f;
-        b = 2.0f * b - 1.0f;
-    }
-    if (active) {
-        float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
-        out[0] = r;
-        out[HW] = g;
-        out[2 * HW] = b;
-        p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
-        if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
-    }
+    const LastPlane lp = last_plane(p, vw);
+    if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
     report_status(p.status, bad);
 }
 
@@ -675,10 +628,7 @@ static int elem_size(int dtype) { return dtype == 0 ? 4 : 2; }
 
 bool lds_variant_supports(const KParams& p, int dtype) {
     const int es = elem_size(dtype);
-    const int tpi = 16 / es;  // texels per 16-byte loader item
-    if (p.Wt % tpi != 0) return false;
-    if (reinterpret_cast<uintptr_t>(p.rgba) % 16 != 0) return false;
-    if (p.s_row % tpi != 0 || p.s_chan % tpi != 0 || p.s_plane % tpi != 0 || p.s_mpi % tpi != 0) return false;
+    if (!volume_stages_in_items(p, dtype)) return false;
     // the in-plane item offset is kept in 32 bits
     const int64_t span = 3 * p.s_chan + (TileCfg<32>::kMaxLines / 4 + 1) * p.s_row + 128;
     if (span >= (int64_t(1) << 31) / es) return false;
@@ -704,24 +654,22 @@ static hipError_t launch_lds_t(const KParams& p, hipStream_t stream) {
     const unsigned grid_x = (p.gate != nullptr || sizeof(TexT) == 4 || (p.flags & (1u << 19))) ? xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)
                                               : static_cast<unsigned>(((n_tiles + 7) / 8) * 8);
     const dim3 grid(grid_x), block(kNT);
-    const bool ac = p.flags & 1u, strict = p.flags & (1u << 4);
     if (p.gate != nullptr) {
         unsigned gg = std::min(grid_x, gated_grid<TexT>(p.view_to_mpi == nullptr && p.views_per_mpi > 1));
 #ifdef GMPI_TUNE  // GMPI_TUNE_GGRID: the gated launch's grid (A/B)
         static const int env_gg = [] { const char* e = getenv("GMPI_TUNE_GGRID"); return e ? atoi(e) : 0; }();
         if (env_gg > 0) gg = std::min(grid_x, static_cast<unsigned>(env_gg));
 #endif
-        const dim3 ggrid(gg);
-        if (ac && strict) hipLaunchKernelGGL((render_lds_gated_kernel<TexT, true, true, TW, MINW, PF, LAYOUT>), ggrid, block, 0, stream, p, tiles_x, tiles_y, n_tiles, grid_x);
-        else if (ac) hipLaunchKernelGGL((render_lds_gated_kernel<TexT, true, false, TW, MINW, PF, LAYOUT>), ggrid, block, 0, stream, p, tiles_x, tiles_y, n_tiles, grid_x);
-        else if (strict) hipLaunchKernelGGL((render_lds_gated_kernel<TexT, false, true, TW, MINW, PF, LAYOUT>), ggrid, block, 0, stream, p, tiles_x, tiles_y, n_tiles, grid_x);
-        else hipLaunchKernelGGL((render_lds_gated_kernel<TexT, false, false, TW, MINW, PF, LAYOUT>), ggrid, block, 0, stream, p, tiles_x, tiles_y, n_tiles, grid_x);
+        dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+            hipLaunchKernelGGL((render_lds_gated_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, TW, MINW, PF, LAYOUT>), dim3(gg), block, 0, stream, p,
+                               tiles_x, tiles_y, n_tiles, grid_x);
+        });
         return hipGetLastError();
     }
-    if (ac && strict) hipLaunchKernelGGL((render_lds_kernel<TexT, true, true, TW, MINW, PF, LAYOUT>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
-    else if (ac) hipLaunchKernelGGL((render_lds_kernel<TexT, true, false, TW, MINW, PF, LAYOUT>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
-    else if (strict) hipLaunchKernelGGL((render_lds_kernel<TexT, false, true, TW, MINW, PF, LAYOUT>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
-    else hipLaunchKernelGGL((render_lds_kernel<TexT, false, false, TW, MINW, PF, LAYOUT>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_lds_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, TW, MINW, PF, LAYOUT>), grid, block, 0, stream, p, tiles_x, tiles_y,
+                           n_tiles);
+    });
     return hipGetLastError();
 }
 
@@ -743,11 +691,11 @@ hipError_t launch_lds(const KParams& p0, int dtype, int tune, hipStream_t stream
     // texels, interleaved (LAYOUT 1, 4 workgroups per CU); 32x16 pixel tiles, one plane of prefetch -- the values the round-1
     // ablations settled on (profiles/r01_ablation.txt; the other combinations are no longer instantiated).
     (void)tune;
-    switch (dtype) {
-        case 0: return launch_lds_t<float, kTileW, 6, 1, 0>(p, stream);
-        case 1: return launch_lds_t<bf16_t, kTileW, 8, 1, 1>(p, stream);
-        default: return launch_lds_t<f16_t, kTileW, 8, 1, 1>(p, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) {
+        using TexT = typename decltype(t)::type;
+        constexpr bool k16 = sizeof(TexT) == 2;
+        return launch_lds_t<TexT, kTileW, (k16 ? 8 : 6), 1, (k16 ? 1 : 0)>(p, stream);
+    });
 }
 
 }  // namespace gmpi

@@ -42,7 +42,7 @@ __device__ __forceinline__ float tap_sample(const TexT* __restrict__ ch, int64_t
     const float t_ne = to_f32(ch[oa + t.xb]);
     const float t_sw = to_f32(ch[ob + t.xa]);
     const float t_se = to_f32(ch[ob + t.xb]);
-    if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= 2u;
+    if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= GMPI_STATUS_RGBA_RANGE;
     return bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, t.f);
 }
 // (r, g, b, alpha) of plane k for one pixel: colour from the shared image (the background on the last plane), alpha from its plane
@@ -61,39 +61,27 @@ __global__ __launch_bounds__(256) void render_shared_kernel(const KParams p, con
     const int px = blockIdx.x * 64 + threadIdx.x;
     const int py = blockIdx.y * 4 + threadIdx.y;
     uint32_t bad = 0;
-    const int m = view_mpi(p, n, bad);
-    const float* __restrict__ dhw = p.dhw + static_cast<int64_t>(m) * p.D * 3;
-    const float ex = p.eye_pos[3 * n + 0], ey = p.eye_pos[3 * n + 1], ez = p.eye_pos[3 * n + 2];
-    if (p.status != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {   // mpi.py:70-72, as the gather kernel
-        const float ez0 = p.eye_pos[2];
-        bool behind = false;
-        for (int k = 0; k < p.D; ++k) behind |= !(dhw[3 * k] >= ez0);
-        if (behind) atomicOr(p.status, 4u);
-    }
+    const View vw = view_setup<AC>(p, n, bad);
+    const int m = vw.m;
+    check_camera_behind(p, vw, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0);  // one lane per view, as the gather kernel
     const bool active = px < p.W && py < p.H;
-    const int64_t HW = static_cast<int64_t>(p.H) * p.W;
+    const int64_t HW = vw.HW;
     const int64_t pix = static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1);
-    const float* __restrict__ rd = p.ray_dir + static_cast<int64_t>(n) * 3 * HW + pix;
-    const float rx = rd[0], ry = rd[HW], rz = rd[2 * HW];
-    const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
-    float dot = rx * zx;
-    dot = dot + ry * zy;
-    dot = dot + rz * zz;
+    const float rx = vw.rays[pix], ry = vw.rays[HW + pix], rz = vw.rays[2 * HW + pix];
+    const float dot = ray_dot(vw, rx, ry, rz);
     const int Ht = p.Ht, Wt = p.Wt;
-    const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
-    const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const bool check_range = (p.flags & (1u << 3)) != 0;
-    const bool check_last = (p.flags & (1u << 2)) != 0;
+    const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
+    const bool check_last = (p.flags & GMPI_FLAG_CHECK_LAST_PLANE) != 0;
     const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
 
     Accum A;
     for (int k = 0; k < p.D; ++k) {
-        const float d = dhw[3 * k + 0], ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
         float ix, iy, s, u, v;
-        plane_coord<AC>(d - ez, ph, pw, ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
-        if (check_last && k == p.D - 1 && !(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
+        plane_coord<AC>(vw.dhw[3 * k] - vw.ez, vw.dhw[3 * k + 1], vw.dhw[3 * k + 2], vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
+        // (leaves_last_plane's test on the u, v the loop has anyway: after the loop it costs the strict bf16 instances 2 VGPRs)
+        if (check_last && k == p.D - 1 && outside_pm1(u, v)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
         const Taps t = make_taps(ix, iy, Ht, Wt);
         const bool last_bg = bgi != nullptr && k == p.D - 1;   // uniform
         float smp[4];
@@ -101,20 +89,7 @@ __global__ __launch_bounds__(256) void render_shared_kernel(const KParams p, con
                                     last_bg ? sh.bs_row : sh.rs_row, t, check_range, bad, smp);
         blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
     }
-    float r = A.r, g = A.g, b = A.b;
-    if (p.flags & (1u << 1)) {
-        r = 2.0f * r - 1.0f;
-        g = 2.0f * g - 1.0f;
-        b = 2.0f * b - 1.0f;
-    }
-    if (active) {
-        float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
-        out[0] = r;
-        out[HW] = g;
-        out[2 * HW] = b;
-        p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
-        if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
-    }
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
     report_status(p.status, bad);
 }
 
@@ -224,7 +199,7 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     const BwdView vw = bwd_view<AC>(p, n);
     const int m = vw.m, D = p.D;
     const float* __restrict__ dhw = vw.dhw;
-    const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * vw.HW;
+    const float* __restrict__ rdv = vw.rays;
     const int Ht = p.Ht, Wt = p.Wt;
     const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
@@ -431,10 +406,8 @@ template <typename TexT>
 static hipError_t launch_shared_t(const KParams& p, const SharedK& sh, hipStream_t stream) {
     const dim3 block(64, 4);
     const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
-    dispatch_bool(p.flags & 1u, [&](auto AC) {
-        dispatch_bool(p.flags & (1u << 4), [&](auto STRICT) {
-            hipLaunchKernelGGL((render_shared_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, sh);
-        });
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_shared_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, sh);
     });
     return hipGetLastError();
 }
@@ -447,7 +420,7 @@ bool shared_tile_supports(const KParams& p) { return p.D <= kSPlanes; }
 
 template <typename TexT>
 static hipError_t launch_shared_backward_t(const KParams& p, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream) {
-    const bool ac = p.flags & 1u;
+    const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
     if (tiles) {
         const int tiles_x = (p.W + kSTW - 1) / kSTW, n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
         const dim3 grid(xcd_grid_per_group(n_tiles, n_tiles), p.N);

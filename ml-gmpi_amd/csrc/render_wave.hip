@@ -197,8 +197,8 @@ __global__ __launch_bounds__(WPB * SPLIT * 64, WPS) void render_wave_kernel(cons
     const float zx = p.z_dir[3 * n + 0], zy = p.z_dir[3 * n + 1], zz = p.z_dir[3 * n + 2];
     const float cx = AC ? static_cast<float>(Wt - 1) * 0.5f : static_cast<float>(Wt);
     const float cy = AC ? static_cast<float>(Ht - 1) * 0.5f : static_cast<float>(Ht);
-    const bool check_range = (p.flags & (1u << 3)) != 0;
-    const bool check_last = (p.flags & (1u << 2)) != 0;
+    const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
+    const bool check_last = (p.flags & GMPI_FLAG_CHECK_LAST_PLANE) != 0;
     const int64_t HW = static_cast<int64_t>(H) * W;
     const float* __restrict__ rdv = p.ray_dir + static_cast<int64_t>(n) * 3 * HW;
     const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(WPB * SPLIT * 64, WPS) void render_wave_kernel(cons
         const float ez0 = p.eye_pos[2];
         bool behind = false;
         for (int k = 0; k < D; ++k) behind |= !(dhw[3 * k] >= ez0);
-        if (behind) atomicOr(p.status, 4u);
+        if (behind) atomicOr(p.status, GMPI_STATUS_CAMERA_BEHIND_PLANE);
     }
 
     // ---- this wave's strip and plane range (no workgroup barrier on the data path; with SPLIT > 1 one at the very end, so a
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(WPB * SPLIT * 64, WPS) void render_wave_kernel(cons
                         for (int q = 0; q < NPC; ++q)
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
-                                if (check_range && IO::bad(L[q][c])) bad |= 2u;
+                                if (check_range && IO::bad(L[q][c])) bad |= GMPI_STATUS_RGBA_RANGE;
                                 if (HALF && IO::unsafe_half(L[q][c])) unsafe = true;
                             }
                     }
@@ -696,10 +696,10 @@ __global__ __launch_bounds__(WPB * SPLIT * 64, WPS) void render_wave_kernel(cons
             const float d = dhw[3 * (D - 1) + 0], ph = dhw[3 * (D - 1) + 1], pw = dhw[3 * (D - 1) + 2];
             float ix, iy, s, u, v;
             plane_coord<AC>(d - ez, ph, pw, ex, ey, rx[j], ry[j], rz[j], cx, cy, ix, iy, s, u, v);
-            if (!(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= 1u;
+            if (!(u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
         }
         float r = A[j].r, g = A[j].g, b = A[j].b;
-        if (p.flags & (1u << 1)) {  // mpi_renderer.py:467  2*c - 1
+        if (p.flags & GMPI_FLAG_OUT_PM1) {  // mpi_renderer.py:467  2*c - 1
             r = 2.0f * r - 1.0f;
             g = 2.0f * g - 1.0f;
             b = 2.0f * b - 1.0f;
@@ -720,10 +720,7 @@ __global__ __launch_bounds__(WPB * SPLIT * 64, WPS) void render_wave_kernel(cons
 // ---- host side ---------------------------------------------------------------------------------------------------
 bool wave_variant_supports(const KParams& p, int dtype) {
     const int es = dtype == 0 ? 4 : 2;
-    const int tpi = 16 / es;  // texels per 16-byte loader item
-    if (p.Wt % tpi != 0) return false;  // items of a box that touches the border must not straddle it
-    if (reinterpret_cast<uintptr_t>(p.rgba) % 16 != 0) return false;
-    if (p.s_row % tpi != 0 || p.s_chan % tpi != 0 || p.s_plane % tpi != 0 || p.s_mpi % tpi != 0) return false;
+    if (!volume_stages_in_items(p, dtype)) return false;
     // offsets inside one channel image are kept in 31 bits
     if (static_cast<int64_t>(p.Ht + 64) * p.s_row * es >= (int64_t(1) << 30)) return false;
     return true;
@@ -734,12 +731,14 @@ static hipError_t launch_wave_t(const KParams& p, hipStream_t stream) {
     const int tiles_x = (p.W + WPB * kSW - 1) / (WPB * kSW), tiles_y = (p.H + kSH - 1) / kSH;
     const int n_tiles = tiles_x * tiles_y * p.N;
     const dim3 grid(((n_tiles + 7) / 8) * 8), block(WPB * SPLIT * 64);
+    auto launch = [&](auto AC) {
+        hipLaunchKernelGGL((render_wave_kernel<TexT, decltype(AC)::value, STRICT, WPB, WPS, SPLIT, HALF, GRPSEL>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+    };
 #ifdef GMPI_FAST_BUILD  // experiment builds (tools/build_tune.sh -DGMPI_FAST_BUILD): align_corners only
-    if (!(p.flags & 1u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((render_wave_kernel<TexT, true, STRICT, WPB, WPS, SPLIT, HALF, GRPSEL>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+    if (!(p.flags & GMPI_FLAG_ALIGN_CORNERS)) return hipErrorInvalidValue;
+    launch(std::true_type{});
 #else
-    if (p.flags & 1u) hipLaunchKernelGGL((render_wave_kernel<TexT, true, STRICT, WPB, WPS, SPLIT, HALF, GRPSEL>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
-    else hipLaunchKernelGGL((render_wave_kernel<TexT, false, STRICT, WPB, WPS, SPLIT, HALF, GRPSEL>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+    dispatch_bool(p.flags & GMPI_FLAG_ALIGN_CORNERS, launch);
 #endif
     return hipGetLastError();
 }
@@ -748,28 +747,29 @@ static hipError_t launch_wave_t(const KParams& p, hipStream_t stream) {
 // mode stage fp16 RGBA (HALF: 8 bytes per texel, the fp32 conversion folded into v_fma_mix_f32).
 template <int WPB, int WPS, int SPLIT, int GRPSEL = 0>
 static hipError_t launch_wave_d(const KParams& p, int dtype, hipStream_t stream, bool half = true) {
-    if (dtype == 0) return launch_wave_t<float, WPB, WPS, SPLIT, false, GRPSEL, false>(p, stream);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using TexT = typename decltype(t)::type;
+        constexpr bool k16 = sizeof(TexT) == 2;
 #ifdef GMPI_TUNE
-    if (!half) return dtype == 1 ? launch_wave_t<bf16_t, WPB, WPS, SPLIT, false, 0, false>(p, stream) : launch_wave_t<f16_t, WPB, WPS, SPLIT, false, 0, false>(p, stream);
+        if constexpr (k16) {
+            if (!half) return launch_wave_t<TexT, WPB, WPS, SPLIT, false, 0, false>(p, stream);
+        }
 #else
-    (void)half;
+        (void)half;
 #endif
-    return dtype == 1 ? launch_wave_t<bf16_t, WPB, WPS, SPLIT, true, GRPSEL, false>(p, stream) : launch_wave_t<f16_t, WPB, WPS, SPLIT, true, GRPSEL, false>(p, stream);
+        return launch_wave_t<TexT, WPB, WPS, SPLIT, k16, GRPSEL, false>(p, stream);
+    });
 }
 
 static hipError_t launch_wave_strict(const KParams& p, int dtype, hipStream_t stream) {  // one configuration: 4 strips per workgroup, unsplit
-    switch (dtype) {
-        case 0: return launch_wave_t<float, 4, 3, 1, false, 0, true>(p, stream);
-        case 1: return launch_wave_t<bf16_t, 4, 3, 1, false, 0, true>(p, stream);
-        default: return launch_wave_t<f16_t, 4, 3, 1, false, 0, true>(p, stream);
-    }
+    return dispatch_dtype(dtype, [&](auto t) { return launch_wave_t<typename decltype(t)::type, 4, 3, 1, false, 0, true>(p, stream); });
 }
 
 hipError_t launch_wave(const KParams& p0, int dtype, int tune, hipStream_t stream) {
     KParams p = p0;
 #ifdef GMPI_TUNE
     p.flags |= static_cast<uint32_t>(tune & 0xf00) << 16;  // 256: no memory traffic, 512: loader only, 1024: no LDS stores, 2048: box statistics in status[1..3]
-    if (p.flags & (1u << 4)) return launch_wave_strict(p, dtype, stream);
+    if (p.flags & GMPI_FLAG_STRICT_ORDER) return launch_wave_strict(p, dtype, stream);
     switch (tune & 0xff) {
         case 1: return launch_wave_d<4, 3, 1>(p, dtype, stream, false);   // fp32 texels in LDS (round 2's first strip kernel)
         case 2: return launch_wave_d<4, 3, 3>(p, dtype, stream);
@@ -789,7 +789,7 @@ hipError_t launch_wave(const KParams& p0, int dtype, int tune, hipStream_t strea
     // strips (at most 2 waves per SIMD, config 2) the split does not pay; the 2-waves-per-SIMD build (no register pressure:
     // 213 VGPRs, no scratch) is 5-8 % faster there than the 168-VGPR one.
     const int64_t strips = static_cast<int64_t>(p.N) * ((p.W + kSW - 1) / kSW) * ((p.H + kSH - 1) / kSH);
-    if (p.flags & (1u << 4)) return launch_wave_strict(p, dtype, stream);  // strict order: sequential association, fp32 texels
+    if (p.flags & GMPI_FLAG_STRICT_ORDER) return launch_wave_strict(p, dtype, stream);  // strict order: sequential association, fp32 texels
     if (strips <= 512 && p.D >= 12) return launch_wave_d<2, 3, 6>(p, dtype, stream);
     if (strips <= 1024 && p.D >= 6) return launch_wave_d<4, 3, 3>(p, dtype, stream);
     if (strips <= 2048) return launch_wave_d<4, 2, 1>(p, dtype, stream);
