@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .hip_mpi import _call, _ptr
 
 
 def shard_views(n_views: int, rank: int, world_size: int, mode: str = "strided") -> List[int]:
@@ -38,7 +39,6 @@ def frames_to_uint8(rgb_pm1: torch.Tensor, depth: Optional[torch.Tensor], near: 
     device tensors to write into (e.g. slices of a path-long buffer)."""
     if not rgb_pm1.is_cuda:
         raise _lib.GmpiError("frames_to_uint8 needs device tensors (no CPU path)")
-    lib = _lib.load_library()
     rgb_pm1 = rgb_pm1.contiguous()
     N, _, H, W = rgb_pm1.shape
     img8 = out[0] if out is not None else torch.empty((N, H, W, 3), dtype=torch.uint8, device=rgb_pm1.device)
@@ -48,11 +48,7 @@ def frames_to_uint8(rgb_pm1: torch.Tensor, depth: Optional[torch.Tensor], near: 
         depth = depth.contiguous()
         dep8 = out[1] if out is not None else torch.empty((N, H, W, 1), dtype=torch.uint8, device=rgb_pm1.device)
         assert dep8.is_contiguous() and tuple(dep8.shape) == (N, H, W, 1) and dep8.dtype is torch.uint8
-    with torch.cuda.device(rgb_pm1.device):
-        _lib.check(lib.gmpi_frames_to_uint8_launch(
-            rgb_pm1.data_ptr(), depth.data_ptr() if depth is not None else None, N, H, W, float(near), float(far),
-            img8.data_ptr(), dep8.data_ptr() if dep8 is not None else None,
-            torch.cuda.current_stream(rgb_pm1.device).cuda_stream), "gmpi_frames_to_uint8_launch")
+    _call("gmpi_frames_to_uint8_launch", rgb_pm1.device, rgb_pm1.data_ptr(), _ptr(depth), N, H, W, float(near), float(far), img8.data_ptr(), _ptr(dep8))
     return img8, dep8
 
 

@@ -159,13 +159,12 @@ class _StatusRing:
             if int(self.host_words[slot, 0]) != 0:
                 word_tensor = self.host_words[slot].clone()
                 self._clean_slot(slot)            # (a slot that tripped: clean for its next user)
-                if errors is None:
+                try:
                     mpi.raise_on_status(word_tensor, params=params, keep=keep, c2w_mat=c2w_mat, sphere_c=sphere_c)
-                else:
-                    try:
-                        mpi.raise_on_status(word_tensor, params=params, keep=keep, c2w_mat=c2w_mat, sphere_c=sphere_c)
-                    except BaseException as e:  # noqa: BLE001 -- incl. the SystemExit of on_out_of_plane="exit"
-                        errors.append(e)
+                except BaseException as e:  # noqa: BLE001 -- incl. the SystemExit of on_out_of_plane="exit"
+                    if errors is None:
+                        raise
+                    errors.append(e)
 
     def acquire(self) -> int:
         self.retire(block=False)
@@ -228,6 +227,21 @@ def flush_status() -> None:
         raise errors[0]
 
 
+def _status_target(dev: torch.device, stream: int, status: Optional[torch.Tensor], defer_status, plain: bool):
+    """Where a launch ORs its status bits and how they get looked at: (status words, defer_status, ring, slot).  plain: a render on the
+    device outside the autograd bridges -- only such a call lags (a slot of the stream's ring) or uses the stream's shared words; a
+    caller-owned status tensor, the bridges and the recorder library are read back at once ("lag") or get fresh words."""
+    if defer_status == "lag":
+        if status is None and plain:
+            ring = _ring(dev, stream)
+            slot = ring.acquire()   # (raises here what an earlier call asserted)
+            return ring.dev_words[slot], defer_status, ring, slot
+        defer_status = False
+    if status is None:
+        status = _own_status(dev, stream) if plain and not defer_status else torch.zeros(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    return status, defer_status, None, None
+
+
 def _flush_at_exit() -> None:
     """atexit: Python prints but otherwise IGNORES an exception (and a SystemExit) raised by an exit handler -- the process would end with
     status 0 although a render asserted.  So: report, then leave with status 1 (the reference's `sys.exit(1)` / the status of an uncaught
@@ -268,11 +282,100 @@ def _on_device(dev: Optional[torch.device]):
     return torch.cuda.device(dev)
 
 
+def _call(name: str, dev: torch.device, *args, stream: Optional[int] = None) -> None:
+    """The one way into the C ABI: entry `name` of the library with `args` and, last, the handle of `dev`'s current stream (`stream`: the
+    caller has read it already), with `dev` current; a failure is raised under that name.  Tensors that are not on a ROCm device only get
+    here with a `records_only` library -- stream 0, no device context -- and are refused with any other: the real entries would launch on host
+    pointers.  (The library is looked up per call: tests replace `load_library`.)"""
+    lib = _lib.load_library()
+    if dev.type != "cuda":
+        if not getattr(lib, "records_only", False):
+            raise _lib.GmpiError(f"{name} needs tensors on a ROCm device: this package has no CPU path (got {dev})")
+        return _lib.check(getattr(lib, name)(*args, 0), name)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    if dev.index is None or torch.cuda.current_device() == dev.index:   # (as _on_device, without the context object: every launch comes through here)
+        return _lib.check(getattr(lib, name)(*args, stream), name)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, stream), name)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+# The tensors a launch reads, as the struct names them: alive until the launch has been issued, kept by a lagged status entry for the
+# diagnostics of a tripped assertion, saved by the autograd bridges for their backward.
+_Keep = collections.namedtuple("_Keep", "rgba dhw ray_dir eye_pos z_dir view_to_mpi")
+_Scalars = collections.namedtuple("_Scalars", "flags variant rgba_dtype N M D Ht Wt H W views_per_mpi")   # the struct's non-pointer fields
+
+
+def _render_params(scalars: _Scalars, keep: _Keep, color=None, depth=None, T=None, status=None) -> _lib.GmpiRenderParams:
+    """The one builder of GmpiRenderParams: `scalars` and the tensors of `keep`, plus the outputs and status words of a forward launch (a backward passes T alone: the transmittance its sweep starts from).  A workspace is lent afterwards: its size is asked
+    of the library with this struct."""
+    p = _lib.GmpiRenderParams()
+    p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
+    p.flags, p.variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi = scalars   # (the order of _Scalars)
+    rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi = keep
+    p.rgba = rgba.data_ptr()
+    p.rgba_stride[:] = rgba.stride()
+    p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
+    if view_to_mpi is not None:
+        p.view_to_mpi = view_to_mpi.data_ptr()
+    if color is not None:   # a forward launch: outputs and status words (a fresh struct holds NULL everywhere)
+        p.rgb_out, p.depth_out, p.status = color.data_ptr(), depth.data_ptr(), status.data_ptr()
+    if T is not None:
+        p.transmittance_out = T.data_ptr()
+    return p
+
+
+def _shared_color(rgb: torch.Tensor, background: Optional[torch.Tensor]) -> _lib.GmpiSharedColor:
+    """The one builder of GmpiSharedColor: rgb and background [M,3,Ht,Wt], innermost stride 1."""
+    sc = _lib.GmpiSharedColor()
+    sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
+    sc.rgb = rgb.data_ptr()
+    sc.rgb_stride[:] = rgb.stride()[:3]
+    if background is not None:
+        sc.background = background.data_ptr()
+        sc.background_stride[:] = background.stride()[:3]
+    return sc
+
+
+def _lend(p: _lib.GmpiRenderParams, ws: torch.Tensor) -> None:
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+
+
+def _kernel_operand(t: torch.Tensor, inner: int) -> torch.Tensor:
+    """t as the kernels read a texture: stride 1 along dimension `inner` (the innermost), no negative strides; t itself when it is."""
+    return t.contiguous() if t.stride(inner) != 1 or any(s < 0 for s in t.stride()) else t
+
+
 def _f32_on(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     """t as contiguous float32 on dev; the tensor itself when it already is (a no-op `.to().contiguous()` costs ~10 us per call)."""
     if t.dtype is torch.float32 and t.device == dev and t.is_contiguous():
         return t
     return t.to(dev, torch.float32).contiguous()
+
+
+def _view_index(views_per_mpi, view_to_mpi, M: int, N: int, dev: torch.device):
+    """(uniform, view_to_mpi): uniform = k > 0 when every MPI has k consecutive views and no index is needed; otherwise 0 and the index as
+    int32 [N] on dev -- the caller's, or the reference's grouping built from one count per MPI."""
+    uniform = 0
+    if view_to_mpi is None:
+        if isinstance(views_per_mpi, int):
+            uniform = views_per_mpi
+        elif len(set(views_per_mpi)) == 1 and len(views_per_mpi) == M:
+            uniform = int(views_per_mpi[0])
+        else:
+            assert len(views_per_mpi) == M and sum(views_per_mpi) == N
+            view_to_mpi = torch.repeat_interleave(torch.arange(M, dtype=torch.int32),
+                                                  torch.tensor(list(views_per_mpi))).to(dev)
+        if uniform:
+            assert N == M * uniform, f"{N} views for {M} MPIs x {uniform}"
+    if view_to_mpi is not None:
+        view_to_mpi = view_to_mpi.to(dev, torch.int32).contiguous()
+        assert view_to_mpi.shape == (N,)
+    return uniform, view_to_mpi
 
 
 def _cat(parts: Union[torch.Tensor, Sequence[torch.Tensor]]) -> torch.Tensor:
@@ -427,190 +530,120 @@ class MPI(nn.Module):
         if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
-        if _shared is not None and torch.is_grad_enabled() and not _in_autograd_fn:
-            # shared-colour layout (render_views_shared): rgba is the alpha tensor, _shared = (rgb, background or None)
-            if self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
-                raise NotImplementedError("the shared-colour render has no gradient w.r.t. the plane geometry or the camera tensors "
-                                          "(geometry_grad=True): render the expanded volume (expand_shared_color) with render_views for that")
-            if rgba.requires_grad or any(t is not None and t.requires_grad for t in _shared):
+        if torch.is_grad_enabled() and not _in_autograd_fn:
+            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _shared)
+            if bridge is not None:
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
-                color, depth, T, st = _SharedRenderFunction.apply(_shared[0], rgba, _shared[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
+                color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
-        if _shared is None and torch.is_grad_enabled() and not _in_autograd_fn and (
-                rgba.requires_grad or (self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)))):
-            # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
-            kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
-                          out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
-                          status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
-            color, depth, T, st = _RenderFunction.apply(rgba, self, dhw, ray_dir, eye_pos, z_dir, kwargs)
-            return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
-        lib = _lib.load_library()
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
         #  tests/test_install_reference.py drives the reference's own MPIRenderer.render into this module with it)
         on_device = rgba.is_cuda
-        if not on_device and not getattr(lib, "records_only", False):
+        if not on_device and not getattr(_lib.load_library(), "records_only", False):
             raise _lib.GmpiError("MPI.forward needs tensors on a ROCm device: this package has no CPU path "
                                  f"(got rgba on {rgba.device})")
         dev = rgba.device
+        # -- inputs: a storage dtype the kernels take, innermost stride 1; the camera and plane tensors as contiguous fp32 on the volume's device
         rgba_in = rgba   # (as the caller passed it: the identity the full-range-check cache is keyed on)
-        if rgba.dtype not in _DTYPES:
-            rgba = rgba.float()
-        if rgba.stride(4) != 1 or any(s < 0 for s in rgba.stride()):
-            rgba = rgba.contiguous()
+        rgba = _kernel_operand(rgba if rgba.dtype in _DTYPES else rgba.float(), 4)
         M, D, _, Ht, Wt = rgba.shape
         sh_rgb = sh_bg = None
-        if _shared is not None:   # one storage dtype for the three tensors, innermost stride 1
+        if _shared is not None:   # one storage dtype for the three tensors
             for t in _shared:
                 if t is not None and t.dtype != rgba_in.dtype:   # (no quiet cast: an fp32 colour image next to bf16 alphas would be rounded unseen)
                     raise TypeError(f"shared-colour render: rgb, alpha and background must have one storage dtype, got {t.dtype} next to alpha in {rgba_in.dtype}")
-
-            def _like_alpha(t):
-                t = t.to(dev, rgba.dtype)   # (a dtype the kernels do not store -- float64 -- becomes fp32 with the alpha tensor)
-                return t.contiguous() if t.stride(3) != 1 or any(s_ < 0 for s_ in t.stride()) else t
-            sh_rgb = _like_alpha(_shared[0])
-            sh_bg = None if _shared[1] is None else _like_alpha(_shared[1])
+            # (a dtype the kernels do not store -- float64 -- becomes fp32 with the alpha tensor)
+            sh_rgb, sh_bg = (None if t is None else _kernel_operand(t.to(dev, rgba.dtype), 3) for t in _shared)
         ray_dir, eye_pos, z_dir, dhw = (_f32_on(t, dev) for t in (ray_dir, eye_pos, z_dir, dhw))
         N, _, H, W = ray_dir.shape
         assert eye_pos.shape == (N, 3) and z_dir.shape == (N, 3), (eye_pos.shape, z_dir.shape, N)
         assert dhw.shape == (M, D, 3), (dhw.shape, rgba.shape)
-
-        uniform = 0
-        if view_to_mpi is None:
-            if isinstance(views_per_mpi, int):
-                uniform = views_per_mpi
-            elif len(set(views_per_mpi)) == 1 and len(views_per_mpi) == M:
-                uniform = int(views_per_mpi[0])
-            else:
-                assert len(views_per_mpi) == M and sum(views_per_mpi) == N
-                view_to_mpi = torch.repeat_interleave(torch.arange(M, dtype=torch.int32),
-                                                      torch.tensor(list(views_per_mpi))).to(dev)
-            if uniform:
-                assert N == M * uniform, f"{N} views for {M} MPIs x {uniform}"
-        if view_to_mpi is not None:
-            view_to_mpi = view_to_mpi.to(dev, torch.int32).contiguous()
-            assert view_to_mpi.shape == (N,)
-
+        uniform, view_to_mpi = _view_index(views_per_mpi, view_to_mpi, M, N, dev)
+        keep = _Keep(rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi)
+        # -- outputs: the caller's, or fresh ones
         out = out or {}
-        color = out.get("color")
+        color, depth, T = out.get("color"), out.get("depth"), out.get("T") if want_transmittance else None
         if color is None:
             color = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
-        depth = out.get("depth")
         if depth is None:
             depth = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
-        T = None
-        if want_transmittance:
-            T = out.get("T")
-            if T is None:
-                T = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+        if T is None and want_transmittance:
+            T = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+        variant = _lib.VARIANTS[self.variant]
+        if _shared is not None:   # (the shared-colour entries know AUTO and GATHER)
+            variant = _lib.VARIANT_GATHER if self.variant == "gather" else _lib.VARIANT_AUTO
+        scalars = _Scalars(self._flags(out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint), variant, _DTYPES[rgba.dtype],
+                           N, M, D, Ht, Wt, H, W, max(uniform, 1))
+        current = torch.cuda.current_stream(dev) if on_device else None
+        stream = current.cuda_stream if on_device else 0
         # (from here to the launch -- status slot, workspace, parameter struct -- under the stream's lock: see _stream_lock)
-        lock = _stream_lock(dev, torch.cuda.current_stream(dev).cuda_stream) if on_device else contextlib.nullcontext()
-        with lock:
-            lag = defer_status == "lag" and status is None and on_device and not _in_autograd_fn
-            if defer_status == "lag" and not lag:
-                defer_status = False   # (a caller-owned status tensor, the autograd bridge, the recorder library: read back at once)
-            ring = slot = None
-            if lag:
-                ring = _ring(dev, torch.cuda.current_stream(dev).cuda_stream)
-                slot = ring.acquire()   # (raises here what an earlier call asserted)
-                status = ring.dev_words[slot]
-            elif status is None:
-                if on_device and not defer_status and not _in_autograd_fn:
-                    status = _own_status(dev, torch.cuda.current_stream(dev).cuda_stream)
-                else:
-                    status = torch.zeros(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-
-            flags = 0
-            if self._align_corners:
-                flags |= _lib.FLAG_ALIGN_CORNERS
-            if out_pm1:
-                flags |= _lib.FLAG_OUT_PM1
-            if check_last_plane:
-                flags |= _lib.FLAG_CHECK_LAST_PLANE
-            if self.range_check != "off":
-                flags |= _lib.FLAG_CHECK_RANGE
-            if self.strict_order:
-                flags |= _lib.FLAG_STRICT_ORDER
-            if frontal_hint:
-                flags |= _lib.FLAG_HINT_FRONTAL
-            if tilted_hint:
-                flags |= _lib.FLAG_HINT_TILTED
-            if oblique_hint:
-                flags |= _lib.FLAG_HINT_OBLIQUE
-
-            p = _lib.GmpiRenderParams()
-            p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
-            p.flags = flags
-            p.variant = _lib.VARIANTS[self.variant]
-            if _shared is not None:   # (the shared-colour entries know AUTO and GATHER)
-                p.variant = _lib.VARIANT_GATHER if self.variant == "gather" else _lib.VARIANT_AUTO
-            p.rgba_dtype = _DTYPES[rgba.dtype]
-            p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W = N, M, D, Ht, Wt, H, W
-            p.views_per_mpi = max(uniform, 1)
-            p.rgba = rgba.data_ptr()
-            for i, s in enumerate(rgba.stride()):
-                p.rgba_stride[i] = s
-            p.view_to_mpi = view_to_mpi.data_ptr() if view_to_mpi is not None else None
-            p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
-            p.rgb_out, p.depth_out = color.data_ptr(), depth.data_ptr()
-            p.transmittance_out = T.data_ptr() if T is not None else None
-            p.status = status.data_ptr()
-            stream = torch.cuda.current_stream(dev).cuda_stream if on_device else 0
+        with _stream_lock(dev, stream) if on_device else contextlib.nullcontext():
+            status, defer_status, ring, slot = _status_target(dev, stream, status, defer_status, on_device and not _in_autograd_fn)
+            p = _render_params(scalars, keep, color, depth, T, status)
             if on_device and _shared is None:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
-                need = int(lib.gmpi_render_workspace_bytes(ctypes.byref(p)))
+                need = int(_lib.load_library().gmpi_render_workspace_bytes(ctypes.byref(p)))
                 if need:
-                    ws = _workspace(dev, stream, need)
-                    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-            with _on_device(dev if on_device else None):
-                ran_full = False
-                if _shared is not None:
-                    sc = _lib.GmpiSharedColor()
-                    sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
-                    sc.rgb = sh_rgb.data_ptr()
-                    for i, s_ in enumerate((sh_rgb.stride(0), sh_rgb.stride(1), sh_rgb.stride(2))):
-                        sc.rgb_stride[i] = s_
-                    if sh_bg is not None:
-                        sc.background = sh_bg.data_ptr()
-                        for i, s_ in enumerate((sh_bg.stride(0), sh_bg.stride(1), sh_bg.stride(2))):
-                            sc.background_stride[i] = s_
-                    if self.range_check == "full":   # the exhaustive pass over the three tensors (never cached: three identities to track)
-                        for t in (rgba, sh_rgb, sh_bg):
-                            if t is not None:
-                                t = t if t.is_contiguous() else t.contiguous()
-                                _lib.check(lib.gmpi_rgba_range_check_launch(t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream),
-                                           "gmpi_rgba_range_check_launch")
-                    _lib.check(lib.gmpi_mpi_render_shared_launch(ctypes.byref(p), ctypes.byref(sc), stream), "gmpi_mpi_render_shared_launch")
-                elif self.range_check == "full" and self._full_check_needed(rgba_in):
-                    vol = rgba if rgba.is_contiguous() else rgba.contiguous()
-                    _lib.check(lib.gmpi_rgba_range_check_launch(vol.data_ptr(), p.rgba_dtype, vol.numel(),
-                                                                status.data_ptr(), stream), "gmpi_rgba_range_check_launch")
-                    ran_full = True
-                if _shared is None:
-                    _lib.check(lib.gmpi_mpi_render_launch(ctypes.byref(p), stream), "gmpi_mpi_render_launch")
+                    _lend(p, _workspace(dev, stream, need))
+            # range_check="full": the exhaustive pass, over the volume unless it is the one that passed last, over the three shared-colour
+            # tensors in every call (never cached: three identities to track)
+            checked = ()
+            if self.range_check == "full":
+                checked = (rgba, sh_rgb, sh_bg) if _shared is not None else (rgba,) if self._full_check_needed(rgba_in) else ()
+            for t in checked:
+                if t is not None:
+                    t = t if t.is_contiguous() else t.contiguous()
+                    _call("gmpi_rgba_range_check_launch", dev, t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream=stream)
+            if _shared is not None:
+                _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(sh_rgb, sh_bg)), stream=stream)
+            else:
+                _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
             res = dict(color=color, depth=depth, T=T, status=status)
             if _in_autograd_fn:  # what the backward needs to rebuild the launch
-                res["_bwd"] = (p, (rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi))
-                if _shared is not None:
-                    res["_bwd"] += ((sh_rgb, sh_bg),)
-            if lag:
+                res["_bwd"] = (p, keep) if _shared is None else (p, keep, (sh_rgb, sh_bg))
+            if ring is not None:
                 ring.host_words[slot].copy_(status, non_blocking=True)
                 ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                ring.pending.append((slot, ev, self, p, (rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi), c2w_mat, sphere_c))
+                ev.record(current)
+                ring.pending.append((slot, ev, self, p, keep, c2w_mat, sphere_c))
             elif not defer_status:
-                try:
-                    self.raise_on_status(status, params=p, keep=(rgba, dhw, ray_dir, eye_pos, z_dir, view_to_mpi),
-                                         c2w_mat=c2w_mat, sphere_c=sphere_c)
-                except BaseException:
-                    # (also a KeyboardInterrupt between the launch and the read-back: the shared words must not keep bits for the next call)
-                    if status.is_cuda:
-                        status.zero_()
-                    self._full_check_passed = None
-                    raise
-                if ran_full:
-                    self._full_check_record(rgba_in)   # (read back and clean: the whole volume is in [0, 1])
+                self._settle(status, p, keep, c2w_mat, sphere_c, rgba_in if _shared is None and checked else None)
             return res
+
+    def _autograd_bridge(self, rgba, dhw, ray_dir, eye_pos, z_dir, shared):
+        """(autograd.Function, its leading tensor arguments) when this call has to be recorded, else None."""
+        geometry = self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir))
+        if shared is None:
+            # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
+            return (_RenderFunction, (rgba,)) if rgba.requires_grad or geometry else None
+        # shared-colour layout (render_views_shared): rgba is the alpha tensor, shared = (rgb, background or None)
+        if geometry:
+            raise NotImplementedError("the shared-colour render has no gradient w.r.t. the plane geometry or the camera tensors "
+                                      "(geometry_grad=True): render the expanded volume (expand_shared_color) with render_views for that")
+        if rgba.requires_grad or any(t is not None and t.requires_grad for t in shared):
+            return _SharedRenderFunction, (shared[0], rgba, shared[1])
+        return None
+
+    def _flags(self, out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint) -> int:
+        return ((_lib.FLAG_ALIGN_CORNERS if self._align_corners else 0) | (_lib.FLAG_OUT_PM1 if out_pm1 else 0)
+                | (_lib.FLAG_CHECK_LAST_PLANE if check_last_plane else 0) | (_lib.FLAG_CHECK_RANGE if self.range_check != "off" else 0)
+                | (_lib.FLAG_STRICT_ORDER if self.strict_order else 0) | (_lib.FLAG_HINT_FRONTAL if frontal_hint else 0)
+                | (_lib.FLAG_HINT_TILTED if tilted_hint else 0) | (_lib.FLAG_HINT_OBLIQUE if oblique_hint else 0))
+
+    def _settle(self, status, p, keep, c2w_mat, sphere_c, fully_checked) -> None:
+        """Reads the status words of a launch back and raises what they assert.  fully_checked: the volume whose exhaustive range pass this
+        call ran, or None."""
+        try:
+            self.raise_on_status(status, params=p, keep=keep, c2w_mat=c2w_mat, sphere_c=sphere_c)
+        except BaseException:
+            # (also a KeyboardInterrupt between the launch and the read-back: the shared words must not keep bits for the next call)
+            if status.is_cuda:
+                status.zero_()
+            self._full_check_passed = None
+            raise
+        if fully_checked is not None:
+            self._full_check_record(fully_checked)   # (read back and clean: the whole volume is in [0, 1])
 
     # -- shared-colour layout ----------------------------------------------------------------------------------------------------------
     def render_views_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
@@ -649,13 +682,9 @@ class MPI(nn.Module):
         if word & _lib.STATUS_OUT_OF_LAST_PLANE:
             msg = "Ray goes out of the last plane"
             if params is not None:
-                lib = _lib.load_library()
                 dev = keep[0].device if keep is not None else status.device   # (a lagged status word arrives as a host tensor)
                 uv = torch.empty((params.N, 4), dtype=torch.float32, device=dev)
-                with torch.cuda.device(dev):
-                    _lib.check(lib.gmpi_last_plane_uv_minmax_launch(ctypes.byref(params), uv.data_ptr(),
-                                                                    torch.cuda.current_stream(dev).cuda_stream),
-                               "gmpi_last_plane_uv_minmax_launch")
+                _call("gmpi_last_plane_uv_minmax_launch", dev, ctypes.byref(params), uv.data_ptr())
                 uv = uv.cpu()
                 mn_u, mx_u, mn_v, mx_v = (float(uv[:, 0].min()), float(uv[:, 1].max()), float(uv[:, 2].min()),
                                           float(uv[:, 3].max()))
@@ -681,6 +710,39 @@ class MPI(nn.Module):
             raise RuntimeError(msg)
 
 
+def _bridge_forward(ctx, mpi, volume, geometry, kwargs, shared=None):
+    """The forward of both autograd bridges: the render with a transmittance buffer private to the node (never a caller-supplied `out["T"]`,
+    which a batch driver reuses across launches; the caller's gets a copy), the scalar fields of its struct kept for the backward.  Returns
+    the result dict, the kept tensors and, for the shared-colour render, its (rgb, background)."""
+    kw = dict(kwargs, want_transmittance=True)
+    user_out = kw.get("out") or {}
+    kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # private T
+    if shared is not None:
+        kw["_shared"] = tuple(None if t is None else t.detach() for t in shared)
+    res = mpi.render_views(volume.detach(), *geometry, _in_autograd_fn=True, **kw)
+    bwd = res.pop("_bwd")   # (p, keep) or (p, keep, (rgb, background))
+    p = bwd[0]
+    if kwargs.get("want_transmittance") and user_out.get("T") is not None:
+        user_out["T"].copy_(res["T"])
+    ctx.scalars = _Scalars(p.flags, p.variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi)
+    ctx.mark_non_differentiable(res["status"])
+    # (an output nobody used arrives as None, not as a zero tensor: "T unused" -> today's launch, told apart from gT = 0 without a reduction)
+    ctx.set_materialize_grads(False)
+    return res, bwd[1], bwd[2] if shared is not None else None
+
+
+def _upstream(ctx, dev, g_color, g_depth, g_T):
+    """The gradients of a bridge's outputs as the entries take them: contiguous fp32; colour always (zeros when the loss does not use it),
+    depth and T as None (NULL) when unused.  A g_T selects the _ex entries (the sweep's suffix sum starts at gT * T_out); the OUT_PM1 factor 2
+    applies to the colour only (inside the kernels)."""
+    if g_color is None:
+        g_color = torch.zeros((ctx.scalars.N, 3, ctx.scalars.H, ctx.scalars.W), dtype=torch.float32, device=dev)
+    g_color = g_color.to(torch.float32).contiguous()
+    g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
+    g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
+    return g_color, g_depth, g_T
+
+
 class _RenderFunction(torch.autograd.Function):
     """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba) and, for an MPI with
     geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir); their _ex forms when the loss
@@ -688,69 +750,35 @@ class _RenderFunction(torch.autograd.Function):
 
     Everything the backward reads is kept through `save_for_backward` (so an in-place update of the volume between
     forward and backward raises instead of producing gradients of overwritten memory), the parameter struct is rebuilt
-    from the saved tensors, and the transmittance the backward sweep starts from lives in a buffer private to this
-    node (never a caller-supplied `out["T"]`, which a batch driver reuses across launches)."""
+    from the saved tensors by the builder the forward used, and the transmittance the backward sweep starts from lives in a
+    buffer private to this node."""
 
     @staticmethod
     def forward(ctx, rgba, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
-        kw = dict(kwargs, want_transmittance=True)
-        user_out = kw.get("out") or {}
-        kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # private T
-        res = mpi.render_views(rgba.detach(), dhw, ray_dir, eye_pos, z_dir, _in_autograd_fn=True, **kw)
-        p, keep = res.pop("_bwd")
-        T = res["T"]
-        if kwargs.get("want_transmittance") and user_out.get("T") is not None:
-            user_out["T"].copy_(T)
-        vol, dhw_d, ray_d, eye_d, zd_d, v2m = keep
-        ctx.has_v2m = v2m is not None
-        ctx.save_for_backward(vol, dhw_d, ray_d, eye_d, zd_d, T, *([v2m] if v2m is not None else []))
-        ctx.scalars = dict(flags=p.flags, variant=p.variant, rgba_dtype=p.rgba_dtype, N=p.N, M=p.M, D=p.D, Ht=p.Ht, Wt=p.Wt,
-                           H=p.H, W=p.W, views_per_mpi=p.views_per_mpi)
+        res, keep, _ = _bridge_forward(ctx, mpi, rgba, (dhw, ray_dir, eye_pos, z_dir), kwargs)
+        ctx.has_v2m = keep.view_to_mpi is not None
+        ctx.save_for_backward(*keep[:5], res["T"], *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.backward_mode = mpi.backward
         ctx.in_dtype, ctx.in_shape = rgba.dtype, tuple(rgba.shape)
         ctx.geometry = mpi.geometry_grad
         ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
-        ctx.mark_non_differentiable(res["status"])
-        # (an output nobody used arrives as None, not as a zero tensor: "T unused" -> today's launch, told apart from gT = 0 without a reduction)
-        ctx.set_materialize_grads(False)
-        return res["color"], res["depth"], T, res["status"]
+        return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_T, g_status):
         lib = _lib.load_library()
         saved = ctx.saved_tensors
-        vol, dhw, ray_dir, eye_pos, z_dir, T = saved[:6]
-        v2m = saved[6] if ctx.has_v2m else None
-        dev = vol.device
-
-        def params():   # the forward's launch, rebuilt from the saved tensors
-            p = _lib.GmpiRenderParams()
-            p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
-            for k, v in ctx.scalars.items():
-                setattr(p, k, v)
-            p.rgba = vol.data_ptr()
-            for i, s in enumerate(vol.stride()):
-                p.rgba_stride[i] = s
-            p.view_to_mpi = v2m.data_ptr() if v2m is not None else None
-            p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
-            p.rgb_out = p.depth_out = p.status = None
-            p.transmittance_out = T.data_ptr()
-            return p
-
-        p = params()
-        if g_color is None:
-            g_color = torch.zeros((p.N, 3, p.H, p.W), dtype=torch.float32, device=dev)
-        g_color = g_color.to(torch.float32).contiguous()
-        g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
-        # gradient w.r.t. the final transmittance (the sweep's suffix sum starts at gT * T_out): the _ex entries; None -> the old ones, NULL.  The
-        # OUT_PM1 factor 2 applies to the colour only (inside the kernels).
-        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        keep, T = _Keep(*saved[:5], saved[6] if ctx.has_v2m else None), saved[5]
+        dev = keep.rgba.device
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        upstream = (g_color.data_ptr(), _ptr(g_depth)) + (() if g_T is None else (g_T.data_ptr(),))
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
         grad = None
         if ctx.needs_input_grad[0]:
             # backward="gather": with a workspace for the sample positions and gradients (N D H W 24 bytes) the launch runs without atomics and WRITES every
             # element of the gradient: no zero-fill, bit-reproducible (render_backward_gather.hip; align_corners=True, uniform views per MPI).  Default and
             # everything else: the tile kernels add into a zero-filled volume.
+            p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved tensors
             need = 0
             if ctx.backward_mode == "gather" and not getattr(lib, "records_only", False):
                 need = int(lib.gmpi_render_backward_workspace_bytes(ctypes.byref(p)))
@@ -761,46 +789,29 @@ class _RenderFunction(torch.autograd.Function):
                 except torch.cuda.OutOfMemoryError:
                     ws = None                                                # (no room for the scratch: the atomics path needs none)
             if ws is not None:
-                p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+                _lend(p, ws)
                 p.flags |= _lib.FLAG_GRAD_OVERWRITE
                 grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
             else:
                 grad = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dev)
-            gstride = (ctypes.c_int64 * 5)(*grad.stride())
-            gz_ptr = g_depth.data_ptr() if g_depth is not None else None
-            with torch.cuda.device(dev):
-                if g_T is None:
-                    _lib.check(lib.gmpi_mpi_render_backward_launch(
-                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, grad.data_ptr(), gstride, stream), "gmpi_mpi_render_backward_launch")
-                else:
-                    _lib.check(lib.gmpi_mpi_render_backward_ex_launch(
-                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, g_T.data_ptr(), grad.data_ptr(), gstride, stream),
-                        "gmpi_mpi_render_backward_ex_launch")
+            _call("gmpi_mpi_render_backward_launch" if g_T is None else "gmpi_mpi_render_backward_ex_launch", dev,
+                  ctypes.byref(p), *upstream, grad.data_ptr(), (ctypes.c_int64 * 5)(*grad.stride()), stream=stream)
             grad = grad.to(ctx.in_dtype)
         geo = [None] * 4   # dhw, ray_dir, eye_pos, z_dir
         want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
         if any(want):
             # gradient w.r.t. the sample positions (render_backward_geometry.hip): every output overwritten, NULL = not wanted; the per-view and
             # per-plane sums go through slabs in a workspace (no atomics: bit-reproducible)
-            p = params()
+            p = _render_params(ctx.scalars, keep, T=T)
             shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
             out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
-            ws = None
+            ws = None   # (held until this call returns: the launch that uses it is on the stream by then)
             if want[0] or want[2] or want[3]:
                 need = int(lib.gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
                 ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-                p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-            ptr = [t.data_ptr() if t is not None else None for t in out]
-            gz_ptr = g_depth.data_ptr() if g_depth is not None else None
-            with torch.cuda.device(dev):
-                if g_T is None:
-                    _lib.check(lib.gmpi_mpi_render_geometry_backward_launch(
-                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, ptr[1], ptr[2], ptr[3], ptr[0], stream),
-                        "gmpi_mpi_render_geometry_backward_launch")
-                else:
-                    _lib.check(lib.gmpi_mpi_render_geometry_backward_ex_launch(
-                        ctypes.byref(p), g_color.data_ptr(), gz_ptr, g_T.data_ptr(), ptr[1], ptr[2], ptr[3], ptr[0], stream),
-                        "gmpi_mpi_render_geometry_backward_ex_launch")
+                _lend(p, ws)
+            _call("gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch", dev,
+                  ctypes.byref(p), *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), stream=stream)
             geo = [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
 
@@ -812,62 +823,25 @@ class _SharedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, alpha, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
-        kw = dict(kwargs, want_transmittance=True)
-        user_out = kw.get("out") or {}
-        kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # private T
-        res = mpi.render_views(alpha.detach(), dhw, ray_dir, eye_pos, z_dir, _in_autograd_fn=True,
-                               _shared=(rgb.detach(), None if background is None else background.detach()), **kw)
-        p, keep, (rgb_d, bg_d) = res.pop("_bwd")
-        T = res["T"]
-        if kwargs.get("want_transmittance") and user_out.get("T") is not None:
-            user_out["T"].copy_(T)
-        alpha_d, dhw_d, ray_d, eye_d, zd_d, v2m = keep
-        ctx.has_bg, ctx.has_v2m = bg_d is not None, v2m is not None
-        ctx.save_for_backward(alpha_d, rgb_d, dhw_d, ray_d, eye_d, zd_d, T, *([bg_d] if bg_d is not None else []), *([v2m] if v2m is not None else []))
-        ctx.scalars = dict(flags=p.flags, variant=p.variant, rgba_dtype=p.rgba_dtype, N=p.N, M=p.M, D=p.D, Ht=p.Ht, Wt=p.Wt,
-                           H=p.H, W=p.W, views_per_mpi=p.views_per_mpi)
+        res, keep, (rgb_d, bg_d) = _bridge_forward(ctx, mpi, alpha, (dhw, ray_dir, eye_pos, z_dir), kwargs, shared=(rgb, background))
+        ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
+        ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, alpha, background)]
-        ctx.mark_non_differentiable(res["status"])
-        ctx.set_materialize_grads(False)
-        return res["color"], res["depth"], T, res["status"]
+        return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_T, g_status):
-        lib = _lib.load_library()
         saved = list(ctx.saved_tensors)
         alpha, rgb, dhw, ray_dir, eye_pos, z_dir, T = saved[:7]
         rest = saved[7:]
         bg = rest.pop(0) if ctx.has_bg else None
-        v2m = rest.pop(0) if ctx.has_v2m else None
+        keep = _Keep(alpha, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
         dev = alpha.device
         want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
         if not any(want) or (g_color is None and g_depth is None and g_T is None):
             return (None,) * 9
-        p = _lib.GmpiRenderParams()
-        p.struct_size = ctypes.sizeof(_lib.GmpiRenderParams)
-        for k, v in ctx.scalars.items():
-            setattr(p, k, v)
-        p.rgba = alpha.data_ptr()
-        for i, s in enumerate(alpha.stride()):
-            p.rgba_stride[i] = s
-        p.view_to_mpi = v2m.data_ptr() if v2m is not None else None
-        p.dhw, p.ray_dir, p.eye_pos, p.z_dir = dhw.data_ptr(), ray_dir.data_ptr(), eye_pos.data_ptr(), z_dir.data_ptr()
-        p.rgb_out = p.depth_out = p.status = None
-        p.transmittance_out = T.data_ptr()
-        sc = _lib.GmpiSharedColor()
-        sc.struct_size = ctypes.sizeof(_lib.GmpiSharedColor)
-        sc.rgb = rgb.data_ptr()
-        for i in range(3):
-            sc.rgb_stride[i] = rgb.stride(i)
-        if bg is not None:
-            sc.background = bg.data_ptr()
-            for i in range(3):
-                sc.background_stride[i] = bg.stride(i)
-        if g_color is None:
-            g_color = torch.zeros((p.N, 3, p.H, p.W), dtype=torch.float32, device=dev)
-        g_color = g_color.to(torch.float32).contiguous()
-        g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
-        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()   # None: the launch stays on the path without a transmittance gradient
+        p = _render_params(ctx.scalars, keep, T=T)
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
         shapes = [(p.M, 3, p.Ht, p.Wt), (p.M, p.D, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)]
         grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
 
@@ -875,12 +849,8 @@ class _SharedRenderFunction(torch.autograd.Function):
             if t is None:
                 return None, None
             return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
-        (gr, gr_s), (ga, ga_s), (gb, gb_s) = ptr_stride(grads[0], (0, 1, 2)), ptr_stride(grads[1], (0, 1, 3)), ptr_stride(grads[2], (0, 1, 2))
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_mpi_render_shared_backward_launch(
-                ctypes.byref(p), ctypes.byref(sc), g_color.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
-                g_T.data_ptr() if g_T is not None else None, gr, gr_s, ga, ga_s, gb, gb_s, torch.cuda.current_stream(dev).cuda_stream),
-                "gmpi_mpi_render_shared_backward_launch")
+        _call("gmpi_mpi_render_shared_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
+              g_color.data_ptr(), _ptr(g_depth), _ptr(g_T), *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
         out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
         return out[0], out[1], out[2], None, None, None, None, None, None
 

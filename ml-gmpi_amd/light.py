@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, poses
-from .hip_mpi import _DTYPES
+from .hip_mpi import _DTYPES, _call, _ptr
 
 EPS = 1e-8  # light_renderer.py:8
 
@@ -54,18 +54,14 @@ def _alpha_operand(mpi_alpha: torch.Tensor) -> torch.Tensor:
 
 def _alpha_depth(mpi_alpha: torch.Tensor, plane_ds: torch.Tensor, want_transmittance: bool):
     """gmpi_alpha_depth_launch -> (depth, T or None), both float32 [B,1,H,W]."""
-    lib = _lib.load_library()
     mpi_alpha = _alpha_operand(mpi_alpha)
     B, D, _, H, W = mpi_alpha.shape
     ds = plane_ds.reshape(-1).to(mpi_alpha.device, torch.float32).contiguous()
     assert ds.numel() == D, f"{ds.shape}, {D}"
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=mpi_alpha.device)
     T = torch.empty((B, 1, H, W), dtype=torch.float32, device=mpi_alpha.device) if want_transmittance else None
-    with torch.cuda.device(mpi_alpha.device):
-        _lib.check(lib.gmpi_alpha_depth_launch(
-            mpi_alpha.data_ptr(), _DTYPES[mpi_alpha.dtype], mpi_alpha.stride(0), mpi_alpha.stride(1), mpi_alpha.stride(3),
-            ds.data_ptr(), B, D, H, W, depth.data_ptr(), T.data_ptr() if T is not None else None,
-            torch.cuda.current_stream(mpi_alpha.device).cuda_stream), "gmpi_alpha_depth_launch")
+    _call("gmpi_alpha_depth_launch", mpi_alpha.device, mpi_alpha.data_ptr(), _DTYPES[mpi_alpha.dtype], mpi_alpha.stride(0),
+          mpi_alpha.stride(1), mpi_alpha.stride(3), ds.data_ptr(), B, D, H, W, depth.data_ptr(), _ptr(T))
     return depth, T
 
 
@@ -88,19 +84,15 @@ class _DepthFunction(torch.autograd.Function):
         mpi_alpha, ds, T = ctx.saved_tensors
         if not ctx.needs_input_grad[0] or (g_depth is None and g_T is None):
             return None, None
-        lib = _lib.load_library()
         alpha = _alpha_operand(mpi_alpha.detach())
         B, D, _, H, W = alpha.shape
         dev = alpha.device
         g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
         g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
         grad = torch.zeros((B, D, 1, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_alpha_depth_backward_ex_launch(
-                alpha.data_ptr(), _DTYPES[alpha.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3), ds.data_ptr(), T.data_ptr(),
-                g_depth.data_ptr() if g_depth is not None else None, g_T.data_ptr() if g_T is not None else None, grad.data_ptr(),
-                grad.stride(0), grad.stride(1), grad.stride(3), B, D, H, W, torch.cuda.current_stream(dev).cuda_stream),
-                "gmpi_alpha_depth_backward_ex_launch")
+        _call("gmpi_alpha_depth_backward_ex_launch", dev, alpha.data_ptr(), _DTYPES[alpha.dtype], alpha.stride(0), alpha.stride(1),
+              alpha.stride(3), ds.data_ptr(), T.data_ptr(), _ptr(g_depth), _ptr(g_T), grad.data_ptr(), grad.stride(0), grad.stride(1),
+              grad.stride(3), B, D, H, W)
         return grad.to(ctx.in_dtype), None
 
 
@@ -174,7 +166,6 @@ class _LightFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = _lib.load_library()
         vol, depth, T, shading, my, mx, xyz_last, light_dir, ds = ctx.saved_tensors
         ka, kd, in_dtype = ctx.misc
         dev = vol.device
@@ -184,10 +175,8 @@ class _LightFunction(torch.autograd.Function):
         g_shading = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         strides = (ctypes.c_int64 * 5)(*vol.stride())
         stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_light_apply_backward_launch(vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(),
-                                                            g_out.data_ptr(), g_rgba.data_ptr(), g_shading.data_ptr(), B, D, H, W,
-                                                            stream), "gmpi_light_apply_backward_launch")
+        _call("gmpi_light_apply_backward_launch", dev, vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(), g_out.data_ptr(),
+              g_rgba.data_ptr(), g_shading.data_ptr(), B, D, H, W, stream=stream)
         with torch.enable_grad():
             d = depth.detach().requires_grad_(True)
             s = _shading_torch(_blur_torch(d, my, mx), xyz_last, light_dir, ka, kd)
@@ -195,11 +184,9 @@ class _LightFunction(torch.autograd.Function):
         g_depth = g_depth.contiguous()
         alpha = vol[:, :, 3:]
         plane = H * W
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_alpha_depth_backward_launch(
-                alpha.data_ptr(), _DTYPES[vol.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3), ds.data_ptr(),
-                T.data_ptr(), g_depth.data_ptr(), g_rgba.data_ptr() + 3 * plane * 4, D * 4 * plane, 4 * plane, W, B, D, H, W,
-                stream), "gmpi_alpha_depth_backward_launch")
+        _call("gmpi_alpha_depth_backward_launch", dev, alpha.data_ptr(), _DTYPES[vol.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3),
+              ds.data_ptr(), T.data_ptr(), g_depth.data_ptr(), g_rgba.data_ptr() + 3 * plane * 4, D * 4 * plane, 4 * plane, W, B, D, H, W,
+              stream=stream)
         return g_rgba.to(in_dtype), None, None, None, None, None, None
 
 
@@ -225,36 +212,28 @@ class LightRenderer:
     @torch.no_grad()
     def blurrer_func(self, depth: torch.Tensor) -> torch.Tensor:
         """[B,1,H,W] -> blurred [B,1,H,W] (torchvision GaussianBlur: reflect padding, ksize x ksize)."""
-        lib = _lib.load_library()
         d = depth.to(torch.float32).contiguous()
         B, _, H, W = d.shape
         out = torch.empty_like(d)
         k = self._k1d.to(d.device)
-        with torch.cuda.device(d.device):
-            _lib.check(lib.gmpi_light_blur_launch(d.data_ptr(), out.data_ptr(), B, H, W, k.data_ptr(), self.blur_ksize,
-                                                  torch.cuda.current_stream(d.device).cuda_stream), "gmpi_light_blur_launch")
+        _call("gmpi_light_blur_launch", d.device, d.data_ptr(), out.data_ptr(), B, H, W, k.data_ptr(), self.blur_ksize)
         return out
 
     @torch.no_grad()
     def shading(self, depth_blurred: torch.Tensor, xyz_last: torch.Tensor, light_direction: torch.Tensor, ka: float,
                 kd: float) -> torch.Tensor:
         """compute_pcl + get_normal + Lambert term: [B,1,H,W], [H,W,3], [B,3] -> shading [B,H,W] = ka + kd*max(-n.l, 0)."""
-        lib = _lib.load_library()
         d = depth_blurred.to(torch.float32).contiguous()
         B, _, H, W = d.shape
         xyz = xyz_last.to(d.device, torch.float32).reshape(H, W, 3).contiguous()
         ld = light_direction.to(d.device, torch.float32).reshape(B, 3).contiguous()
         out = torch.empty((B, H, W), dtype=torch.float32, device=d.device)
-        with torch.cuda.device(d.device):
-            _lib.check(lib.gmpi_light_shading_launch(d.data_ptr(), xyz.data_ptr(), ld.data_ptr(), float(ka), float(kd), B, H, W,
-                                                     out.data_ptr(), torch.cuda.current_stream(d.device).cuda_stream),
-                       "gmpi_light_shading_launch")
+        _call("gmpi_light_shading_launch", d.device, d.data_ptr(), xyz.data_ptr(), ld.data_ptr(), float(ka), float(kd), B, H, W, out.data_ptr())
         return out
 
     # -- light_renderer.py:122-199 ------------------------------------------------------------------------------
     @torch.no_grad()
     def _forward_kernels(self, vol, plane_ds, xyz_last, light_direction, ka, kd):
-        lib = _lib.load_library()
         dev = vol.device
         B, D, _, H, W = vol.shape
         depth, T = compute_depth(vol[:, :, 3:], plane_ds, want_transmittance=True)
@@ -262,10 +241,7 @@ class LightRenderer:
         shading = self.shading(blurred, xyz_last, light_direction, ka, kd)
         out = torch.empty((B, D, 4, H, W), dtype=torch.float32, device=dev)
         strides = (ctypes.c_int64 * 5)(*vol.stride())
-        with torch.cuda.device(dev):
-            _lib.check(lib.gmpi_light_apply_launch(vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(),
-                                                   out.data_ptr(), B, D, H, W, torch.cuda.current_stream(dev).cuda_stream),
-                       "gmpi_light_apply_launch")
+        _call("gmpi_light_apply_launch", dev, vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(), out.data_ptr(), B, D, H, W)
         return out, depth, T, shading
 
     def render_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor,

@@ -17,7 +17,7 @@ import logging
 import numpy as np
 import torch
 
-from .hip_mpi import MPI
+from .hip_mpi import MPI, _call, _cat
 from .pinhole import gen_cam
 from .plane_geometry import compute_plane_dhws, sample_distance
 from .poses import draw_angle_noise, gen_sphere_path, gen_sphere_paths_ahead, host_math
@@ -374,7 +374,6 @@ class MPIRenderer:
         from . import _lib
         if not c2w.is_cuda:
             raise _lib.GmpiError("ray_backend='hip' needs a ROCm device (use ray_backend='torch' on the CPU)")
-        lib = _lib.load_library()
         if c2w.dtype is not torch.float32 or not c2w.is_contiguous():
             c2w = c2w.to(torch.float32).contiguous()
         B, H, W = c2w.shape[0], self.cam.height, self.cam.width
@@ -390,10 +389,8 @@ class MPIRenderer:
                     self._ray_bufs.clear()
                 self._ray_bufs[(B, H, W, stream)] = bufs
         ray, eye, zd = bufs
-        from .hip_mpi import _on_device
-        with _on_device(c2w.device):
-            _lib.check(lib.gmpi_generate_rays_launch(c2w.data_ptr(), dirs.data_ptr(), B, H, W, ray.data_ptr(), eye.data_ptr(),
-                                                     zd.data_ptr(), stream), "gmpi_generate_rays_launch")
+        _call("gmpi_generate_rays_launch", c2w.device, c2w.data_ptr(), dirs.data_ptr(), B, H, W, ray.data_ptr(), eye.data_ptr(), zd.data_ptr(),
+              stream=stream)
         return ray, eye, zd
 
     # ---- render -------------------------------------------------------------------------------------------------
@@ -452,11 +449,10 @@ class MPIRenderer:
                 rays, eyes, zdirs = (given_cam_infos[k] for k in ("batch_ray_dir", "batch_eye_pos", "batch_z_dir"))
             assert len(rays) == batch_size or (isinstance(rays, torch.Tensor) and rays.shape[0] == batch_size), \
                 f"{len(rays)}, {batch_size}"
-            cat = (lambda t: t if isinstance(t, torch.Tensor) else (t[0] if len(t) == 1 else torch.cat(list(t), 0)))
             if self._batched_cam is not None and rays is self._batched_cam[0]:
                 ray_t, eye_t, zd_t = self._batched_cam[1:]             # the lists are views of these tensors
             else:
-                ray_t, eye_t, zd_t = cat(rays), cat(eyes), cat(zdirs)
+                ray_t, eye_t, zd_t = _cat(rays), _cat(eyes), _cat(zdirs)
             self._batched_cam = None
         assert ray_t.shape[0] == batch_size, f"{ray_t.shape[0]}, {batch_size}"
 

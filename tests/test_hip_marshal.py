@@ -1,0 +1,79 @@
+"""The backward bridges' marshalling on the device: a recorder that copies the structs of every `gmpi_mpi_render*` call and then forwards
+the call to the real library (tests/test_marshal_cpu.py has the recorder and the assertions; there the same runs on host tensors).  The
+struct each backward rebuilds must be its forward's, field by field."""
+import pytest
+import torch
+
+from ml_gmpi_amd import _lib
+from ml_gmpi_amd.hip_mpi import MPI
+from test_marshal_cpu import (BACKWARD_ENTRIES, FORWARD_ENTRIES, GEOMETRY_BACKWARD, VOLUME_BACKWARD, H, W, Recorder, check_backward_struct,
+                              loss_of, make_inputs, shared_inputs)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ENTRIES = tuple(e for e in FORWARD_ENTRIES + BACKWARD_ENTRIES if e.startswith("gmpi_mpi_render"))
+
+
+@pytest.fixture
+def rec(monkeypatch):
+    r = Recorder(ENTRIES, real=_lib.load_library())
+    monkeypatch.setattr(_lib, "load_library", lambda: r)
+    return r
+
+
+@pytest.mark.parametrize("uses_T", [False, True])
+@pytest.mark.parametrize("mode", ["atomic", "gather"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_volume_backward_rebuilds_the_forward_struct(rec, dtype, mode, uses_T):
+    vol, *geo = make_inputs(2, dtype, DEV)
+    vol.requires_grad_(True)
+    user_T = torch.empty((2, 1, H, W), device=DEV)
+    res = MPI(backward=mode, strict_order=True, on_out_of_plane="raise").render_views(
+        vol, *geo, out_pm1=True, want_transmittance=True, out={"T": user_T})
+    assert torch.equal(user_T, res["T"]) and user_T.data_ptr() != res["T"].data_ptr()
+    loss_of(res, uses_T).backward()
+    torch.cuda.synchronize()
+    fwd, bwd = rec.calls
+    assert fwd.name == "gmpi_mpi_render_launch" and bwd.name in VOLUME_BACKWARD
+    b = bwd.args[0]
+    assert mode == "gather" or b.workspace is None
+    check_backward_struct(bwd, fwd, uses_T, overwrite=mode == "gather" and b.workspace is not None, user_T=user_T)
+    assert vol.grad.shape == vol.shape and vol.grad.dtype == dtype and bool(torch.isfinite(vol.grad.float()).all())
+
+
+@pytest.mark.parametrize("uses_T", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_geometry_backward_rebuilds_the_forward_struct(rec, dtype, uses_T):
+    vol, *geo = make_inputs(2, dtype, DEV)
+    for t in [vol] + geo:
+        t.requires_grad_(True)
+    res = MPI(geometry_grad=True, on_out_of_plane="raise").render_views(vol, *geo, want_transmittance=True)
+    loss_of(res, uses_T).backward()
+    torch.cuda.synchronize()
+    fwd = rec.calls[0]
+    assert fwd.name == "gmpi_mpi_render_launch" and len(rec.calls) == 3
+    (vb,), (gb,) = rec.named(*VOLUME_BACKWARD), rec.named(*GEOMETRY_BACKWARD)
+    check_backward_struct(vb, fwd, uses_T)
+    check_backward_struct(gb, fwd, uses_T)
+    assert gb.args[0].workspace is not None
+    for t in geo:
+        assert t.grad is not None and t.grad.shape == t.shape
+
+
+@pytest.mark.parametrize("uses_T", [False, True])
+@pytest.mark.parametrize("background", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_shared_backward_rebuilds_the_forward_structs(rec, dtype, background, uses_T):
+    rgb, alpha, bg, geo = shared_inputs(dtype, background, DEV)
+    for t in (rgb, alpha, bg):
+        if t is not None:
+            t.requires_grad_(True)
+    res = MPI(on_out_of_plane="raise").render_views_shared(rgb, alpha, *geo, background=bg, want_transmittance=True)
+    loss_of(res, uses_T).backward()
+    torch.cuda.synchronize()
+    fwd, bwd = rec.calls
+    assert (fwd.name, bwd.name) == ("gmpi_mpi_render_shared_launch", "gmpi_mpi_render_shared_backward_launch")
+    check_backward_struct(bwd, fwd, uses_T)
+    assert bytes(bwd.args[1]) == bytes(fwd.args[1])   # GmpiSharedColor: the same struct
+    assert (bwd.args[4] is not None) == uses_T
+    assert rgb.grad.shape == rgb.shape and alpha.grad.shape == alpha.shape and (bg is None or bg.grad.shape == bg.shape)
