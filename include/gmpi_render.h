@@ -256,10 +256,27 @@ typedef struct GmpiSharedColor {
  * [M, D, 1, Ht, Wt] -- rgba_stride[0], [1], [3] are its MPI, plane and row strides, rgba_stride[2] is ignored, rgba_stride[4] must be 1 -- so the
  * strided view rgba[:, :, 3:] of an ordinary volume is a valid alpha tensor.  Every flag, view_to_mpi / views_per_mpi, transmittance_out and the status
  * bits mean what they mean there; GMPI_FLAG_CHECK_RANGE covers the alpha, colour and background texels the render samples.  D == 1 with a background is
- * legal (the one plane is the background).  One pixel per lane, taps from global memory (any shape, any ray field); params->variant may be AUTO or
- * GATHER (the same kernel today), anything else is GMPI_E_VARIANT.  No workspace.  Stream-ordered, allocates nothing, never synchronises.
+ * legal (the one plane is the background).  params->variant:
+ *   AUTO, GATHER  one pixel per lane, taps from global memory (any shape, any stride, any ray field); the same kernel for both;
+ *   LDS           one workgroup per 32 x 16 pixel tile: per plane the texel box spanned by the tile's four corner pixels is staged in LDS for the four
+ *                 channels at once (the box has the same origin in the alpha plane and in the colour image; alpha streams from HBM, the colour box
+ *                 is re-read per plane from the caches).  A (tile, plane) whose box exceeds the 56 x 27 texel buffer, and a pixel whose footprint
+ *                 lies outside its tile's box (a ray field that is no pinhole camera's), take the direct gather: results do not depend on the path,
+ *                 and with GMPI_FLAG_STRICT_ORDER they are bit-identical to AUTO's.  GMPI_FLAG_CHECK_RANGE then covers every staged texel.  It
+ *                 loads items of 4 texels: the three base pointers and their MPI, channel / plane and row strides must be multiples of 4 texels
+ *                 (16 bytes of fp32, 8 bytes of 16-bit storage; any Wt), else GMPI_E_VARIANT -- gmpi_render_shared_supports() says so beforehand.
+ *                 With Wt % 4 != 0 the last item of a texel row reaches up to 3 texels past Wt (they are read and replaced by zeros): inside the
+ *                 row stride for every row but the LAST row of each tensor, behind which that many elements must be readable memory -- the
+ *                 caller's duty, neither the launch nor the query can see the allocation (the Python layer checks the storage and falls back);
+ *   anything else GMPI_E_VARIANT.
+ * No workspace.  Stream-ordered, allocates nothing, never synchronises.
  */
 int gmpi_mpi_render_shared_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, void *stream);
+
+/* Whether gmpi_mpi_render_shared_launch can run these parameters with params->variant: 1 yes, 0 no (the launch would return GMPI_E_VARIANT only
+ * because this variant's kernel cannot take them: another variant can), negative GMPI_E_* for what the launch refuses whatever the kernel.  For
+ * GMPI_VARIANT_LDS it is 1 whenever the three base pointers and all their outer strides are multiples of 16 bytes.  Launches nothing. */
+int gmpi_render_shared_supports(const GmpiRenderParams *params, const GmpiSharedColor *shared);
 
 /*
  * Gradient of gmpi_mpi_render_shared_launch w.r.t. the three tensors:  d rgb = sum over the planes that use rgb of d rgba[:, k, 0:3],
@@ -268,13 +285,14 @@ int gmpi_mpi_render_shared_launch(const GmpiRenderParams *params, const GmpiShar
  * grad_shared_rgb [M,3,Ht,Wt], grad_alpha [M,D,1,Ht,Wt] and grad_background [M,3,Ht,Wt] are fp32, caller-zeroed and ADDED into (atomicAdd); each has
  * three element strides (MPI, channel or plane, row; innermost 1); each may be NULL and is then skipped (all three NULL: GMPI_E_NULL; a
  * grad_background without a background: GMPI_E_NULL).
- * variant GATHER: one pixel per lane, 16 global atomics per pixel and plane.  Anything else: one workgroup per 32 x 16 pixel tile; the alpha gradient
+ * variant GATHER: one pixel per lane, 16 global atomics per pixel and plane.  AUTO: one workgroup per 32 x 16 pixel tile; the alpha gradient
  * is staged in LDS and flushed per plane, the colour gradient is summed in LDS ACROSS the planes in a window of 64 x 32 texels, which is flushed
  * whenever the tile's texel boxes have drifted out of it and at the end of the tile: with the FFHQ geometry and 32 planes 2.8 / 3.9 / 6.1 flushes per
  * tile on average at 256^2 / 512^2 / 1024^2 (instead of 32 per-plane flushes of the colour channels; up to one per plane for strongly tilted cameras
  * at 1024^2 -- DESIGN.md 3.3c has the counts).  D > 128 (more planes than the tile kernel's tables hold) takes the one-pixel-per-lane kernel, several
  * times slower.  The tile kernel's texel boxes assume a pinhole ray field (see ray_dir above); this is NOT checked: a pixel whose taps fall outside its
  * tile's box adds them straight to global memory, so any ray field gives correct gradients, an irregular one at the one-pixel-per-lane kernel's speed.
+ * Any other variant is GMPI_E_VARIANT: GMPI_VARIANT_LDS names a forward kernel only (the backward of a forward launched with it is AUTO's).
  */
 int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const float *grad_rgb_out,
                                            const float *grad_depth, const float *grad_transmittance, float *grad_shared_rgb,
@@ -394,7 +412,10 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
 /* what: 0 ABI version, 1 sizeof(GmpiRenderParams), 2 target arch number (950), 3 LDS bytes the
  * LDS variant uses per workgroup, 4 pixel-tile width, 5 pixel-tile height, 6 whether
  * GMPI_VARIANT_WAVE is built in, 7 GMPI_VARIANT_DMA (retired: 0), 8 GMPI_VARIANT_BAND, 9 the number of 256 x 8 pixel bands from which
- * GMPI_VARIANT_AUTO uses the band kernel on bf16 volumes, 10 the number of 128 x 8 pixel bands on fp32 volumes.  Unknown -> -1.                                        */
+ * GMPI_VARIANT_AUTO uses the band kernel on bf16 volumes, 10 the number of 128 x 8 pixel bands on fp32 volumes, 11 whether the atomics-free
+ * backward is built in; the staged shared-colour forward (gmpi_mpi_render_shared_launch with GMPI_VARIANT_LDS): 12 its pixel-tile width (a tile
+ * is 512 / width pixels high), 13 the texels per row and 14 the rows its staging buffer holds per plane (a box's first column is rounded down to
+ * a multiple of 4 texels before it is held against 13).  Unknown -> -1.                                        */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

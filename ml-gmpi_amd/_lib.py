@@ -33,6 +33,7 @@ EXPORTS = (
     "gmpi_mpi_render_geometry_backward_ex_launch",
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
+    "gmpi_render_shared_supports",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -190,6 +191,8 @@ def load_library():
     lib.gmpi_mpi_render_shared_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp]
     i64p = ctypes.POINTER(ctypes.c_int64)
+    lib.gmpi_render_shared_supports.restype = ctypes.c_int
+    lib.gmpi_render_shared_supports.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor)]
     lib.gmpi_mpi_render_shared_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp,
                                                            vp, i64p, vp, i64p, vp, i64p, vp]

@@ -27,6 +27,9 @@ uint64_t backward_gather_workspace_bytes(const KParams& p);                 // r
 uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
 hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared.hip
 hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream);   // render_shared.hip
+hipError_t launch_shared_forward(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared_forward.hip
+bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh);   // render_shared_forward.hip
+int shared_forward_query(int what);                                         // render_shared_forward.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 
@@ -485,15 +488,16 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, 
                                            static_cast<hipStream_t>(stream)));
 }
 
-// shared-colour entries: params->rgba = the alpha planes (rgba_stride[2] ignored); checks of to_kparams + the GmpiSharedColor struct
-static int to_shared(const GmpiRenderParams* params, const GmpiSharedColor* shared, bool need_outputs, KParams& p, SharedK& sh) {
+// shared-colour entries: params->rgba = the alpha planes (rgba_stride[2] ignored); checks of to_kparams + the GmpiSharedColor struct.
+// forward: the forward launch and its support query, which know GMPI_VARIANT_LDS; the backward knows AUTO and GATHER only.
+static int to_shared(const GmpiRenderParams* params, const GmpiSharedColor* shared, bool forward, KParams& p, SharedK& sh) {
     if (params == nullptr || shared == nullptr) return GMPI_E_NULL;
     if (params->struct_size != sizeof(GmpiRenderParams) || shared->struct_size != sizeof(GmpiSharedColor)) return GMPI_E_ABI;
     GmpiRenderParams q = *params;
     q.rgba_stride[2] = 1;   // (ignored: the alpha tensor has one channel)
-    const int rc = to_kparams(&q, p, need_outputs, true);
+    const int rc = to_kparams(&q, p, forward, true);   // (the forward needs the output pointers)
     if (rc != GMPI_OK) return rc;
-    if (params->variant != GMPI_VARIANT_AUTO && params->variant != GMPI_VARIANT_GATHER) return GMPI_E_VARIANT;
+    if (params->variant != GMPI_VARIANT_AUTO && params->variant != GMPI_VARIANT_GATHER && !(forward && params->variant == GMPI_VARIANT_LDS)) return GMPI_E_VARIANT;
     if (shared->rgb == nullptr) return GMPI_E_NULL;
     for (int i = 0; i < 3; ++i)
         if (shared->rgb_stride[i] < 0 || (shared->background != nullptr && shared->background_stride[i] < 0)) return GMPI_E_STRIDE;
@@ -512,8 +516,21 @@ int gmpi_mpi_render_shared_launch(const GmpiRenderParams* params, const GmpiShar
     const int rc = to_shared(params, shared, true, p, sh);
     if (rc != GMPI_OK) return rc;
     if (p.N == 0) return GMPI_OK;
+    if (params->variant == GMPI_VARIANT_LDS) {   // the staged kernel, only on request: AUTO and GATHER keep the one-pixel-per-lane kernel
+        if (!shared_forward_supports(p, params->rgba_dtype, sh)) return GMPI_E_VARIANT;
+        return hip_rc(launch_shared_forward(p, params->rgba_dtype, sh, static_cast<hipStream_t>(stream)));
+    }
     if (p.N > 65535) return GMPI_E_SHAPE;   // the view index is grid.z
     return hip_rc(launch_shared(p, params->rgba_dtype, sh, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_render_shared_supports(const GmpiRenderParams* params, const GmpiSharedColor* shared) {
+    KParams p;
+    SharedK sh;
+    const int rc = to_shared(params, shared, true, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (params->variant == GMPI_VARIANT_LDS) return shared_forward_supports(p, params->rgba_dtype, sh) ? 1 : 0;
+    return p.N > 65535 ? GMPI_E_SHAPE : 1;
 }
 
 int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb_out, const float* grad_depth,
@@ -668,6 +685,7 @@ int gmpi_query(int32_t what) {
         case 9: return static_cast<int>(kAutoBandMin);
         case 10: return static_cast<int>(kAutoBandMinF32);
         case 11: return 1;  // the atomics-free backward (pixel pass + texel gather) is built in
+        case 12: case 13: case 14: return shared_forward_query(what);
         default: return -1;
     }
 }

@@ -16,44 +16,6 @@
 
 namespace gmpi {
 
-// The four taps of one footprint: clamped addresses, weights of taps outside the texture zeroed (gather_sample's rule).
-struct Taps {
-    Footprint f;
-    int xa, xb, ya, yb;
-    bool x0in, x1in, y0in, y1in;
-};
-__device__ __forceinline__ Taps make_taps(float ix, float iy, int Ht, int Wt) {
-    Taps t;
-    t.f = footprint(ix, iy, Ht, Wt);
-    t.x0in = t.f.x0 >= 0 && t.f.x0 <= Wt - 1, t.x1in = t.f.x0 >= -1 && t.f.x0 <= Wt - 2;
-    t.y0in = t.f.y0 >= 0 && t.f.y0 <= Ht - 1, t.y1in = t.f.y0 >= -1 && t.f.y0 <= Ht - 2;
-    if (!(t.x0in && t.y0in)) t.f.nw = 0.0f;
-    if (!(t.x1in && t.y0in)) t.f.ne = 0.0f;
-    if (!(t.x0in && t.y1in)) t.f.sw = 0.0f;
-    if (!(t.x1in && t.y1in)) t.f.se = 0.0f;
-    t.xa = min(max(t.f.x0, 0), Wt - 1), t.xb = min(max(t.f.x0 + 1, 0), Wt - 1);
-    t.ya = min(max(t.f.y0, 0), Ht - 1), t.yb = min(max(t.f.y0 + 1, 0), Ht - 1);
-    return t;
-}
-template <typename TexT, bool STRICT>
-__device__ __forceinline__ float tap_sample(const TexT* __restrict__ ch, int64_t s_row, const Taps& t, bool check_range, uint32_t& bad) {
-    const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
-    const float t_nw = to_f32(ch[oa + t.xa]);
-    const float t_ne = to_f32(ch[oa + t.xb]);
-    const float t_sw = to_f32(ch[ob + t.xa]);
-    const float t_se = to_f32(ch[ob + t.xb]);
-    if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= GMPI_STATUS_RGBA_RANGE;
-    return bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, t.f);
-}
-// (r, g, b, alpha) of plane k for one pixel: colour from the shared image (the background on the last plane), alpha from its plane
-template <typename TexT, bool STRICT>
-__device__ __forceinline__ void shared_sample(const TexT* __restrict__ alpha_plane, int64_t a_row, const TexT* __restrict__ col, int64_t c_chan,
-                                              int64_t c_row, const Taps& t, bool check_range, uint32_t& bad, float (&smp)[4]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) smp[c] = tap_sample<TexT, STRICT>(col + c * c_chan, c_row, t, check_range, bad);
-    smp[3] = tap_sample<TexT, STRICT>(alpha_plane, a_row, t, check_range, bad);
-}
-
 // ---- forward: render_gather_kernel with the colour taken from one image -------------------------------------------------------------------------
 template <typename TexT, bool AC, bool STRICT>
 __global__ __launch_bounds__(256) void render_shared_kernel(const KParams p, const SharedK sh) {

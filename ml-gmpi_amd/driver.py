@@ -173,10 +173,35 @@ class ViewBatchDriver:
         HIP stream while the next batch renders -- the copy of the whole path (64 frames of 512^2: 67 MB) then hides behind the render launches instead
         of following them; adds `img8_host`, `dep8_host` (buffers of the driver, reused by the next call of the same shape: consume or copy them).
         """
-        r = self.renderer
         assert mpi_rgbas.shape[0] == 1, "render_path draws many views of one MPI"
+        r = self.renderer
+
+        def launch(dhw, ray, eye, zd, **kw):
+            r.mpi.render_views(mpi_rgbas, dhw, ray, eye, zd, **kw)
+        return self._render_path(launch, mpi_rgbas.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
+
+    @torch.no_grad()
+    def render_path_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, render_size: int, yaws: Sequence[float], pitches: Sequence[float],
+                           background: Optional[torch.Tensor] = None, indices: Optional[Sequence[int]] = None, to_uint8: bool = False,
+                           depth_range=None, want_transmittance: bool = False, to_host: bool = False, variant: Optional[str] = "lds"):
+        """`render_path` of ONE shared-colour MPI -- rgb [1,3,Ht,Wt], alpha [1,D,1,Ht,Wt] (may be the view `rgba[:, :, 3:]`), background [1,3,Ht,Wt]
+        or None -- without building the volume `expand_shared_color(rgb, alpha, background)`: the same grouping of poses and rays, single status
+        read-back, uint8 epilogue, second-stream copies and returned dict.  `variant`: the kernel of `MPI.render_views_shared`; "lds" is the staged
+        forward (it falls back to the one-pixel kernel for tensors it cannot take), None the renderer's own variant.  The default is "lds": it measures
+        11-21 % faster than the one-pixel kernel at every shape timed, the camera path included (profiles/shared_color_forward.txt)."""
+        from .shared_color import _check
+        _check(rgb, alpha, background)
+        assert alpha.shape[0] == 1, "render_path_shared draws many views of one MPI"
+        r = self.renderer
+
+        def launch(dhw, ray, eye, zd, **kw):
+            r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=background, variant=variant, **kw)
+        return self._render_path(launch, alpha.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
+
+    def _render_path(self, launch, dev, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host):
+        """The body of `render_path` and `render_path_shared`: `launch(dhw, ray_dir, eye_pos, z_dir, **render_views keywords)` renders one batch."""
+        r = self.renderer
         idx = list(range(len(yaws))) if indices is None else list(indices)
-        dev = mpi_rgbas.device
         n = len(idx)
         rgb = torch.empty((n, 3, render_size, render_size), dtype=torch.float32, device=dev)
         dep = torch.empty((n, 1, render_size, render_size), dtype=torch.float32, device=dev)
@@ -185,7 +210,7 @@ class ViewBatchDriver:
         if render_size != r.render_h or render_size != r.render_w:
             r.set_cam(r.cam_fov, render_size, render_size)
         dhw = r._dhw_on_device()
-        pipe = to_host and to_uint8 and mpi_rgbas.is_cuda
+        pipe = to_host and to_uint8 and dev.type == "cuda"
         if pipe:
             near, far = depth_range if depth_range is not None else (r.plane_min_d, r.plane_max_d)
             img8 = torch.empty((n, render_size, render_size, 3), dtype=torch.uint8, device=dev)
@@ -218,9 +243,8 @@ class ViewBatchDriver:
             out = dict(color=rgb[s:s + len(chunk)], depth=dep[s:s + len(chunk)])
             if T is not None:
                 out["T"] = T[s:s + len(chunk)]
-            r.mpi.render_views(mpi_rgbas, dhw, ray_t, eye_t, zd_t,
-                               views_per_mpi=len(chunk), check_last_plane=True, out_pm1=True,
-                               want_transmittance=want_transmittance, status=status, defer_status=True, out=out)
+            launch(dhw, ray_t, eye_t, zd_t, views_per_mpi=len(chunk), check_last_plane=True, out_pm1=True,
+                   want_transmittance=want_transmittance, status=status, defer_status=True, out=out)
             if pipe:   # this batch's frames: uint8 on the device, then to the host behind an event -- next to the next batch's render
                 e = s + len(chunk)
                 frames_to_uint8(rgb[s:e], dep[s:e], near, far, out=(img8[s:e], dep8[s:e]))
@@ -244,12 +268,29 @@ class ViewBatchDriver:
     def render_seeds(self, mpi_rgbas: torch.Tensor, render_size: int, views_per_mpi: int = 1, **render_kwargs):
         """Random-pose renders of a stack of MPIs [B,D,4,Ht,Wt] (prepare_fake_data.py:58-66 /
         fid_evaluation.py:116 pattern), `batch` MPIs per launch.  Returns the renderer's 4-tuple, concatenated."""
+        def render(s):
+            return self.renderer.render(mpi_rgbas[s:s + self.batch], render_size, render_size, views_per_mpi=views_per_mpi, **render_kwargs)
+        return self._render_seeds(render, mpi_rgbas.shape[0], render_kwargs)
+
+    @torch.no_grad()
+    def render_seeds_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, render_size: int, background: Optional[torch.Tensor] = None,
+                            views_per_mpi: int = 1, variant: Optional[str] = "lds", **render_kwargs):
+        """`render_seeds` of a stack of shared-colour MPIs -- rgb [B,3,Ht,Wt], alpha [B,D,1,Ht,Wt], background [B,3,Ht,Wt] or None -- through
+        `MPIRenderer.render_shared`, `batch` MPIs per launch: the poses, the returned 4-tuple and the consumption of the torch RNG of `render_seeds`
+        on the expanded volume.  `variant` as in `render_path_shared` (default "lds" for the same reason)."""
+        def render(s):
+            e = s + self.batch
+            return self.renderer.render_shared(rgb[s:e], alpha[s:e], render_size, render_size, background_rgb=None if background is None else background[s:e],
+                                               variant=variant, views_per_mpi=views_per_mpi, **render_kwargs)
+        return self._render_seeds(render, alpha.shape[0], render_kwargs)
+
+    def _render_seeds(self, render, n_mpis, render_kwargs):
+        """The loop of `render_seeds` and `render_seeds_shared`: `render(first MPI of the batch)` -> the renderer's 4-tuple."""
         from .hip_mpi import flush_status
         outs = []
         render_kwargs.setdefault("defer_status", "lag")   # (no frame leaves this method before every launch's assertions have been looked at)
-        for s in range(0, mpi_rgbas.shape[0], self.batch):
-            outs.append(self.renderer.render(mpi_rgbas[s:s + self.batch], render_size, render_size,
-                                             views_per_mpi=views_per_mpi, **render_kwargs))
+        for s in range(0, n_mpis, self.batch):
+            outs.append(render(s))
         if render_kwargs["defer_status"] == "lag":
             flush_status()
         return tuple(torch.cat([o[i] for o in outs], 0) for i in range(len(outs[0])))

@@ -16,6 +16,7 @@ import contextlib
 import ctypes
 import sys
 import threading
+import warnings
 import weakref
 from typing import List, Optional, Sequence, Union
 
@@ -350,6 +351,36 @@ def _kernel_operand(t: torch.Tensor, inner: int) -> torch.Tensor:
     return t.contiguous() if t.stride(inner) != 1 or any(s < 0 for s in t.stride()) else t
 
 
+def _readable_past_last_row(t: torch.Tensor, extra: int) -> bool:
+    """True when `extra` elements past t's last element still lie inside t's storage."""
+    last = t.storage_offset() + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    return (last + 1 + extra) * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def _staged_forward_takes(p, sc, tensors) -> bool:
+    """Whether GMPI_VARIANT_LDS of the shared-colour forward can run this launch: gmpi_render_shared_supports (alignment of the three tensors), and,
+    for a texture width that is no multiple of 4, that the padding its loader reads behind the LAST row of each tensor is allocated (behind every
+    other row it is the row stride's).  Errors the launch would raise are raised here, under the query's name."""
+    rc = _lib.load_library().gmpi_render_shared_supports(ctypes.byref(p), ctypes.byref(sc))
+    if rc < 0:
+        _lib.check(rc, "gmpi_render_shared_supports")
+    pad = -p.Wt % 4
+    return rc == 1 and all(t is None or _readable_past_last_row(t, pad) for t in tensors)
+
+
+_LDS_FALLBACK_WARNED = False
+
+
+def _warn_lds_fallback() -> None:
+    """Once per process: variant="lds" was asked for by name and the one-pixel-per-lane kernel ran (every such launch is counted in
+    `MPI.shared_lds_fallbacks`)."""
+    global _LDS_FALLBACK_WARNED
+    if not _LDS_FALLBACK_WARNED:
+        _LDS_FALLBACK_WARNED = True
+        warnings.warn('shared-colour render: variant="lds" cannot take these tensors (base pointers and outer strides must be multiples of 4 texels); '
+                      "the one-pixel-per-lane kernel runs instead (counted in MPI.shared_lds_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
+
+
 def _f32_on(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     """t as contiguous float32 on dev; the tensor itself when it already is (a no-op `.to().contiguous()` costs ~10 us per call)."""
     if t.dtype is torch.float32 and t.device == dev and t.is_contiguous():
@@ -430,6 +461,7 @@ class MPI(nn.Module):
         self.range_check = range_check
         self.on_out_of_plane = on_out_of_plane
         self._full_check_passed = None   # (weakref to the volume's base tensor, fingerprint): see _volume_fingerprint
+        self.shared_lds_fallbacks = 0    # shared-colour launches that asked for "lds" and ran AUTO's kernel instead (a debug counter)
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -513,7 +545,7 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _shared=None):
+                     _shared=None, _shared_variant: Optional[str] = None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -536,6 +568,8 @@ class MPI(nn.Module):
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
+                if _shared is not None:
+                    kwargs["_shared_variant"] = _shared_variant
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -572,8 +606,10 @@ class MPI(nn.Module):
         if T is None and want_transmittance:
             T = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
         variant = _lib.VARIANTS[self.variant]
-        if _shared is not None:   # (the shared-colour entries know AUTO and GATHER)
-            variant = _lib.VARIANT_GATHER if self.variant == "gather" else _lib.VARIANT_AUTO
+        if _shared is not None:   # (the shared-colour entries know AUTO, GATHER and LDS; LDS is asked for below, once the struct exists)
+            shared_variant = self.variant if _shared_variant is None else _shared_variant
+            assert shared_variant in _lib.VARIANTS, shared_variant
+            variant = _lib.VARIANT_GATHER if shared_variant == "gather" else _lib.VARIANT_AUTO
         scalars = _Scalars(self._flags(out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint), variant, _DTYPES[rgba.dtype],
                            N, M, D, Ht, Wt, H, W, max(uniform, 1))
         current = torch.cuda.current_stream(dev) if on_device else None
@@ -596,7 +632,14 @@ class MPI(nn.Module):
                     t = t if t.is_contiguous() else t.contiguous()
                     _call("gmpi_rgba_range_check_launch", dev, t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream=stream)
             if _shared is not None:
-                _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(sh_rgb, sh_bg)), stream=stream)
+                sc = _shared_color(sh_rgb, sh_bg)
+                if shared_variant == "lds" and on_device:   # the staged forward where it can take these tensors (alignment), else AUTO's kernel
+                    p.variant = _lib.VARIANT_LDS
+                    if not _staged_forward_takes(p, sc, (rgba, sh_rgb, sh_bg)):
+                        p.variant = _lib.VARIANT_AUTO
+                        self.shared_lds_fallbacks += 1
+                        _warn_lds_fallback()
+                _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
             else:
                 _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
             res = dict(color=color, depth=depth, T=T, status=status)
@@ -647,12 +690,14 @@ class MPI(nn.Module):
 
     # -- shared-colour layout ----------------------------------------------------------------------------------------------------------
     def render_views_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
-                            z_dir: torch.Tensor, background: Optional[torch.Tensor] = None, **kwargs):
+                            z_dir: torch.Tensor, background: Optional[torch.Tensor] = None, variant: Optional[str] = None, **kwargs):
         """`render_views` of the volume `expand_shared_color(rgb, alpha, background)` without building it: rgb [M,3,Ht,Wt] colours every plane
         (all but the last when `background` [M,3,Ht,Wt] is given), alpha [M,D,1,Ht,Wt] may be the view `rgba[:, :, 3:]` of a volume.  Same
         keyword arguments, returned dict and status handling as `render_views`; under autograd the gradient reaches rgb, alpha and background
-        (gmpi_mpi_render_shared_backward_launch: the colour gradient is summed over the planes on the chip).  variant "gather" forces the
-        one-pixel-per-lane kernels, every other variant lets the library choose.  No gradient w.r.t. the geometry (NotImplementedError with
+        (gmpi_mpi_render_shared_backward_launch: the colour gradient is summed over the planes on the chip).  `variant` (None: the module's own):
+        "gather" forces the one-pixel-per-lane kernels; "lds" selects the staged forward (render_shared_forward.hip: texel boxes of 32 x 16 pixel
+        tiles through LDS) when gmpi_render_shared_supports says it can take the three tensors (base pointers and outer strides multiples of 4
+        texels) and AUTO's kernel otherwise -- the backward is the tile backward either way; every other variant lets the library choose.  No gradient w.r.t. the geometry (NotImplementedError with
         geometry_grad=True and a camera / dhw tensor that requires grad).  The three tensors must have ONE dtype (TypeError otherwise: nothing is
         cast behind the caller's back).  range_check="full" runs the exhaustive pass over the three tensors in EVERY call (the volume path's
         "unchanged volume" cache is not kept for three tensors), and that pass reads contiguous memory: a strided alpha view such as
@@ -662,7 +707,7 @@ class MPI(nn.Module):
         from .shared_color import _check
         _check(rgb, alpha, background)
         assert "_shared" not in kwargs
-        return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _shared=(rgb, background), **kwargs)
+        return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _shared=(rgb, background), _shared_variant=variant, **kwargs)
 
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
     def raise_on_status(self, status: torch.Tensor, params=None, keep=None, c2w_mat=None, sphere_c=None):
@@ -724,7 +769,9 @@ def _bridge_forward(ctx, mpi, volume, geometry, kwargs, shared=None):
     p = bwd[0]
     if kwargs.get("want_transmittance") and user_out.get("T") is not None:
         user_out["T"].copy_(res["T"])
-    ctx.scalars = _Scalars(p.flags, p.variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi)
+    # (the staged shared-colour forward is a forward variant only: its backward is AUTO's, the tile backward)
+    bwd_variant = _lib.VARIANT_AUTO if shared is not None and p.variant == _lib.VARIANT_LDS else p.variant
+    ctx.scalars = _Scalars(p.flags, bwd_variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi)
     ctx.mark_non_differentiable(res["status"])
     # (an output nobody used arrives as None, not as a zero tensor: "T unused" -> today's launch, told apart from gT = 0 without a reduction)
     ctx.set_materialize_grads(False)

@@ -419,6 +419,7 @@ class MPIRenderer:
         views_per_mpi = int(ext.pop("views_per_mpi", 1))
         want_T = bool(ext.pop("want_transmittance", False))
         shared = ext.pop("_shared", None)   # render_shared: (rgb, background or None); batch_mpi_rgbas is then the alpha tensor
+        shared_variant = ext.pop("_shared_variant", None)
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -461,7 +462,7 @@ class MPIRenderer:
             batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
             check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
             c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-            **({} if shared is None else {"_shared": shared}))
+            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}))
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
@@ -469,15 +470,16 @@ class MPIRenderer:
         return res["color"], res["depth"], c2w, cam_angles
 
 
-    def render_shared(self, batch_mpi_rgb, batch_mpi_alpha, render_h, render_w, *, background_rgb=None, **kwargs):
+    def render_shared(self, batch_mpi_rgb, batch_mpi_alpha, render_h, render_w, *, background_rgb=None, variant=None, **kwargs):
         """`render` of the volume `expand_shared_color(batch_mpi_rgb, batch_mpi_alpha, background_rgb)` without building it (the layout GMPI's
         generator holds before it concatenates): batch_mpi_rgb [B,3,Ht,Wt], batch_mpi_alpha [B,D,1,Ht,Wt] (may be the view `rgba[:, :, 3:]`),
         background_rgb [B,3,Ht,Wt] or None = the last plane's own colour.  Keyword arguments, return tuple, pose sampling and the consumption of
-        the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the expanded volume."""
+        the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the expanded volume.  `variant`: the kernel, as
+        in `MPI.render_views_shared` (None: the renderer's own; "lds": the staged forward)."""
         from .shared_color import _check
         _check(batch_mpi_rgb, batch_mpi_alpha, background_rgb)
         assert "_shared" not in kwargs
-        return self.render(batch_mpi_alpha, render_h, render_w, _shared=(batch_mpi_rgb, background_rgb), **kwargs)
+        return self.render(batch_mpi_alpha, render_h, render_w, _shared=(batch_mpi_rgb, background_rgb), _shared_variant=variant, **kwargs)
 
 
 class _RaysFromC2W(torch.autograd.Function):

@@ -1,6 +1,7 @@
 """Times the shared-colour layout (one colour image per MPI + D alpha planes + a background image) against the volume path it replaces, through the
 C ABI, with HIP events (medians): at 256^2 x 8, 512^2 x 4 and 1024^2 x 4 with 32 planes in fp32 the whole G-step (forward, zero-fill, backward),
-at 1024^2 x 96 x 4 (fp32, bf16) the forward only.
+at 1024^2 x 96 x 4 (fp32, bf16) the forward only, and one camera-path launch (8 views of ONE 512^2 x 96 MPI along a yaw sweep of +-0.3 rad), forward only.
+The shared forward is timed twice: the one-pixel-per-lane kernel ("shared_fwd": variant auto) and the staged kernel ("shared_fwd_staged": variant lds).
 
   baseline  materialise the expanded volume as the generator does (expand + two cat), forward (variant auto), zero-fill of the volume gradient,
             volume backward (tile kernels), plane sum of the colour gradient (the backward of the generator's expand)
@@ -14,10 +15,12 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [("256", 8, 32, "f32", 1), ("512", 4, 32, "f32", 1), ("1024", 4, 32, "f32", 1), ("1024", 4, 96, "f32", 0), ("1024", 4, 96, "bf16", 0)]
+# (S, MPIs, planes, storage, with backward, views per MPI)
+SHAPES = [("256", 8, 32, "f32", 1, 1), ("512", 4, 32, "f32", 1, 1), ("1024", 4, 32, "f32", 1, 1), ("1024", 4, 96, "f32", 0, 1), ("1024", 4, 96, "bf16", 0, 1),
+          ("512", 1, 96, "f32", 0, 8)]
 
 
-def one(S, B, D, dtype_name, with_backward, reps):
+def one(S, B, D, dtype_name, with_backward, reps, V=1):
     import torch
     sys.path.insert(0, ROOT)
     import ml_gmpi_amd
@@ -42,20 +45,25 @@ def one(S, B, D, dtype_name, with_backward, reps):
     rgb = torch.rand((B, 3, S, S), device=dev, generator=g).to(dtype)
     alpha = torch.rand((B, D, 1, S, S), device=dev, generator=g).to(dtype)
     bg = torch.rand((B, 3, S, S), device=dev, generator=g).to(dtype)
-    gc = torch.randn((B, 3, S, S), device=dev, generator=g)
-    gd = torch.randn((B, 1, S, S), device=dev, generator=g)
+    N = B * V
+    gc = torch.randn((N, 3, S, S), device=dev, generator=g)
+    gd = torch.randn((N, 1, S, S), device=dev, generator=g)
     torch.manual_seed(3)
-    cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
+    if V == 1:
+        cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
+    else:   # a camera path: V views of every MPI along a yaw sweep
+        yaws = torch.linspace(-0.3, 0.3, V).repeat(B).reshape(N, 1)
+        cam = r.sample_cam_poses(N, 0.0, 0.0, 0.0, 0.0, False, given_yaws=yaws, given_pitches=torch.zeros((N, 1)))
     ray, eye, zd = torch.cat(cam[3]), torch.cat(cam[4]), torch.cat(cam[5])
     dhw = r._dhw_on_device().expand(B, -1, -1).contiguous()
-    kw = dict(views_per_mpi=1, check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True)
+    kw = dict(views_per_mpi=V, check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True)
     base_mem = torch.cuda.memory_allocated(dev)
-    row = dict(S=S, B=B, D=D, dtype=dtype_name)
+    row = dict(S=S, B=B, D=D, dtype=dtype_name, views=N)
 
     # ---- baseline: the volume path of the parent commit ------------------------------------------------------------------------------------------
     torch.cuda.reset_peak_memory_stats(dev)
     vol = expand_shared_color(rgb, alpha, bg)
-    out = {k: torch.empty(s, device=dev) for k, s in (("color", (B, 3, S, S)), ("depth", (B, 1, S, S)), ("T", (B, 1, S, S)))}
+    out = {k: torch.empty(s, device=dev) for k, s in (("color", (N, 3, S, S)), ("depth", (N, 1, S, S)), ("T", (N, 1, S, S)))}
     with torch.no_grad():
         res = r.mpi.render_views(vol, dhw, ray, eye, zd, out=out, _in_autograd_fn=True, **kw)
     p = res.pop("_bwd")[0]   # (the tuple also holds the volume: dropped here, so that `del vol` below frees it)
@@ -110,6 +118,12 @@ def one(S, B, D, dtype_name, with_backward, reps):
     row["shared_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
     with torch.no_grad():
         row["shared_fwd"] = timed(lambda: r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, **kw))
+        staged = r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, variant="lds", _in_autograd_fn=True, **kw)
+        assert staged.pop("_bwd")[0].variant == _lib.VARIANT_LDS, "the staged kernel did not take this launch"
+        row["shared_fwd_staged"] = timed(lambda: r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, variant="lds", **kw))
+        row["staged_vs_one_pixel"] = row["shared_fwd_staged"] / row["shared_fwd"]
+        row["staged_vs_auto_on_volume"] = row["shared_fwd_staged"] / row["base_fwd"]
+        row["staged_vs_expand_plus_auto"] = row["shared_fwd_staged"] / (row["base_expand"] + row["base_fwd"])
     if with_backward:
         row["shared_fill"] = timed(lambda: (g_rgb.zero_(), g_alpha.zero_(), g_bg.zero_()))
         row["shared_bwd_tile"] = timed(tile)
@@ -127,14 +141,14 @@ def one(S, B, D, dtype_name, with_backward, reps):
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--one":
-        S, B, D, dt, bw, reps = sys.argv[2:8]
-        one(int(S), int(B), int(D), dt, int(bw), int(reps))
+        S, B, D, dt, bw, reps, V = sys.argv[2:9]
+        one(int(S), int(B), int(D), dt, int(bw), int(reps), int(V))
         sys.exit(0)
     reps = sys.argv[1] if len(sys.argv) > 1 else "15"
     print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape")
-    for S, B, D, dt, bw in SHAPES:
+    for S, B, D, dt, bw, V in SHAPES:
         try:
-            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), dt, str(bw), reps], timeout=240).returncode
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), dt, str(bw), reps, str(V)], timeout=240).returncode
         except subprocess.TimeoutExpired:   # (run() has killed the child)
             rc = "time limit of 240 s"
         if rc != 0:
