@@ -32,8 +32,11 @@ extern "C" {
 
 #define GMPI_ABI_VERSION 2
 
-/* storage type of the RGBA volume; arithmetic is always fp32 (mpi_renderer.py:446 `.float()`) */
-enum { GMPI_DTYPE_F32 = 0, GMPI_DTYPE_BF16 = 1, GMPI_DTYPE_F16 = 2 };
+/* storage type of the RGBA volume; arithmetic is always fp32 (mpi_renderer.py:446 `.float()`).
+ * GMPI_DTYPE_U8: 8 bits per channel, code c in 0..255 stands for the fp32 value c / 255 (the correctly rounded quotient): rendering such a volume
+ * is by definition rendering that fp32 volume.  gmpi_mpi_render_launch and gmpi_render_workspace_bytes take it; every other entry returns
+ * GMPI_E_DTYPE for it (no gradients, no shared-colour layout, no shading, no range pass: every code is in [0, 1]). */
+enum { GMPI_DTYPE_F32 = 0, GMPI_DTYPE_BF16 = 1, GMPI_DTYPE_F16 = 2, GMPI_DTYPE_U8 = 3 };
 
 /* GmpiRenderParams.flags */
 enum {
@@ -109,7 +112,7 @@ enum {
     GMPI_E_NULL = -1,        /* required pointer is NULL                      */
     GMPI_E_SHAPE = -2,       /* non-positive / inconsistent extent; N > 65535 views for the gather kernel
                                 or the backward (split the batch)             */
-    GMPI_E_DTYPE = -3,       /* unknown rgba_dtype                            */
+    GMPI_E_DTYPE = -3,       /* unknown rgba_dtype, or one this entry does not take (GMPI_DTYPE_U8 anywhere but the forward) */
     GMPI_E_STRIDE = -4,      /* innermost rgba stride != 1 or negative stride */
     GMPI_E_ABI = -5,         /* struct_size does not match this library       */
     GMPI_E_VARIANT = -6,     /* requested kernel variant cannot run this shape */
@@ -170,7 +173,13 @@ uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams *params);
  * GMPI_VARIANT_AUTO picks the kernel from the launch shape; for large launches over bf16 / fp32 volumes with a workspace it enqueues
  * the band kernel and the tile kernel together and shares out the views on the device: the band kernel takes every view whose
  * texel boxes fit its staging buffers (mildly tilted cameras), the tile kernel the others.  An explicit variant that cannot
- * take the parameters returns GMPI_E_VARIANT. */
+ * take the parameters returns GMPI_E_VARIANT.
+ * GMPI_DTYPE_U8 volumes have two kernels: GATHER (the one-pixel-per-lane kernel: any shape, any stride) and LDS (render_u8.hip: 32 x 16 pixel tiles,
+ * per plane a box of up to 64 x 32 raw RGBA texels in LDS, 4 bytes each; it loads 4 texels of a channel row at a time: Wt, the base pointer and the
+ * row, channel, plane and MPI strides must be multiples of 4 bytes, else GMPI_E_VARIANT).  WAVE and BAND are GMPI_E_VARIANT; AUTO is LDS where
+ * it can take the tensors, else GATHER, whatever the camera hints say.  No workspace.  GMPI_FLAG_CHECK_RANGE is accepted and never sets a bit.
+ * With GMPI_FLAG_STRICT_ORDER both are bit-identical to the render of the fp32 volume c / 255; without it the LDS kernel interpolates the codes
+ * and scales the sample by RN(1/255) once per channel (about 2e-7 from the strict result). */
 int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
 
 /*
@@ -415,7 +424,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * GMPI_VARIANT_AUTO uses the band kernel on bf16 volumes, 10 the number of 128 x 8 pixel bands on fp32 volumes, 11 whether the atomics-free
  * backward is built in; the staged shared-colour forward (gmpi_mpi_render_shared_launch with GMPI_VARIANT_LDS): 12 its pixel-tile width (a tile
  * is 512 / width pixels high), 13 the texels per row and 14 the rows its staging buffer holds per plane (a box's first column is rounded down to
- * a multiple of 4 texels before it is held against 13).  Unknown -> -1.                                        */
+ * a multiple of 4 texels before it is held against 13); 15 is unused (-1); the staged kernel for GMPI_DTYPE_U8 volumes: 16 its pixel-tile width (a tile
+ * is 512 / width pixels high), 17 the texels per row and 18 the rows its staging buffer holds per plane (first column rounded down to a multiple of 4
+ * texels, as for 13).  Unknown -> -1.                                        */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

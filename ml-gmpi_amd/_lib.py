@@ -14,6 +14,7 @@ _LIB = None
 
 ABI_VERSION = 2
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
+DTYPE_U8 = 3   # 8 bits per channel, code c = c / 255: the forward render only (every other entry returns GMPI_E_DTYPE for it)
 FLAG_ALIGN_CORNERS, FLAG_OUT_PM1, FLAG_CHECK_LAST_PLANE, FLAG_CHECK_RANGE, FLAG_STRICT_ORDER, FLAG_HINT_FRONTAL, FLAG_HINT_TILTED = 1, 2, 4, 8, 16, 32, 64
 FLAG_HINT_OBLIQUE = 256     # advisory: some camera axis more than 0.35 rad off the MPI normal (views that share an MPI then stay on the tile kernel)
 FLAG_GRAD_OVERWRITE = 128   # backward only: grad_rgba's content is not needed (with the backward's workspace every element is written: no zero-fill)
@@ -54,7 +55,7 @@ EXPORTS = (
 _ERRORS = {
     -1: "GMPI_E_NULL (required pointer is NULL)",
     -2: "GMPI_E_SHAPE (non-positive or inconsistent extent, or more than 65535 views for the gather kernel / the backward)",
-    -3: "GMPI_E_DTYPE (unknown rgba dtype)",
+    -3: "GMPI_E_DTYPE (unknown rgba dtype, or uint8 storage handed to an entry other than the forward render)",
     -4: "GMPI_E_STRIDE (innermost rgba stride must be 1, strides non-negative)",
     -5: "GMPI_E_ABI (GmpiRenderParams size mismatch between binding and library)",
     -6: "GMPI_E_VARIANT (requested kernel variant cannot run this shape)",

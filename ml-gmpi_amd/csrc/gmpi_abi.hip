@@ -30,6 +30,9 @@ hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh
 hipError_t launch_shared_forward(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared_forward.hip
 bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh);   // render_shared_forward.hip
 int shared_forward_query(int what);                                         // render_shared_forward.hip
+hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
+bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
+int u8_variant_query(int what);                                             // render_u8.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 
@@ -243,7 +246,8 @@ __global__ __launch_bounds__(256) void selftest_division_kernel(uint64_t pairs, 
     }
 }
 
-static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, bool need_volume = false) {
+// takes_u8: the entry has kernels for GMPI_DTYPE_U8 (the forward launch and its workspace query); every other caller refuses the type here.
+static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, bool need_volume = false, bool takes_u8 = false) {
     if (q == nullptr) return GMPI_E_NULL;
     if (q->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
     if (q->flags & ~static_cast<uint32_t>(GMPI_FLAG_ALL)) return GMPI_E_FLAGS;  // undefined bits never reach a kernel
@@ -256,7 +260,7 @@ static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, 
     if (need_outputs && (q->rgb_out == nullptr || q->depth_out == nullptr)) return GMPI_E_NULL;
     if (need_outputs || need_volume) {
         if (q->rgba == nullptr || q->z_dir == nullptr) return GMPI_E_NULL;
-        if (q->rgba_dtype < GMPI_DTYPE_F32 || q->rgba_dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
+        if (q->rgba_dtype < GMPI_DTYPE_F32 || q->rgba_dtype > (takes_u8 ? GMPI_DTYPE_U8 : GMPI_DTYPE_F16)) return GMPI_E_DTYPE;
         if (q->rgba_stride[4] != 1) return GMPI_E_STRIDE;
         for (int i = 0; i < 4; ++i)
             if (q->rgba_stride[i] < 0) return GMPI_E_STRIDE;
@@ -344,11 +348,23 @@ extern "C" {
 int gmpi_mpi_render_launch(const GmpiRenderParams* params, void* stream) {
     if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;  // no views
     KParams p;
-    const int rc = to_kparams(params, p, true);
+    const int rc = to_kparams(params, p, true, false, true);
     if (rc != GMPI_OK) return rc;
     if (p.N == 0) return GMPI_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int variant = params->variant;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) {
+        // 8-bit volumes: one staged kernel and the gather kernel.  AUTO is the staged kernel wherever it can take the tensors -- no threshold, and the
+        // camera hints change nothing; nothing below this block sees the type.
+        const bool staged = u8_variant_supports(p);
+        if (variant == GMPI_VARIANT_AUTO) variant = staged ? GMPI_VARIANT_LDS : GMPI_VARIANT_GATHER;
+        if (variant == GMPI_VARIANT_GATHER) {
+            if (p.N > 65535) return GMPI_E_SHAPE;  // the gather kernel puts the view index in grid.z
+            return hip_rc(launch_gather(p, GMPI_DTYPE_U8, st));
+        }
+        if (variant == GMPI_VARIANT_LDS && staged) return hip_rc(launch_u8(p, st));
+        return GMPI_E_VARIANT;  // WAVE, BAND: not built for this type; LDS: these tensors are not aligned for its loader
+    }
     if (variant == GMPI_VARIANT_AUTO) {
         // Measured on MI355X at steady clocks (profiles/r02_variants.txt, "small launches"): the tile kernel wins on large
         // launches (configs 3-5: 32 waves per CU hide its latencies, its shared 32x16 boxes tolerate tilted cameras); the strip
@@ -425,7 +441,8 @@ int gmpi_mpi_render_launch(const GmpiRenderParams* params, void* stream) {
 
 uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams* params) {
     KParams p;
-    if (to_kparams(params, p, true) != GMPI_OK || p.N == 0) return 0;
+    if (to_kparams(params, p, true, false, true) != GMPI_OK || p.N == 0) return 0;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) return 0;  // neither of its kernels wants scratch
     if (params->variant == GMPI_VARIANT_BAND) return band_workspace_bytes(p, params->rgba_dtype);
     if (params->variant == GMPI_VARIANT_AUTO && auto_takes_band(p, params->rgba_dtype)) return band_workspace_bytes(p, params->rgba_dtype);
     return 0;
@@ -686,6 +703,7 @@ int gmpi_query(int32_t what) {
         case 10: return static_cast<int>(kAutoBandMinF32);
         case 11: return 1;  // the atomics-free backward (pixel pass + texel gather) is built in
         case 12: case 13: case 14: return shared_forward_query(what);
+        case 16: case 17: case 18: return u8_variant_query(what);  // (15: unused)
         default: return -1;
     }
 }

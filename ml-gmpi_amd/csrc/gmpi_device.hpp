@@ -109,17 +109,35 @@ struct f16_t { _Float16 v; };
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return __uint_as_float(static_cast<uint32_t>(v.bits) << 16); }
 __device__ __forceinline__ float to_f32(f16_t v) { return static_cast<float>(v.v); }
+// 8-bit storage (GMPI_DTYPE_U8): code c in 0..255 stands for the fp32 value c / 255, the correctly rounded quotient.  A bare c * RN(1/255) misses it for
+// 126 of the 256 codes; one correction step (div_by_recip below, written out: the residual e is exact) gives it for all 256
+// (tests/test_u8_storage_cpu.py restates this in numpy and checks every code).  Not an upcast any more: three VALU ops per texel.
+struct u8_t { uint8_t code; };
+constexpr float kInv255 = 1.0f / 255.0f;  // RN(1/255)
+__device__ __forceinline__ float unorm8_to_f32(float c) {  // c: the code as a float (v_cvt_f32_ubyte0..3 are exact)
+    const float q = c * kInv255;
+    const float e = __builtin_fmaf(-q, 255.0f, c);
+    return __builtin_fmaf(e, kInv255, q);
+}
+__device__ __forceinline__ float to_f32(u8_t v) { return unorm8_to_f32(static_cast<float>(v.code)); }
 
 // Host side: a run-time dtype (GMPI_DTYPE_F32 / _BF16 / _F16 = 0 / 1 / 2, validated by the C ABI) or flag picks the template instance.
 // f is a generic lambda: it gets TypeTag<float | bf16_t | f16_t>{} (storage type: `typename decltype(t)::type`), resp. std::true_type{} /
 // std::false_type{} (`decltype(b)::value`), and its result is passed on.
+// The three floating-point storage types ONLY.  GMPI_DTYPE_U8 has instances of two forward kernels (render_gather.hip, render_u8.hip), whose
+// launchers pick them before they come here; every other entry refuses the type with GMPI_E_DTYPE.  Should one forget to: nothing is launched
+// and hipErrorInvalidValue comes back -- never another type's instance.
 template <typename T> struct TypeTag { using type = T; };
 template <typename F>
 inline auto dispatch_dtype(int dtype, F&& f) {
+    using R = decltype(f(TypeTag<float>{}));
     switch (dtype) {
-        case 0: return f(TypeTag<float>{});
-        case 1: return f(TypeTag<bf16_t>{});
-        default: return f(TypeTag<f16_t>{});
+        case GMPI_DTYPE_F32: return f(TypeTag<float>{});
+        case GMPI_DTYPE_BF16: return f(TypeTag<bf16_t>{});
+        case GMPI_DTYPE_F16: return f(TypeTag<f16_t>{});
+        default:
+            if constexpr (std::is_void_v<R>) return;
+            else return static_cast<R>(hipErrorInvalidValue);
     }
 }
 template <typename F>

@@ -58,6 +58,7 @@ static hipError_t launch_gather_t(const KParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) {
+    if (dtype == GMPI_DTYPE_U8) return launch_gather_t<u8_t>(p, stream);  // (8-bit codes: to_f32 is the division by 255; only the forward takes them)
     return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, stream); });
 }
 

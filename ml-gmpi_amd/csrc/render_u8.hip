@@ -1,0 +1,251 @@
+// render_u8.hip -- GMPI_VARIANT_LDS for GMPI_DTYPE_U8 volumes: the tile kernel's frame over 8-bit texels.
+//
+// A code c in 0..255 stands for the fp32 value c / 255 (to_f32(u8_t), gmpi_device.hpp): rendering the volume is by definition rendering that fp32
+// volume.  One workgroup of 512 threads owns a 32 x 16 pixel tile (one pixel per thread) and walks the D planes front to back; per plane the texel
+// box spanned by the tile's four corner pixels is staged in LDS, two buffers, one barrier per plane, the loads of plane k + 1 in flight while
+// plane k is composited (render_lds.hip has the why of all that).
+//
+// What is new is the LDS image: the RAW texels, interleaved, one dword (R | G << 8 | B << 16 | A << 24) per texel, 64 texels x 32 rows.
+//  * A pixel's 2 x 2 footprint is two ds_read2_b32 (texels x, x + 1 of rows y and y + 1) instead of the fp32 planes' eight.
+//  * Row pitch 64 dwords: ds_read2_b32 banks by (a / 4) mod 32 per 32-lane half, and a half wave is one pixel row of the tile.  Its lanes read
+//    consecutive texels (the warp is near-identity), and where a tilted row crosses from texel row y to y + 1 the two runs keep distinct x: with a
+//    pitch that is a multiple of the 32 banks they do not collide as long as the row spans at most 32 texels.  (More than one texel per pixel
+//    wraps around the banks in any one-dword-per-texel layout: a tilted camera's 47-texel boxes do.  That conflict rate has not been measured.)
+//  * The volume is planar.  One loader item = 4 texels of one channel row = one dword load from each of the four channel images through the
+//    plane's buffer descriptor (scalar offset = channel), 8 v_perm_b32 to interleave them, one 16-byte LDS store: 16 items per box row, 32 rows,
+//    exactly one item per thread, the thread -> item map fixed at compile time.  A 16-byte item (16 texels) would need Wt, the base pointer and
+//    every stride to be multiples of 16 bytes and the box origin rounded down to 16 texels (up to 15 dead columns of the 64); the 4-texel item asks
+//    for multiples of 4 only, keeps more volumes on the staged path, and is what the tile kernel does for 16-bit texel pairs.
+//  * Items outside the box or outside the texture take the offset the hardware range check rejects: they come back as zeros without touching
+//    memory, which IS padding_mode="zeros"; nothing is exec-masked.
+//  * The prefetch does not cross a chunk of the per-plane table (64 planes): the load issued behind a chunk's last plane is rejected as a whole,
+//    and the next chunk's first plane is loaded after the table rebuild -- one exposed load latency per chunk (twice at D = 96).
+//
+// Arithmetic.  GMPI_FLAG_STRICT_ORDER: every tap is converted first (c / 255, three VALU ops) and the sample is gather_sample's sum: bit-identical
+// to the gather kernel and to the oracle on the fp32 volume.  Default: the CODES are interpolated (v_cvt_f32_ubyte0..3 are exact) and the sample is
+// scaled by RN(1/255) once per channel: 4 multiplies instead of 16 conversions; the error is a few ulp of 255, divided by 255: about 2e-7.
+//
+// A (tile, plane) whose box exceeds the buffer (texture much finer than the image, NaN / inf corners) takes gather_plane for that plane, and so does
+// a single pixel whose footprint lies outside its tile's box (a ray field that is no pinhole camera's).  Weights of taps outside the texture are
+// zeroed as gather_sample zeroes them, so in strict-order mode a pixel's bits do not depend on the path; in default mode gather_plane converts per
+// tap, which differs from the staged sample by the 2e-7 above.  GMPI_FLAG_CHECK_RANGE has nothing to test: every code is in [0, 1].
+#include "gmpi_device.hpp"
+
+namespace gmpi {
+
+constexpr int kUW = 32, kUH = 16, kUThreads = kUW * kUH;   // pixel tile, one pixel per thread
+constexpr int kUPitch = 64, kURows = 32;                   // staging buffer: texels (dwords) per row, rows
+constexpr int kUTPI = 4, kUCols = kUPitch / kUTPI;         // texels per loader item, items per row
+constexpr int kUBufWords = kURows * kUPitch;               // 2048 dwords = 8 KB
+constexpr int kUChunk = 64;                                // planes per table refill
+constexpr float kUBoxEps = 1.0f / 64;                      // slack on the corner-derived box (fp32 error of ix is < 1e-3 texel)
+static_assert(kURows * kUCols == kUThreads, "one loader item per thread");
+static_assert(kUPitch % 32 == 0, "row pitch: a multiple of the 32 banks of ds_read2_b32");
+static_assert(2 * kUBufWords * 4 + kUChunk * 48 <= 40 * 1024, "4 workgroups per CU");
+
+// (strict-order instances: 6 waves per SIMD -- at 8 the 16 per-tap conversions push one of them 12 bytes into scratch)
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
+    // Per plane of the chunk, written once by one thread so that the 8 waves do not repeat the address arithmetic on their scalar units:
+    //   box:  qx0 (a multiple of 4), by0, items per row (0: not staged), rows
+    //   org:  byte address of the box origin (texel row by0, column qx0 of channel 0) = words 0, 1 of the plane's buffer descriptor, RN(1 / hh).
+    //         The origin may lie before the image: only lanes inside the texture pass the range test.
+    //   geo:  zdiff = d - eye_z, hw = w / 2, hh = h / 2, RN(1 / hw)
+    __shared__ int4 box[kUChunk];
+    __shared__ int4 org[kUChunk];
+    __shared__ float4 geo[kUChunk];
+    __shared__ __attribute__((aligned(16))) uint32_t stage[2][kUBufWords];
+
+    // ---- blockIdx -> tile: every XCD gets a contiguous run of the tiles of every group of views that share an MPI (gmpi_device.hpp) -------------
+    const int tid = threadIdx.x;
+    const int tiles_per_view = tiles_x * tiles_y;
+    const int tile_id = xcd_item_per_group(static_cast<int>(blockIdx.x), tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles);
+    if (tile_id >= n_tiles) return;
+    int n, trem;
+    item_to_view(p, tile_id, tiles_per_view, n, trem);   // (views that share one MPI are interleaved per tile position)
+    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
+
+    uint32_t bad = 0;
+    const View vw = view_setup<AC>(p, n, bad);
+    check_camera_behind(p, vw, trem == 0 && tid == 0);   // once per view
+    const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
+    const int64_t HW = vw.HW;
+    const float* __restrict__ rdv = vw.rays;
+    const u8_t* __restrict__ vol = static_cast<const u8_t*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+
+    // ---- this thread's pixel (out-of-image lanes shadow the last row / column) --------------------------------------------------------------------
+    const int px = txi * kUW + (tid % kUW), py = tyi * kUH + (tid / kUW);
+    const bool active = px < W && py < H;
+    const int64_t pix = static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
+    const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
+    const float dot = ray_dot(vw, rx, ry, rz);
+    const float rcp_rz = 1.0f / rz;   // correctly rounded; hoisted out of the plane loop (div_by_recip)
+    Accum A;
+    const int cx0 = txi * kUW, cx1 = min(cx0 + kUW - 1, W - 1);
+    const int cy0 = tyi * kUH, cy1 = min(cy0 + kUH - 1, H - 1);
+
+    // ---- loader role: item column lcol of box row lrow; byte offset from the box origin (one byte per texel and channel) ---------------------------
+    const int lrow = tid / kUCols, lcol = tid - lrow * kUCols;
+    const uint32_t l_off = static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kUTPI * lcol;
+    const int chan_bytes = __builtin_amdgcn_readfirstlane(static_cast<int>(p.s_chan));
+
+    for (int kc = 0; kc < D; kc += kUChunk) {
+        const int kn = min(kUChunk, D - kc);
+        __syncthreads();   // the previous chunk's table and buffers are no longer read
+        for (int t = tid; t < kn; t += kUThreads) {
+            const int k = kc + t;
+            const float zdiff = vw.dhw[3 * k] - vw.ez, ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
+            float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
+            bool finite = true;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * W + ((c & 1) ? cx1 : cx0);
+                float ix, iy, s, u, v;
+                plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], vw.cx, vw.cy, ix, iy, s, u, v);
+                finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);   // false for NaN too
+                mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
+            }
+            int4 bb = make_int4(0, 0, 0, 0);
+            if (finite) {
+                const int bx0 = static_cast<int>(floorf(mnx - kUBoxEps)), bx1 = static_cast<int>(floorf(mxx + kUBoxEps)) + 1;   // first and last texel column
+                const int by0 = static_cast<int>(floorf(mny - kUBoxEps)), by1 = static_cast<int>(floorf(mxy + kUBoxEps)) + 1;
+                bb.x = bx0 & ~(kUTPI - 1), bb.y = by0;
+                bb.z = (bx1 - bb.x) / kUTPI + 1, bb.w = by1 - by0 + 1;
+                if (bb.z > kUCols || bb.w > kURows) bb = make_int4(0, 0, 0, 0);
+            }
+            box[t] = bb;
+            const float hw = pw * 0.5f, hh = ph * 0.5f;   // exact halves: (2x) / w == x / (w / 2)
+            const uint64_t o = reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + bb.x);
+            org[t] = make_int4(static_cast<int>(o & 0xffffffffu), static_cast<int>((o >> 32) & 0xffffu), __float_as_int(1.0f / hh), 0);
+            geo[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
+        }
+        __syncthreads();   // table published
+
+        // the four loads of plane t of the chunk; past the end of the chunk, or for a box that is not staged, every offset is rejected.  Issued
+        // unconditionally: with the same memory operations on every path the loads stay in flight across the compositing of the plane before.
+        auto issue_loads = [&](int t, uint32_t (&L)[4]) {
+            const int4 bb = box[min(t, kn - 1)];
+            const int4 oo = org[min(t, kn - 1)];
+            const int qx0 = __builtin_amdgcn_readfirstlane(bb.x), by0 = __builtin_amdgcn_readfirstlane(bb.y);
+            const int nq = t < kn ? __builtin_amdgcn_readfirstlane(bb.z) : 0, nrows = __builtin_amdgcn_readfirstlane(bb.w);
+            // the descriptor must be provably wave-uniform, or every buffer load is wrapped in a waterfall loop
+            const uint32_t b_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(oo.x));
+            const uint32_t b_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(oo.y));
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((static_cast<uint64_t>(b_hi) << 32) | b_lo), 0,
+                                                                                  static_cast<int>(0x80000000u), 0x00020000);
+            const int gx = qx0 + kUTPI * lcol, gy = by0 + lrow;   // (Wt is a multiple of 4: an item lies inside the texture row or outside it)
+            // (bitwise on purpose: `&&` would be lowered to exec-mask control flow)
+            const bool ok = (lcol < nq) & (lrow < nrows) & (gx >= 0) & (gx < Wt) & (gy >= 0) & (gy < Ht);
+            const uint32_t off = ok ? l_off : 0x80000000u;   // == num_records: rejected, reads as zero
+            L[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
+            L[1] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, chan_bytes, 0);
+            L[2] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 2 * chan_bytes, 0);
+            L[3] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 3 * chan_bytes, 0);
+        };
+        // registers -> LDS: (r0 r1 r2 r3), (g0 ..), (b0 ..), (a0 ..) -> four texels (r g b a); lanes outside the box stay idle
+        auto store_box = [&](int t, uint32_t* buf, const uint32_t (&L)[4]) {
+            const int4 bb = box[t];
+            const int nq = __builtin_amdgcn_readfirstlane(bb.z), nrows = __builtin_amdgcn_readfirstlane(bb.w);
+            const uint32_t rg_lo = __builtin_amdgcn_perm(L[1], L[0], 0x05010400u);   // g1 r1 g0 r0
+            const uint32_t rg_hi = __builtin_amdgcn_perm(L[1], L[0], 0x07030602u);   // g3 r3 g2 r2
+            const uint32_t ba_lo = __builtin_amdgcn_perm(L[3], L[2], 0x05010400u);   // a1 b1 a0 b0
+            const uint32_t ba_hi = __builtin_amdgcn_perm(L[3], L[2], 0x07030602u);
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            u32x4 o;
+            o.x = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x05040100u);   // texel x:     a0 b0 g0 r0
+            o.y = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x07060302u);   // texel x + 1
+            o.z = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x05040100u);
+            o.w = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x07060302u);
+            if ((lcol < nq) & (lrow < nrows)) *reinterpret_cast<u32x4*>(buf + lrow * kUPitch + kUTPI * lcol) = o;
+        };
+        auto composite = [&](int t, const uint32_t* __restrict__ buf) {
+            const int k = kc + t;
+            const int4 bb = box[t];
+            const int qx0 = __builtin_amdgcn_readfirstlane(bb.x), by0 = __builtin_amdgcn_readfirstlane(bb.y);
+            const int nq = __builtin_amdgcn_readfirstlane(bb.z), nrows = __builtin_amdgcn_readfirstlane(bb.w);
+            const float4 g = geo[t];
+            if (nq == 0) {   // uniform: the box does not fit -- everybody takes the direct gather (exact doublings of the table's halves)
+                gather_plane<u8_t, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
+                return;
+            }
+            float ix, iy, s;
+            if (STRICT) {
+                float u, v;
+                plane_coord<AC>(g.x, g.z + g.z, g.y + g.y, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
+            } else {   // the same quotients through hoisted reciprocals (div_by_recip: correctly rounded, so ix, iy, s are the same bits)
+                plane_coord_recip<AC>(g.x, g.y, g.z, g.w, __int_as_float(org[t].z), vw.ex, vw.ey, rx, ry, rz, rcp_rz, vw.cx, vw.cy, ix, iy, s);
+            }
+            // gather_sample's footprint: weights of taps outside the texture are zero (the box holds zeros there anyway: same products, same bits)
+            Footprint f = footprint(ix, iy, Ht, Wt);
+            const bool x0in = f.x0 >= 0 && f.x0 <= Wt - 1, x1in = f.x0 >= -1 && f.x0 <= Wt - 2;
+            const bool y0in = f.y0 >= 0 && f.y0 <= Ht - 1, y1in = f.y0 >= -1 && f.y0 <= Ht - 2;
+            if (!(x0in && y0in)) f.nw = 0.0f;
+            if (!(x1in && y0in)) f.ne = 0.0f;
+            if (!(x0in && y1in)) f.sw = 0.0f;
+            if (!(x1in && y1in)) f.se = 0.0f;
+            const int lx = f.x0 - qx0, ly = f.y0 - by0;
+            const bool inb = (lx >= 0) & (ly >= 0) & (lx + 1 < kUTPI * nq) & (ly + 1 < nrows);
+            const bool any_w = (f.nw != 0.0f) | (f.ne != 0.0f) | (f.sw != 0.0f) | (f.se != 0.0f);
+            if (__builtin_expect((!inb) & any_w, 0)) {   // per lane: a pixel whose taps the box does not hold (no pinhole ray field)
+                gather_plane<u8_t, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
+                return;
+            }
+            // a footprint outside the box with every weight zero (the sentinel corner of NaN / far-off coordinates) reads texel (0, 0) of the box
+            const uint32_t idx = inb ? static_cast<uint32_t>(ly * kUPitch + lx) : 0u;
+            const uint32_t t_nw = buf[idx], t_ne = buf[idx + 1], t_sw = buf[idx + kUPitch], t_se = buf[idx + kUPitch + 1];   // two ds_read2_b32
+            float smp[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float c_nw = static_cast<float>((t_nw >> (8 * c)) & 0xffu), c_ne = static_cast<float>((t_ne >> (8 * c)) & 0xffu);
+                const float c_sw = static_cast<float>((t_sw >> (8 * c)) & 0xffu), c_se = static_cast<float>((t_se >> (8 * c)) & 0xffu);
+                if (STRICT) smp[c] = bilerp<true>(unorm8_to_f32(c_nw), unorm8_to_f32(c_ne), unorm8_to_f32(c_sw), unorm8_to_f32(c_se), f);
+                else smp[c] = bilerp<false>(c_nw, c_ne, c_sw, c_se, f) * kInv255;
+            }
+            blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
+        };
+
+        uint32_t L[4];
+        issue_loads(0, L);
+        for (int t = 0; t < kn; ++t) {
+            uint32_t* buf = stage[t & 1];
+            store_box(t, buf, L);
+            __syncthreads();          // box t visible; everybody is done reading box t - 1 (the other buffer)
+            issue_loads(t + 1, L);    // in flight while plane t is composited
+            composite(t, buf);
+        }
+    }
+    const LastPlane lp = last_plane(p, vw);
+    if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    report_status(p.status, bad);
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------------------
+// The analogue of volume_stages_in_items for one-byte texels and 4-texel items: an item of a box that touches the border does not straddle it
+// (Wt % 4), every item is a naturally aligned dword (base pointer and strides in BYTES), and the in-box byte offsets are kept in 32 bits.
+bool u8_variant_supports(const KParams& p) {
+    if (p.Wt % kUTPI != 0 || reinterpret_cast<uintptr_t>(p.rgba) % kUTPI != 0) return false;
+    if (p.s_row % kUTPI != 0 || p.s_chan % kUTPI != 0 || p.s_plane % kUTPI != 0 || p.s_mpi % kUTPI != 0) return false;
+    return 3 * p.s_chan + (kURows + 1) * p.s_row + 128 < (int64_t(1) << 31);
+}
+
+int u8_variant_query(int what) {
+    switch (what) {
+        case 16: return kUW;
+        case 17: return kUPitch;
+        case 18: return kURows;
+        default: return -1;
+    }
+}
+
+hipError_t launch_u8(const KParams& p, hipStream_t stream) {
+    const int tiles_x = (p.W + kUW - 1) / kUW, tiles_y = (p.H + kUH - 1) / kUH;
+    const int n_tiles = tiles_x * tiles_y * p.N;
+    const dim3 grid(xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)), block(kUThreads);
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+    });
+    return hipGetLastError();
+}
+
+}  // namespace gmpi

@@ -26,7 +26,16 @@ from torch import nn
 
 from . import _lib
 
-_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16, torch.uint8: _lib.DTYPE_U8}
+
+
+def _refuse_uint8(what: str, *tensors) -> None:
+    """uint8 storage (code c = c / 255, quantized.py) is read by the forward render of an RGBA volume alone.  Everything else refuses it here,
+    before any launch, instead of casting the codes 0..255 to values."""
+    for t in tensors:
+        if t is not None and t.dtype is torch.uint8:
+            raise TypeError(f"{what} does not take uint8 storage: pass dequantize_volume(q) (ml_gmpi_amd.quantized), or render the RGBA volume "
+                            "with MPI.render_views / MPIRenderer.render, which read the 8-bit codes as they are")
 
 
 # Per-(device, stream) state of this module -- the scratch lent to the C ABI, the status words -- lives in small LRU caches (a program that
@@ -551,7 +560,8 @@ class MPI(nn.Module):
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
         camera axis lies more than 0.35 rad off the normal (GMPI_FLAG_HINT_OBLIQUE: views that share an MPI then go to the tile kernel at once).
 
-        rgba [M,D,4,Ht,Wt] (f32/bf16/f16, any outer strides, innermost contiguous), dhw [M,D,3],
+        rgba [M,D,4,Ht,Wt] (f32/bf16/f16, or uint8 codes c that stand for c / 255 -- quantized.py; any outer strides, innermost contiguous;
+        a uint8 volume is read as it is: no cast, no copy, no gradient, no exhaustive range pass -- every code is in [0, 1]), dhw [M,D,3],
         ray_dir [N,3,H,W], eye_pos [N,3], z_dir [N,3].  View n samples MPI `view_to_mpi[n]`; without it,
         `views_per_mpi` (an int or one count per MPI) gives the reference's grouping.
         Returns dict(color, depth[, T], status).  With `defer_status=True` the status word is not read back
@@ -562,7 +572,13 @@ class MPI(nn.Module):
         if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
+        if _shared is not None:
+            _refuse_uint8("the shared-colour render", rgba, *_shared)
         if torch.is_grad_enabled() and not _in_autograd_fn:
+            if rgba.dtype is torch.uint8 and self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
+                raise NotImplementedError("no gradient flows through a uint8 volume, w.r.t. the plane geometry and the camera tensors included "
+                                          "(geometry_grad=True): render dequantize_volume(q) (ml_gmpi_amd.quantized) for that, or detach the "
+                                          "camera and dhw tensors")
             bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _shared)
             if bridge is not None:
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
@@ -625,7 +641,7 @@ class MPI(nn.Module):
             # range_check="full": the exhaustive pass, over the volume unless it is the one that passed last, over the three shared-colour
             # tensors in every call (never cached: three identities to track)
             checked = ()
-            if self.range_check == "full":
+            if self.range_check == "full" and rgba.dtype is not torch.uint8:   # (8-bit codes are in [0, 1] by construction: nothing to pass over)
                 checked = (rgba, sh_rgb, sh_bg) if _shared is not None else (rgba,) if self._full_check_needed(rgba_in) else ()
             for t in checked:
                 if t is not None:

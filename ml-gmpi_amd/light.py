@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, poses
-from .hip_mpi import _DTYPES, _call, _ptr
+from .hip_mpi import _DTYPES, _call, _ptr, _refuse_uint8
 
 EPS = 1e-8  # light_renderer.py:8
 
@@ -28,6 +28,7 @@ def compute_depth(mpi_alpha: torch.Tensor, plane_ds: torch.Tensor, want_transmit
 
     Differentiable w.r.t. mpi_alpha (as the reference's plain-torch `LightRenderer.compute_depth`, light_renderer.py:82-100), through both
     outputs: the backward is gmpi_alpha_depth_backward_ex_launch.  plane_ds gets no gradient."""
+    _refuse_uint8("compute_depth", mpi_alpha)
     if not mpi_alpha.is_cuda:
         raise _lib.GmpiError("compute_depth needs tensors on a ROCm device (no CPU path)")
     assert mpi_alpha.ndim == 5 and mpi_alpha.shape[2] == 1, f"{mpi_alpha.shape}"
@@ -251,6 +252,7 @@ class LightRenderer:
         * shading, 0, 1) or None), colours in float32.  Equal to `render(expand_shared_color(rgb, alpha, background))` split again; the step
         counter, cur_ka / cur_kd and the torch RNG advance as in `render`.  The depth comes from the differentiable `compute_depth` kernel (one
         pass over the alpha planes), the rest is image-sized torch: differentiable w.r.t. rgb, alpha and background."""
+        _refuse_uint8("LightRenderer.render_shared", rgb, alpha, background)
         if not alpha.is_cuda:
             raise _lib.GmpiError("LightRenderer.render_shared needs tensors on a ROCm device (no CPU path)")
         from .shared_color import _check
@@ -285,6 +287,7 @@ class LightRenderer:
     def render(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
         """batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3] -> shaded MPI [B,D,4,H,W] float32
         (differentiable w.r.t. batch_mpi)."""
+        _refuse_uint8("LightRenderer.render", batch_mpi)
         if not batch_mpi.is_cuda:
             raise _lib.GmpiError("LightRenderer.render needs tensors on a ROCm device (no CPU path)")
         dev = batch_mpi.device
