@@ -141,7 +141,11 @@ typedef struct GmpiRenderParams {
     int32_t views_per_mpi;   /* used when view_to_mpi == NULL (>=1)                    */
 
     const void *rgba;        /* [M, D, 4, Ht, Wt] planar RGBA in [0,1]                 */
-    int64_t rgba_stride[5];  /* element strides; [4] must be 1; 0 allowed on [0] (expand) */
+    int64_t rgba_stride[5];  /* element strides; [4] must be 1; 0 allowed on [0] (expand).  One exception, for GMPI_DTYPE_U8 at the forward launch and
+                                its workspace query: the channels-last ("interleaved") layout of 8-bit images, [M, D, Ht, Wt, 4] in memory seen as
+                                [M, D, 4, Ht, Wt]: [2] == 1 and [4] == 4 with [3] >= 4 Wt (one RGBA texel = 4 consecutive bytes; the strides count
+                                bytes; [0] and [1] as ever).  [4] == 4 with any other dtype or channel stride, and any other texel stride, is
+                                GMPI_E_STRIDE.                                                                                                   */
     const int32_t *view_to_mpi; /* [N] or NULL                                          */
     const float *dhw;        /* [M, D, 3] (distance, height, width), contiguous         */
     const float *ray_dir;    /* [N, 3, H, W] unit ray directions, contiguous.  The LDS-staged variants (LDS, WAVE, BAND and therefore AUTO)
@@ -179,7 +183,11 @@ uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams *params);
  * row, channel, plane and MPI strides must be multiples of 4 bytes, else GMPI_E_VARIANT).  WAVE and BAND are GMPI_E_VARIANT; AUTO is LDS where
  * it can take the tensors, else GATHER, whatever the camera hints say.  No workspace.  GMPI_FLAG_CHECK_RANGE is accepted and never sets a bit.
  * With GMPI_FLAG_STRICT_ORDER both are bit-identical to the render of the fp32 volume c / 255; without it the LDS kernel interpolates the codes
- * and scales the sample by RN(1/255) once per channel (about 2e-7 from the strict result). */
+ * and scales the sample by RN(1/255) once per channel (about 2e-7 from the strict result).
+ * An interleaved GMPI_DTYPE_U8 volume (rgba_stride above) is read in place by the same two kernels, in instances of their own: GATHER loads one texel
+ * (4 bytes, any alignment) per tap and takes any Wt; LDS loads 4 texels (16 bytes) at a time and wants Wt a multiple of 4 and the base pointer and the
+ * row, plane and MPI strides multiples of 4 bytes, else GMPI_E_VARIANT; AUTO, WAVE, BAND, workspace and flags as for the planar layout.  Same codes, same
+ * result: both kernels give the planar volume's bits, in both modes (gmpi_query(20) says whether the layout is built in). */
 int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
 
 /*
@@ -426,7 +434,7 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * is 512 / width pixels high), 13 the texels per row and 14 the rows its staging buffer holds per plane (a box's first column is rounded down to
  * a multiple of 4 texels before it is held against 13); 15 is unused (-1); the staged kernel for GMPI_DTYPE_U8 volumes: 16 its pixel-tile width (a tile
  * is 512 / width pixels high), 17 the texels per row and 18 the rows its staging buffer holds per plane (first column rounded down to a multiple of 4
- * texels, as for 13).  Unknown -> -1.                                        */
+ * texels, as for 13); 19 is unused (-1); 20 whether the interleaved GMPI_DTYPE_U8 layout (GmpiRenderParams.rgba_stride) is built in.  Unknown -> -1.                                        */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

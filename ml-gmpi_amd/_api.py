@@ -6,12 +6,12 @@ from .driver import ViewBatchDriver, shard_views, render_views_sharded, frames_t
 from .install import install, uninstall
 from .light import LightRenderer, compute_depth
 from .shared_color import expand_shared_color, split_shared_color
-from .quantized import quantize_volume, dequantize_volume
+from .quantized import quantize_volume, dequantize_volume, layers_as_volume, volume_as_layers
 
 __all__ = [
     "GmpiError", "build_extension", "library_path", "load_library",
     "MPI", "HipMPI", "flush_status", "MPIRenderer", "PRESETS", "make_renderer", "rays_from_c2w",
     "ViewBatchDriver", "shard_views", "render_views_sharded", "frames_to_uint8", "dump_frames",
     "install", "uninstall", "compute_depth", "LightRenderer", "expand_shared_color", "split_shared_color",
-    "quantize_volume", "dequantize_volume",
+    "quantize_volume", "dequantize_volume", "layers_as_volume", "volume_as_layers",
 ]

@@ -56,7 +56,7 @@ _ERRORS = {
     -1: "GMPI_E_NULL (required pointer is NULL)",
     -2: "GMPI_E_SHAPE (non-positive or inconsistent extent, or more than 65535 views for the gather kernel / the backward)",
     -3: "GMPI_E_DTYPE (unknown rgba dtype, or uint8 storage handed to an entry other than the forward render)",
-    -4: "GMPI_E_STRIDE (innermost rgba stride must be 1, strides non-negative)",
+    -4: "GMPI_E_STRIDE (innermost rgba stride must be 1 -- or 4 with channel stride 1 for interleaved uint8 texels in the forward render --, strides non-negative)",
     -5: "GMPI_E_ABI (GmpiRenderParams size mismatch between binding and library)",
     -6: "GMPI_E_VARIANT (requested kernel variant cannot run this shape)",
     -7: "GMPI_E_FLAGS (undefined bit in GmpiRenderParams.flags)",

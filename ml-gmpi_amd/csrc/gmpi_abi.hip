@@ -250,6 +250,7 @@ __global__ __launch_bounds__(256) void selftest_division_kernel(uint64_t pairs, 
 static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, bool need_volume = false, bool takes_u8 = false) {
     if (q == nullptr) return GMPI_E_NULL;
     if (q->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    bool interleaved = false;
     if (q->flags & ~static_cast<uint32_t>(GMPI_FLAG_ALL)) return GMPI_E_FLAGS;  // undefined bits never reach a kernel
     if (q->N < 0 || q->M <= 0 || q->D <= 0 || q->Ht <= 0 || q->Wt <= 0 || q->H <= 0 || q->W <= 0) return GMPI_E_SHAPE;
     if (q->view_to_mpi == nullptr) {
@@ -261,10 +262,12 @@ static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, 
     if (need_outputs || need_volume) {
         if (q->rgba == nullptr || q->z_dir == nullptr) return GMPI_E_NULL;
         if (q->rgba_dtype < GMPI_DTYPE_F32 || q->rgba_dtype > (takes_u8 ? GMPI_DTYPE_U8 : GMPI_DTYPE_F16)) return GMPI_E_DTYPE;
-        if (q->rgba_stride[4] != 1) return GMPI_E_STRIDE;
+        // channels-last codes: texel stride 4 with channel stride 1, for GMPI_DTYPE_U8 at the entries that take the type -- and nothing else with [4] != 1
+        interleaved = takes_u8 && q->rgba_dtype == GMPI_DTYPE_U8 && q->rgba_stride[4] == 4 && q->rgba_stride[2] == 1;
+        if (q->rgba_stride[4] != 1 && !interleaved) return GMPI_E_STRIDE;
         for (int i = 0; i < 4; ++i)
             if (q->rgba_stride[i] < 0) return GMPI_E_STRIDE;
-        if (q->rgba_stride[3] < q->Wt || q->rgba_stride[2] == 0 || q->rgba_stride[1] == 0) return GMPI_E_STRIDE;
+        if (q->rgba_stride[3] < (interleaved ? 4 : 1) * static_cast<int64_t>(q->Wt) || q->rgba_stride[2] == 0 || q->rgba_stride[1] == 0) return GMPI_E_STRIDE;
     }
     p.rgba = q->rgba;
     p.view_to_mpi = q->view_to_mpi;
@@ -278,7 +281,7 @@ static int to_kparams(const GmpiRenderParams* q, KParams& p, bool need_outputs, 
     p.status = q->status;
     p.s_mpi = q->rgba_stride[0];
     p.s_plane = q->rgba_stride[1];
-    p.s_chan = q->rgba_stride[2];
+    p.s_chan = interleaved ? 0 : q->rgba_stride[2];   // (0: u8_interleaved, gmpi_device.hpp -- the other strides then count bytes)
     p.s_row = q->rgba_stride[3];
     p.N = q->N, p.M = q->M, p.D = q->D, p.Ht = q->Ht, p.Wt = q->Wt, p.H = q->H, p.W = q->W;
     p.views_per_mpi = q->view_to_mpi ? 1 : q->views_per_mpi;
@@ -703,7 +706,7 @@ int gmpi_query(int32_t what) {
         case 10: return static_cast<int>(kAutoBandMinF32);
         case 11: return 1;  // the atomics-free backward (pixel pass + texel gather) is built in
         case 12: case 13: case 14: return shared_forward_query(what);
-        case 16: case 17: case 18: return u8_variant_query(what);  // (15: unused)
+        case 16: case 17: case 18: case 20: return u8_variant_query(what);  // (15, 19: unused)
         default: return -1;
     }
 }

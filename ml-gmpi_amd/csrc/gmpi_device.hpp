@@ -35,7 +35,7 @@ struct KParams {
     float* depth_out;
     float* T_out;
     uint32_t* status;
-    int64_t s_mpi, s_plane, s_chan, s_row;  // element strides of rgba [M,D,4,Ht,Wt] (col stride 1)
+    int64_t s_mpi, s_plane, s_chan, s_row;  // element strides of rgba [M,D,4,Ht,Wt] (col stride 1; rgba8_t instances: bytes, texel stride 4, s_chan unused)
     int32_t N, M, D, Ht, Wt, H, W, views_per_mpi;
     uint32_t flags;
     void* ws;           // caller's workspace (GmpiRenderParams.workspace): the band kernel's geometry table
@@ -120,6 +120,22 @@ __device__ __forceinline__ float unorm8_to_f32(float c) {  // c: the code as a f
     return __builtin_fmaf(e, kInv255, q);
 }
 __device__ __forceinline__ float to_f32(u8_t v) { return unorm8_to_f32(static_cast<float>(v.code)); }
+// The same codes, channels-last (GMPI_DTYPE_U8 with rgba_stride[2] == 1 and rgba_stride[4] == 4): one texel = the four bytes R, G, B, A.  A storage type of
+// its own, so that no other instance carries a texel stride.  The strides of such a volume count BYTES (tex_offset); alignment 1: a base pointer may
+// sit at any byte.
+struct rgba8_t { uint8_t c[4]; };
+template <typename TexT>
+__device__ __forceinline__ const TexT* tex_offset(const TexT* p, int64_t n) { return p + n; }
+__device__ __forceinline__ const rgba8_t* tex_offset(const rgba8_t* p, int64_t n) {
+    return reinterpret_cast<const rgba8_t*>(reinterpret_cast<const uint8_t*>(p) + n);
+}
+// One texel as the dword R | G << 8 | B << 16 | A << 24: a single 4-byte load at byte alignment (the memcpy says so).
+__device__ __forceinline__ uint32_t load_texel(const rgba8_t* p, int64_t byte_off) {
+    uint32_t t;
+    __builtin_memcpy(&t, reinterpret_cast<const uint8_t*>(p) + byte_off, 4);
+    return t;
+}
+__device__ __forceinline__ float texel_code(uint32_t t, int c) { return static_cast<float>((t >> (8 * c)) & 0xffu); }   // v_cvt_f32_ubyte<c>: exact
 
 // Host side: a run-time dtype (GMPI_DTYPE_F32 / _BF16 / _F16 = 0 / 1 / 2, validated by the C ABI) or flag picks the template instance.
 // f is a generic lambda: it gets TypeTag<float | bf16_t | f16_t>{} (storage type: `typename decltype(t)::type`), resp. std::true_type{} /
@@ -149,6 +165,9 @@ template <typename F>
 inline auto dispatch_ac_strict(uint32_t flags, F&& f) {
     return dispatch_bool(flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) { return dispatch_bool(flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) { return f(AC, STRICT); }); });
 }
+// Host side: a GMPI_DTYPE_U8 volume is channels-last (the rgba8_t instances).  to_kparams (gmpi_abi.hip) says so through s_chan = 0, which no planar
+// volume has (its channel stride is validated to be non-zero); s_mpi, s_plane and s_row then count bytes.
+inline __host__ bool u8_interleaved(const KParams& p) { return p.s_chan == 0; }
 // Host side: the volume can be staged in 16-byte loader items -- items of a box that touches the border do not straddle it, and every item is aligned.
 inline __host__ bool volume_stages_in_items(const KParams& p, int dtype) {
     const int tpi = 16 / (dtype == GMPI_DTYPE_F32 ? 4 : 2);  // texels per item
@@ -344,15 +363,24 @@ __device__ __forceinline__ void gather_sample(const TexT* __restrict__ pl, int64
     const int xa = min(max(f.x0, 0), Wt - 1), xb = min(max(f.x0 + 1, 0), Wt - 1);
     const int ya = min(max(f.y0, 0), Ht - 1), yb = min(max(f.y0 + 1, 0), Ht - 1);
     const int64_t oa = static_cast<int64_t>(ya) * s_row, ob = static_cast<int64_t>(yb) * s_row;
+    if constexpr (std::is_same_v<TexT, rgba8_t>) {   // one load per tap; every code is in [0, 1]: nothing for check_range to test
+        const uint32_t t_nw = load_texel(pl, oa + 4 * xa), t_ne = load_texel(pl, oa + 4 * xb);
+        const uint32_t t_sw = load_texel(pl, ob + 4 * xa), t_se = load_texel(pl, ob + 4 * xb);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const TexT* __restrict__ ch = pl + c * s_chan;
-        const float t_nw = to_f32(ch[oa + xa]);
-        const float t_ne = to_f32(ch[oa + xb]);
-        const float t_sw = to_f32(ch[ob + xa]);
-        const float t_se = to_f32(ch[ob + xb]);
-        if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= GMPI_STATUS_RGBA_RANGE;
-        smp[c] = bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, f);
+        for (int c = 0; c < 4; ++c)   // to_f32(u8_t) per tap, as the planar instance: the same bits
+            smp[c] = bilerp<STRICT>(unorm8_to_f32(texel_code(t_nw, c)), unorm8_to_f32(texel_code(t_ne, c)), unorm8_to_f32(texel_code(t_sw, c)),
+                                    unorm8_to_f32(texel_code(t_se, c)), f);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const TexT* __restrict__ ch = pl + c * s_chan;
+            const float t_nw = to_f32(ch[oa + xa]);
+            const float t_ne = to_f32(ch[oa + xb]);
+            const float t_sw = to_f32(ch[ob + xa]);
+            const float t_se = to_f32(ch[ob + xb]);
+            if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) bad |= GMPI_STATUS_RGBA_RANGE;
+            smp[c] = bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, f);
+        }
     }
 }
 
@@ -430,7 +458,7 @@ __device__ __forceinline__ void gather_plane(const KParams& p, const View& vw, c
                                              float rx, float ry, float rz, float dot, CheckT check_range, uint32_t& bad, Accum& A) {
     float ix, iy, s, u, v, smp[4];
     plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
-    gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
+    gather_sample<TexT, STRICT>(tex_offset(vol, static_cast<int64_t>(k) * p.s_plane), p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
     blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
 }
 

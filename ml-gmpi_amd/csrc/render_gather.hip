@@ -29,7 +29,7 @@ __global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kern
     const float rx = vw.rays[pix], ry = vw.rays[HW + pix], rz = vw.rays[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
     const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
 
     Accum A;
 #pragma unroll 2
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kern
         float ix, iy, s, u, v;
         plane_coord<AC>(d - vw.ez, ph, pw, vw.ex, vw.ey, rx, ry, rz, vw.cx, vw.cy, ix, iy, s, u, v);
         float smp[4];
-        gather_sample<TexT, STRICT>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
+        gather_sample<TexT, STRICT>(tex_offset(vol, static_cast<int64_t>(k) * p.s_plane), p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, check_range, bad, smp);
         blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
     }
     const LastPlane lp = last_plane(p, vw);
@@ -58,6 +58,7 @@ static hipError_t launch_gather_t(const KParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) {
+    if (dtype == GMPI_DTYPE_U8 && u8_interleaved(p)) return launch_gather_t<rgba8_t>(p, stream);  // (channels-last codes: one texel load per tap)
     if (dtype == GMPI_DTYPE_U8) return launch_gather_t<u8_t>(p, stream);  // (8-bit codes: to_f32 is the division by 255; only the forward takes them)
     return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, stream); });
 }

@@ -43,9 +43,12 @@ static_assert(kURows * kUCols == kUThreads, "one loader item per thread");
 static_assert(kUPitch % 32 == 0, "row pitch: a multiple of the 32 banks of ds_read2_b32");
 static_assert(2 * kUBufWords * 4 + kUChunk * 48 <= 40 * 1024, "4 workgroups per CU");
 
-// (strict-order instances: 6 waves per SIMD -- at 8 the 16 per-tap conversions push one of them 12 bytes into scratch)
-template <bool AC, bool STRICT>
-__global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
+// TexT = u8_t: the planar volume above.  TexT = rgba8_t: a channels-last volume (texel stride 4 bytes, gmpi_device.hpp), whose memory image IS the LDS
+// image: one loader item = 4 texels = one 16-byte buffer load and one 16-byte LDS store, no v_perm; strides and offsets count bytes, a box row is one
+// run of 16 bytes per item.  The item's dword alignment is what u8_variant_supports asks for.  Everything behind the LDS image is the same code:
+// the kernel body is this one function, the two kernels below are its instances (the planar one keeps its name and its template arguments).
+template <typename TexT, bool AC, bool STRICT>
+__device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles) {
     // Per plane of the chunk, written once by one thread so that the 8 waves do not repeat the address arithmetic on their scalar units:
     //   box:  qx0 (a multiple of 4), by0, items per row (0: not staged), rows
     //   org:  byte address of the box origin (texel row by0, column qx0 of channel 0) = words 0, 1 of the plane's buffer descriptor, RN(1 / hh).
@@ -71,7 +74,9 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
     const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
     const int64_t HW = vw.HW;
     const float* __restrict__ rdv = vw.rays;
-    const u8_t* __restrict__ vol = static_cast<const u8_t*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    constexpr bool kPacked = std::is_same_v<TexT, rgba8_t>;
+    constexpr int kTexelBytes = kPacked ? 4 : 1;   // bytes from one texel of a row to the next
+    const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
 
     // ---- this thread's pixel (out-of-image lanes shadow the last row / column) --------------------------------------------------------------------
     const int px = txi * kUW + (tid % kUW), py = tyi * kUH + (tid / kUW);
@@ -86,8 +91,8 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
 
     // ---- loader role: item column lcol of box row lrow; byte offset from the box origin (one byte per texel and channel) ---------------------------
     const int lrow = tid / kUCols, lcol = tid - lrow * kUCols;
-    const uint32_t l_off = static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kUTPI * lcol;
-    const int chan_bytes = __builtin_amdgcn_readfirstlane(static_cast<int>(p.s_chan));
+    const uint32_t l_off = static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kTexelBytes * kUTPI * lcol;
+    const int chan_bytes = __builtin_amdgcn_readfirstlane(static_cast<int>(p.s_chan));   // (planar only)
 
     for (int kc = 0; kc < D; kc += kUChunk) {
         const int kn = min(kUChunk, D - kc);
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
             }
             box[t] = bb;
             const float hw = pw * 0.5f, hh = ph * 0.5f;   // exact halves: (2x) / w == x / (w / 2)
-            const uint64_t o = reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + bb.x);
+            const uint64_t o = reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + kTexelBytes * bb.x);
             org[t] = make_int4(static_cast<int>(o & 0xffffffffu), static_cast<int>((o >> 32) & 0xffffu), __float_as_int(1.0f / hh), 0);
             geo[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
         }
@@ -137,25 +142,35 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
             // (bitwise on purpose: `&&` would be lowered to exec-mask control flow)
             const bool ok = (lcol < nq) & (lrow < nrows) & (gx >= 0) & (gx < Wt) & (gy >= 0) & (gy < Ht);
             const uint32_t off = ok ? l_off : 0x80000000u;   // == num_records: rejected, reads as zero
-            L[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
-            L[1] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, chan_bytes, 0);
-            L[2] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 2 * chan_bytes, 0);
-            L[3] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 3 * chan_bytes, 0);
+            if constexpr (kPacked) {   // four texels as they lie in memory
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+                L[0] = q.x, L[1] = q.y, L[2] = q.z, L[3] = q.w;
+            } else {
+                L[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
+                L[1] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, chan_bytes, 0);
+                L[2] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 2 * chan_bytes, 0);
+                L[3] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 3 * chan_bytes, 0);
+            }
         };
         // registers -> LDS: (r0 r1 r2 r3), (g0 ..), (b0 ..), (a0 ..) -> four texels (r g b a); lanes outside the box stay idle
         auto store_box = [&](int t, uint32_t* buf, const uint32_t (&L)[4]) {
             const int4 bb = box[t];
             const int nq = __builtin_amdgcn_readfirstlane(bb.z), nrows = __builtin_amdgcn_readfirstlane(bb.w);
-            const uint32_t rg_lo = __builtin_amdgcn_perm(L[1], L[0], 0x05010400u);   // g1 r1 g0 r0
-            const uint32_t rg_hi = __builtin_amdgcn_perm(L[1], L[0], 0x07030602u);   // g3 r3 g2 r2
-            const uint32_t ba_lo = __builtin_amdgcn_perm(L[3], L[2], 0x05010400u);   // a1 b1 a0 b0
-            const uint32_t ba_hi = __builtin_amdgcn_perm(L[3], L[2], 0x07030602u);
             typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             u32x4 o;
-            o.x = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x05040100u);   // texel x:     a0 b0 g0 r0
-            o.y = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x07060302u);   // texel x + 1
-            o.z = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x05040100u);
-            o.w = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x07060302u);
+            if constexpr (kPacked) {
+                o.x = L[0], o.y = L[1], o.z = L[2], o.w = L[3];
+            } else {
+                const uint32_t rg_lo = __builtin_amdgcn_perm(L[1], L[0], 0x05010400u);   // g1 r1 g0 r0
+                const uint32_t rg_hi = __builtin_amdgcn_perm(L[1], L[0], 0x07030602u);   // g3 r3 g2 r2
+                const uint32_t ba_lo = __builtin_amdgcn_perm(L[3], L[2], 0x05010400u);   // a1 b1 a0 b0
+                const uint32_t ba_hi = __builtin_amdgcn_perm(L[3], L[2], 0x07030602u);
+                o.x = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x05040100u);   // texel x:     a0 b0 g0 r0
+                o.y = __builtin_amdgcn_perm(ba_lo, rg_lo, 0x07060302u);   // texel x + 1
+                o.z = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x05040100u);
+                o.w = __builtin_amdgcn_perm(ba_hi, rg_hi, 0x07060302u);
+            }
             if ((lcol < nq) & (lrow < nrows)) *reinterpret_cast<u32x4*>(buf + lrow * kUPitch + kUTPI * lcol) = o;
         };
         auto composite = [&](int t, const uint32_t* __restrict__ buf) {
@@ -165,7 +180,7 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
             const int nq = __builtin_amdgcn_readfirstlane(bb.z), nrows = __builtin_amdgcn_readfirstlane(bb.w);
             const float4 g = geo[t];
             if (nq == 0) {   // uniform: the box does not fit -- everybody takes the direct gather (exact doublings of the table's halves)
-                gather_plane<u8_t, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
+                gather_plane<TexT, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
                 return;
             }
             float ix, iy, s;
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
             const bool inb = (lx >= 0) & (ly >= 0) & (lx + 1 < kUTPI * nq) & (ly + 1 < nrows);
             const bool any_w = (f.nw != 0.0f) | (f.ne != 0.0f) | (f.sw != 0.0f) | (f.se != 0.0f);
             if (__builtin_expect((!inb) & any_w, 0)) {   // per lane: a pixel whose taps the box does not hold (no pinhole ray field)
-                gather_plane<u8_t, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
+                gather_plane<TexT, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
                 return;
             }
             // a footprint outside the box with every weight zero (the sentinel corner of NaN / far-off coordinates) reads texel (0, 0) of the box
@@ -220,10 +235,27 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
     report_status(p.status, bad);
 }
 
+// (strict-order instances: 6 waves per SIMD -- at 8 the 16 per-tap conversions push one of them 12 bytes into scratch)
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<u8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles);
+}
+// (the packed loader holds fewer registers: at 7 waves per SIMD asked for, the strict-order instances take 61 / 63 VGPRs without scratch -- 8 waves;
+//  with 6 asked for the allocator spreads to 73 / 75 -- 6 waves)
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 7 : 8) void render_rgba8_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<rgba8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 // The analogue of volume_stages_in_items for one-byte texels and 4-texel items: an item of a box that touches the border does not straddle it
 // (Wt % 4), every item is a naturally aligned dword (base pointer and strides in BYTES), and the in-box byte offsets are kept in 32 bits.
 bool u8_variant_supports(const KParams& p) {
+    if (u8_interleaved(p)) {   // the same rule in bytes: an item is 4 texels = 16 bytes at dword alignment, a box row at most 64 texels = 256 bytes
+        if (p.Wt % kUTPI != 0 || reinterpret_cast<uintptr_t>(p.rgba) % 4 != 0) return false;
+        if (p.s_row % 4 != 0 || p.s_plane % 4 != 0 || p.s_mpi % 4 != 0) return false;
+        return (kURows + 1) * p.s_row + 4 * kUPitch + 128 < (int64_t(1) << 31);
+    }
     if (p.Wt % kUTPI != 0 || reinterpret_cast<uintptr_t>(p.rgba) % kUTPI != 0) return false;
     if (p.s_row % kUTPI != 0 || p.s_chan % kUTPI != 0 || p.s_plane % kUTPI != 0 || p.s_mpi % kUTPI != 0) return false;
     return 3 * p.s_chan + (kURows + 1) * p.s_row + 128 < (int64_t(1) << 31);
@@ -234,6 +266,7 @@ int u8_variant_query(int what) {
         case 16: return kUW;
         case 17: return kUPitch;
         case 18: return kURows;
+        case 20: return 1;   // the channels-last instances (rgba8_t) are built in
         default: return -1;
     }
 }
@@ -242,8 +275,10 @@ hipError_t launch_u8(const KParams& p, hipStream_t stream) {
     const int tiles_x = (p.W + kUW - 1) / kUW, tiles_y = (p.H + kUH - 1) / kUH;
     const int n_tiles = tiles_x * tiles_y * p.N;
     const dim3 grid(xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)), block(kUThreads);
+    const bool packed = u8_interleaved(p);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+        if (packed) hipLaunchKernelGGL((render_rgba8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+        else hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
     });
     return hipGetLastError();
 }

@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .quantized import is_interleaved
 
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16, torch.uint8: _lib.DTYPE_U8}
 
@@ -360,6 +361,13 @@ def _kernel_operand(t: torch.Tensor, inner: int) -> torch.Tensor:
     return t.contiguous() if t.stride(inner) != 1 or any(s < 0 for s in t.stride()) else t
 
 
+def _volume_operand(rgba: torch.Tensor) -> torch.Tensor:
+    """The RGBA volume as the forward reads it: a storage dtype the kernels take; innermost stride 1, or the interleaved uint8 layout as it is."""
+    if is_interleaved(rgba):   # (quantized.py)
+        return rgba
+    return _kernel_operand(rgba if rgba.dtype in _DTYPES else rgba.float(), 4)
+
+
 def _readable_past_last_row(t: torch.Tensor, extra: int) -> bool:
     """True when `extra` elements past t's last element still lie inside t's storage."""
     last = t.storage_offset() + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
@@ -561,7 +569,8 @@ class MPI(nn.Module):
         camera axis lies more than 0.35 rad off the normal (GMPI_FLAG_HINT_OBLIQUE: views that share an MPI then go to the tile kernel at once).
 
         rgba [M,D,4,Ht,Wt] (f32/bf16/f16, or uint8 codes c that stand for c / 255 -- quantized.py; any outer strides, innermost contiguous;
-        a uint8 volume is read as it is: no cast, no copy, no gradient, no exhaustive range pass -- every code is in [0, 1]), dhw [M,D,3],
+        a uint8 volume is read as it is: no cast, no copy, no gradient, no exhaustive range pass -- every code is in [0, 1]; so is a channels-last
+        uint8 volume, `layers_as_volume(layers)` of [M,D,Ht,Wt,4] layers: channel stride 1, texel stride 4), dhw [M,D,3],
         ray_dir [N,3,H,W], eye_pos [N,3], z_dir [N,3].  View n samples MPI `view_to_mpi[n]`; without it,
         `views_per_mpi` (an int or one count per MPI) gives the reference's grouping.
         Returns dict(color, depth[, T], status).  With `defer_status=True` the status word is not read back
@@ -595,9 +604,9 @@ class MPI(nn.Module):
             raise _lib.GmpiError("MPI.forward needs tensors on a ROCm device: this package has no CPU path "
                                  f"(got rgba on {rgba.device})")
         dev = rgba.device
-        # -- inputs: a storage dtype the kernels take, innermost stride 1; the camera and plane tensors as contiguous fp32 on the volume's device
+        # -- inputs: a storage dtype the kernels take, innermost stride 1 (or uint8 texels of 4 bytes: quantized.is_interleaved); the camera and plane tensors as contiguous fp32 on the volume's device
         rgba_in = rgba   # (as the caller passed it: the identity the full-range-check cache is keyed on)
-        rgba = _kernel_operand(rgba if rgba.dtype in _DTYPES else rgba.float(), 4)
+        rgba = _volume_operand(rgba)
         M, D, _, Ht, Wt = rgba.shape
         sh_rgb = sh_bg = None
         if _shared is not None:   # one storage dtype for the three tensors

@@ -3,14 +3,19 @@
 along a yaw sweep of +-0.3 rad (config 4):
 
   u8_lds, u8_gather        the staged kernel of render_u8.hip and the gather kernel's uint8 instance
+  u8i_lds, u8i_gather      the same two kernels over the SAME codes held channels-last (layers_as_volume of [M, D, Ht, Wt, 4] layers), read in place;
+                           their results are asserted to be the planar volume's, bit for bit
+  u8i_copy_plus_lds        `.contiguous()` of the channels-last view + the planar staged kernel in one timed region: what a holder of layers paid
+                           before the layout was read in place
   bf16_auto, bf16_lds      dequantize_volume(q, bfloat16) rendered with variant auto (the band kernel where it applies) and with the tile kernel
   f32_auto, f32_lds        the same on dequantize_volume(q)
   deq_bf16_plus_auto       dequantise to bf16 + variant auto in one timed region: what a holder of 8-bit data pays without the type
 
-and the peak device memory above the inputs of one u8 render and of one dequantise-and-render (torch.cuda.max_memory_allocated).  Every shape
+and the peak device memory above the inputs of one u8 render, of one in-place render of the channels-last volume (u8i_peak_mb), of one
+copy-and-render of it (u8i_copy_peak_mb) and of one dequantise-and-render (torch.cuda.max_memory_allocated).  Every shape
 runs in a child process of its own under a time limit; the first failure ends the run.  One pass over the shapes says nothing about the spread
 between passes (clocks settle, boxes differ): `passes` repeats the whole pass in one session, each under a "== pass i ==" header, and
-profiles/u8_storage.txt records three.  usage: python tools/time_u8_storage.py [reps [passes]]   (defaults 15 and 3)"""
+profiles/u8_storage.txt and profiles/u8_interleaved.txt record three.  usage: python tools/time_u8_storage.py [reps [passes]]   (defaults 15 and 3)"""
 import os
 import subprocess
 import sys
@@ -24,7 +29,7 @@ def one(name, S, B, D, V, reps):
     import torch
     sys.path.insert(0, ROOT)
     import ml_gmpi_amd
-    from ml_gmpi_amd import MPI, dequantize_volume
+    from ml_gmpi_amd import MPI, dequantize_volume, layers_as_volume
     dev = torch.device("cuda:0")
 
     def timed(fn, n=reps):
@@ -69,6 +74,32 @@ def one(name, S, B, D, V, reps):
     row["u8_gather"] = timed(lambda: render("gather", q))
     ref = {k: v.clone() for k, v in out.items()}   # (the gather kernel's default-mode result: what the float renders are held against below)
 
+    # the same codes channels-last, read in place
+    qi = layers_as_volume(q.permute(0, 1, 3, 4, 2).contiguous())
+    assert qi.stride(2) == 1 and qi.stride(4) == 4
+    row["u8i_gather"] = timed(lambda: render("gather", qi))
+    assert all(torch.equal(out[k], ref[k]) for k in out), "interleaved gather != planar gather"
+    render("lds", q)
+    staged = {k: v.clone() for k, v in out.items()}
+    row["u8i_lds"] = timed(lambda: render("lds", qi))
+    assert all(torch.equal(out[k], staged[k]) for k in out), "interleaved staged != planar staged"
+    del staged
+
+    def copy_and_render():
+        render("lds", qi.contiguous())
+    for key, fn in (("u8i_peak_mb", lambda: render("auto", qi)), ("u8i_copy_peak_mb", copy_and_render)):
+        fn()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base_mem = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        fn()
+        torch.cuda.synchronize()
+        row[key] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    row["u8i_copy_plus_lds"] = timed(copy_and_render)
+    del qi
+    torch.cuda.empty_cache()
+
     def deq_and_render():
         render("auto", dequantize_volume(q, torch.bfloat16))
     deq_and_render()
@@ -94,6 +125,9 @@ def one(name, S, B, D, V, reps):
     assert int(status[0].item()) == 0, int(status[0].item())
     for k in ("u8_gather", "bf16_auto", "bf16_lds", "f32_auto", "f32_lds", "deq_bf16_plus_auto"):
         row["u8_lds_vs_" + k] = row["u8_lds"] / row[k]
+    for k in ("u8_lds", "u8i_gather", "bf16_auto", "bf16_lds", "u8i_copy_plus_lds"):
+        row["u8i_lds_vs_" + k] = row["u8i_lds"] / row[k]
+    row["u8i_gather_vs_u8_gather"] = row["u8i_gather"] / row["u8_gather"]
     try:
         clock = f"{torch.cuda.clock_rate()} MHz"
     except Exception:  # noqa: BLE001 -- no SMI binding in this torch
