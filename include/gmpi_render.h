@@ -317,6 +317,58 @@ int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams *params, const
                                            float *grad_background, const int64_t *grad_background_stride, void *stream);
 
 /*
+ * Depth-alpha layout: what GMPI's "depth2alpha" generator produces (torgba_cond_on_pos_enc: "depth2alpha", networks_vanilla_depth2alpha.py:650-663) --
+ * ONE colour image and ONE depth image per MPI and, optionally, a colour image for the last plane; no alpha planes.  The alpha of texel x on plane k is
+ *     t = plane_z[k] - depth[x];   t = min(max(t, z_lo), z_hi);   alpha = (t - z_lo) / z_den
+ * in fp32, one rounding per step, the division IEEE (depth stored in 16 bits is upcast first: exact).  By definition the result is the render of the
+ * volume with these alphas and GmpiSharedColor's colours (expand_depth_alpha in the Python package is the executable definition); with
+ * GMPI_FLAG_STRICT_ORDER it is bit-identical to gmpi_mpi_render_launch on that volume, which is never materialised.  The caller rounds the constants:
+ * z_lo = (float)lo, z_hi = (float)hi, z_den = (float)(hi - lo + 1e-8) with the sum formed in double (the reference divides by z_hi - z_lo + 1e-8).
+ */
+typedef struct GmpiDepthAlpha {
+    uint32_t struct_size;   /* = sizeof(GmpiDepthAlpha)                                              */
+    const float *plane_z;   /* [D], or [M, D]: the (normalised) depth of every plane, device memory   */
+    int64_t plane_z_stride; /* elements from one MPI's table to the next; 0 = one table for all MPIs  */
+    float z_lo, z_hi;       /* the ramp's bounds, z_lo < z_hi                                         */
+    float z_den;            /* the ramp's divisor, > 0                                                */
+} GmpiDepthAlpha;
+
+/*
+ * The fused render over a depth-alpha MPI.  `params` as for gmpi_mpi_render_launch, except: params->rgba points at the DEPTH image seen as
+ * [M, 1, 1, Ht, Wt] -- rgba_stride[0] and [3] are its MPI and row strides, [1] and [2] are ignored, [4] must be 1; params->D is the number of planes
+ * (of dhw and plane_z).  `shared` carries rgb and background as for gmpi_mpi_render_shared_launch; the three images have the storage type
+ * params->rgba_dtype (GMPI_DTYPE_U8: GMPI_E_DTYPE).  Every flag, view_to_mpi / views_per_mpi, transmittance_out and the status bits mean what they mean
+ * there.  GMPI_FLAG_CHECK_RANGE covers every computed alpha tap (a NaN depth sets GMPI_STATUS_RGBA_RANGE) and the colour texels that are read: a plane
+ * whose alpha sample is exactly 0 is skipped, colour taps and blend (with a = 0 the blend is the identity in fp32: w = 0, (1 - 0) + 1e-10 rounds to 1
+ * -- for finite colour texels and a finite plane depth 1/(1/(s dot)); a NaN or infinite one gives NaN on the volume path, 0 * x, and nothing here; and
+ * the colour texels under an alpha sample of 0 are not range-checked, which they are on the volume path).
+ * One kernel, one pixel per lane, taps from global memory (any shape, any stride, any ray field): GMPI_VARIANT_AUTO and GMPI_VARIANT_GATHER run
+ * it, any other variant is GMPI_E_VARIANT.  z_lo >= z_hi or z_den <= 0 (or a NaN among them): GMPI_E_SHAPE; a negative plane_z_stride:
+ * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
+ * never synchronises.  Not built: staged / tile variants, 8-bit storage, gradients w.r.t. the geometry, skipping planes from a depth min/max
+ * pre-pass (gmpi_query(22) says whether the layout itself is built in).
+ */
+int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
+
+/*
+ * Gradient of gmpi_mpi_render_depth_launch w.r.t. the three images -- torch autograd's through expand_depth_alpha: the clamp passes the gradient
+ * where z_lo <= plane_z[k] - depth <= z_hi (bounds included), d alpha / d depth = -1 / z_den there and 0 elsewhere, so the gradient of all D alpha
+ * planes lands in ONE depth image; the colours as in gmpi_mpi_render_shared_backward_launch.  grad_rgb_out, grad_depth, grad_transmittance and
+ * params->transmittance_out as there.  Behind the surface every plane is (almost) exactly opaque, so the forward's transmittance underflows for most
+ * pixels: the kernel then re-walks the ramp samples front to back in mantissa x 2^exponent form before its back-to-front sweep -- the common path of
+ * this layout, not the rare one.  grad_shared_rgb [M,3,Ht,Wt], grad_depth_image [M,1,Ht,Wt] and grad_background [M,3,Ht,Wt] are fp32, caller-zeroed
+ * and ADDED into (atomicAdd); each has three element strides (MPI, channel, row; innermost 1; the depth image's channel stride is ignored); each may
+ * be NULL and is then skipped (all three NULL: GMPI_E_NULL; a grad_background without a background: GMPI_E_NULL).  No atomic is issued for a term that
+ * is exactly zero (planes of weight 0, clamped taps, zero bilinear weights).  One kernel, one pixel per lane (AUTO and GATHER; anything else
+ * GMPI_E_VARIANT); N <= 65535.
+ */
+int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                          const float *grad_rgb_out, const float *grad_depth, const float *grad_transmittance,
+                                          float *grad_shared_rgb, const int64_t *grad_shared_rgb_stride, float *grad_depth_image,
+                                          const int64_t *grad_depth_image_stride, float *grad_background, const int64_t *grad_background_stride,
+                                          void *stream);
+
+/*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the
  * normalised grid on the LAST plane per view (what mpi.py:106-109 print).  uv_minmax: [N,4] float.
  * Uses N, M, D, H, W, flags(ALIGN_CORNERS), view_to_mpi/views_per_mpi, dhw, ray_dir, eye_pos.
@@ -434,7 +486,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * is 512 / width pixels high), 13 the texels per row and 14 the rows its staging buffer holds per plane (a box's first column is rounded down to
  * a multiple of 4 texels before it is held against 13); 15 is unused (-1); the staged kernel for GMPI_DTYPE_U8 volumes: 16 its pixel-tile width (a tile
  * is 512 / width pixels high), 17 the texels per row and 18 the rows its staging buffer holds per plane (first column rounded down to a multiple of 4
- * texels, as for 13); 19 is unused (-1); 20 whether the interleaved GMPI_DTYPE_U8 layout (GmpiRenderParams.rgba_stride) is built in.  Unknown -> -1.                                        */
+ * texels, as for 13); 19 is unused (-1); 20 whether the interleaved GMPI_DTYPE_U8 layout (GmpiRenderParams.rgba_stride) is built in; 21 is unused (-1);
+ * 22 whether the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in.  Unknown -> -1.                                        */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

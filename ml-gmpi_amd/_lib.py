@@ -35,6 +35,8 @@ EXPORTS = (
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
+    "gmpi_mpi_render_depth_launch",
+    "gmpi_mpi_render_depth_backward_launch",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -91,6 +93,15 @@ class GmpiSharedColor(ctypes.Structure):
         ("struct_size", ctypes.c_uint32),
         ("rgb", ctypes.c_void_p), ("rgb_stride", ctypes.c_int64 * 3),
         ("background", ctypes.c_void_p), ("background_stride", ctypes.c_int64 * 3),
+    ]
+
+
+class GmpiDepthAlpha(ctypes.Structure):
+    """Field-for-field mirror of `struct GmpiDepthAlpha` in include/gmpi_render.h."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("plane_z", ctypes.c_void_p), ("plane_z_stride", ctypes.c_int64),
+        ("z_lo", ctypes.c_float), ("z_hi", ctypes.c_float), ("z_den", ctypes.c_float),
     ]
 
 
@@ -197,6 +208,11 @@ def load_library():
     lib.gmpi_mpi_render_shared_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp,
                                                            vp, i64p, vp, i64p, vp, i64p, vp]
+    lib.gmpi_mpi_render_depth_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_depth_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha), vp]
+    lib.gmpi_mpi_render_depth_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_depth_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha),
+                                                          vp, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int

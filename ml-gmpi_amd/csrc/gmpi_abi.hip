@@ -30,6 +30,8 @@ hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh
 hipError_t launch_shared_forward(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared_forward.hip
 bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh);   // render_shared_forward.hip
 int shared_forward_query(int what);                                         // render_shared_forward.hip
+hipError_t launch_depth(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, hipStream_t stream);   // render_depth.hip
+hipError_t launch_depth_backward(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth.hip
 hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
 bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
 int u8_variant_query(int what);                                             // render_u8.hip
@@ -553,24 +555,21 @@ int gmpi_render_shared_supports(const GmpiRenderParams* params, const GmpiShared
     return p.N > 65535 ? GMPI_E_SHAPE : 1;
 }
 
-int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb_out, const float* grad_depth,
-                                           const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride, float* grad_alpha,
-                                           const int64_t* grad_alpha_stride, float* grad_background, const int64_t* grad_background_stride, void* stream) {
-    KParams p;
-    SharedK sh;
-    const int rc = to_shared(params, shared, false, p, sh);
-    if (rc != GMPI_OK) return rc;
+// The gradient arguments of the shared-colour and depth-alpha backward entries (grad_mid: the alpha planes, resp. the depth image) -> g.  A launch
+// without views (p.N == 0) is GMPI_OK before any stride is looked at.
+static int to_shared_grads(const GmpiRenderParams* params, const KParams& p, const SharedK& sh, const float* grad_rgb_out, const float* grad_depth,
+                           const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride, float* grad_mid,
+                           const int64_t* grad_mid_stride, float* grad_background, const int64_t* grad_background_stride, SharedG& g) {
     if (grad_rgb_out == nullptr) return GMPI_E_NULL;
-    if (grad_shared_rgb == nullptr && grad_alpha == nullptr && grad_background == nullptr) return GMPI_E_NULL;
+    if (grad_shared_rgb == nullptr && grad_mid == nullptr && grad_background == nullptr) return GMPI_E_NULL;
     if (grad_background != nullptr && sh.bg == nullptr) return GMPI_E_NULL;
-    if ((grad_shared_rgb != nullptr && grad_shared_rgb_stride == nullptr) || (grad_alpha != nullptr && grad_alpha_stride == nullptr) ||
+    if ((grad_shared_rgb != nullptr && grad_shared_rgb_stride == nullptr) || (grad_mid != nullptr && grad_mid_stride == nullptr) ||
         (grad_background != nullptr && grad_background_stride == nullptr))
         return GMPI_E_NULL;
     if (p.N == 0) return GMPI_OK;
     if (p.N > 65535) return GMPI_E_SHAPE;
-    SharedG g{};
     g.g_out = grad_rgb_out, g.g_depth = grad_depth, g.g_T = grad_transmittance;
-    g.g_rgb = grad_shared_rgb, g.g_alpha = grad_alpha, g.g_bg = grad_background;
+    g.g_rgb = grad_shared_rgb, g.g_alpha = grad_mid, g.g_bg = grad_background;
     auto ok3 = [&](const int64_t* s, int64_t rows_of) {   // MPI stride may be 0 only for one MPI; rows must not overlap
         return (s[0] > 0 || params->M == 1) && s[0] >= 0 && s[1] > 0 && s[2] >= rows_of;
     };
@@ -579,14 +578,75 @@ int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const
         g.gr_mpi = grad_shared_rgb_stride[0], g.gr_chan = grad_shared_rgb_stride[1], g.gr_row = grad_shared_rgb_stride[2];
     }
     if (g.g_alpha) {
-        if (!ok3(grad_alpha_stride, p.Wt)) return GMPI_E_STRIDE;
-        g.ga_mpi = grad_alpha_stride[0], g.ga_plane = grad_alpha_stride[1], g.ga_row = grad_alpha_stride[2];
+        if (!ok3(grad_mid_stride, p.Wt)) return GMPI_E_STRIDE;
+        g.ga_mpi = grad_mid_stride[0], g.ga_plane = grad_mid_stride[1], g.ga_row = grad_mid_stride[2];
     }
     if (g.g_bg) {
         if (!ok3(grad_background_stride, p.Wt)) return GMPI_E_STRIDE;
         g.gb_mpi = grad_background_stride[0], g.gb_chan = grad_background_stride[1], g.gb_row = grad_background_stride[2];
     }
+    return GMPI_OK;
+}
+
+int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb_out, const float* grad_depth,
+                                           const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride, float* grad_alpha,
+                                           const int64_t* grad_alpha_stride, float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    KParams p;
+    SharedK sh;
+    int rc = to_shared(params, shared, false, p, sh);
+    if (rc != GMPI_OK) return rc;
+    SharedG g{};
+    rc = to_shared_grads(params, p, sh, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride, grad_alpha, grad_alpha_stride,
+                         grad_background, grad_background_stride, g);
+    if (rc != GMPI_OK || p.N == 0) return rc;
     return hip_rc(launch_shared_backward(p, params->rgba_dtype, sh, g, params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
+}
+
+// depth-alpha entries: params->rgba = the depth image (rgba_stride[1], [2] ignored); the checks of to_shared (AUTO and GATHER only) + the GmpiDepthAlpha struct.
+static int to_depth(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* da, bool forward, KParams& p, SharedK& sh, DepthK& dk) {
+    if (params == nullptr || shared == nullptr || da == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams) || da->struct_size != sizeof(GmpiDepthAlpha)) return GMPI_E_ABI;
+    GmpiRenderParams q = *params;
+    q.rgba_stride[1] = 1;   // (ignored: the depth image has one plane)
+    const int rc = to_shared(&q, shared, forward, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (params->variant == GMPI_VARIANT_LDS) return GMPI_E_VARIANT;   // (to_shared lets the shared-colour forward's staged kernel through)
+    if (da->plane_z == nullptr) return GMPI_E_NULL;
+    if (da->plane_z_stride < 0) return GMPI_E_STRIDE;
+    if (!(da->z_lo < da->z_hi) || !(da->z_den > 0.0f)) return GMPI_E_SHAPE;
+    p.s_plane = 0;
+    dk.plane_z = da->plane_z, dk.pz_stride = da->plane_z_stride;
+    dk.lo = da->z_lo, dk.hi = da->z_hi, dk.den = da->z_den, dk.rden = 1.0f / da->z_den;
+    return GMPI_OK;
+}
+
+int gmpi_mpi_render_depth_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, void* stream) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    const int rc = to_depth(params, shared, depth_alpha, true, p, sh, dk);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return GMPI_OK;
+    if (p.N > 65535) return GMPI_E_SHAPE;   // the view index is grid.z
+    return hip_rc(launch_depth(p, params->rgba_dtype, sh, dk, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                          const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
+                                          const int64_t* grad_shared_rgb_stride, float* grad_depth_image, const int64_t* grad_depth_image_stride,
+                                          float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    int rc = to_depth(params, shared, depth_alpha, false, p, sh, dk);
+    if (rc != GMPI_OK) return rc;
+    int64_t gd_stride[3] = {0, 1, 0};   // (the depth image's channel stride is ignored)
+    if (grad_depth_image != nullptr && grad_depth_image_stride != nullptr) gd_stride[0] = grad_depth_image_stride[0], gd_stride[2] = grad_depth_image_stride[2];
+    SharedG g{};
+    rc = to_shared_grads(params, p, sh, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride, grad_depth_image,
+                         grad_depth_image_stride != nullptr ? gd_stride : nullptr, grad_background, grad_background_stride, g);
+    if (rc != GMPI_OK || p.N == 0) return rc;
+    return hip_rc(launch_depth_backward(p, params->rgba_dtype, sh, dk, g, static_cast<hipStream_t>(stream)));
 }
 
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {
@@ -707,6 +767,7 @@ int gmpi_query(int32_t what) {
         case 11: return 1;  // the atomics-free backward (pixel pass + texel gather) is built in
         case 12: case 13: case 14: return shared_forward_query(what);
         case 16: case 17: case 18: case 20: return u8_variant_query(what);  // (15, 19: unused)
+        case 22: return 1;  // the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in  (21: unused)
         default: return -1;
     }
 }

@@ -1,9 +1,9 @@
-// gmpi_backward.hpp -- the ONE home of what the backward kernels of the render share.  Seven kernels run the same back-to-front sweep
+// gmpi_backward.hpp -- the ONE home of what the backward kernels of the render share.  Eight kernels run the same back-to-front sweep
 // (render_backward.hip: one pixel per lane, tile, tile2; render_backward_gather.hip: pixel_pass; render_backward_geometry.hip: geometry_pixel;
-// render_shared.hip: shared_backward, shared_tile), and the claims of DESIGN.md section 3.3 -- the forward's quotients and texels, bit-reproducible
+// render_shared.hip: shared_backward, shared_tile; render_depth.hip: depth_backward), and the claims of DESIGN.md section 3.3 -- the forward's quotients and texels, bit-reproducible
 // gather and geometry passes, gT entering S in every sweep -- hold because they all run THIS code:
 //   BwdView / bwd_view              what is uniform over a view: the forward's View / view_setup (gmpi_device.hpp)
-//   BwdPixel / bwd_pixel_setup      the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
+//   BwdPixel / bwd_pixel_setup(_with)   the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
 //   tile_box                        texel box of a pixel tile on one plane, from its four corner pixels
@@ -107,14 +107,15 @@ struct BwdPixel {
     }
 };
 
-// The start of the sweep for pixel (px, py) of view n.  g_rgb / g_depth / g_T: the upstream gradients (g_depth, g_T may be nullptr); vol: channel 0 of
-// the view's MPI -- the RGBA volume, or the alpha planes of the shared-colour layout (s_chan = 0).
+// The start of the sweep for pixel (px, py) of view n.  g_rgb / g_depth / g_T: the upstream gradients (g_depth, g_T may be nullptr); total(t_fwd): the
+// pixel's final transmittance as an XT, given the forward's value (see MASKED for its default) -- total_transmittance for the layouts that store alpha
+// planes (bwd_pixel_setup below), a walk over its own samples for the depth-alpha layout (render_depth.hip).
 // MASKED: the workgroup keeps lanes outside the image (they pass its barriers): the pixel index is clamped, an inactive lane loads its ray but
 // contributes nothing, and t_fwd defaults to 1.  Not MASKED: the lane is known to be inside the image (`active` is ignored), t_fwd defaults to 0.
-template <typename TexT, bool AC, bool MASKED>
-__device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
-                                                const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
-                                                const TexT* __restrict__ vol) {
+template <bool MASKED, typename Total>
+__device__ __forceinline__ void bwd_pixel_setup_with(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
+                                                     const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
+                                                     Total&& total) {
     if (!MASKED) active = true;
     const int64_t HW = vw.HW;
     const int64_t pix = MASKED ? static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1) : static_cast<int64_t>(py) * p.W + px;
@@ -128,8 +129,17 @@ __device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, 
     bp.gr = active ? scale * g[0] : 0.f, bp.gg = active ? scale * g[HW] : 0.f, bp.gb = active ? scale * g[2 * HW] : 0.f;
     bp.gz = (active && g_depth) ? g_depth[static_cast<int64_t>(n) * HW + pix] : 0.0f;
     const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : (MASKED ? 1.0f : 0.0f);
-    if (active) bp.T = total_transmittance<TexT, AC>(p, vw.dhw, vol, t_fwd, p.T_out != nullptr, vw.ex, vw.ey, vw.ez, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy);
+    if (active) bp.T = total(t_fwd);
     if (active && g_T) bp.S = g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
+}
+// vol: channel 0 of the view's MPI -- the RGBA volume, or the alpha planes of the shared-colour layout (s_chan = 0).
+template <typename TexT, bool AC, bool MASKED>
+__device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
+                                                const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
+                                                const TexT* __restrict__ vol) {
+    bwd_pixel_setup_with<MASKED>(bp, p, vw, n, px, py, active, g_rgb, g_depth, g_T, [&](float t_fwd) {
+        return total_transmittance<TexT, AC>(p, vw.dhw, vol, t_fwd, p.T_out != nullptr, vw.ex, vw.ey, vw.ez, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy);
+    });
 }
 
 // Where the pixel's ray meets plane k of its view's MPI, by the forward's strict-order chain (compiler divisions).

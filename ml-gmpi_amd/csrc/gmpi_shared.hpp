@@ -16,7 +16,7 @@ struct SharedG {
     const float* g_depth;  // [N,1,H,W] or nullptr
     const float* g_T;      // [N,1,H,W] or nullptr
     float* g_rgb;          // [M,3,Ht,Wt] or nullptr, added into
-    float* g_alpha;        // [M,D,1,Ht,Wt] or nullptr
+    float* g_alpha;        // [M,D,1,Ht,Wt] or nullptr (depth-alpha layout: the gradient of the depth image [M,1,Ht,Wt]; ga_plane unused)
     float* g_bg;           // [M,3,Ht,Wt] or nullptr
     int64_t gr_mpi, gr_chan, gr_row, ga_mpi, ga_plane, ga_row, gb_mpi, gb_chan, gb_row;
 };
@@ -58,6 +58,41 @@ __device__ __forceinline__ void shared_sample(const TexT* __restrict__ alpha_pla
 #pragma unroll
     for (int c = 0; c < 3; ++c) smp[c] = tap_sample<TexT, STRICT>(col + c * c_chan, c_row, t, check_range, bad);
     smp[3] = tap_sample<TexT, STRICT>(alpha_plane, a_row, t, check_range, bad);
+}
+
+// ---- depth-alpha layout (GmpiDepthAlpha, include/gmpi_render.h; render_depth.hip): no alpha planes, ONE depth image per MPI; the alpha of texel x on
+// plane k is the ramp  (clamp(plane_z[k] - depth[x], lo, hi) - lo) / den,  one rounding per step (expand_depth_alpha, depth_alpha.py).
+struct DepthK {
+    const float* plane_z;   // [D], or [M, D] with pz_stride = its MPI stride (0: one table for all)
+    int64_t pz_stride;
+    float lo, hi, den;      // the ramp's three constants as the caller rounded them
+    float rden;             // RN(1 / den), for div_by_recip
+};
+// The four taps of one footprint as ramp values; in[i]: tap i's difference lies inside [lo, hi], bounds included (where torch.clamp passes a gradient).
+struct RampTaps {
+    float a[4];   // nw, ne, sw, se
+    bool in[4];
+};
+// STRICT: the IEEE division.  Otherwise the same quotient through the rounded reciprocal (div_by_recip is correctly rounded for these operands:
+// the numerator is 0 or a multiple of ulp(lo), far from the denormals).  NaN stays NaN, as in torch.clamp.
+template <bool STRICT>
+__device__ __forceinline__ float depth_ramp(float pz, float d, const DepthK& dk, bool& inside) {
+    float t = pz - d;
+    inside = t >= dk.lo && t <= dk.hi;
+    t = t < dk.lo ? dk.lo : t;
+    t = t > dk.hi ? dk.hi : t;
+    const float num = t - dk.lo;
+    return STRICT ? num / dk.den : div_by_recip(num, dk.den, dk.rden);
+}
+template <typename TexT, bool STRICT>
+__device__ __forceinline__ RampTaps ramp_taps(const TexT* __restrict__ depth, int64_t s_row, const Taps& t, float pz, const DepthK& dk) {
+    const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
+    const float d_nw = to_f32(depth[oa + t.xa]), d_ne = to_f32(depth[oa + t.xb]);
+    const float d_sw = to_f32(depth[ob + t.xa]), d_se = to_f32(depth[ob + t.xb]);
+    RampTaps r;
+    r.a[0] = depth_ramp<STRICT>(pz, d_nw, dk, r.in[0]), r.a[1] = depth_ramp<STRICT>(pz, d_ne, dk, r.in[1]);
+    r.a[2] = depth_ramp<STRICT>(pz, d_sw, dk, r.in[2]), r.a[3] = depth_ramp<STRICT>(pz, d_se, dk, r.in[3]);
+    return r;
 }
 
 }  // namespace gmpi

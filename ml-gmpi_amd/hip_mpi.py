@@ -352,6 +352,33 @@ def _shared_color(rgb: torch.Tensor, background: Optional[torch.Tensor]) -> _lib
     return sc
 
 
+def _depth_alpha(plane_z: torch.Tensor, z_lo: float, z_hi: float) -> _lib.GmpiDepthAlpha:
+    """The one builder of GmpiDepthAlpha: plane_z fp32 [D] or [M,D] on the device (innermost stride 1), the ramp's constants rounded as
+    `depth_alpha.ramp_constants` rounds them."""
+    from .depth_alpha import ramp_constants
+    da = _lib.GmpiDepthAlpha()
+    da.struct_size = ctypes.sizeof(_lib.GmpiDepthAlpha)
+    da.plane_z = plane_z.data_ptr()
+    da.plane_z_stride = plane_z.stride(0) if plane_z.ndim == 2 else 0
+    da.z_lo, da.z_hi, da.z_den = ramp_constants(z_lo, z_hi)
+    return da
+
+
+def _depth_operands(rgb, depth, plane_z, z_bounds, background, n_planes: int):
+    """What `render_views` takes for the depth-alpha layout: (the depth image as the view [M,1,1,Ht,Wt], _shared = (rgb, background), _depth =
+    (plane_z as contiguous fp32 on the device, z_lo, z_hi)); the checks that need no launch."""
+    from .depth_alpha import _check
+    _check(rgb, depth, plane_z, background)
+    _refuse_uint8("the depth-alpha render", rgb, depth, background)
+    for t in (rgb, background):
+        if t is not None and t.dtype != depth.dtype:   # (no quiet cast, as in the shared-colour render)
+            raise TypeError(f"depth-alpha render: rgb, depth and background must have one storage dtype, got {t.dtype} next to depth in {depth.dtype}")
+    assert plane_z.shape[-1] == n_planes, f"plane_z holds {plane_z.shape[-1]} planes, dhw {n_planes}"
+    z_lo, z_hi = (float(v) for v in z_bounds)
+    assert z_lo < z_hi, (z_lo, z_hi)
+    return depth.unsqueeze(1), (rgb, background), (_f32_on(plane_z.detach(), depth.device), z_lo, z_hi)
+
+
 def _lend(p: _lib.GmpiRenderParams, ws: torch.Tensor) -> None:
     p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
 
@@ -562,7 +589,7 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _shared=None, _shared_variant: Optional[str] = None):
+                     _shared=None, _shared_variant: Optional[str] = None, _depth=None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -588,13 +615,15 @@ class MPI(nn.Module):
                 raise NotImplementedError("no gradient flows through a uint8 volume, w.r.t. the plane geometry and the camera tensors included "
                                           "(geometry_grad=True): render dequantize_volume(q) (ml_gmpi_amd.quantized) for that, or detach the "
                                           "camera and dhw tensors")
-            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _shared)
+            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _shared, _depth)
             if bridge is not None:
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
                 if _shared is not None:
                     kwargs["_shared_variant"] = _shared_variant
+                if _depth is not None:
+                    kwargs["_depth"] = _depth
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -608,6 +637,8 @@ class MPI(nn.Module):
         rgba_in = rgba   # (as the caller passed it: the identity the full-range-check cache is keyed on)
         rgba = _volume_operand(rgba)
         M, D, _, Ht, Wt = rgba.shape
+        if _depth is not None:   # (the depth-alpha layout: rgba is the depth image [M,1,1,Ht,Wt]; the planes are dhw's and plane_z's)
+            D = dhw.shape[1]
         sh_rgb = sh_bg = None
         if _shared is not None:   # one storage dtype for the three tensors
             for t in _shared:
@@ -651,20 +682,24 @@ class MPI(nn.Module):
             # tensors in every call (never cached: three identities to track)
             checked = ()
             if self.range_check == "full" and rgba.dtype is not torch.uint8:   # (8-bit codes are in [0, 1] by construction: nothing to pass over)
-                checked = (rgba, sh_rgb, sh_bg) if _shared is not None else (rgba,) if self._full_check_needed(rgba_in) else ()
+                # (a depth image is no [0, 1] tensor: the pass covers the two colour images)
+                checked = (sh_rgb, sh_bg) if _depth is not None else (rgba, sh_rgb, sh_bg) if _shared is not None else (rgba,) if self._full_check_needed(rgba_in) else ()
             for t in checked:
                 if t is not None:
                     t = t if t.is_contiguous() else t.contiguous()
                     _call("gmpi_rgba_range_check_launch", dev, t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream=stream)
             if _shared is not None:
                 sc = _shared_color(sh_rgb, sh_bg)
-                if shared_variant == "lds" and on_device:   # the staged forward where it can take these tensors (alignment), else AUTO's kernel
+                if shared_variant == "lds" and on_device and _depth is None:   # the staged forward where it can take these tensors (alignment), else AUTO's kernel
                     p.variant = _lib.VARIANT_LDS
                     if not _staged_forward_takes(p, sc, (rgba, sh_rgb, sh_bg)):
                         p.variant = _lib.VARIANT_AUTO
                         self.shared_lds_fallbacks += 1
                         _warn_lds_fallback()
-                _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
+                if _depth is not None:
+                    _call("gmpi_mpi_render_depth_launch", dev, ctypes.byref(p), ctypes.byref(sc), ctypes.byref(_depth_alpha(*_depth)), stream=stream)
+                else:
+                    _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
             else:
                 _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
             res = dict(color=color, depth=depth, T=T, status=status)
@@ -679,18 +714,20 @@ class MPI(nn.Module):
                 self._settle(status, p, keep, c2w_mat, sphere_c, rgba_in if _shared is None and checked else None)
             return res
 
-    def _autograd_bridge(self, rgba, dhw, ray_dir, eye_pos, z_dir, shared):
+    def _autograd_bridge(self, rgba, dhw, ray_dir, eye_pos, z_dir, shared, depth=None):
         """(autograd.Function, its leading tensor arguments) when this call has to be recorded, else None."""
         geometry = self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir))
         if shared is None:
             # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
             return (_RenderFunction, (rgba,)) if rgba.requires_grad or geometry else None
-        # shared-colour layout (render_views_shared): rgba is the alpha tensor, shared = (rgb, background or None)
+        # shared-colour layout (render_views_shared): rgba is the alpha tensor, shared = (rgb, background or None); depth-alpha layout
+        # (render_views_depth): rgba is the depth image, depth = (plane_z, z_lo, z_hi)
         if geometry:
-            raise NotImplementedError("the shared-colour render has no gradient w.r.t. the plane geometry or the camera tensors "
-                                      "(geometry_grad=True): render the expanded volume (expand_shared_color) with render_views for that")
+            what, expand = ("shared-colour", "expand_shared_color") if depth is None else ("depth-alpha", "expand_depth_alpha")
+            raise NotImplementedError(f"the {what} render has no gradient w.r.t. the plane geometry or the camera tensors "
+                                      f"(geometry_grad=True): render the expanded volume ({expand}) with render_views for that")
         if rgba.requires_grad or any(t is not None and t.requires_grad for t in shared):
-            return _SharedRenderFunction, (shared[0], rgba, shared[1])
+            return _SharedRenderFunction if depth is None else _DepthRenderFunction, (shared[0], rgba, shared[1])
         return None
 
     def _flags(self, out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint) -> int:
@@ -733,6 +770,25 @@ class MPI(nn.Module):
         _check(rgb, alpha, background)
         assert "_shared" not in kwargs
         return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _shared=(rgb, background), _shared_variant=variant, **kwargs)
+
+    # -- depth-alpha layout ------------------------------------------------------------------------------------------------------------
+    def render_views_depth(self, rgb: torch.Tensor, depth: torch.Tensor, plane_z: torch.Tensor, z_bounds, dhw: torch.Tensor, ray_dir: torch.Tensor,
+                           eye_pos: torch.Tensor, z_dir: torch.Tensor, background: Optional[torch.Tensor] = None, **kwargs):
+        """`render_views` of the volume `expand_depth_alpha(rgb, depth, plane_z, *z_bounds, background)` without building it: rgb [M,3,Ht,Wt], depth
+        [M,1,Ht,Wt] (any outer strides), plane_z [D] or [M,D] (the normalised plane depths the generator compares the depth with), z_bounds =
+        (z_lo, z_hi) (`depth_alpha_bounds(z_range, n_z_bins)`), background [M,3,Ht,Wt] or None = the last plane's own colour.  Same keyword
+        arguments, returned dict and status handling as `render_views_shared`.  One kernel: `variant=` takes None, "auto" or "gather" (any other name:
+        ValueError); the module's own variant is read as `render_views_shared` reads it ("gather" as such, every other one is the library's choice).  Under autograd the gradient
+        reaches rgb, depth and background in their own dtypes (gmpi_mpi_render_depth_backward_launch: the gradient of all D alpha planes lands in
+        the one depth image); none w.r.t. plane_z or the geometry (NotImplementedError with geometry_grad=True and a camera / dhw tensor that
+        requires grad).  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
+        background (a depth image is no [0, 1] tensor); "touched" also sets the range bit for a NaN depth some pixel samples."""
+        assert "_shared" not in kwargs and "_depth" not in kwargs
+        variant = kwargs.pop("variant", None)   # (None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
+        if variant not in (None, "auto", "gather"):
+            raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
+        depth5, shared, depth_alpha = _depth_operands(rgb, depth, plane_z, z_bounds, background, dhw.shape[1])
+        return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _shared=shared, _shared_variant=variant, _depth=depth_alpha, **kwargs)
 
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
     def raise_on_status(self, status: torch.Tensor, params=None, keep=None, c2w_mat=None, sphere_c=None):
@@ -923,6 +979,46 @@ class _SharedRenderFunction(torch.autograd.Function):
             return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
         _call("gmpi_mpi_render_shared_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
               g_color.data_ptr(), _ptr(g_depth), _ptr(g_T), *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
+        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
+        return out[0], out[1], out[2], None, None, None, None, None, None
+
+
+class _DepthRenderFunction(torch.autograd.Function):
+    """autograd bridge of the depth-alpha render, built like `_SharedRenderFunction`: forward = gmpi_mpi_render_depth_launch, backward =
+    gmpi_mpi_render_depth_backward_launch into zero-filled fp32 gradients of rgb, the depth image and the background."""
+
+    @staticmethod
+    def forward(ctx, rgb, depth, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+        res, keep, (rgb_d, bg_d) = _bridge_forward(ctx, mpi, depth, (dhw, ray_dir, eye_pos, z_dir), kwargs, shared=(rgb, background))
+        ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
+        plane_z, ctx.z_lo, ctx.z_hi = kwargs["_depth"]
+        ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], plane_z, *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
+        ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, depth, background)]
+        return res["color"], res["depth"], res["T"], res["status"]
+
+    @staticmethod
+    def backward(ctx, g_color, g_depth, g_T, g_status):
+        saved = list(ctx.saved_tensors)
+        depth, rgb, dhw, ray_dir, eye_pos, z_dir, T, plane_z = saved[:8]
+        rest = saved[8:]
+        bg = rest.pop(0) if ctx.has_bg else None
+        keep = _Keep(depth, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
+        dev = depth.device
+        want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
+        if not any(want) or (g_color is None and g_depth is None and g_T is None):
+            return (None,) * 9
+        p = _render_params(ctx.scalars, keep, T=T)
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        shapes = [(p.M, 3, p.Ht, p.Wt), (p.M, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)]
+        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+
+        def ptr_stride(t):
+            if t is None:
+                return None, None
+            return t.data_ptr(), (ctypes.c_int64 * 3)(*t.stride()[:3])
+        _call("gmpi_mpi_render_depth_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
+              ctypes.byref(_depth_alpha(plane_z, ctx.z_lo, ctx.z_hi)), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T),
+              *ptr_stride(grads[0]), *ptr_stride(grads[1]), *ptr_stride(grads[2]))
         out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
         return out[0], out[1], out[2], None, None, None, None, None, None
 

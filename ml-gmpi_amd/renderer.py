@@ -420,6 +420,7 @@ class MPIRenderer:
         want_T = bool(ext.pop("want_transmittance", False))
         shared = ext.pop("_shared", None)   # render_shared: (rgb, background or None); batch_mpi_rgbas is then the alpha tensor
         shared_variant = ext.pop("_shared_variant", None)
+        depth_alpha = ext.pop("_depth", None)   # render_depth: (plane_z, z_lo, z_hi); batch_mpi_rgbas is then the depth image [B,1,1,Ht,Wt]
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -462,7 +463,7 @@ class MPIRenderer:
             batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
             check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
             c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}))
+            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}), **({} if depth_alpha is None else {"_depth": depth_alpha}))
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
@@ -480,6 +481,22 @@ class MPIRenderer:
         _check(batch_mpi_rgb, batch_mpi_alpha, background_rgb)
         assert "_shared" not in kwargs
         return self.render(batch_mpi_alpha, render_h, render_w, _shared=(batch_mpi_rgb, background_rgb), _shared_variant=variant, **kwargs)
+
+
+    def render_depth(self, batch_rgb, batch_depth, render_h, render_w, *, z_range, n_z_bins, plane_z=None, background_rgb=None, **kwargs):
+        """`render` of the volume `expand_depth_alpha(batch_rgb, batch_depth, plane_z, *depth_alpha_bounds(z_range, n_z_bins), background_rgb)`
+        without building it (the output of GMPI's "depth2alpha" generator): batch_rgb [B,3,Ht,Wt], batch_depth [B,1,Ht,Wt], background_rgb
+        [B,3,Ht,Wt] or None = the last plane's own colour.  plane_z [D] or [B,D]: None takes this renderer's normalised plane depths,
+        `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with.  Keyword arguments, return tuple, pose
+        sampling and the consumption of the torch RNG are `render`'s."""
+        from .depth_alpha import depth_alpha_bounds
+        from .hip_mpi import _depth_operands
+        if plane_z is None:
+            plane_z = self.get_xyz_single_res(batch_depth.shape[-2], batch_depth.shape[-1], only_z=True)[1].reshape(-1)
+        assert "_shared" not in kwargs and "_depth" not in kwargs
+        depth5, shared, depth_alpha = _depth_operands(batch_rgb, batch_depth, plane_z, depth_alpha_bounds(z_range, n_z_bins), background_rgb,
+                                                      self.dynamic_mpi_plane_dhws.shape[0])
+        return self.render(depth5, render_h, render_w, _shared=shared, _depth=depth_alpha, **kwargs)
 
 
 class _RaysFromC2W(torch.autograd.Function):

@@ -1,0 +1,189 @@
+"""Times the depth-alpha layout (one colour image, one depth image and a background image per MPI; the alpha of plane k is a ramp of plane_z[k] - depth)
+against the two paths that render it through tensors the layout does not need, through the C ABI, with HIP events (medians): 256^2 x 32 x 8, 512^2 x 32 x 4
+and 1024^2 x 32 x 4 in fp32 the forward and the whole step (forward, zero-fill, backward), 1024^2 x 96 x 4 the forward only; each with n_z_bins = 4 (a ramp
+several planes wide) and 256 (a step).
+
+  depth    the new path: forward, zero-fill of the three gradient images, backward (render_depth.hip: one pixel per lane, both)
+  volume   expand_depth_alpha (the ramp + the generator's expand and two cat), forward (variant auto), zero-fill of the volume gradient, volume backward
+           (tile kernels), autograd through the expand (plane sums of the colour gradient, the clamp's mask and the plane sum for the depth)
+  shared   the alpha planes materialised (depth_alpha_planes), render_views_shared (variant auto: one pixel per lane), zero-fill of the three gradients,
+           shared backward (tile kernel), autograd through the ramp
+
+and the peak device memory of one pass of each above the inputs (torch.cuda.max_memory_allocated).  Every shape runs in a child process of its own under a
+time limit; the first failure ends the run.  usage: python tools/time_depth_alpha.py [reps] [passes]"""
+import ctypes
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# (S, MPIs, planes, with backward)
+SHAPES = [("256", 8, 32, 1), ("512", 4, 32, 1), ("1024", 4, 32, 1), ("1024", 4, 96, 0)]
+N_Z_BINS = (4, 256)
+
+
+def one(S, B, D, n_z_bins, with_backward, reps):
+    import torch
+    sys.path.insert(0, ROOT)
+    import ml_gmpi_amd
+    from ml_gmpi_amd import _lib, depth_alpha_bounds, depth_alpha_planes, expand_depth_alpha
+    from ml_gmpi_amd.hip_mpi import _depth_alpha, _shared_color
+    lib = _lib.load_library()
+    dev = torch.device("cuda:0")
+    cs = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn, n=reps):
+        for _ in range(3):
+            fn()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        for e0, e1 in evs:
+            e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return sorted(a.elapsed_time(b) for a, b in evs)[n // 2]   # median
+
+    r = ml_gmpi_amd.make_renderer("FFHQ", n_planes=D, device=dev, on_out_of_plane="raise")
+    r.set_cam(r.cam_fov, S, S)
+    g = torch.Generator(device=dev).manual_seed(7000)
+    rgb = torch.rand((B, 3, S, S), device=dev, generator=g)
+    bg = torch.rand((B, 3, S, S), device=dev, generator=g)
+    # a smooth surface with texel noise between the planes: 5 x 5 noise upsampled to 0.15 + 0.7 c, + 0.02 (U - 0.5)
+    coarse = torch.rand((B, 1, 5, 5), device=dev, generator=g)
+    depth = 0.15 + 0.7 * torch.nn.functional.interpolate(coarse, size=(S, S), mode="bilinear", align_corners=True)
+    depth = (depth + 0.02 * (torch.rand((B, 1, S, S), device=dev, generator=g) - 0.5)).contiguous()
+    plane_z = torch.linspace(0, 1, D, device=dev)
+    zb = depth_alpha_bounds(1, n_z_bins)
+    gc = torch.randn((B, 3, S, S), device=dev, generator=g)
+    gd = torch.randn((B, 1, S, S), device=dev, generator=g)
+    torch.manual_seed(3)
+    cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
+    ray, eye, zd = torch.cat(cam[3]), torch.cat(cam[4]), torch.cat(cam[5])
+    dhw = r._dhw_on_device().expand(B, -1, -1).contiguous()
+    kw = dict(check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True)
+    out = {k: torch.empty(s, device=dev) for k, s in (("color", (B, 3, S, S)), ("depth", (B, 1, S, S)), ("T", (B, 1, S, S)))}
+    s3 = lambda t, dims: (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
+    base_mem = torch.cuda.memory_allocated(dev)
+    row = dict(S=S, B=B, D=D, n_z_bins=n_z_bins)
+
+    def backward_struct(p):
+        q = _lib.GmpiRenderParams.from_buffer_copy(p)
+        q.rgb_out = q.depth_out = q.status = None
+        return q
+
+    # ---- volume: the expanded volume through the volume kernels --------------------------------------------------------------------------------
+    torch.cuda.reset_peak_memory_stats(dev)
+    ins = [t.clone().requires_grad_(True) for t in (rgb, depth, bg)] if with_backward else [rgb, depth, bg]
+    vol_graph = expand_depth_alpha(ins[0], ins[1], plane_z, *zb, ins[2])
+    vol = vol_graph.detach()
+    with torch.no_grad():
+        res = r.mpi.render_views(vol, dhw, ray, eye, zd, out=out, _in_autograd_fn=True, **kw)
+    p = res.pop("_bwd")[0]
+    frac_T = float((out["T"] < 1e-30).float().mean())   # pixels whose forward transmittance underflows: the backward re-walks those
+    if with_backward:
+        pb = backward_struct(p)
+        grad = torch.zeros_like(vol)
+        gs = (ctypes.c_int64 * 5)(*grad.stride())
+        bwd = lambda: _lib.check(lib.gmpi_mpi_render_backward_launch(ctypes.byref(pb), gc.data_ptr(), gd.data_ptr(), grad.data_ptr(), gs, cs), "backward")
+        bwd()
+        through_expand = lambda: torch.autograd.grad(vol_graph, ins, grad, retain_graph=True)
+        through_expand()
+    torch.cuda.synchronize()
+    row["volume_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    with torch.no_grad():
+        row["volume_expand"] = timed(lambda: expand_depth_alpha(rgb, depth, plane_z, *zb, bg))
+        row["volume_fwd"] = timed(lambda: r.mpi.render_views(vol, dhw, ray, eye, zd, out=out, **kw))
+    if with_backward:
+        row["volume_fill"] = timed(lambda: grad.zero_())
+        row["volume_bwd"] = timed(bwd)
+        row["volume_expand_bwd"] = timed(through_expand)
+        del grad, bwd, through_expand
+    del vol, vol_graph, res, p, ins
+    torch.cuda.empty_cache()
+    assert torch.cuda.memory_allocated(dev) - base_mem <= 4 * out["color"].numel() * 8, "the volume is still alive"
+
+    # ---- shared: the alpha planes materialised, shared-colour kernels ---------------------------------------------------------------------------
+    torch.cuda.reset_peak_memory_stats(dev)
+    dep_in = depth.clone().requires_grad_(True) if with_backward else depth
+    alpha_graph = depth_alpha_planes(dep_in, plane_z, *zb)
+    alpha = alpha_graph.detach()
+    with torch.no_grad():
+        res = r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, _in_autograd_fn=True, **kw)
+    p = res.pop("_bwd")[0]
+    sc = _shared_color(rgb, bg)
+    if with_backward:
+        ps = backward_struct(p)
+        g_rgb, g_alpha, g_bg = torch.zeros_like(rgb), torch.zeros_like(alpha), torch.zeros_like(bg)
+        st = (s3(g_rgb, (0, 1, 2)), s3(g_alpha, (0, 1, 3)), s3(g_bg, (0, 1, 2)))
+        sbwd = lambda: _lib.check(lib.gmpi_mpi_render_shared_backward_launch(
+            ctypes.byref(ps), ctypes.byref(sc), gc.data_ptr(), gd.data_ptr(), None, g_rgb.data_ptr(), st[0], g_alpha.data_ptr(), st[1], g_bg.data_ptr(), st[2], cs),
+            "shared backward")
+        sbwd()
+        through_ramp = lambda: torch.autograd.grad(alpha_graph, dep_in, g_alpha, retain_graph=True)
+        through_ramp()
+    torch.cuda.synchronize()
+    row["shared_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    with torch.no_grad():
+        row["shared_planes"] = timed(lambda: depth_alpha_planes(depth, plane_z, *zb))
+        row["shared_fwd"] = timed(lambda: r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, **kw))
+    if with_backward:
+        row["shared_fill"] = timed(lambda: (g_rgb.zero_(), g_alpha.zero_(), g_bg.zero_()))
+        row["shared_bwd"] = timed(sbwd)
+        row["shared_planes_bwd"] = timed(through_ramp)
+        del g_alpha, sbwd, through_ramp
+    del alpha, alpha_graph, res, p, dep_in
+    torch.cuda.empty_cache()
+
+    # ---- depth: the new path ---------------------------------------------------------------------------------------------------------------------
+    torch.cuda.reset_peak_memory_stats(dev)
+    with torch.no_grad():
+        res = r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, _in_autograd_fn=True, **kw)
+    p = res.pop("_bwd")[0]
+    da = _depth_alpha(plane_z, *zb)
+    if with_backward:
+        pd = backward_struct(p)
+        d_rgb, d_dep, d_bg = torch.zeros_like(rgb), torch.zeros_like(depth), torch.zeros_like(bg)
+        st = (s3(d_rgb, (0, 1, 2)), s3(d_dep, (0, 1, 2)), s3(d_bg, (0, 1, 2)))
+        dbwd = lambda: _lib.check(lib.gmpi_mpi_render_depth_backward_launch(
+            ctypes.byref(pd), ctypes.byref(sc), ctypes.byref(da), gc.data_ptr(), gd.data_ptr(), None, d_rgb.data_ptr(), st[0], d_dep.data_ptr(), st[1],
+            d_bg.data_ptr(), st[2], cs), "depth backward")
+        dbwd()
+    torch.cuda.synchronize()
+    row["depth_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    with torch.no_grad():
+        row["depth_fwd"] = timed(lambda: r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, **kw))
+    if with_backward:
+        row["depth_fill"] = timed(lambda: (d_rgb.zero_(), d_dep.zero_(), d_bg.zero_()))
+        row["depth_bwd"] = timed(dbwd)
+        row["volume_total"] = row["volume_expand"] + row["volume_fwd"] + row["volume_fill"] + row["volume_bwd"] + row["volume_expand_bwd"]
+        row["shared_total"] = row["shared_planes"] + row["shared_fwd"] + row["shared_fill"] + row["shared_bwd"] + row["shared_planes_bwd"]
+        row["depth_total"] = row["depth_fwd"] + row["depth_fill"] + row["depth_bwd"]
+    row["fwd_vs_volume"] = row["depth_fwd"] / (row["volume_expand"] + row["volume_fwd"])
+    row["fwd_vs_shared"] = row["depth_fwd"] / (row["shared_planes"] + row["shared_fwd"])
+    row["fwd_vs_auto_on_existing_volume"] = row["depth_fwd"] / row["volume_fwd"]
+    row["T_underflow_frac"] = frac_T
+    try:
+        clock = f"{torch.cuda.clock_rate()} MHz"
+    except Exception:  # noqa: BLE001 -- no SMI binding in this torch
+        clock = "n/a"
+    print("ROW " + " ".join(f"{k}={v:.3f}" if isinstance(v, float) else f"{k}={v}" for k, v in row.items()) + f" device={torch.cuda.get_device_name(0)!r} clock={clock}",
+          flush=True)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--one":
+        S, B, D, n, bw, reps = sys.argv[2:8]
+        one(int(S), int(B), int(D), int(n), int(bw), int(reps))
+        sys.exit(0)
+    reps = sys.argv[1] if len(sys.argv) > 1 else "15"
+    passes = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape;", passes, "passes")
+    for k in range(passes):
+        print(f"== pass {k + 1} ==", flush=True)
+        for S, B, D, bw in SHAPES:
+            for n in N_Z_BINS:
+                try:
+                    rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), str(n), str(bw), reps], timeout=240).returncode
+                except subprocess.TimeoutExpired:   # (run() has killed the child)
+                    rc = "time limit of 240 s"
+                if rc != 0:
+                    print(f"shape {S} x {B} x {D} n_z_bins {n}: exit status {rc}; stopping")
+                    sys.exit(1)
