@@ -345,8 +345,8 @@ typedef struct GmpiDepthAlpha {
  * One kernel, one pixel per lane, taps from global memory (any shape, any stride, any ray field): GMPI_VARIANT_AUTO and GMPI_VARIANT_GATHER run
  * it, any other variant is GMPI_E_VARIANT.  z_lo >= z_hi or z_den <= 0 (or a NaN among them): GMPI_E_SHAPE; a negative plane_z_stride:
  * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
- * never synchronises.  Not built: staged / tile variants, 8-bit storage, gradients w.r.t. the geometry, skipping planes from a depth min/max
- * pre-pass (gmpi_query(22) says whether the layout itself is built in).
+ * never synchronises.  Not built: a staged / tile forward (the backward has a tile entry, below), 8-bit storage, gradients w.r.t. the geometry,
+ * skipping planes from a depth min/max pre-pass (gmpi_query(22) says whether the layout itself is built in).
  */
 int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
 
@@ -367,6 +367,24 @@ int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams *params, const 
                                           float *grad_shared_rgb, const int64_t *grad_shared_rgb_stride, float *grad_depth_image,
                                           const int64_t *grad_depth_image_stride, float *grad_background, const int64_t *grad_background_stride,
                                           void *stream);
+
+/*
+ * gmpi_mpi_render_depth_backward_launch with a tile kernel: same arguments, same checks, same error codes, same gradients up to the order of the
+ * adds.  One workgroup per 32 x 16 pixel tile; the gradients of the colour image AND of the depth image are summed in LDS across the planes, in one
+ * window of 64 x 32 texels x 4 channels (64-bit fixed point), which is flushed -- one atomicAdd per non-zero texel -- whenever the tile's texel boxes
+ * have drifted out of it, and at the end of the tile; with a background, the colour channels once more after the last plane.  There is no per-plane
+ * flush: all D alpha planes have one destination.  Routing: GMPI_VARIANT_GATHER launches the one-pixel-per-lane kernel of
+ * gmpi_mpi_render_depth_backward_launch; so does D > gmpi_query(23) = 128 (more planes than the tile kernel's table holds), several times slower with
+ * a wide ramp; everything else (GMPI_VARIANT_AUTO) launches the tile kernel.  Any other variant is GMPI_E_VARIANT.  The texel boxes assume a pinhole
+ * ray field (see ray_dir above); this is NOT checked: a pixel whose taps fall outside its tile's box adds them straight to global memory, and so
+ * does a tile whose box on a plane exceeds the window (strong minification) and a value outside the fixed-point range (colours far outside [0, 1],
+ * non-finite gradients): any input gives the one-pixel kernel's gradients, an irregular one at its speed.
+ */
+int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                               const float *grad_rgb_out, const float *grad_depth, const float *grad_transmittance,
+                                               float *grad_shared_rgb, const int64_t *grad_shared_rgb_stride, float *grad_depth_image,
+                                               const int64_t *grad_depth_image_stride, float *grad_background,
+                                               const int64_t *grad_background_stride, void *stream);
 
 /*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the
@@ -487,7 +505,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * a multiple of 4 texels before it is held against 13); 15 is unused (-1); the staged kernel for GMPI_DTYPE_U8 volumes: 16 its pixel-tile width (a tile
  * is 512 / width pixels high), 17 the texels per row and 18 the rows its staging buffer holds per plane (first column rounded down to a multiple of 4
  * texels, as for 13); 19 is unused (-1); 20 whether the interleaved GMPI_DTYPE_U8 layout (GmpiRenderParams.rgba_stride) is built in; 21 is unused (-1);
- * 22 whether the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in.  Unknown -> -1.                                        */
+ * 22 whether the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in; 23 the number of planes the depth-alpha tile backward
+ * (gmpi_mpi_render_depth_backward_tile_launch) takes: more go to the one-pixel-per-lane kernel.  Unknown -> -1.                        */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

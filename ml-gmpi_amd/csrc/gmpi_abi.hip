@@ -32,6 +32,9 @@ bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh);   
 int shared_forward_query(int what);                                         // render_shared_forward.hip
 hipError_t launch_depth(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, hipStream_t stream);   // render_depth.hip
 hipError_t launch_depth_backward(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth.hip
+hipError_t launch_depth_backward_tile(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth_tile.hip
+bool depth_tile_supports(const KParams& p);                                 // render_depth_tile.hip
+int depth_tile_planes();                                                    // render_depth_tile.hip
 hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
 bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
 int u8_variant_query(int what);                                             // render_u8.hip
@@ -631,10 +634,11 @@ int gmpi_mpi_render_depth_launch(const GmpiRenderParams* params, const GmpiShare
     return hip_rc(launch_depth(p, params->rgba_dtype, sh, dk, static_cast<hipStream_t>(stream)));
 }
 
-int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
-                                          const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
-                                          const int64_t* grad_shared_rgb_stride, float* grad_depth_image, const int64_t* grad_depth_image_stride,
-                                          float* grad_background, const int64_t* grad_background_stride, void* stream) {
+// Both depth-alpha backward entries: one argument check, one marshalling; `tile`: the entry that may launch the tile kernel.
+static int depth_backward(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, const float* grad_rgb_out,
+                          const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride,
+                          float* grad_depth_image, const int64_t* grad_depth_image_stride, float* grad_background, const int64_t* grad_background_stride,
+                          void* stream, bool tile) {
     KParams p;
     SharedK sh;
     DepthK dk;
@@ -646,7 +650,26 @@ int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams* params, const 
     rc = to_shared_grads(params, p, sh, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride, grad_depth_image,
                          grad_depth_image_stride != nullptr ? gd_stride : nullptr, grad_background, grad_background_stride, g);
     if (rc != GMPI_OK || p.N == 0) return rc;
+    // the tile kernel's box table holds 128 planes (gmpi_query(23)): more take the one-pixel-per-lane kernel, and so does GATHER by name
+    if (tile && params->variant != GMPI_VARIANT_GATHER && depth_tile_supports(p))
+        return hip_rc(launch_depth_backward_tile(p, params->rgba_dtype, sh, dk, g, static_cast<hipStream_t>(stream)));
     return hip_rc(launch_depth_backward(p, params->rgba_dtype, sh, dk, g, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_depth_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                          const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
+                                          const int64_t* grad_shared_rgb_stride, float* grad_depth_image, const int64_t* grad_depth_image_stride,
+                                          float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    return depth_backward(params, shared, depth_alpha, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride,
+                          grad_depth_image, grad_depth_image_stride, grad_background, grad_background_stride, stream, false);
+}
+
+int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                               const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
+                                               const int64_t* grad_shared_rgb_stride, float* grad_depth_image, const int64_t* grad_depth_image_stride,
+                                               float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    return depth_backward(params, shared, depth_alpha, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride,
+                          grad_depth_image, grad_depth_image_stride, grad_background, grad_background_stride, stream, true);
 }
 
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {
@@ -768,6 +791,7 @@ int gmpi_query(int32_t what) {
         case 12: case 13: case 14: return shared_forward_query(what);
         case 16: case 17: case 18: case 20: return u8_variant_query(what);  // (15, 19: unused)
         case 22: return 1;  // the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in  (21: unused)
+        case 23: return depth_tile_planes();  // planes the depth-alpha tile backward takes (more: the one-pixel-per-lane kernel)
         default: return -1;
     }
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "gmpi_backward.hpp"
 #include "gmpi_device.hpp"
 
 namespace gmpi {
@@ -93,6 +94,43 @@ __device__ __forceinline__ RampTaps ramp_taps(const TexT* __restrict__ depth, in
     r.a[0] = depth_ramp<STRICT>(pz, d_nw, dk, r.in[0]), r.a[1] = depth_ramp<STRICT>(pz, d_ne, dk, r.in[1]);
     r.a[2] = depth_ramp<STRICT>(pz, d_sw, dk, r.in[2]), r.a[3] = depth_ramp<STRICT>(pz, d_se, dk, r.in[3]);
     return r;
+}
+
+// d times each of four tap weights added to the texels of a footprint.  THE WEIGHT GATES THE ADDRESS, as in render_shared.hip's scatter4: make_taps
+// zeroes the weight of a tap outside the texture and leaves x0 / y0 unclamped (-2 .. Wt, -2 .. Ht), so only a tap whose weight is not zero may be
+// written -- whatever d is (a NaN or infinite gradient times a zero weight is NaN, never a reason to write).  A term that is exactly zero costs no
+// atomic either.
+__device__ __forceinline__ void add_taps(float* __restrict__ ch, int64_t s_row, const Footprint& f, float d, float w_nw, float w_ne, float w_sw, float w_se) {
+    const int64_t oa = static_cast<int64_t>(f.y0) * s_row + f.x0, ob = oa + s_row;
+    const float v_nw = d * w_nw, v_ne = d * w_ne, v_sw = d * w_sw, v_se = d * w_se;
+    if (w_nw != 0.0f && v_nw != 0.0f) atomicAdd(ch + oa, v_nw);
+    if (w_ne != 0.0f && v_ne != 0.0f) atomicAdd(ch + oa + 1, v_ne);
+    if (w_sw != 0.0f && v_sw != 0.0f) atomicAdd(ch + ob, v_sw);
+    if (w_se != 0.0f && v_se != 0.0f) atomicAdd(ch + ob + 1, v_se);
+}
+
+// The final transmittance the depth-alpha backward sweeps start from (bwd_pixel_setup_with's `total`; both backward kernels of the layout call this
+// one text): the forward's value when it is usable (total_transmittance's rule), else a front-to-back walk over the RAMP samples in the extended
+// representation -- total_transmittance reads alpha planes, which do not exist here.  bp: the pixel's ray (set before `total` is called).
+template <typename TexT, bool AC>
+__device__ __forceinline__ XT depth_total_transmittance(const KParams& p, const BwdView& vw, const BwdPixel& bp, const TexT* __restrict__ depth,
+                                                        const float* __restrict__ pz, const DepthK& dk, float t_fwd) {
+    XT t{1.0f, 0};
+    if (p.T_out != nullptr && t_fwd >= 1e-30f) {   // the forward's value is usable (total_transmittance's rule)
+        t.m = t_fwd;
+        t.renorm();
+        return t;
+    }
+    for (int k = 0; k < p.D; ++k) {
+        float ix, iy, s;
+        pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
+        const Taps tp = make_taps(ix, iy, p.Ht, p.Wt);
+        const RampTaps r = ramp_taps<TexT, false>(depth, p.s_row, tp, pz[k], dk);
+        const float a = bilerp<false>(r.a[0], r.a[1], r.a[2], r.a[3], tp.f);
+        t.m *= (1.0f - a) + 1e-10f;
+        t.renorm();
+    }
+    return t;
 }
 
 }  // namespace gmpi

@@ -65,19 +65,8 @@ __global__ __launch_bounds__(256) void render_depth_kernel(const KParams p, cons
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------------------------
-// d times each of four tap weights added to the texels of a footprint.  THE WEIGHT GATES THE ADDRESS, as in render_shared.hip's scatter4: make_taps
-// zeroes the weight of a tap outside the texture and leaves x0 / y0 unclamped (-2 .. Wt, -2 .. Ht), so only a tap whose weight is not zero may be
-// written -- whatever d is (a NaN or infinite gradient times a zero weight is NaN, never a reason to write).  A term that is exactly zero costs no
-// atomic either.
-__device__ __forceinline__ void add_taps(float* __restrict__ ch, int64_t s_row, const Footprint& f, float d, float w_nw, float w_ne, float w_sw, float w_se) {
-    const int64_t oa = static_cast<int64_t>(f.y0) * s_row + f.x0, ob = oa + s_row;
-    const float v_nw = d * w_nw, v_ne = d * w_ne, v_sw = d * w_sw, v_se = d * w_se;
-    if (w_nw != 0.0f && v_nw != 0.0f) atomicAdd(ch + oa, v_nw);
-    if (w_ne != 0.0f && v_ne != 0.0f) atomicAdd(ch + oa + 1, v_ne);
-    if (w_sw != 0.0f && v_sw != 0.0f) atomicAdd(ch + ob, v_sw);
-    if (w_se != 0.0f && v_se != 0.0f) atomicAdd(ch + ob + 1, v_se);
-}
-
+// (add_taps -- d times each of four tap weights, THE WEIGHT GATES THE ADDRESS -- and depth_total_transmittance live in gmpi_shared.hpp: the tile
+// backward, render_depth_tile.hip, runs the same two texts.)
 // The sweep starts from the pixel's final transmittance.  Behind the surface every plane is (almost) exactly opaque, om = 1e-10 per plane: the
 // forward's T_out underflows for most pixels of this layout, so the front-to-back re-walk in the extended representation (XT) is the
 // common path here.  It walks the ramp samples (total_transmittance reads alpha planes, which do not exist).
@@ -103,24 +92,8 @@ __global__ __launch_bounds__(256) void render_depth_backward_kernel(const KParam
     float* __restrict__ g_dep = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
 
     BwdPixel bp;
-    bwd_pixel_setup_with<false>(bp, p, vw, n, px, py, true, g.g_out, g.g_depth, g.g_T, [&](float t_fwd) {
-        XT t{1.0f, 0};
-        if (p.T_out != nullptr && t_fwd >= 1e-30f) {   // the forward's value is usable (total_transmittance's rule)
-            t.m = t_fwd;
-            t.renorm();
-            return t;
-        }
-        for (int k = 0; k < D; ++k) {
-            float ix, iy, s;
-            pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
-            const Taps tp = make_taps(ix, iy, Ht, Wt);
-            const RampTaps r = ramp_taps<TexT, false>(depth, p.s_row, tp, pz[k], dk);
-            const float a = bilerp<false>(r.a[0], r.a[1], r.a[2], r.a[3], tp.f);
-            t.m *= (1.0f - a) + 1e-10f;
-            t.renorm();
-        }
-        return t;
-    });
+    bwd_pixel_setup_with<false>(bp, p, vw, n, px, py, true, g.g_out, g.g_depth, g.g_T,
+                                [&](float t_fwd) { return depth_total_transmittance<TexT, AC>(p, vw, bp, depth, pz, dk, t_fwd); });
     for (int k = D - 1; k >= 0; --k) {
         float ix, iy, s;
         pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);

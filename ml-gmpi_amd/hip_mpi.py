@@ -589,7 +589,7 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _shared=None, _shared_variant: Optional[str] = None, _depth=None):
+                     _shared=None, _shared_variant: Optional[str] = None, _depth=None, _depth_backward: str = "pixel"):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -624,6 +624,7 @@ class MPI(nn.Module):
                     kwargs["_shared_variant"] = _shared_variant
                 if _depth is not None:
                     kwargs["_depth"] = _depth
+                    kwargs["_depth_backward"] = _depth_backward   # (read by _DepthRenderFunction; the forward does not depend on it)
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -782,11 +783,21 @@ class MPI(nn.Module):
         reaches rgb, depth and background in their own dtypes (gmpi_mpi_render_depth_backward_launch: the gradient of all D alpha planes lands in
         the one depth image); none w.r.t. plane_z or the geometry (NotImplementedError with geometry_grad=True and a camera / dhw tensor that
         requires grad).  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
-        background (a depth image is no [0, 1] tensor); "touched" also sets the range bit for a NaN depth some pixel samples."""
-        assert "_shared" not in kwargs and "_depth" not in kwargs
+        background (a depth image is no [0, 1] tensor); "touched" also sets the range bit for a NaN depth some pixel samples.
+        `depth_backward`: "pixel" (the default) back-propagates with the one-pixel-per-lane kernel; "tile" with
+        gmpi_mpi_render_depth_backward_tile_launch -- one workgroup per 32 x 16 pixel tile, the gradients of rgb and depth summed in LDS across
+        the planes: the same gradients up to the order of the adds.  The tile backward assumes a pinhole ray field like the other staged kernels
+        (any other gives correct gradients at the one-pixel kernel's speed) and takes D <= 128; with more planes, or with the "gather" variant,
+        the entry launches the one-pixel-per-lane kernel.  Any other name: ValueError.  The forward does not depend on it."""
+        assert "_shared" not in kwargs and "_depth" not in kwargs and "_depth_backward" not in kwargs
         variant = kwargs.pop("variant", None)   # (None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
         if variant not in (None, "auto", "gather"):
             raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
+        depth_backward = kwargs.pop("depth_backward", "pixel")
+        if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
+            raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
+        if depth_backward != "pixel":   # (the default: exactly the call without the argument)
+            kwargs["_depth_backward"] = depth_backward
         depth5, shared, depth_alpha = _depth_operands(rgb, depth, plane_z, z_bounds, background, dhw.shape[1])
         return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _shared=shared, _shared_variant=variant, _depth=depth_alpha, **kwargs)
 
@@ -983,12 +994,18 @@ class _SharedRenderFunction(torch.autograd.Function):
         return out[0], out[1], out[2], None, None, None, None, None, None
 
 
+# render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
+_DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch"}
+
+
 class _DepthRenderFunction(torch.autograd.Function):
     """autograd bridge of the depth-alpha render, built like `_SharedRenderFunction`: forward = gmpi_mpi_render_depth_launch, backward =
-    gmpi_mpi_render_depth_backward_launch into zero-filled fp32 gradients of rgb, the depth image and the background."""
+    gmpi_mpi_render_depth_backward_launch (depth_backward="tile": gmpi_mpi_render_depth_backward_tile_launch) into zero-filled fp32 gradients of
+    rgb, the depth image and the background."""
 
     @staticmethod
     def forward(ctx, rgb, depth, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+        ctx.backward_entry = _DEPTH_BACKWARD_ENTRIES[kwargs.get("_depth_backward", "pixel")]
         res, keep, (rgb_d, bg_d) = _bridge_forward(ctx, mpi, depth, (dhw, ray_dir, eye_pos, z_dir), kwargs, shared=(rgb, background))
         ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
         plane_z, ctx.z_lo, ctx.z_hi = kwargs["_depth"]
@@ -1016,7 +1033,7 @@ class _DepthRenderFunction(torch.autograd.Function):
             if t is None:
                 return None, None
             return t.data_ptr(), (ctypes.c_int64 * 3)(*t.stride()[:3])
-        _call("gmpi_mpi_render_depth_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
+        _call(ctx.backward_entry, dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
               ctypes.byref(_depth_alpha(plane_z, ctx.z_lo, ctx.z_hi)), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T),
               *ptr_stride(grads[0]), *ptr_stride(grads[1]), *ptr_stride(grads[2]))
         out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]

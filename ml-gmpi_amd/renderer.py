@@ -421,6 +421,7 @@ class MPIRenderer:
         shared = ext.pop("_shared", None)   # render_shared: (rgb, background or None); batch_mpi_rgbas is then the alpha tensor
         shared_variant = ext.pop("_shared_variant", None)
         depth_alpha = ext.pop("_depth", None)   # render_depth: (plane_z, z_lo, z_hi); batch_mpi_rgbas is then the depth image [B,1,1,Ht,Wt]
+        depth_backward = ext.pop("_depth_backward", None)   # render_depth(depth_backward="tile")
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -463,7 +464,8 @@ class MPIRenderer:
             batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
             check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
             c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}), **({} if depth_alpha is None else {"_depth": depth_alpha}))
+            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}), **({} if depth_alpha is None else {"_depth": depth_alpha}),
+            **({} if depth_backward is None else {"_depth_backward": depth_backward}))
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
@@ -488,9 +490,17 @@ class MPIRenderer:
         without building it (the output of GMPI's "depth2alpha" generator): batch_rgb [B,3,Ht,Wt], batch_depth [B,1,Ht,Wt], background_rgb
         [B,3,Ht,Wt] or None = the last plane's own colour.  plane_z [D] or [B,D]: None takes this renderer's normalised plane depths,
         `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with.  Keyword arguments, return tuple, pose
-        sampling and the consumption of the torch RNG are `render`'s."""
+        sampling and the consumption of the torch RNG are `render`'s.  `depth_backward`: "pixel" (default) or "tile", as in
+        `MPI.render_views_depth` -- the tile backward assumes a pinhole ray field (this renderer's rays are one) and takes D <= 128, else the
+        one-pixel-per-lane kernel runs; any other name is a ValueError before anything is launched."""
         from .depth_alpha import depth_alpha_bounds
-        from .hip_mpi import _depth_operands
+        from .hip_mpi import _DEPTH_BACKWARD_ENTRIES, _depth_operands
+        depth_backward = kwargs.pop("depth_backward", "pixel")
+        if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
+            raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
+        assert "_depth_backward" not in kwargs
+        if depth_backward != "pixel":
+            kwargs["_depth_backward"] = depth_backward
         if plane_z is None:
             plane_z = self.get_xyz_single_res(batch_depth.shape[-2], batch_depth.shape[-1], only_z=True)[1].reshape(-1)
         assert "_shared" not in kwargs and "_depth" not in kwargs

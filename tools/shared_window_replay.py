@@ -1,7 +1,13 @@
 """CPU replay of the colour window of render_shared_tile_kernel (ml-gmpi_amd/csrc/render_shared.hip): per 32 x 16 pixel tile the texel boxes of the
 planes (from the tile's corner pixels, fp32 coordinate chain), the `inside` test and the re-anchor rule, and from them how often a tile flushes
 its colour window to global memory -- at the shapes and poses tools/time_shared_color.py times (FFHQ preset, 32 planes, torch.manual_seed(3)) and
-at the 2-sigma corner of the pose range.  No GPU needed.  usage: python tools/shared_window_replay.py"""
+at the 2-sigma corner of the pose range.  No GPU needed.  usage: python tools/shared_window_replay.py [--window WxH] [--box WxH] [--one-window]
+
+--window / --box: the window and the largest staged box in texels (defaults: the shared kernel's 64x32 and 56x27).  --one-window replays
+render_depth_tile_kernel (ml-gmpi_amd/csrc/render_depth_tile.hip): the box limit is the window itself unless --box is given, and the background's
+flush after the last plane empties the colour channels only -- the window stays filled (its depth channel), so that flush is not counted as a
+window flush: with a background every tile has one colour-channel flush on top of the counts printed."""
+import argparse
 import os
 import sys
 
@@ -41,8 +47,9 @@ def boxes(dhw, ray, eye, S):
     return out
 
 
-def flushes(bb, background):
-    """bb [D, 4] of one tile -> number of non-empty flushes of the colour window (the kernel's sweep, every gradient wanted)."""
+def flushes(bb, background, one_window=False):
+    """bb [D, 4] of one tile -> number of non-empty flushes of the colour window (the kernel's sweep, every gradient wanted).  one_window: the
+    background's flush leaves the window filled (render_depth_tile_kernel) and is not counted."""
     D = bb.shape[0]
     wx0 = wy0 = 0
     is_open = filled = False
@@ -59,15 +66,33 @@ def flushes(bb, background):
                 wy0 = y + ny - CH if (front[2] > 0 and front[1] < y) else y
                 is_open = True
             filled = True
-        if k == D - 1 and background and is_open and D > 1:
+        if k == D - 1 and background and is_open and D > 1 and not one_window:
             count += filled
             filled = False
     return count + filled
 
 
 def main():
+    global AP, AR, CW, CH
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window", default=None, help="WxH of the window in texels")
+    ap.add_argument("--box", default=None, help="WxH of the largest box that is staged")
+    ap.add_argument("--one-window", action="store_true", help="replay render_depth_tile_kernel: one window for colour and depth")
+    args = ap.parse_args()
+    if args.window:
+        CW, CH = (int(v) for v in args.window.lower().split("x"))
+    if args.one_window:
+        AP, AR = CW, CH
+    if args.box:
+        AP, AR = (int(v) for v in args.box.lower().split("x"))
+    assert AP <= CW and AR <= CH, "a staged box must fit the window"
+    one_window = args.one_window
     D = 32
-    print("colour-window flushes per tile (non-empty flushes of the 64 x 32 window; alpha is flushed once per plane on top), D = 32, FFHQ preset")
+    if one_window:
+        print(f"window flushes per tile (non-empty flushes of the {CW} x {CH} window, all four channels; boxes up to {AP} x {AR} are staged; with a background one "
+              "flush of the colour channels on top), D = 32, FFHQ preset")
+    else:
+        print(f"colour-window flushes per tile (non-empty flushes of the {CW} x {CH} window; alpha is flushed once per plane on top), D = 32, FFHQ preset")
     print(f"{'case':34s} {'tiles':>6s} {'mean':>6s} {'max':>4s} {'tiles with 1 / 2 flushes':>26s} {'not staged planes':>18s}")
     for S, B, extreme in ((256, 8, False), (512, 4, False), (1024, 4, False), (256, 2, True), (512, 2, True), (1024, 2, True)):
         kw = dict(PRESETS["FFHQ"])
@@ -87,7 +112,7 @@ def main():
         dhw = r.static_mpi_plane_dhws.reshape(-1, 3).numpy()
         bb = boxes(dhw, ray, eye, S)
         for background in (True, False):
-            cnt = np.array([flushes(bb[n, :, t], background) for n in range(bb.shape[0]) for t in range(bb.shape[2])])
+            cnt = np.array([flushes(bb[n, :, t], background, one_window) for n in range(bb.shape[0]) for t in range(bb.shape[2])])
             name = f"{S}^2 x {B} {'2-sigma poses' if extreme else 'timed poses'} {'bg' if background else 'no bg'}"
             print(f"{name:34s} {cnt.size:6d} {cnt.mean():6.2f} {cnt.max():4d} {(cnt == 1).sum():12d} / {(cnt == 2).sum():<11d} {int((bb[..., 2] == 0).sum()):18d}")
         if not extreme:

@@ -4,6 +4,10 @@ and 1024^2 x 32 x 4 in fp32 the forward and the whole step (forward, zero-fill, 
 several planes wide) and 256 (a step).
 
   depth    the new path: forward, zero-fill of the three gradient images, backward (render_depth.hip: one pixel per lane, both)
+  depth, tile backward    the same forward and zero-fill with gmpi_mpi_render_depth_backward_tile_launch (render_depth_tile.hip: one workgroup per
+           32 x 16 pixel tile, one LDS window for all planes): columns `depth_bwd_tile`, `depth_total_tile`.  The two depth backwards are timed
+           ALTERNATELY in the same child (pixel, tile, pixel, tile, ...), and their gradients are compared per image (`tile_check`: the largest
+           |tile - pixel| / (1e-5 max|pixel| + 1e-7) over the three images, <= 1 passes; a failure ends the run)
   volume   expand_depth_alpha (the ramp + the generator's expand and two cat), forward (variant auto), zero-fill of the volume gradient, volume backward
            (tile kernels), autograd through the expand (plane sums of the colour gradient, the clamp's mask and the plane sum for the depth)
   shared   the alpha planes materialised (depth_alpha_planes), render_views_shared (variant auto: one pixel per lane), zero-fill of the three gradients,
@@ -40,6 +44,16 @@ def one(S, B, D, n_z_bins, with_backward, reps):
             e0.record(); fn(); e1.record()
         torch.cuda.synchronize()
         return sorted(a.elapsed_time(b) for a, b in evs)[n // 2]   # median
+
+    def timed_alternately(fa, fb, n=reps):
+        for _ in range(3):
+            fa(); fb()
+        evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(n)]
+        for e0, e1, e2, e3 in evs:
+            e0.record(); fa(); e1.record()
+            e2.record(); fb(); e3.record()
+        torch.cuda.synchronize()
+        return sorted(e[0].elapsed_time(e[1]) for e in evs)[n // 2], sorted(e[2].elapsed_time(e[3]) for e in evs)[n // 2]
 
     r = ml_gmpi_amd.make_renderer("FFHQ", n_planes=D, device=dev, on_out_of_plane="raise")
     r.set_cam(r.cam_fov, S, S)
@@ -142,20 +156,30 @@ def one(S, B, D, n_z_bins, with_backward, reps):
         pd = backward_struct(p)
         d_rgb, d_dep, d_bg = torch.zeros_like(rgb), torch.zeros_like(depth), torch.zeros_like(bg)
         st = (s3(d_rgb, (0, 1, 2)), s3(d_dep, (0, 1, 2)), s3(d_bg, (0, 1, 2)))
-        dbwd = lambda: _lib.check(lib.gmpi_mpi_render_depth_backward_launch(
+        depth_backward = lambda entry: lambda: _lib.check(entry(
             ctypes.byref(pd), ctypes.byref(sc), ctypes.byref(da), gc.data_ptr(), gd.data_ptr(), None, d_rgb.data_ptr(), st[0], d_dep.data_ptr(), st[1],
             d_bg.data_ptr(), st[2], cs), "depth backward")
+        dbwd, dbwd_tile = depth_backward(lib.gmpi_mpi_render_depth_backward_launch), depth_backward(lib.gmpi_mpi_render_depth_backward_tile_launch)
+        # the results at the timed size: tile against one pixel per lane, per gradient image
         dbwd()
+        want = [t.clone() for t in (d_rgb, d_dep, d_bg)]
+        for t in (d_rgb, d_dep, d_bg):
+            t.zero_()
+        dbwd_tile()
+        row["tile_check"] = max(float((t - w).abs().max()) / (1e-5 * float(w.abs().max()) + 1e-7) for t, w in zip((d_rgb, d_dep, d_bg), want))
+        assert all(float(w.abs().max()) > 0 for w in want) and row["tile_check"] <= 1.0, ("tile backward against the one-pixel backward", row["tile_check"])
+        del want
     torch.cuda.synchronize()
     row["depth_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
     with torch.no_grad():
         row["depth_fwd"] = timed(lambda: r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, **kw))
     if with_backward:
         row["depth_fill"] = timed(lambda: (d_rgb.zero_(), d_dep.zero_(), d_bg.zero_()))
-        row["depth_bwd"] = timed(dbwd)
+        row["depth_bwd"], row["depth_bwd_tile"] = timed_alternately(dbwd, dbwd_tile)
         row["volume_total"] = row["volume_expand"] + row["volume_fwd"] + row["volume_fill"] + row["volume_bwd"] + row["volume_expand_bwd"]
         row["shared_total"] = row["shared_planes"] + row["shared_fwd"] + row["shared_fill"] + row["shared_bwd"] + row["shared_planes_bwd"]
         row["depth_total"] = row["depth_fwd"] + row["depth_fill"] + row["depth_bwd"]
+        row["depth_total_tile"] = row["depth_fwd"] + row["depth_fill"] + row["depth_bwd_tile"]
     row["fwd_vs_volume"] = row["depth_fwd"] / (row["volume_expand"] + row["volume_fwd"])
     row["fwd_vs_shared"] = row["depth_fwd"] / (row["shared_planes"] + row["shared_fwd"])
     row["fwd_vs_auto_on_existing_volume"] = row["depth_fwd"] / row["volume_fwd"]
