@@ -1,14 +1,18 @@
-// gmpi_backward.hpp -- the ONE home of what the backward kernels of the render share.  Eight kernels run the same back-to-front sweep
+// gmpi_backward.hpp -- the ONE home of what the backward kernels of the render share.  Nine kernels run the same back-to-front sweep
 // (render_backward.hip: one pixel per lane, tile, tile2; render_backward_gather.hip: pixel_pass; render_backward_geometry.hip: geometry_pixel;
-// render_shared.hip: shared_backward, shared_tile; render_depth.hip: depth_backward), and the claims of DESIGN.md section 3.3 -- the forward's quotients and texels, bit-reproducible
-// gather and geometry passes, gT entering S in every sweep -- hold because they all run THIS code:
+// render_shared.hip: shared_backward, shared_tile; render_depth.hip: depth_backward; render_depth_tile.hip: depth_tile), and the claims of DESIGN.md
+// section 3.3 -- the forward's quotients and texels, bit-reproducible gather and geometry passes, gT entering S in every sweep -- hold because they
+// all run THIS code:
 //   BwdView / bwd_view              what is uniform over a view: the forward's View / view_setup (gmpi_device.hpp)
 //   BwdPixel / bwd_pixel_setup(_with)   the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
 //   tile_box                        texel box of a pixel tile on one plane, from its four corner pixels
 //   cvt_rpi_i32, fix_split, to_fix, abs_bits, lds_barrier, wave_max_u32, wave_max_bits     the fixed-point and wave primitives of the staged scatters
-// A change to the sweep is made here, never in a kernel.
+//   the cross-plane tile frame      what shared_tile and depth_tile stage their cross-plane sums with: the tile constants (kTileW .. kTilePlanes, kCW, kCH),
+//                                   TileFrame / tile_frame / tile_frame_box / tile_grid, FixScale / fix_scale, lds_add_taps, MovingWindow and its flush
+//                                   (their tap prefetch, fetch_taps, knows the shared-colour structs and lives in gmpi_shared.hpp)
+// A change to the sweep or to the frame is made here, never in a kernel.
 #pragma once
 #include "gmpi_device.hpp"
 
@@ -294,5 +298,114 @@ __device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));
     return v;
 }
+
+// ---- the cross-plane tile frame -------------------------------------------------------------------------------------------------------------------
+// What render_shared_tile_kernel (render_shared.hip) and render_depth_tile_kernel (render_depth_tile.hip) share: one workgroup of kTileThreads lanes per
+// kTileW x kTileH pixel tile, the planes' texel boxes in a table of kTilePlanes entries, and gradients that belong to ONE image summed across the planes in
+// a window of kCW x kCH texels of 64-bit fixed-point words that moves with the boxes.  What a kernel keeps for itself: its LDS, its box limit, its
+// scales and destinations (the flush's sink) and its BARRIERS -- nothing here contains one; the kernels' headers say which barrier orders what.
+constexpr int kTileW = 32, kTileH = 16, kTileThreads = kTileW * kTileH;
+constexpr int kCW = 64, kCH = 32;      // the window, per channel (64-bit words: 16 KiB a channel)
+constexpr int kTilePlanes = 128;       // planes a tile launch can take (the box table; the bound on a cell's sum: 512 pixels x 128 planes = 2^16 terms)
+constexpr int kFixBits = 40;           // a staged term is scaled to below 2^41 (to_fix takes |w| < 2^43)
+inline bool tile_planes_fit(const KParams& p) { return p.D <= kTilePlanes; }
+
+// The tile and the pixel of this lane.  tile < 0: the workgroup is one of the grid's padding (the grid is a multiple of 8) and returns as a whole.
+struct TileFrame {
+    int tile, txi, tyi;
+    int px, py;               // this lane's pixel
+    bool active;              // ... lies inside the image
+    int cx0, cx1, cy0, cy1;   // the tile's corner pixels, clamped into the image
+};
+__device__ __forceinline__ TileFrame tile_frame(const KParams& p, int tiles_x) {
+    TileFrame t;
+    const int tid = threadIdx.x;
+    const int n_tiles = tiles_x * ((p.H + kTileH - 1) / kTileH);
+    const int tile = xcd_item_per_group(static_cast<int>(blockIdx.x), n_tiles, n_tiles);
+    t.tile = tile >= n_tiles ? -1 : tile;
+    t.tyi = tile / tiles_x, t.txi = tile - t.tyi * tiles_x;
+    t.px = t.txi * kTileW + (tid % kTileW), t.py = t.tyi * kTileH + (tid / kTileW);
+    t.active = t.px < p.W && t.py < p.H;
+    t.cx0 = t.txi * kTileW, t.cx1 = min(t.cx0 + kTileW - 1, p.W - 1);
+    t.cy0 = t.tyi * kTileH, t.cy1 = min(t.cy0 + kTileH - 1, p.H - 1);
+    return t;
+}
+// the tile's texel box on plane k of the view; staged (nx > 0) when it fits pitch x rows
+template <bool AC>
+__device__ __forceinline__ int4 tile_frame_box(const KParams& p, const BwdView& vw, const TileFrame& t, int k, int pitch, int rows) {
+    return tile_box<AC>(p, vw, vw.rays, vw.dhw[3 * k] - vw.ez, vw.dhw[3 * k + 1], vw.dhw[3 * k + 2], t.cx0, t.cx1, t.cy0, t.cy1, pitch, rows);
+}
+// host side: what tile_frame expects of the launch (grid.x tiles in xcd_item_per_group's order, grid.y views)
+struct TileGrid { int tiles_x, n_tiles; dim3 grid; };
+inline TileGrid tile_grid(const KParams& p) {
+    const int tiles_x = (p.W + kTileW - 1) / kTileW, n_tiles = tiles_x * ((p.H + kTileH - 1) / kTileH);
+    return TileGrid{tiles_x, n_tiles, dim3(xcd_grid_per_group(n_tiles, n_tiles), p.N)};
+}
+
+// The power-of-two scale of a fixed-point sum from max_bits = abs_bits of the largest term M: 2^(bits - e), e = floor(log2 M), so that a term is below
+// 2^(bits + 1).  stage: M is neither zero nor Inf / NaN; otherwise nothing is staged and scale = inv = 0.
+struct FixScale { bool stage; float scale, inv; };
+__device__ __forceinline__ FixScale fix_scale(uint32_t max_bits, int bits) {
+    const bool stage = max_bits != 0u && max_bits < 0x7f800000u;
+    const int shf = min(bits - (static_cast<int>(max_bits >> 23) - 127), 126);
+    return FixScale{stage, stage ? __builtin_amdgcn_ldexpf(1.0f, shf) : 0.0f, stage ? __builtin_amdgcn_ldexpf(1.0f, -shf) : 0.0f};
+}
+// d times each of four tap weights added to the 2 x 2 cells at `cell` of an LDS array of 64-bit fixed-point words: the LDS twin of add_taps
+// (gmpi_shared.hpp), with its rule -- the weight gates the add (a zero weight marks a tap outside the texture or off the ramp).
+__device__ __forceinline__ void lds_add_taps(unsigned long long* __restrict__ cell, int pitch, float d, float w_nw, float w_ne, float w_sw, float w_se,
+                                             float scale) {
+    if (w_nw != 0.0f) atomicAdd(cell, to_fix(d * w_nw, scale));
+    if (w_ne != 0.0f) atomicAdd(cell + 1, to_fix(d * w_ne, scale));
+    if (w_sw != 0.0f) atomicAdd(cell + pitch, to_fix(d * w_sw, scale));
+    if (w_se != 0.0f) atomicAdd(cell + pitch + 1, to_fix(d * w_se, scale));
+}
+
+// The moving window: anchor (the texel of cell (0, 0)), the rows in use since they were last reset, and whether it has been anchored at all.  Every
+// member is workgroup-uniform and lives in registers: all of it is computed from the box table and launch constants.  Channel c of the window is the
+// kCW x kCH block at acc + c kCW kCH.  The boxes of a tile drift over the planes by parallax; when the next plane's box leaves the window the kernel
+// flushes it and re-anchors it with the box at the end it drifts away from, so that the window's whole slack lies ahead (the direction is taken from
+// the boxes of the two ends of the sweep: nearer planes lie towards box_front).
+struct MovingWindow {
+    int x0 = 0, y0 = 0, row0 = kCH, row1 = 0;
+    bool open = false;
+
+    __device__ __forceinline__ bool covers(const int4& bb) const {
+        return open && bb.x >= x0 && bb.y >= y0 && bb.x + bb.z <= x0 + kCW && bb.y + bb.w <= y0 + kCH;
+    }
+    __device__ __forceinline__ void reset_rows() { row0 = kCH, row1 = 0; }
+    __device__ __forceinline__ void anchor(const int4& bb, const int4& box_front) {
+        x0 = (box_front.z > 0 && box_front.x < bb.x) ? bb.x + bb.z - kCW : bb.x;
+        y0 = (box_front.z > 0 && box_front.y < bb.y) ? bb.y + bb.w - kCH : bb.y;
+        reset_rows();
+        open = true;
+    }
+    __device__ __forceinline__ void grow(const int4& bb) { row0 = min(row0, bb.y - y0), row1 = max(row1, bb.y + bb.w - y0); }
+    // the footprint's 2 x 2 cells lie inside the window (whatever the box says: this is what keeps wild coordinates out); cell: the index of its nw cell
+    __device__ __forceinline__ bool holds(const Footprint& f) const {
+        const int wx = f.x0 - x0, wy = f.y0 - y0;
+        return wx >= 0 && wy >= 0 && wx + 1 < kCW && wy + 1 < kCH;
+    }
+    __device__ __forceinline__ int cell(const Footprint& f) const { return (f.y0 - y0) * kCW + (f.x0 - x0); }
+    // Channels [0, nc) of the rows in use -> sink(c, gx, gy, value): every non-zero cell is zeroed and, when its texel (gx, gy) lies inside the
+    // texture, handed over as a float (the one rounding of a staged sum; the sink applies its scale's inverse and adds to its destination).  A wave
+    // takes 64 consecutive texels of one row and channel.  The row range is left as it is.
+    template <typename Sink>
+    __device__ __forceinline__ void flush(unsigned long long* __restrict__ acc, int tid, int nc, int Ht, int Wt, Sink&& sink) const {
+        if (row1 <= row0) return;
+        const int rows = row1 - row0;
+        for (int i = tid; i < rows * nc * kCW; i += kTileThreads) {
+            const int line = i / kCW, x = i - line * kCW;   // line = (row, channel)
+            const int lr = line / nc, c = line - lr * nc, row = row0 + lr;
+            unsigned long long* __restrict__ src = acc + (c * kCH + row) * kCW + x;
+            const long long v = static_cast<long long>(*src);
+            if (v != 0) {
+                *src = 0ull;
+                const int gx = x0 + x, gy = y0 + row;
+                // (a cell outside the texture only ever receives zero weights: belt and braces)
+                if (gx >= 0 && gx < Wt && gy >= 0 && gy < Ht) sink(c, gx, gy, static_cast<float>(static_cast<double>(v)));
+            }
+        }
+    }
+};
 
 }  // namespace gmpi

@@ -109,6 +109,39 @@ __device__ __forceinline__ void add_taps(float* __restrict__ ch, int64_t s_row, 
     if (w_se != 0.0f && v_se != 0.0f) atomicAdd(ch + ob + 1, v_se);
 }
 
+// ---- the tap prefetch of the tile backwards (render_shared_tile_kernel, render_depth_tile_kernel) ------------------------------------------------
+// Plane k for one pixel, first half: coordinates and the 16 tap loads, issued together one plane ahead of their use (the scatter of the plane before
+// runs while they are in flight).  v: per channel the taps nw, ne, sw, se -- r, g, b from the colour image (the background on the last plane) and a
+// fourth channel from fourth + k fourth_plane with row stride fourth_row (alpha plane k; the one depth image with a plane stride of 0).  An inactive
+// lane gets the neutral footprint {-2, -2, no weight}: inside no box, nothing to add.
+struct Tap { float s; Footprint f; float v[16]; };
+template <bool AC, typename TexT>
+__device__ __forceinline__ void fetch_taps(Tap& tp, bool active, const KParams& p, const BwdView& vw, const BwdPixel& bp, int k, const SharedK& sh,
+                                           const TexT* __restrict__ rgb, const TexT* __restrict__ bgi, const TexT* __restrict__ fourth, int64_t fourth_plane,
+                                           int64_t fourth_row) {
+    tp.s = 0.0f;
+    tp.f = Footprint{-2, -2, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tp.v[i] = 0.0f;
+    if (active) {
+        float ix, iy;
+        pixel_plane_coord<AC>(vw, bp, k, ix, iy, tp.s);
+        const Taps t = make_taps(ix, iy, p.Ht, p.Wt);
+        tp.f = t.f;
+        const bool last_bg = bgi != nullptr && k == p.D - 1;
+        const TexT* __restrict__ col = last_bg ? bgi : rgb;
+        const int64_t c_chan = last_bg ? sh.bs_chan : sh.rs_chan, c_row = last_bg ? sh.bs_row : sh.rs_row;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const TexT* __restrict__ ch = c < 3 ? col + c * c_chan : fourth + static_cast<int64_t>(k) * fourth_plane;
+            const int64_t s_row = c < 3 ? c_row : fourth_row;
+            const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
+            tp.v[4 * c + 0] = to_f32(ch[oa + t.xa]), tp.v[4 * c + 1] = to_f32(ch[oa + t.xb]);
+            tp.v[4 * c + 2] = to_f32(ch[ob + t.xa]), tp.v[4 * c + 3] = to_f32(ch[ob + t.xb]);
+        }
+    }
+}
+
 // The final transmittance the depth-alpha backward sweeps start from (bwd_pixel_setup_with's `total`; both backward kernels of the layout call this
 // one text): the forward's value when it is usable (total_transmittance's rule), else a front-to-back walk over the RAMP samples in the extended
 // representation -- total_transmittance reads alpha planes, which do not exist here.  bp: the pixel's ray (set before `total` is called).

@@ -110,22 +110,24 @@ __global__ __launch_bounds__(256) void render_shared_backward_kernel(const KPara
 }
 
 // ---- backward, one workgroup per pixel tile ------------------------------------------------------------------------------------------------
-// A 32 x 16 pixel tile touches a small texel box on every plane (tile_box, gmpi_backward.hpp).
+// A 32 x 16 pixel tile touches a small texel box on every plane (tile_box, gmpi_backward.hpp).  The frame -- tile order, box table, the moving window and
+// its flush, the fixed-point scale and adds -- is "the cross-plane tile frame" of gmpi_backward.hpp; the tap prefetch is fetch_taps (gmpi_shared.hpp).
 //
 // ALPHA: as the volume kernels do it -- the 4 adds of a pixel go to a copy of the plane's box in LDS (64-bit fixed point, scaled per plane to the
 // tile's largest |d alpha|: that gradient holds S / om and has no bound known in advance), the box is flushed with one global atomic per texel.
 // Two boxes alternate, so that the flush of plane t + 1 and the scatter of plane t need no barrier between them: ONE barrier per plane, and that
 // barrier orders LDS only (lds_barrier); the taps of plane t - 1 are fetched before plane t is scattered.
 //
-// COLOUR, the point of this kernel: every plane's colour gradient belongs to the same image, so it is summed in LDS across ALL planes, in a window of
-// kCW x kCH texels x 3 channels.  The window does NOT hold the union of the tile's per-plane boxes: the boxes drift over the planes by parallax -- with
+// COLOUR, the point of this kernel: every plane's colour gradient belongs to the same image, so it is summed in LDS across ALL planes, in a
+// MovingWindow of 3 channels.  The window does NOT hold the union of the tile's per-plane boxes: the boxes drift over the planes by parallax -- with
 // the FFHQ geometry (planes 0.2473 wide) 1.1 / 1.7 / 3.3 texels per plane in x and 0.5 / 1.1 / 2.3 in y on average at 256^2 / 512^2 / 1024^2, 30-100 texels
-// over 32 planes against 29 x 13 texels of slack around a 35 x 19 box; and the last plane is a larger background plane whose box lies elsewhere.  So when the
-// next plane's box leaves the window, the window is flushed and re-anchored with the box at the end it drifts away from, so that the window's whole slack
-// lies ahead (the direction is taken from the boxes of the two ends of the sweep).  Colour flushes per tile (tools/shared_window_replay.py, 32 planes, the
-// poses tools/time_shared_color.py draws): 2.8 / 3.9 / 6.1 on average at 256^2 / 512^2 / 1024^2 (max 4 / 7 / 13) instead of 32 per-plane flushes; at the
-// 2-sigma corner of the pose range 6.6 / 10.8 / 18.1 (max 31 at 1024^2: one per plane).  A plane whose own box does not fit the alpha
-// box (strong minification, degenerate rays) scatters straight to global memory, both gradients, as in render_backward.hip.
+// over 32 planes against 29 x 13 texels of slack around a 35 x 19 box; and the last plane is a larger background plane whose box lies elsewhere.  So the
+// window moves (MovingWindow's re-anchor rule).  Colour flushes per tile (tools/shared_window_replay.py, 32 planes, the poses tools/time_shared_color.py
+// draws): 2.8 / 3.9 / 6.1 on average at 256^2 / 512^2 / 1024^2 (max 4 / 7 / 13) instead of 32 per-plane flushes; at the 2-sigma corner of the pose range
+// 6.6 / 10.8 / 18.1 (max 31 at 1024^2: one per plane).  A plane whose own box does not fit the alpha box (strong minification, degenerate rays)
+// scatters straight to global memory, both gradients, as in render_backward.hip.
+// A colour flush empties all the window holds, so its row range is reset after EVERY flush, the background's included.  The per-plane barrier is also the
+// one a colour flush relies on (every add of the planes behind is complete); one more follows the flush, before the next add.
 //
 // FIXED POINT of the colour window.  The scale cannot follow the planes; it is fixed per tile before the sweep from M = max over the tile's pixels
 // of max(|gR|, |gG|, |gB|) (OUT_PM1's factor 2 included).  A term is gC w_k weight with w_k = a_k T_k <= 1 (alpha in [0, 1]: T_k <= (1 + 1e-10)^k) and a
@@ -137,48 +139,35 @@ __global__ __launch_bounds__(256) void render_shared_backward_kernel(const KPara
 // the running sum.  Integer sums are exact and order-independent; the only fp32 rounding of the staged part is the conversion at the flush.
 // (Plain fp32 LDS adds were not shipped: ds_add_f32 retires ~0.2 T lane-adds/s against ~9 T for ds_add_u64 on this part -- tools/ubench/lds_atomic_rate.hip,
 // render_backward.hip.)
-constexpr int kSTW = 32, kSTH = 16, kSThreads = kSTW * kSTH;
-constexpr int kSAP = 56, kSAR = 27;            // alpha box: pitch, rows (64-bit words; two boxes of 11.8 KB)
-constexpr int kCW = 64, kCH = 32;              // colour window (3 channels of 64-bit words: 48 KB)
-constexpr int kSPlanes = 128;                  // planes a tile kernel launch can take (its tables)
-constexpr int kSAlphaBits = 40, kSColBits = 40;   // largest staged term < 2^41 (to_fix takes |w| < 2^43)
+constexpr int kSAP = 56, kSAR = 27;   // alpha box: pitch, rows (64-bit words; two boxes of 11.8 KB); also the largest box whose plane is staged at all
 
 template <typename TexT, bool AC>
-__global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KParams p, const SharedK sh, const SharedG g, const int tiles_x) {
-    __shared__ int4 box[kSPlanes];        // bx0, by0, nx (<= 0: not staged), ny
-    __shared__ uint32_t gmax[kSPlanes];   // per plane: largest |d alpha| of the tile, fp32 bits
-    __shared__ uint32_t cmax;             // largest |gC| of the tile, fp32 bits
+__global__ __launch_bounds__(kTileThreads) void render_shared_tile_kernel(const KParams p, const SharedK sh, const SharedG g, const int tiles_x) {
+    __shared__ int4 box[kTilePlanes];        // bx0, by0, nx (<= 0: not staged), ny
+    __shared__ uint32_t gmax[kTilePlanes];   // per plane: largest |d alpha| of the tile, fp32 bits
+    __shared__ uint32_t cmax;                // largest |gC| of the tile, fp32 bits
     __shared__ unsigned long long acc_a[2][kSAP * kSAR];
     __shared__ unsigned long long acc_c[3 * kCW * kCH];
     const int tid = threadIdx.x;
     const int n = blockIdx.y;
-    const int n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
-    const int tile = xcd_item_per_group(static_cast<int>(blockIdx.x), n_tiles, n_tiles);
-    if (tile >= n_tiles) return;   // (whole workgroup: the grid is padded to a multiple of 8)
-    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-    const int px = txi * kSTW + (tid % kSTW), py = tyi * kSTH + (tid / kSTW);
-    const bool active = px < p.W && py < p.H;
+    const TileFrame tf = tile_frame(p, tiles_x);
+    if (tf.tile < 0) return;
+    const bool active = tf.active;
     const BwdView vw = bwd_view<AC>(p, n);
     const int m = vw.m, D = p.D;
-    const float* __restrict__ dhw = vw.dhw;
-    const float* __restrict__ rdv = vw.rays;
     const int Ht = p.Ht, Wt = p.Wt;
     const TexT* __restrict__ alpha = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(m) * p.s_mpi;
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi;
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr;
     float* __restrict__ ga = g.g_alpha ? g.g_alpha + static_cast<int64_t>(m) * g.ga_mpi : nullptr;
     BwdPixel bp;
-    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, g.g_out, g.g_depth, g.g_T, alpha);
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, tf.px, tf.py, active, g.g_out, g.g_depth, g.g_T, alpha);
 
-    for (int i = tid; i < 2 * kSAP * kSAR; i += kSThreads) (&acc_a[0][0])[i] = 0ull;
-    for (int i = tid; i < 3 * kCW * kCH; i += kSThreads) acc_c[i] = 0ull;
+    for (int i = tid; i < 2 * kSAP * kSAR; i += kTileThreads) (&acc_a[0][0])[i] = 0ull;
+    for (int i = tid; i < 3 * kCW * kCH; i += kTileThreads) acc_c[i] = 0ull;
     if (tid == 0) cmax = 0u;
-
-    // ---- per-plane texel boxes of the tile (from its four corner pixels) -----------------------------------------------------------------------
-    const int cx0 = txi * kSTW, cx1 = min(cx0 + kSTW - 1, p.W - 1);
-    const int cy0 = tyi * kSTH, cy1 = min(cy0 + kSTH - 1, p.H - 1);
-    for (int k = tid; k < D; k += kSThreads) {
-        box[k] = tile_box<AC>(p, vw, rdv, dhw[3 * k] - vw.ez, dhw[3 * k + 1], dhw[3 * k + 2], cx0, cx1, cy0, cy1, kSAP, kSAR);
+    for (int k = tid; k < D; k += kTileThreads) {
+        box[k] = tile_frame_box<AC>(p, vw, tf, k, kSAP, kSAR);
         gmax[k] = 0u;
     }
     __syncthreads();   // zero fills, tables, cmax = 0
@@ -188,32 +177,7 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     }
 
     struct Grad { float d[4]; Footprint f; };
-    struct Tap { float s; Footprint f; float v[16]; };   // v: per channel (r, g, b, alpha) the taps nw, ne, sw, se
-    // plane k for this pixel, first half: coordinates and the 16 tap loads (issued one plane ahead of their use: the scatter of the plane before
-    // runs while they are in flight)
-    auto fetch = [&](int k, Tap& tp) {
-        tp.s = 0.0f;
-        tp.f = Footprint{-2, -2, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tp.v[i] = 0.0f;
-        if (active) {
-            float ix, iy;
-            pixel_plane_coord<AC>(vw, bp, k, ix, iy, tp.s);
-            const Taps t = make_taps(ix, iy, Ht, Wt);
-            tp.f = t.f;
-            const bool last_bg = bgi != nullptr && k == D - 1;
-            const TexT* __restrict__ col = last_bg ? bgi : rgb;
-            const int64_t c_chan = last_bg ? sh.bs_chan : sh.rs_chan, c_row = last_bg ? sh.bs_row : sh.rs_row;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const TexT* __restrict__ ch = c < 3 ? col + c * c_chan : alpha + static_cast<int64_t>(k) * p.s_plane;
-                const int64_t s_row = c < 3 ? c_row : p.s_row;
-                const int64_t oa = static_cast<int64_t>(t.ya) * s_row, ob = static_cast<int64_t>(t.yb) * s_row;
-                tp.v[4 * c + 0] = to_f32(ch[oa + t.xa]), tp.v[4 * c + 1] = to_f32(ch[oa + t.xb]);
-                tp.v[4 * c + 2] = to_f32(ch[ob + t.xa]), tp.v[4 * c + 3] = to_f32(ch[ob + t.xb]);
-            }
-        }
-    };
+    auto fetch = [&](int k, Tap& tp) { fetch_taps<AC>(tp, active, p, vw, bp, k, sh, rgb, bgi, alpha, p.s_plane, p.s_row); };
     // second half: bilinear samples (tap_sample's arithmetic), BwdPixel::plane, the tile maximum of |d alpha|
     auto grads = [&](int k, const Tap& tp, Grad& G) {
         G.d[0] = G.d[1] = G.d[2] = G.d[3] = 0.0f;
@@ -228,29 +192,15 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
         if ((tid & 63) == 0 && wm != 0u) atomicMax(&gmax[k], wm);
     };
 
-    // the colour window: anchor (texel of cell 0,0), the rows in use since the last flush.  All workgroup-uniform.
-    int wx0 = 0, wy0 = 0, wrow0 = kCH, wrow1 = 0;
-    bool w_open = false;
-    float cscale = 0.0f, cinv = 0.0f;
-    bool cstage = false;
-    // window -> global memory (one atomic per texel and channel, a wave = 64 consecutive texels of one row) and reset
+    MovingWindow win;   // the colour window
+    FixScale cs{false, 0.0f, 0.0f};
+    // window -> global memory (one atomic per texel and channel) and reset
     auto flush_colour = [&](const ColTarget& ct) {
-        if (wrow1 > wrow0 && ct.base != nullptr) {
-            const int rows = wrow1 - wrow0;
-            for (int i = tid; i < rows * 3 * kCW; i += kSThreads) {
-                const int line = i / kCW, x = i - line * kCW;      // line = (row, channel)
-                const int row = wrow0 + line / 3, c = line - (line / 3) * 3;
-                unsigned long long* __restrict__ src = acc_c + (c * kCH + row) * kCW + x;
-                const long long v = static_cast<long long>(*src);
-                const int gx = wx0 + x, gy = wy0 + row;
-                if (v != 0) {
-                    *src = 0ull;
-                    if (gx >= 0 && gx < Wt && gy >= 0 && gy < Ht)   // (a cell outside the texture only ever receives zero weights: belt and braces)
-                        atomicAdd(ct.base + c * ct.s_chan + static_cast<int64_t>(gy) * ct.s_row + gx, static_cast<float>(static_cast<double>(v)) * cinv);
-                }
-            }
-        }
-        wrow0 = kCH, wrow1 = 0;
+        if (ct.base != nullptr)
+            win.flush(acc_c, tid, 3, Ht, Wt, [&](int c, int gx, int gy, float v) {
+                atomicAdd(ct.base + c * ct.s_chan + static_cast<int64_t>(gy) * ct.s_row + gx, v * cs.inv);
+            });
+        win.reset_rows();
     };
     // scatter of one plane: alpha into its box (per-plane scale), colour into the window (tile scale); what is not staged goes straight to global memory
     auto scatter = [&](int k, const Grad& G, const ColTarget& ct, bool col_staged) {
@@ -261,35 +211,20 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
         const int lx = f.x0 - bb.x, ly = f.y0 - bb.y;
         const bool in_box = bb.z > 0 && lx >= 0 && ly >= 0 && lx + 1 < bb.z && ly + 1 < bb.w;
         if (ga != nullptr && mb != 0u && any_w) {
-            const bool staged = in_box && mb < 0x7f800000u;
-            if (staged) {
-                const int shf = min(kSAlphaBits - (static_cast<int>(mb >> 23) - 127), 126);
-                const float sc = __builtin_amdgcn_ldexpf(1.0f, shf);
-                unsigned long long* __restrict__ l0 = &acc_a[k & 1][ly * kSAP + lx];
-                const float d = G.d[3];
-                if (f.nw != 0.0f) atomicAdd(l0, to_fix(d * f.nw, sc));
-                if (f.ne != 0.0f) atomicAdd(l0 + 1, to_fix(d * f.ne, sc));
-                if (f.sw != 0.0f) atomicAdd(l0 + kSAP, to_fix(d * f.sw, sc));
-                if (f.se != 0.0f) atomicAdd(l0 + kSAP + 1, to_fix(d * f.se, sc));
+            const FixScale as = fix_scale(mb, kFixBits);
+            if (in_box && as.stage) {
+                lds_add_taps(&acc_a[k & 1][ly * kSAP + lx], kSAP, G.d[3], f.nw, f.ne, f.sw, f.se, as.scale);
             } else {
                 scatter4(ga + static_cast<int64_t>(k) * g.ga_plane, g.ga_row, f, G.d[3]);
             }
         }
         if (ct.base != nullptr && any_w) {
-            const int wx = f.x0 - wx0, wy = f.y0 - wy0;
             const float dm = fmaxf(fmaxf(fabsf(G.d[0]), fabsf(G.d[1])), fabsf(G.d[2]));
-            // (dm * cscale < 2^42 is false for NaN; in_box implies the footprint lies inside the window, the second test keeps wild coordinates out)
-            const bool staged = col_staged && in_box && wx >= 0 && wy >= 0 && wx + 1 < kCW && wy + 1 < kCH && (dm * cscale < 4398046511104.0f);
+            // (dm * scale < 2^42 is false for NaN; in_box implies the footprint lies inside the window, holds() keeps wild coordinates out)
+            const bool staged = col_staged && in_box && win.holds(f) && (dm * cs.scale < 4398046511104.0f);
             if (staged) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    unsigned long long* __restrict__ l0 = acc_c + (c * kCH + wy) * kCW + wx;
-                    const float d = G.d[c];
-                    if (f.nw != 0.0f) atomicAdd(l0, to_fix(d * f.nw, cscale));
-                    if (f.ne != 0.0f) atomicAdd(l0 + 1, to_fix(d * f.ne, cscale));
-                    if (f.sw != 0.0f) atomicAdd(l0 + kCW, to_fix(d * f.sw, cscale));
-                    if (f.se != 0.0f) atomicAdd(l0 + kCW + 1, to_fix(d * f.se, cscale));
-                }
+                for (int c = 0; c < 3; ++c) lds_add_taps(acc_c + c * (kCH * kCW) + win.cell(f), kCW, G.d[c], f.nw, f.ne, f.sw, f.se, cs.scale);
             } else if (dm != 0.0f) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) scatter4(ct.base + c * ct.s_chan, ct.s_row, f, G.d[c]);
@@ -299,12 +234,10 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     // box of plane k -> global memory and reset (the plane's own scale)
     auto flush_alpha = [&](int k) {
         const int4 bb = box[k];
-        const uint32_t mb = gmax[k];
-        if (!(ga != nullptr && bb.z > 0 && mb != 0u && mb < 0x7f800000u)) return;
-        const int shf = min(kSAlphaBits - (static_cast<int>(mb >> 23) - 127), 126);
-        const float inv = __builtin_amdgcn_ldexpf(1.0f, -shf);
+        const FixScale as = fix_scale(gmax[k], kFixBits);
+        if (!(ga != nullptr && bb.z > 0 && as.stage)) return;
         float* __restrict__ gp = ga + static_cast<int64_t>(k) * g.ga_plane;
-        for (int i = tid; i < bb.w * kSAP; i += kSThreads) {
+        for (int i = tid; i < bb.w * kSAP; i += kTileThreads) {
             const int row = i / kSAP, x = i - row * kSAP;
             unsigned long long* __restrict__ src = &acc_a[k & 1][i];
             const long long v = static_cast<long long>(*src);
@@ -312,7 +245,7 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
             if (v != 0) {
                 *src = 0ull;
                 if (gx >= 0 && gx < Wt && gy >= 0 && gy < Ht)
-                    atomicAdd(gp + static_cast<int64_t>(gy) * g.ga_row + gx, static_cast<float>(static_cast<double>(v)) * inv);
+                    atomicAdd(gp + static_cast<int64_t>(gy) * g.ga_row + gx, static_cast<float>(static_cast<double>(v)) * as.inv);
             }
         }
     };
@@ -323,30 +256,21 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
     fetch(D - 1, tp);
     grads(D - 1, tp, G);
     __syncthreads();   // cmax, gmax[D - 1] complete
-    {
-        const uint32_t cm = cmax;
-        cstage = cm != 0u && cm < 0x7f800000u;
-        const int shf = min(kSColBits - (static_cast<int>(cm >> 23) - 127), 126);
-        cscale = cstage ? __builtin_amdgcn_ldexpf(1.0f, shf) : 0.0f, cinv = cstage ? __builtin_amdgcn_ldexpf(1.0f, -shf) : 0.0f;
-    }
+    cs = fix_scale(cmax, kFixBits);
     const int4 box_front = box[0];
     for (int k = D - 1; k >= 0; --k) {
         const ColTarget ct = colour_target(sh, g, m, k, D);
         const int4 bb = box[k];
-        const bool want_window = cstage && ct.base != nullptr && bb.z > 0;   // uniform
+        const bool want_window = cs.stage && ct.base != nullptr && bb.z > 0;   // uniform
         if (want_window) {
-            const bool inside = w_open && bb.x >= wx0 && bb.y >= wy0 && bb.x + bb.z <= wx0 + kCW && bb.y + bb.w <= wy0 + kCH;
-            if (!inside) {
-                if (w_open) {   // the previous planes' adds are complete (the barrier that ended the last iteration)
+            if (!win.covers(bb)) {
+                if (win.open) {   // the previous planes' adds are complete (the barrier that ended the last iteration)
                     flush_colour(colour_target(sh, g, m, k + 1, D));
                     lds_barrier();
                 }
-                // re-anchor: the box at the end of the window it drifts away from (boxes of nearer planes: towards box_front)
-                wx0 = (box_front.z > 0 && box_front.x < bb.x) ? bb.x + bb.z - kCW : bb.x;
-                wy0 = (box_front.z > 0 && box_front.y < bb.y) ? bb.y + bb.w - kCH : bb.y;
-                w_open = true;
+                win.anchor(bb, box_front);
             }
-            wrow0 = min(wrow0, bb.y - wy0), wrow1 = max(wrow1, bb.y + bb.w - wy0);
+            win.grow(bb);
         }
         if (k > 0) fetch(k - 1, tp);   // (in flight across the scatter)
         scatter(k, G, ct, want_window);
@@ -354,13 +278,13 @@ __global__ __launch_bounds__(kSThreads) void render_shared_tile_kernel(const KPa
         if (k + 1 < D) flush_alpha(k + 1);
         lds_barrier();   // plane k's adds and gmax[k - 1] complete; box (k + 1) & 1 is clean for plane k - 1
         // the last plane's colour belongs to the background image: its own flush (the window stays where it is)
-        if (k == D - 1 && bgi != nullptr && w_open && D > 1) {
+        if (k == D - 1 && bgi != nullptr && win.open && D > 1) {
             flush_colour(ct);
             lds_barrier();
         }
     }
     flush_alpha(0);
-    if (w_open) flush_colour(colour_target(sh, g, m, 0, D));
+    if (win.open) flush_colour(colour_target(sh, g, m, 0, D));
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------
@@ -378,15 +302,14 @@ hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStre
     return dispatch_dtype(dtype, [&](auto t) { return launch_shared_t<typename decltype(t)::type>(p, sh, stream); });
 }
 
-bool shared_tile_supports(const KParams& p) { return p.D <= kSPlanes; }
+bool shared_tile_supports(const KParams& p) { return tile_planes_fit(p); }
 
 template <typename TexT>
 static hipError_t launch_shared_backward_t(const KParams& p, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream) {
     const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
     if (tiles) {
-        const int tiles_x = (p.W + kSTW - 1) / kSTW, n_tiles = tiles_x * ((p.H + kSTH - 1) / kSTH);
-        const dim3 grid(xcd_grid_per_group(n_tiles, n_tiles), p.N);
-        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_shared_tile_kernel<TexT, decltype(AC)::value>), grid, dim3(kSThreads), 0, stream, p, sh, g, tiles_x); });
+        const TileGrid tg = tile_grid(p);
+        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_shared_tile_kernel<TexT, decltype(AC)::value>), tg.grid, dim3(kTileThreads), 0, stream, p, sh, g, tg.tiles_x); });
     } else {
         const dim3 block(64, 4);
         const dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);

@@ -316,6 +316,58 @@ def test_backward_tilted_poses_move_the_colour_window():
         _compare(got, ref64, ref32, torch.float32, f"tilted {variant}", True, True)
 
 
+def _staged_tile_planes(dhw, ray, eye, T):
+    """(staged, all) (tile, plane) pairs of render_shared_tile_kernel for these views, replayed on the CPU: tools/shared_window_replay.py's boxes() with its
+    default box limit, the kernel's 56 x 27."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("shared_window_replay", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools",
+                                                                                       "shared_window_replay.py"))
+    replay = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(replay)
+    assert (replay.AP, replay.AR) == (56, 27)
+    bb = replay.boxes(dhw[0].numpy(), ray.numpy(), eye.numpy(), T)
+    return int((bb[..., 2] > 0).sum()), int(bb[..., 2].size)
+
+
+def test_backward_minification_every_tile_scatters_straight_to_global_memory():
+    """64 x 64 pixels over 256 x 256 texels: a 32 x 16 pixel tile covers 63 .. 128 x 37 .. 65 texels on every plane, more than the 56 x 27 box the
+    tile kernel stages, so the whole launch takes the direct scatter of both gradients.  Replayed on the CPU (tools/shared_window_replay.py, boxes(),
+    --box 56x27): 0 of the 96 (tile, plane) pairs -- 2 views x 8 tiles x 6 planes -- are staged; asserted below."""
+    S, T, D = 64, 256, 6
+    rgba, dhw, ray, eye, zd = _random_case(seed=11, B=2, D=D, S=S, T=T)
+    assert _staged_tile_planes(dhw, ray, eye, T) == (0, 96)
+    parts = _parts(rgba)
+    parts = (parts[0], (parts[1] * 0.2), parts[2])
+    g = np.random.default_rng(3)
+    gc = g.standard_normal((2, 3, S, S)).astype(np.float32)
+    gd = g.standard_normal((2, 1, S, S)).astype(np.float32)
+    ref64 = _reference_grads(parts, dhw, ray, eye, zd, [0, 1], gc, gd, None, False, torch.float64)
+    ref32 = _reference_grads(parts, dhw, ray, eye, zd, [0, 1], gc, gd, None, False, torch.float32)
+    for variant in ("auto", "gather"):
+        ins, _ = _hip_grads(parts, dhw, ray, eye, zd, 1, gc, gd, None, False, variant)
+        got = [i.grad.double().cpu().numpy() for i in ins]
+        _compare(got, ref64, ref32, torch.float32, f"minification {variant}", True, True)
+
+
+def test_backward_ragged_sizes_100_pixels_over_77_texels():
+    """100 x 100 pixels (4 x 7 tiles, the last column 4 pixels wide, the last row 4 pixels high) over 77 x 77 texels, 7 planes, three MPIs with a
+    background: lanes outside the image, tiles clamped at both image borders, a texture that is no multiple of anything."""
+    S, T, D, B = 100, 77, 7, 3
+    rgba, dhw, ray, eye, zd = _random_case(seed=4, B=B, D=D, S=S, T=T)
+    parts = _parts(rgba)
+    g = np.random.default_rng(4)
+    gc = g.standard_normal((B, 3, S, S)).astype(np.float32)
+    gd = g.standard_normal((B, 1, S, S)).astype(np.float32)
+    gT = g.standard_normal((B, 1, S, S)).astype(np.float32)
+    ref64 = _reference_grads(parts, dhw, ray, eye, zd, [0, 1, 2], gc, gd, gT, True, torch.float64)
+    ref32 = _reference_grads(parts, dhw, ray, eye, zd, [0, 1, 2], gc, gd, gT, True, torch.float32)
+    for variant in ("auto", "gather"):
+        ins, _ = _hip_grads(parts, dhw, ray, eye, zd, 1, gc, gd, gT, True, variant)
+        got = [i.grad.double().cpu().numpy() for i in ins]
+        _compare(got, ref64, ref32, torch.float32, f"ragged {variant}", True, True)
+
+
 def test_backward_rgb_grad_excludes_the_background_plane_and_partial_needs():
     from ml_gmpi_amd import MPI
     parts, dhw, ray, eye, zd, v2m, gc, gd, gT = _bwd_case(8, 64, True, torch.float32)

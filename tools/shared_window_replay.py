@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ml_gmpi_amd.renderer import MPIRenderer, PRESETS  # noqa: E402
 
-TW, TH, AP, AR, CW, CH = 32, 16, 56, 27, 64, 32   # kSTW, kSTH, kSAP, kSAR, kCW, kCH
+TW, TH, AP, AR, CW, CH = 32, 16, 56, 27, 64, 32   # kTileW, kTileH (gmpi_backward.hpp), kSAP, kSAR (render_shared.hip), kCW, kCH (gmpi_backward.hpp)
 
 
 def boxes(dhw, ray, eye, S):
