@@ -345,10 +345,36 @@ typedef struct GmpiDepthAlpha {
  * One kernel, one pixel per lane, taps from global memory (any shape, any stride, any ray field): GMPI_VARIANT_AUTO and GMPI_VARIANT_GATHER run
  * it, any other variant is GMPI_E_VARIANT.  z_lo >= z_hi or z_den <= 0 (or a NaN among them): GMPI_E_SHAPE; a negative plane_z_stride:
  * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
- * never synchronises.  Not built: a staged / tile forward (the backward has a tile entry, below), 8-bit storage, gradients w.r.t. the geometry,
- * skipping planes from a depth min/max pre-pass (gmpi_query(22) says whether the layout itself is built in).
+ * never synchronises.  A window forward has an entry of its own (gmpi_mpi_render_depth_window_launch, below: this entry keeps its one kernel and
+ * still refuses GMPI_VARIANT_LDS).  Not built: 8-bit storage, gradients w.r.t. the geometry (gmpi_query(22) says whether the layout itself is
+ * built in).
  */
 int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
+
+/*
+ * gmpi_mpi_render_depth_launch with a window kernel: same arguments, same checks, same error codes, THE SAME BITS in both modes (default and
+ * GMPI_FLAG_STRICT_ORDER), the same status words.  One workgroup per 32 x 16 pixel tile, planes front to back; every tap is read from one window of
+ * gmpi_query(26) x gmpi_query(27) = 64 x 32 texels x 4 channels (R, G, B, depth; fp32) in LDS, which is reloaded whenever the tile's texel boxes have
+ * drifted out of it (and, with a background, its colour channels once more before the last plane).  The box table is refilled every gmpi_query(28)
+ * planes: any D.  While a window is loaded its depth texels are reduced to their minimum: a plane that lies in front of the ramp for the whole
+ * window (RN(plane_z[k] - min) <= z_lo, no NaN among the texels) is skipped for every pixel whose ray lies between the tile's corner rays -- exactly
+ * the planes the one-pixel kernel skips pixel by pixel.  Routing: GMPI_VARIANT_AUTO launches the window kernel, GMPI_VARIANT_GATHER the
+ * one-pixel-per-lane kernel of gmpi_mpi_render_depth_launch; any other variant is GMPI_E_VARIANT.  The loader reads items of 16 bytes: base pointers and
+ * the MPI / channel / row strides of the three images must be multiples of 16 bytes, or AUTO is GMPI_E_VARIANT too (ask
+ * gmpi_render_depth_window_supports).  Any Wt: the last item of a row whose width is no multiple of 4 texels reads up to 3 texels of the row's
+ * padding; behind the LAST row of each image that padding must be allocated -- the caller's duty, neither the launch nor the query can see the
+ * allocation (the Python layer checks the storage and falls back).  The texel boxes assume a pinhole ray field (see ray_dir above); this is NOT
+ * checked: a pixel whose taps fall outside the window reads them from global memory, and so does a tile whose box on a plane exceeds the window
+ * (strong minification, corners that are not finite) -- any input gives the one-pixel kernel's pixels, an irregular one at its speed.  One
+ * difference: a tap OUTSIDE the texture reads a zero from the window where the one-pixel kernel reads the clamped border texel; both multiply it by a
+ * zero weight, so results and range bit differ only where that border texel is not finite resp. not in [0, 1].
+ */
+int gmpi_mpi_render_depth_window_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                        void *stream);
+
+/* 1: gmpi_mpi_render_depth_window_launch takes these arguments (for GMPI_VARIANT_AUTO: with the window kernel), 0: GMPI_VARIANT_AUTO and the
+ * loader cannot take the tensors (alignment), negative: the error code the launch would return.  Launches nothing. */
+int gmpi_render_depth_window_supports(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha);
 
 /*
  * Gradient of gmpi_mpi_render_depth_launch w.r.t. the three images -- torch autograd's through expand_depth_alpha: the clamp passes the gradient
@@ -506,7 +532,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * is 512 / width pixels high), 17 the texels per row and 18 the rows its staging buffer holds per plane (first column rounded down to a multiple of 4
  * texels, as for 13); 19 is unused (-1); 20 whether the interleaved GMPI_DTYPE_U8 layout (GmpiRenderParams.rgba_stride) is built in; 21 is unused (-1);
  * 22 whether the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in; 23 the number of planes the depth-alpha tile backward
- * (gmpi_mpi_render_depth_backward_tile_launch) takes: more go to the one-pixel-per-lane kernel.  Unknown -> -1.                        */
+ * (gmpi_mpi_render_depth_backward_tile_launch) takes: more go to the one-pixel-per-lane kernel; 24 is unused (-1); the depth-alpha window forward
+ * (gmpi_mpi_render_depth_window_launch): 25 whether it is built in, 26 / 27 the width / height of its window in texels, 28 the planes per refill of
+ * its box table.  Unknown -> -1.                                                                                                      */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -36,6 +36,8 @@ EXPORTS = (
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
     "gmpi_mpi_render_depth_launch",
+    "gmpi_mpi_render_depth_window_launch",
+    "gmpi_render_depth_window_supports",
     "gmpi_mpi_render_depth_backward_launch",
     "gmpi_mpi_render_depth_backward_tile_launch",
     "gmpi_last_plane_uv_minmax_launch",
@@ -211,6 +213,10 @@ def load_library():
                                                            vp, i64p, vp, i64p, vp, i64p, vp]
     lib.gmpi_mpi_render_depth_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha), vp]
+    lib.gmpi_mpi_render_depth_window_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_depth_window_launch.argtypes = list(lib.gmpi_mpi_render_depth_launch.argtypes)   # (the same signature)
+    lib.gmpi_render_depth_window_supports.restype = ctypes.c_int
+    lib.gmpi_render_depth_window_supports.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha)]
     lib.gmpi_mpi_render_depth_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha),
                                                           vp, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp]

@@ -35,6 +35,9 @@ hipError_t launch_depth_backward(const KParams& p, int dtype, const SharedK& sh,
 hipError_t launch_depth_backward_tile(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth_tile.hip
 bool depth_tile_supports(const KParams& p);                                 // render_depth_tile.hip
 int depth_tile_planes();                                                    // render_depth_tile.hip
+hipError_t launch_depth_window(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, hipStream_t stream);   // render_depth_window.hip
+bool depth_window_supports(const KParams& p, int dtype, const SharedK& sh);   // render_depth_window.hip
+int depth_window_query(int what);                                           // render_depth_window.hip
 hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
 bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
 int u8_variant_query(int what);                                             // render_u8.hip
@@ -634,6 +637,33 @@ int gmpi_mpi_render_depth_launch(const GmpiRenderParams* params, const GmpiShare
     return hip_rc(launch_depth(p, params->rgba_dtype, sh, dk, static_cast<hipStream_t>(stream)));
 }
 
+// The window forward (render_depth_window.hip), only through this entry: gmpi_mpi_render_depth_launch keeps its one kernel.  AUTO: the window kernel, where
+// its loader can take the tensors; GATHER: the one-pixel-per-lane kernel.
+int gmpi_mpi_render_depth_window_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, void* stream) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    const int rc = to_depth(params, shared, depth_alpha, true, p, sh, dk);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return GMPI_OK;
+    if (params->variant == GMPI_VARIANT_GATHER) {
+        if (p.N > 65535) return GMPI_E_SHAPE;   // the view index is grid.z
+        return hip_rc(launch_depth(p, params->rgba_dtype, sh, dk, static_cast<hipStream_t>(stream)));
+    }
+    if (!depth_window_supports(p, params->rgba_dtype, sh)) return GMPI_E_VARIANT;
+    return hip_rc(launch_depth_window(p, params->rgba_dtype, sh, dk, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_render_depth_window_supports(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    const int rc = to_depth(params, shared, depth_alpha, true, p, sh, dk);
+    if (rc != GMPI_OK) return rc;
+    if (params->variant == GMPI_VARIANT_GATHER) return p.N > 65535 ? GMPI_E_SHAPE : 1;
+    return depth_window_supports(p, params->rgba_dtype, sh) ? 1 : 0;
+}
+
 // Both depth-alpha backward entries: one argument check, one marshalling; `tile`: the entry that may launch the tile kernel.
 static int depth_backward(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, const float* grad_rgb_out,
                           const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride,
@@ -792,6 +822,8 @@ int gmpi_query(int32_t what) {
         case 16: case 17: case 18: case 20: return u8_variant_query(what);  // (15, 19: unused)
         case 22: return 1;  // the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in  (21: unused)
         case 23: return depth_tile_planes();  // planes the depth-alpha tile backward takes (more: the one-pixel-per-lane kernel)
+        case 25: return 1;  // the depth-alpha window forward (gmpi_mpi_render_depth_window_launch) is built in  (24: unused)
+        case 26: case 27: case 28: return depth_window_query(what);
         default: return -1;
     }
 }

@@ -36,47 +36,7 @@ constexpr float kFBoxEps = 1.0f / 64;                      // slack on the corne
 static_assert(kFRows * kFCols <= kFThreads, "one loader item per thread and channel");
 static_assert(2 * kFBufFloats * 4 + kFChunk * 16 <= 53 * 1024, "3 workgroups per CU");
 
-typedef uint32_t f_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t f_u32x2 __attribute__((ext_vector_type(2)));
-
-// one loader item: 4 texels of storage -> fp32
-template <typename TexT> struct Item4;
-template <> struct Item4<float> {
-    using Raw = f_u32x4;
-    static __device__ __forceinline__ Raw load(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
-        return __builtin_bit_cast(Raw, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
-    }
-    static __device__ __forceinline__ float4 cvt(const Raw& v) {
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-};
-template <> struct Item4<bf16_t> {
-    using Raw = f_u32x2;
-    static __device__ __forceinline__ Raw load(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
-        return __builtin_bit_cast(Raw, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
-    }
-    static __device__ __forceinline__ float4 cvt(const Raw& v) {
-        return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-    }
-};
-template <> struct Item4<f16_t> {
-    using Raw = f_u32x2;
-    static __device__ __forceinline__ Raw load(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
-        return __builtin_bit_cast(Raw, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
-    }
-    static __device__ __forceinline__ float4 cvt(const Raw& v) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const uint32_t vx = v.x, vy = v.y;
-        const h2 a = __builtin_bit_cast(h2, vx), b = __builtin_bit_cast(h2, vy);
-        return make_float4(static_cast<float>(a.x), static_cast<float>(a.y), static_cast<float>(b.x), static_cast<float>(b.y));
-    }
-};
-
-// [0, 1] test on fp32 bit patterns: non-negative floats order like unsigned ints; negative values, NaN and inf compare above 1.0; -0.0 is legal
-__device__ __forceinline__ bool f_out_of_unit(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return !(b <= 0x3f800000u || b == 0x80000000u);
-}
+// (Item4 -- one loader item, 4 texels of storage -> fp32 -- and f_out_of_unit live in gmpi_shared.hpp: render_depth_window.hip loads with them too)
 
 template <typename TexT, bool AC, bool STRICT>
 __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(const KParams p, const SharedK sh, const int tiles_x, const int tiles_y,

@@ -130,6 +130,13 @@ def dump_frames(save_dir: str, task: str, start_index: int, img8, angles, depth=
     return paths
 
 
+# The depth-alpha forward `render_path_depth` and `render_seeds_depth` take by default.  The project's rule: a staged kernel becomes a driver default only
+# when it measures faster than the one-pixel kernel by more than the spread of the passes at EVERY timed shape (as "lds" did for the shared-colour
+# layout).  The window forward does not: it is slower at 512^2 and 1024^2 x 32 planes and faster only at 96 planes with a step-like ramp and on the
+# camera path (profiles/depth_alpha_window.txt).  So the default is the one-pixel kernel, and "window" is asked for by name.
+DEPTH_FORWARD_DEFAULT = "pixel"
+
+
 class ViewBatchDriver:
     """Renders a camera path / a batch of seeds with an `MPIRenderer`, `batch` views per launch, device-resident."""
 
@@ -198,8 +205,28 @@ class ViewBatchDriver:
             r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=background, variant=variant, **kw)
         return self._render_path(launch, alpha.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
 
+    @torch.no_grad()
+    def render_path_depth(self, rgb: torch.Tensor, depth: torch.Tensor, render_size: int, yaws: Sequence[float], pitches: Sequence[float], *,
+                          z_range, n_z_bins, plane_z: Optional[torch.Tensor] = None, background: Optional[torch.Tensor] = None,
+                          indices: Optional[Sequence[int]] = None, to_uint8: bool = False, depth_range=None, want_transmittance: bool = False,
+                          to_host: bool = False, depth_forward: Optional[str] = DEPTH_FORWARD_DEFAULT):
+        """`render_path` of ONE depth-alpha MPI -- rgb [1,3,Ht,Wt], depth [1,1,Ht,Wt], background [1,3,Ht,Wt] or None; z_range, n_z_bins and
+        plane_z as in `MPIRenderer.render_depth` -- without building the volume `expand_depth_alpha(...)`: the same grouping of poses and rays,
+        single status read-back, uint8 epilogue, second-stream copies and returned dict.  `depth_forward`: the kernel of
+        `MPI.render_views_depth`, "pixel" or "window" (the same bits).  DEPTH_FORWARD_DEFAULT says which one is the default, and why."""
+        from .depth_alpha import depth_alpha_bounds
+        assert depth.shape[0] == 1, "render_path_depth draws many views of one MPI"
+        r = self.renderer
+        if plane_z is None:
+            plane_z = r.get_xyz_single_res(depth.shape[-2], depth.shape[-1], only_z=True)[1].reshape(-1)
+        z_bounds = depth_alpha_bounds(z_range, n_z_bins)
+
+        def launch(dhw, ray, eye, zd, **kw):
+            r.mpi.render_views_depth(rgb, depth, plane_z, z_bounds, dhw, ray, eye, zd, background=background, depth_forward=depth_forward, **kw)
+        return self._render_path(launch, depth.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
+
     def _render_path(self, launch, dev, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host):
-        """The body of `render_path` and `render_path_shared`: `launch(dhw, ray_dir, eye_pos, z_dir, **render_views keywords)` renders one batch."""
+        """The body of `render_path`, `render_path_shared` and `render_path_depth`: `launch(dhw, ray_dir, eye_pos, z_dir, **render_views keywords)` renders one batch."""
         r = self.renderer
         idx = list(range(len(yaws))) if indices is None else list(indices)
         n = len(idx)
@@ -284,8 +311,23 @@ class ViewBatchDriver:
                                                variant=variant, views_per_mpi=views_per_mpi, **render_kwargs)
         return self._render_seeds(render, alpha.shape[0], render_kwargs)
 
+    @torch.no_grad()
+    def render_seeds_depth(self, rgb: torch.Tensor, depth: torch.Tensor, render_size: int, *, z_range, n_z_bins,
+                           plane_z: Optional[torch.Tensor] = None, background: Optional[torch.Tensor] = None, views_per_mpi: int = 1,
+                           depth_forward: Optional[str] = DEPTH_FORWARD_DEFAULT, **render_kwargs):
+        """`render_seeds` of a stack of depth-alpha MPIs -- rgb [B,3,Ht,Wt], depth [B,1,Ht,Wt], background [B,3,Ht,Wt] or None; plane_z [D], [B,D]
+        or None -- through `MPIRenderer.render_depth`, `batch` MPIs per launch: the poses, the returned 4-tuple and the consumption of the torch RNG
+        of `render_seeds` on the expanded volume.  `depth_forward` as in `render_path_depth`."""
+        def render(s):
+            e = s + self.batch
+            return self.renderer.render_depth(rgb[s:e], depth[s:e], render_size, render_size, z_range=z_range, n_z_bins=n_z_bins,
+                                              plane_z=plane_z[s:e] if plane_z is not None and plane_z.ndim == 2 else plane_z,
+                                              background_rgb=None if background is None else background[s:e], depth_forward=depth_forward,
+                                              views_per_mpi=views_per_mpi, **render_kwargs)
+        return self._render_seeds(render, depth.shape[0], render_kwargs)
+
     def _render_seeds(self, render, n_mpis, render_kwargs):
-        """The loop of `render_seeds` and `render_seeds_shared`: `render(first MPI of the batch)` -> the renderer's 4-tuple."""
+        """The loop of `render_seeds`, `render_seeds_shared` and `render_seeds_depth`: `render(first MPI of the batch)` -> the renderer's 4-tuple."""
         from .hip_mpi import flush_status
         outs = []
         render_kwargs.setdefault("defer_status", "lag")   # (no frame leaves this method before every launch's assertions have been looked at)

@@ -412,7 +412,30 @@ def _staged_forward_takes(p, sc, tensors) -> bool:
     return rc == 1 and all(t is None or _readable_past_last_row(t, pad) for t in tensors)
 
 
+def _window_forward_takes(p, sc, da, tensors) -> bool:
+    """Whether the window forward of the depth-alpha layout can run this launch: gmpi_render_depth_window_supports (16-byte alignment of the three
+    images) and, as for the staged shared-colour forward, allocated padding behind the LAST row of each tensor when the texture width is no
+    multiple of 4.  Errors the launch would raise are raised here, under the query's name."""
+    rc = _lib.load_library().gmpi_render_depth_window_supports(ctypes.byref(p), ctypes.byref(sc), ctypes.byref(da))
+    if rc < 0:
+        _lib.check(rc, "gmpi_render_depth_window_supports")
+    pad = -p.Wt % 4
+    return rc == 1 and all(t is None or _readable_past_last_row(t, pad) for t in tensors)
+
+
 _LDS_FALLBACK_WARNED = False
+_WINDOW_FALLBACK_WARNED = False
+
+
+def _warn_window_fallback() -> None:
+    """Once per process: depth_forward="window" was asked for and the one-pixel-per-lane kernel ran (every such launch is counted in
+    `MPI.depth_window_fallbacks`)."""
+    global _WINDOW_FALLBACK_WARNED
+    if not _WINDOW_FALLBACK_WARNED:
+        _WINDOW_FALLBACK_WARNED = True
+        warnings.warn('depth-alpha render: depth_forward="window" cannot take these tensors (base pointers and outer strides must be multiples of '
+                      "16 bytes); the one-pixel-per-lane kernel runs instead (counted in MPI.depth_window_fallbacks; this warning is given once)",
+                      RuntimeWarning, stacklevel=4)
 
 
 def _warn_lds_fallback() -> None:
@@ -506,6 +529,7 @@ class MPI(nn.Module):
         self.on_out_of_plane = on_out_of_plane
         self._full_check_passed = None   # (weakref to the volume's base tensor, fingerprint): see _volume_fingerprint
         self.shared_lds_fallbacks = 0    # shared-colour launches that asked for "lds" and ran AUTO's kernel instead (a debug counter)
+        self.depth_window_fallbacks = 0  # depth-alpha launches that asked for depth_forward="window" and ran the one-pixel kernel instead
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -589,7 +613,8 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _shared=None, _shared_variant: Optional[str] = None, _depth=None, _depth_backward: str = "pixel"):
+                     _shared=None, _shared_variant: Optional[str] = None, _depth=None, _depth_backward: str = "pixel",
+                     _depth_forward: str = "pixel"):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -625,6 +650,8 @@ class MPI(nn.Module):
                 if _depth is not None:
                     kwargs["_depth"] = _depth
                     kwargs["_depth_backward"] = _depth_backward   # (read by _DepthRenderFunction; the forward does not depend on it)
+                    if _depth_forward != "pixel":
+                        kwargs["_depth_forward"] = _depth_forward
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -698,7 +725,15 @@ class MPI(nn.Module):
                         self.shared_lds_fallbacks += 1
                         _warn_lds_fallback()
                 if _depth is not None:
-                    _call("gmpi_mpi_render_depth_launch", dev, ctypes.byref(p), ctypes.byref(sc), ctypes.byref(_depth_alpha(*_depth)), stream=stream)
+                    da = _depth_alpha(*_depth)
+                    entry = "gmpi_mpi_render_depth_launch"
+                    if _depth_forward == "window":   # the window forward where its loader can take these tensors (alignment), else today's entry
+                        if _window_forward_takes(p, sc, da, (rgba, sh_rgb, sh_bg)):
+                            entry = "gmpi_mpi_render_depth_window_launch"
+                        else:
+                            self.depth_window_fallbacks += 1
+                            _warn_window_fallback()
+                    _call(entry, dev, ctypes.byref(p), ctypes.byref(sc), ctypes.byref(da), stream=stream)
                 else:
                     _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
             else:
@@ -788,8 +823,14 @@ class MPI(nn.Module):
         gmpi_mpi_render_depth_backward_tile_launch -- one workgroup per 32 x 16 pixel tile, the gradients of rgb and depth summed in LDS across
         the planes: the same gradients up to the order of the adds.  The tile backward assumes a pinhole ray field like the other staged kernels
         (any other gives correct gradients at the one-pixel kernel's speed) and takes D <= 128; with more planes, or with the "gather" variant,
-        the entry launches the one-pixel-per-lane kernel.  Any other name: ValueError.  The forward does not depend on it."""
-        assert "_shared" not in kwargs and "_depth" not in kwargs and "_depth_backward" not in kwargs
+        the entry launches the one-pixel-per-lane kernel.  Any other name: ValueError.  The forward does not depend on it.
+        `depth_forward`: "pixel" (the default, also None) renders with the one-pixel-per-lane kernel; "window" with
+        gmpi_mpi_render_depth_window_launch -- one workgroup per 32 x 16 pixel tile, every tap read from one window of rgb and depth texels in LDS
+        that moves with the tile's texel boxes, planes in front of the window's nearest depth skipped per tile: the same bits in both modes, the
+        same status words.  Its loader needs base pointers and outer strides that are multiples of 16 bytes (and, for a width that is no multiple
+        of 4, allocated padding behind the last row): tensors it cannot take render with the one-pixel kernel, counted in
+        `depth_window_fallbacks`, one RuntimeWarning per process.  Any other name: ValueError.  The backward does not depend on it."""
+        assert "_shared" not in kwargs and "_depth" not in kwargs and "_depth_backward" not in kwargs and "_depth_forward" not in kwargs
         variant = kwargs.pop("variant", None)   # (None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
         if variant not in (None, "auto", "gather"):
             raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
@@ -798,6 +839,9 @@ class MPI(nn.Module):
             raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
         if depth_backward != "pixel":   # (the default: exactly the call without the argument)
             kwargs["_depth_backward"] = depth_backward
+        depth_forward = _depth_forward_name(kwargs.pop("depth_forward", "pixel"))
+        if depth_forward != "pixel":
+            kwargs["_depth_forward"] = depth_forward
         depth5, shared, depth_alpha = _depth_operands(rgb, depth, plane_z, z_bounds, background, dhw.shape[1])
         return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _shared=shared, _shared_variant=variant, _depth=depth_alpha, **kwargs)
 
@@ -992,6 +1036,15 @@ class _SharedRenderFunction(torch.autograd.Function):
               g_color.data_ptr(), _ptr(g_depth), _ptr(g_T), *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
         out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
         return out[0], out[1], out[2], None, None, None, None, None, None
+
+
+# render_views_depth(depth_forward=...): None reads as "pixel"; anything but the two names is refused before any call
+def _depth_forward_name(depth_forward) -> str:
+    if depth_forward is None:
+        return "pixel"
+    if depth_forward not in ("pixel", "window"):
+        raise ValueError(f'depth_forward is "pixel" or "window", not {depth_forward!r}')
+    return depth_forward
 
 
 # render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)

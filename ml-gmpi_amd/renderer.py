@@ -422,6 +422,7 @@ class MPIRenderer:
         shared_variant = ext.pop("_shared_variant", None)
         depth_alpha = ext.pop("_depth", None)   # render_depth: (plane_z, z_lo, z_hi); batch_mpi_rgbas is then the depth image [B,1,1,Ht,Wt]
         depth_backward = ext.pop("_depth_backward", None)   # render_depth(depth_backward="tile")
+        depth_forward = ext.pop("_depth_forward", None)     # render_depth(depth_forward="window")
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -465,7 +466,8 @@ class MPIRenderer:
             check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
             c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
             **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}), **({} if depth_alpha is None else {"_depth": depth_alpha}),
-            **({} if depth_backward is None else {"_depth_backward": depth_backward}))
+            **({} if depth_backward is None else {"_depth_backward": depth_backward}),
+            **({} if depth_forward is None else {"_depth_forward": depth_forward}))
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
@@ -492,9 +494,14 @@ class MPIRenderer:
         `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with.  Keyword arguments, return tuple, pose
         sampling and the consumption of the torch RNG are `render`'s.  `depth_backward`: "pixel" (default) or "tile", as in
         `MPI.render_views_depth` -- the tile backward assumes a pinhole ray field (this renderer's rays are one) and takes D <= 128, else the
-        one-pixel-per-lane kernel runs; any other name is a ValueError before anything is launched."""
+        one-pixel-per-lane kernel runs; any other name is a ValueError before anything is launched.  `depth_forward`: "pixel" (default) or
+        "window", as in `MPI.render_views_depth` -- the window forward gives the same bits."""
         from .depth_alpha import depth_alpha_bounds
-        from .hip_mpi import _DEPTH_BACKWARD_ENTRIES, _depth_operands
+        from .hip_mpi import _DEPTH_BACKWARD_ENTRIES, _depth_forward_name, _depth_operands
+        depth_forward = _depth_forward_name(kwargs.pop("depth_forward", "pixel"))
+        assert "_depth_forward" not in kwargs
+        if depth_forward != "pixel":
+            kwargs["_depth_forward"] = depth_forward
         depth_backward = kwargs.pop("depth_backward", "pixel")
         if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
             raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')

@@ -1,12 +1,15 @@
 """CPU replay of the colour window of render_shared_tile_kernel (ml-gmpi_amd/csrc/render_shared.hip): per 32 x 16 pixel tile the texel boxes of the
 planes (from the tile's corner pixels, fp32 coordinate chain), the `inside` test and the re-anchor rule, and from them how often a tile flushes
 its colour window to global memory -- at the shapes and poses tools/time_shared_color.py times (FFHQ preset, 32 planes, torch.manual_seed(3)) and
-at the 2-sigma corner of the pose range.  No GPU needed.  usage: python tools/shared_window_replay.py [--window WxH] [--box WxH] [--one-window]
+at the 2-sigma corner of the pose range.  No GPU needed.  usage: python tools/shared_window_replay.py [--window WxH] [--box WxH] [--one-window | --forward]
 
 --window / --box: the window and the largest staged box in texels (defaults: the shared kernel's 64x32 and 56x27).  --one-window replays
 render_depth_tile_kernel (ml-gmpi_amd/csrc/render_depth_tile.hip): the box limit is the window itself unless --box is given, and the background's
 flush after the last plane empties the colour channels only -- the window stays filled (its depth channel), so that flush is not counted as a
-window flush: with a background every tile has one colour-channel flush on top of the counts printed."""
+window flush: with a background every tile has one colour-channel flush on top of the counts printed.  --forward replays
+render_depth_window_kernel (ml-gmpi_amd/csrc/render_depth_window.hip): the front-to-back sweep, a box staged when it fits the window once widened to
+whole loader items of 4 texels, the anchor column a multiple of 4, the drift direction taken from the next staged box of the 64-plane table chunk;
+it counts whole-window LOADS per tile (with a background one reload of the colour channels on top) and the planes that are not staged."""
 import argparse
 import os
 import sys
@@ -72,28 +75,68 @@ def flushes(bb, background, one_window=False):
     return count + filled
 
 
+FWD_CHUNK, FWD_ITEM = 64, 4   # kWChunk, kWTPI (render_depth_window.hip)
+
+
+def forward_staged(bb):
+    """bb [..., 4] boxes staged against the window itself (boxes(..) with AP, AR = CW, CH) -> the same with nx = 0 where the box, widened to whole
+    loader items, exceeds the window."""
+    x, nx = bb[..., 0], bb[..., 2]
+    wide = -(-(x + nx) // FWD_ITEM) * FWD_ITEM - (x // FWD_ITEM) * FWD_ITEM
+    out = bb.copy()
+    out[..., 2] = np.where(wide <= CW, nx, 0)
+    return out
+
+
+def loads(bb):
+    """bb [D, 4] of one tile -> number of whole-window loads of the forward's front-to-back sweep."""
+    D = bb.shape[0]
+    wx0 = wy0 = dx = dy = 0
+    is_open = False
+    count = 0
+    for k in range(D):
+        x, y, nx, ny = (int(v) for v in bb[k])
+        if nx == 0:
+            continue
+        if not (is_open and x >= wx0 and y >= wy0 and x + nx <= wx0 + CW and y + ny <= wy0 + CH):
+            ahead = [b for b in bb[k + 1:min(k - k % FWD_CHUNK + FWD_CHUNK, D)] if b[2] > 0]
+            if ahead:   # the drift: centres of this box and of the next staged one of the chunk
+                ddx, ddy = 2 * int(ahead[0][0]) + int(ahead[0][2]) - (2 * x + nx), 2 * int(ahead[0][1]) + int(ahead[0][3]) - (2 * y + ny)
+                dx, dy = ddx or dx, ddy or dy
+            wx0 = -(-(x + nx) // FWD_ITEM) * FWD_ITEM - CW if dx < 0 else (x // FWD_ITEM) * FWD_ITEM
+            wy0 = y + ny - CH if dy < 0 else y
+            is_open = True
+            count += 1
+    return count
+
+
 def main():
     global AP, AR, CW, CH
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", default=None, help="WxH of the window in texels")
     ap.add_argument("--box", default=None, help="WxH of the largest box that is staged")
     ap.add_argument("--one-window", action="store_true", help="replay render_depth_tile_kernel: one window for colour and depth")
+    ap.add_argument("--forward", action="store_true", help="replay render_depth_window_kernel: window loads of the front-to-back sweep")
     args = ap.parse_args()
     if args.window:
         CW, CH = (int(v) for v in args.window.lower().split("x"))
-    if args.one_window:
+    if args.one_window or args.forward:
         AP, AR = CW, CH
     if args.box:
         AP, AR = (int(v) for v in args.box.lower().split("x"))
     assert AP <= CW and AR <= CH, "a staged box must fit the window"
     one_window = args.one_window
     D = 32
-    if one_window:
+    if args.forward:
+        print(f"window loads per tile (whole reloads of the {CW} x {CH} window, all four channels; boxes that fit it once widened to items of {FWD_ITEM} texels are "
+              "staged; with a background one reload of the colour channels on top), D = 32, FFHQ preset")
+    elif one_window:
         print(f"window flushes per tile (non-empty flushes of the {CW} x {CH} window, all four channels; boxes up to {AP} x {AR} are staged; with a background one "
               "flush of the colour channels on top), D = 32, FFHQ preset")
     else:
         print(f"colour-window flushes per tile (non-empty flushes of the {CW} x {CH} window; alpha is flushed once per plane on top), D = 32, FFHQ preset")
-    print(f"{'case':34s} {'tiles':>6s} {'mean':>6s} {'max':>4s} {'tiles with 1 / 2 flushes':>26s} {'not staged planes':>18s}")
+    what = "loads" if args.forward else "flushes"
+    print(f"{'case':34s} {'tiles':>6s} {'mean':>6s} {'max':>4s} {'tiles with 1 / 2 ' + what:>26s} {'not staged planes':>18s}")
     for S, B, extreme in ((256, 8, False), (512, 4, False), (1024, 4, False), (256, 2, True), (512, 2, True), (1024, 2, True)):
         kw = dict(PRESETS["FFHQ"])
         kw.update(n_mpi_planes=D, plan_spatial_enlarge_factor=1.001, plane_distances_sample_method="inverse", cam_sample_method="truncated_gaussian",
@@ -111,8 +154,13 @@ def main():
         ray, eye = torch.cat(cam[3]).numpy(), torch.cat(cam[4]).numpy()
         dhw = r.static_mpi_plane_dhws.reshape(-1, 3).numpy()
         bb = boxes(dhw, ray, eye, S)
+        if args.forward:
+            bb = forward_staged(bb)
         for background in (True, False):
-            cnt = np.array([flushes(bb[n, :, t], background, one_window) for n in range(bb.shape[0]) for t in range(bb.shape[2])])
+            if args.forward:
+                cnt = np.array([loads(bb[n, :, t]) for n in range(bb.shape[0]) for t in range(bb.shape[2])])
+            else:
+                cnt = np.array([flushes(bb[n, :, t], background, one_window) for n in range(bb.shape[0]) for t in range(bb.shape[2])])
             name = f"{S}^2 x {B} {'2-sigma poses' if extreme else 'timed poses'} {'bg' if background else 'no bg'}"
             print(f"{name:34s} {cnt.size:6d} {cnt.mean():6.2f} {cnt.max():4d} {(cnt == 1).sum():12d} / {(cnt == 2).sum():<11d} {int((bb[..., 2] == 0).sum()):18d}")
         if not extreme:

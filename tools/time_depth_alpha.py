@@ -13,20 +13,26 @@ several planes wide) and 256 (a step).
   shared   the alpha planes materialised (depth_alpha_planes), render_views_shared (variant auto: one pixel per lane), zero-fill of the three gradients,
            shared backward (tile kernel), autograd through the ramp
 
+  depth, window forward   `depth_forward="window"` (render_depth_window.hip: one workgroup per 32 x 16 pixel tile, every tap from one moving LDS window, planes
+           in front of the window's nearest depth skipped): column `depth_fwd_window`.  The two forwards are timed ALTERNATELY in the same child (pixel,
+           window, pixel, window, ...) -- `depth_fwd` is the one-pixel kernel's median of that interleaved run -- and their outputs are compared
+           (`window_check`: 1 when colour, depth and T are bit-equal; anything else ends the run).  `window_vs_pixel` = depth_fwd_window / depth_fwd.
+           A last shape is the 8-view camera path of ONE 512^2 x 96 MPI (views_per_mpi = 8), forward only.
+
 and the peak device memory of one pass of each above the inputs (torch.cuda.max_memory_allocated).  Every shape runs in a child process of its own under a
-time limit; the first failure ends the run.  usage: python tools/time_depth_alpha.py [reps] [passes]"""
+time limit; the first failure ends the run.  usage: python tools/time_depth_alpha.py [--forward] [reps] [passes]   (--forward: no backward at any shape)"""
 import ctypes
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# (S, MPIs, planes, with backward)
-SHAPES = [("256", 8, 32, 1), ("512", 4, 32, 1), ("1024", 4, 32, 1), ("1024", 4, 96, 0)]
+# (S, MPIs, planes, with backward, views per MPI)
+SHAPES = [("256", 8, 32, 1, 1), ("512", 4, 32, 1, 1), ("1024", 4, 32, 1, 1), ("1024", 4, 96, 0, 1), ("512", 1, 96, 0, 8)]
 N_Z_BINS = (4, 256)
 
 
-def one(S, B, D, n_z_bins, with_backward, reps):
+def one(S, B, D, n_z_bins, with_backward, reps, views=1):
     import torch
     sys.path.insert(0, ROOT)
     import ml_gmpi_amd
@@ -66,17 +72,23 @@ def one(S, B, D, n_z_bins, with_backward, reps):
     depth = (depth + 0.02 * (torch.rand((B, 1, S, S), device=dev, generator=g) - 0.5)).contiguous()
     plane_z = torch.linspace(0, 1, D, device=dev)
     zb = depth_alpha_bounds(1, n_z_bins)
-    gc = torch.randn((B, 3, S, S), device=dev, generator=g)
-    gd = torch.randn((B, 1, S, S), device=dev, generator=g)
+    N = B * views
+    gc = torch.randn((N, 3, S, S), device=dev, generator=g)
+    gd = torch.randn((N, 1, S, S), device=dev, generator=g)
     torch.manual_seed(3)
-    cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
+    if views > 1:   # a camera path: yaw across the pose range, a little pitch
+        gy = torch.linspace(-1, 1, N).reshape(N, 1) * (2 * r.horizontal_std)
+        gp = torch.linspace(-1, 1, N).reshape(N, 1) * r.vertical_std
+        cam = r.sample_cam_poses(N, 0.0, 0.0, 0.0, 0.0, False, given_yaws=gy, given_pitches=gp)
+    else:
+        cam = r.sample_cam_poses(B, r.horizontal_mean, r.horizontal_std, r.vertical_mean, r.vertical_std, True)
     ray, eye, zd = torch.cat(cam[3]), torch.cat(cam[4]), torch.cat(cam[5])
     dhw = r._dhw_on_device().expand(B, -1, -1).contiguous()
-    kw = dict(check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True)
-    out = {k: torch.empty(s, device=dev) for k, s in (("color", (B, 3, S, S)), ("depth", (B, 1, S, S)), ("T", (B, 1, S, S)))}
+    kw = dict(check_last_plane=True, out_pm1=True, want_transmittance=True, defer_status=True, views_per_mpi=views)
+    out = {k: torch.empty(s, device=dev) for k, s in (("color", (N, 3, S, S)), ("depth", (N, 1, S, S)), ("T", (N, 1, S, S)))}
     s3 = lambda t, dims: (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
     base_mem = torch.cuda.memory_allocated(dev)
-    row = dict(S=S, B=B, D=D, n_z_bins=n_z_bins)
+    row = dict(S=S, B=B, D=D, n_z_bins=n_z_bins, views=N)
 
     def backward_struct(p):
         q = _lib.GmpiRenderParams.from_buffer_copy(p)
@@ -172,7 +184,20 @@ def one(S, B, D, n_z_bins, with_backward, reps):
     torch.cuda.synchronize()
     row["depth_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
     with torch.no_grad():
-        row["depth_fwd"] = timed(lambda: r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, **kw))
+        # the two forwards at the timed size: the window kernel must give the one-pixel kernel's bits
+        fwd = lambda how: lambda: r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, depth_forward=how, **kw)
+        fwd("pixel")()
+        want = {k: v.clone() for k, v in out.items()}
+        for v in out.values():
+            v.fill_(-7.0)
+        fwd("window")()
+        row["window_check"] = int(all(torch.equal(out[k], want[k]) for k in out) and r.mpi.depth_window_fallbacks == 0)
+        assert row["window_check"] == 1, "window forward against the one-pixel forward"
+        del want
+        row["depth_fwd"], row["depth_fwd_window"] = timed_alternately(fwd("pixel"), fwd("window"))
+    row["window_vs_pixel"] = row["depth_fwd_window"] / row["depth_fwd"]
+    row["window_vs_auto_on_existing_volume"] = row["depth_fwd_window"] / row["volume_fwd"]
+    row["window_vs_volume"] = row["depth_fwd_window"] / (row["volume_expand"] + row["volume_fwd"])
     if with_backward:
         row["depth_fill"] = timed(lambda: (d_rgb.zero_(), d_dep.zero_(), d_bg.zero_()))
         row["depth_bwd"], row["depth_bwd_tile"] = timed_alternately(dbwd, dbwd_tile)
@@ -194,18 +219,20 @@ def one(S, B, D, n_z_bins, with_backward, reps):
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--one":
-        S, B, D, n, bw, reps = sys.argv[2:8]
-        one(int(S), int(B), int(D), int(n), int(bw), int(reps))
+        S, B, D, n, bw, reps, views = sys.argv[2:9]
+        one(int(S), int(B), int(D), int(n), int(bw), int(reps), int(views))
         sys.exit(0)
-    reps = sys.argv[1] if len(sys.argv) > 1 else "15"
-    passes = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    argv = [a for a in sys.argv[1:] if a != "--forward"]
+    forward_only = len(argv) != len(sys.argv) - 1
+    reps = argv[0] if len(argv) > 0 else "15"
+    passes = int(argv[1]) if len(argv) > 1 else 3
     print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape;", passes, "passes")
     for k in range(passes):
         print(f"== pass {k + 1} ==", flush=True)
-        for S, B, D, bw in SHAPES:
+        for S, B, D, bw, views in SHAPES:
             for n in N_Z_BINS:
                 try:
-                    rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), str(n), str(bw), reps], timeout=240).returncode
+                    rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), str(n), str(0 if forward_only else bw), reps, str(views)], timeout=240).returncode
                 except subprocess.TimeoutExpired:   # (run() has killed the child)
                     rc = "time limit of 240 s"
                 if rc != 0:
