@@ -346,8 +346,8 @@ typedef struct GmpiDepthAlpha {
  * it, any other variant is GMPI_E_VARIANT.  z_lo >= z_hi or z_den <= 0 (or a NaN among them): GMPI_E_SHAPE; a negative plane_z_stride:
  * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
  * never synchronises.  A window forward has an entry of its own (gmpi_mpi_render_depth_window_launch, below: this entry keeps its one kernel and
- * still refuses GMPI_VARIANT_LDS).  Not built: 8-bit storage, gradients w.r.t. the geometry (gmpi_query(22) says whether the layout itself is
- * built in).
+ * still refuses GMPI_VARIANT_LDS).  Gradients w.r.t. the geometry: gmpi_mpi_render_depth_geometry_backward_launch (gmpi_query(30)).  Not built: 8-bit
+ * storage, gradients w.r.t. plane_z and the ramp's bounds (gmpi_query(22) says whether the layout itself is built in).
  */
 int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
 
@@ -411,6 +411,32 @@ int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams *params, c
                                                float *grad_shared_rgb, const int64_t *grad_shared_rgb_stride, float *grad_depth_image,
                                                const int64_t *grad_depth_image_stride, float *grad_background,
                                                const int64_t *grad_background_stride, void *stream);
+
+/*
+ * gmpi_mpi_render_geometry_backward_ex_launch over the two layouts: the gradient of gmpi_mpi_render_shared_launch / gmpi_mpi_render_depth_launch w.r.t.
+ * the sample POSITIONS -- by definition that of the volume entry on the expanded volume, which is never materialised.  `params`, `shared` and
+ * `depth_alpha` as for the layout's image backward (params->rgba = the alpha planes, resp. the depth image; AUTO and GATHER run the same kernel, any
+ * other variant is GMPI_E_VARIANT; GMPI_DTYPE_U8: GMPI_E_DTYPE; a NULL struct: GMPI_E_NULL; their stride codes); grad_rgb [N,3,H,W], grad_depth and
+ * grad_transmittance [N,1,H,W] or NULL, and the four outputs as for the volume entry: OVERWRITTEN, NULL = not wanted (all four NULL: GMPI_OK, nothing is
+ * launched).  The workspace is the volume entry's: gmpi_render_geometry_backward_workspace_bytes(params, grad_dhw != NULL) bytes (it depends on N, H, W
+ * and D only), 256-byte aligned, else GMPI_E_WORKSPACE when grad_eye_pos, grad_z_dir or grad_dhw is wanted.  The formulas are the volume entry's; only
+ * the source of the four taps per channel and of the sweep's starting transmittance differs:
+ *   shared-colour  channels 0-2 from rgb[m] (background[m] on plane D-1 when given), channel 3 from alpha[m,k]; the start is transmittance_out, with
+ *                  the re-walk over the alpha planes when it underflowed;
+ *   depth-alpha    channel 3's taps are the ramp of each depth tap -- the forward's correctly rounded quotient for the launch's mode, 0 outside the
+ *                  texture -- so the alpha sample and its position derivative are those of the expanded volume with zeros padding; the start is the
+ *                  re-walk over the ramp samples (the common path of this layout).  A plane whose four ramp taps are all exactly 0 is skipped for that
+ *                  pixel, colour taps included (a NaN colour texel under such a region reaches no gradient); a zero alpha SAMPLE alone does not skip.
+ * plane_z as [D] or [M,D], any view_to_mpi / views_per_mpi, GMPI_FLAG_OUT_PM1, GMPI_FLAG_STRICT_ORDER (the forward's chain for the flags), fp32 / bf16 /
+ * fp16 storage.  No atomics: every output is bit-reproducible.  No status bit is set.  No gradient w.r.t. plane_z or the ramp's bounds.
+ * gmpi_query(30) == 1 says that both entries are built in.
+ */
+int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const float *grad_rgb,
+                                                    const float *grad_depth, const float *grad_transmittance, float *grad_ray_dir,
+                                                    float *grad_eye_pos, float *grad_z_dir, float *grad_dhw, void *stream);
+int gmpi_mpi_render_depth_geometry_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                                   const float *grad_rgb, const float *grad_depth, const float *grad_transmittance,
+                                                   float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw, void *stream);
 
 /*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the
@@ -534,7 +560,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * 22 whether the depth-alpha layout (gmpi_mpi_render_depth_launch) is built in; 23 the number of planes the depth-alpha tile backward
  * (gmpi_mpi_render_depth_backward_tile_launch) takes: more go to the one-pixel-per-lane kernel; 24 is unused (-1); the depth-alpha window forward
  * (gmpi_mpi_render_depth_window_launch): 25 whether it is built in, 26 / 27 the width / height of its window in texels, 28 the planes per refill of
- * its box table.  Unknown -> -1.                                                                                                      */
+ * its box table; 29 is unused (-1); 30 whether the geometry backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_shared_geometry_backward_launch,
+ * gmpi_mpi_render_depth_geometry_backward_launch) is built in.  Unknown -> -1.                                                          */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -40,6 +40,8 @@ EXPORTS = (
     "gmpi_render_depth_window_supports",
     "gmpi_mpi_render_depth_backward_launch",
     "gmpi_mpi_render_depth_backward_tile_launch",
+    "gmpi_mpi_render_shared_geometry_backward_launch",
+    "gmpi_mpi_render_depth_geometry_backward_launch",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -222,6 +224,11 @@ def load_library():
                                                           vp, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp]
     lib.gmpi_mpi_render_depth_backward_tile_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_backward_tile_launch.argtypes = list(lib.gmpi_mpi_render_depth_backward_launch.argtypes)   # (the same signature)
+    lib.gmpi_mpi_render_shared_geometry_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shared_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gmpi_mpi_render_depth_geometry_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_depth_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha),
+                                                                   vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int

@@ -43,6 +43,8 @@ bool u8_variant_supports(const KParams& p);                                 // r
 int u8_variant_query(int what);                                             // render_u8.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
+hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
+                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 
 // ---- min/max of the normalised grid on the last plane (mpi.py:103-109 diagnostics) --------------
 template <bool AC>
@@ -498,13 +500,10 @@ int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams* params, con
                                                        stream);
 }
 
-int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
-                                                const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
-                                                float* grad_dhw, void* stream) {
-    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
-    KParams p;
-    const int rc = to_kparams(params, p, false, true);
-    if (rc != GMPI_OK) return rc;
+// What the three geometry backward entries check once their structs are read: GMPI_OK with *launch = false when there is nothing to do.
+static int geometry_backward_args(const KParams& p, const float* grad_rgb, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir, float* grad_dhw,
+                                  bool* launch) {
+    *launch = false;
     if (grad_rgb == nullptr) return GMPI_E_NULL;
     if (p.N > 65535 || p.M > 65535 || 6 + 3 * static_cast<int64_t>(p.D) > (int64_t(1) << 31) - 1) return GMPI_E_SHAPE;   // grid.y: views / MPIs, grid.x: components
     if (grad_ray_dir == nullptr && grad_eye_pos == nullptr && grad_z_dir == nullptr && grad_dhw == nullptr) return GMPI_OK;
@@ -512,6 +511,20 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, 
         const uint64_t need = geometry_backward_workspace_bytes(p, grad_dhw != nullptr);
         if (p.ws == nullptr || p.ws_bytes < need || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return GMPI_E_WORKSPACE;
     }
+    *launch = true;
+    return GMPI_OK;
+}
+
+int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
+                                                const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
+                                                float* grad_dhw, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
+    KParams p;
+    int rc = to_kparams(params, p, false, true);
+    if (rc != GMPI_OK) return rc;
+    bool launch;
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    if (!launch) return rc;
     return hip_rc(launch_backward_geometry(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw,
                                            static_cast<hipStream_t>(stream)));
 }
@@ -702,6 +715,36 @@ int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams* params, c
                           grad_depth_image, grad_depth_image_stride, grad_background, grad_background_stride, stream, true);
 }
 
+// The geometry backward over the two layouts: the layout's own struct checks (to_shared / to_depth, as its image backward), then the volume entry's.
+int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb, const float* grad_depth,
+                                                    const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
+                                                    float* grad_dhw, void* stream) {
+    KParams p;
+    SharedK sh;
+    int rc = to_shared(params, shared, false, p, sh);
+    if (rc != GMPI_OK || p.N == 0) return rc;
+    bool launch;
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    if (!launch) return rc;
+    return hip_rc(launch_backward_geometry_layout(p, params->rgba_dtype, sh, nullptr, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos,
+                                                  grad_z_dir, grad_dhw, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_depth_geometry_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                                   const float* grad_rgb, const float* grad_depth, const float* grad_transmittance, float* grad_ray_dir,
+                                                   float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, void* stream) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    int rc = to_depth(params, shared, depth_alpha, false, p, sh, dk);
+    if (rc != GMPI_OK || p.N == 0) return rc;
+    bool launch;
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    if (!launch) return rc;
+    return hip_rc(launch_backward_geometry_layout(p, params->rgba_dtype, sh, &dk, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos,
+                                                  grad_z_dir, grad_dhw, static_cast<hipStream_t>(stream)));
+}
+
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {
     KParams p;
     const int rc = to_kparams(params, p, false);
@@ -824,6 +867,7 @@ int gmpi_query(int32_t what) {
         case 23: return depth_tile_planes();  // planes the depth-alpha tile backward takes (more: the one-pixel-per-lane kernel)
         case 25: return 1;  // the depth-alpha window forward (gmpi_mpi_render_depth_window_launch) is built in  (24: unused)
         case 26: case 27: case 28: return depth_window_query(what);
+        case 30: return 1;  // the geometry backward of the shared-colour and depth-alpha layouts is built in  (29: unused)
         default: return -1;
     }
 }

@@ -188,7 +188,8 @@ __device__ __forceinline__ void fetch_taps(Tap& tp, bool active, const KParams& 
 // The final transmittance the depth-alpha backward sweeps start from (bwd_pixel_setup_with's `total`; both backward kernels of the layout call this
 // one text): the forward's value when it is usable (total_transmittance's rule), else a front-to-back walk over the RAMP samples in the extended
 // representation -- total_transmittance reads alpha planes, which do not exist here.  bp: the pixel's ray (set before `total` is called).
-template <typename TexT, bool AC>
+// STRICT: the ramp and its bilinear sample as the strict-order forward rounds them (the geometry pass, whose strict-order sweep divides by those).
+template <typename TexT, bool AC, bool STRICT = false>
 __device__ __forceinline__ XT depth_total_transmittance(const KParams& p, const BwdView& vw, const BwdPixel& bp, const TexT* __restrict__ depth,
                                                         const float* __restrict__ pz, const DepthK& dk, float t_fwd) {
     XT t{1.0f, 0};
@@ -201,8 +202,8 @@ __device__ __forceinline__ XT depth_total_transmittance(const KParams& p, const 
         float ix, iy, s;
         pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
         const Taps tp = make_taps(ix, iy, p.Ht, p.Wt);
-        const RampTaps r = ramp_taps<TexT, false>(depth, p.s_row, tp, pz[k], dk);
-        const float a = bilerp<false>(r.a[0], r.a[1], r.a[2], r.a[3], tp.f);
+        const RampTaps r = ramp_taps<TexT, STRICT>(depth, p.s_row, tp, pz[k], dk);
+        const float a = bilerp<STRICT>(r.a[0], r.a[1], r.a[2], r.a[3], tp.f);
         t.m *= (1.0f - a) + 1e-10f;
         t.renorm();
     }

@@ -15,7 +15,25 @@
 // workgroup in a fixed order (DPP within a row of 16 lanes, the four rows by readlane, one LDS slot per wave and plane, the waves in order) and
 // written to this tile's slot of a slab in the caller's workspace; geometry_reduce_kernel then sums the slabs in a fixed order.  No atomics: every
 // output is bit-reproducible from run to run.  Any view_to_mpi, any ray field (each pixel gathers its own taps), 64-bit volume offsets.
+//
+// ONE frame (geometry_pixel_kernel), three TAP SOURCES, selected by the layout structs the kernel is instantiated with (SourceOf).  The frame
+// depends on the input layout in two places only: where the 4 x 4 tap values
+// t[c][nw, ne, sw, se] of a plane come from, and where the sweep's starting transmittance comes from.  A source is a small struct with
+//   start(bp, ...)            the per-pixel setup (bwd_pixel_setup / bwd_pixel_setup_with, gmpi_backward.hpp) with the layout's transmittance walk
+//   taps<STRICT>(k, ix, iy, q)   the 16 tap values of plane k and the fractions; false = the plane is the identity of this pixel's sweep: skipped
+//   VolumeSource   the RGBA volume (no layout struct): four channels of one plane; never skips
+//   SharedSource   the shared-colour layout (SharedK): channels 0-2 from rgb[m] (background[m] on plane D - 1 when one is
+//                  given: uniform per plane), channel 3 from alpha[m, k]; the start is the volume's (KParams carries the alpha planes with s_chan = 0)
+//   DepthSource    the depth-alpha layout (SharedK, DepthK): channel 3's taps are the RAMP of each depth tap (depth_ramp: the forward's
+//                  correctly rounded quotient for the launch's mode), 0 outside the texture, so that the frame's bilinear sample and its dix[3] /
+//                  diy[3] are, term for term, those of the expanded volume with zeros padding; the start is depth_total_transmittance (the re-walk
+//                  is this layout's common path); in strict-order mode the alpha sample and the re-walk round as the strict forward does.  A plane whose four ramp taps are all exactly 0 is skipped WITHOUT loading its colour taps (the
+//                  forward never reads colour under a zero alpha sample): with a = 0 and zero tap differences it adds nothing to any gradient and
+//                  leaves T and S as they are (om rounds to 1).  NOT skipped: an alpha SAMPLE of 0 with a non-zero tap under a zero bilinear
+//                  weight -- its one-sided position derivative is not zero.
+// The layout kernels set no status bits.
 #include "gmpi_backward.hpp"
+#include "gmpi_shared.hpp"
 
 #include <algorithm>
 
@@ -46,8 +64,12 @@ struct Taps {
     float wx0, wx1, wy0, wy1;
 };
 
-template <typename TexT>
-__device__ __forceinline__ void gather_taps(const TexT* __restrict__ pl, int64_t s_chan, int64_t s_row, int Ht, int Wt, float ix, float iy, Taps& q) {
+// Where the four taps of a footprint are read (addresses clamped into the texture) and which of them lie inside it; fills q's fractions.
+struct TapPos {
+    int xa, xb, ya, yb;
+    bool nw, ne, sw, se;
+};
+__device__ __forceinline__ TapPos tap_pos(int Ht, int Wt, float ix, float iy, Taps& q) {
     const float fx0 = floorf(ix), fy0 = floorf(iy);
     q.wx1 = ix - fx0, q.wx0 = (fx0 + 1.0f) - ix;
     q.wy1 = iy - fy0, q.wy0 = (fy0 + 1.0f) - iy;
@@ -55,25 +77,142 @@ __device__ __forceinline__ void gather_taps(const TexT* __restrict__ pl, int64_t
     const int y0 = (fy0 >= -2.0f && fy0 <= static_cast<float>(Ht)) ? static_cast<int>(fy0) : -2;
     const bool x0in = x0 >= 0 && x0 <= Wt - 1, x1in = x0 >= -1 && x0 <= Wt - 2;
     const bool y0in = y0 >= 0 && y0 <= Ht - 1, y1in = y0 >= -1 && y0 <= Ht - 2;
-    const int xa = min(max(x0, 0), Wt - 1), xb = min(max(x0 + 1, 0), Wt - 1);
-    const int ya = min(max(y0, 0), Ht - 1), yb = min(max(y0 + 1, 0), Ht - 1);
-    const int64_t oa = static_cast<int64_t>(ya) * s_row, ob = static_cast<int64_t>(yb) * s_row;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const TexT* __restrict__ ch = pl + c * s_chan;
-        const float nw = to_f32(ch[oa + xa]), ne = to_f32(ch[oa + xb]), sw = to_f32(ch[ob + xa]), se = to_f32(ch[ob + xb]);
-        q.t[c][0] = (x0in && y0in) ? nw : 0.0f;
-        q.t[c][1] = (x1in && y0in) ? ne : 0.0f;
-        q.t[c][2] = (x0in && y1in) ? sw : 0.0f;
-        q.t[c][3] = (x1in && y1in) ? se : 0.0f;
-    }
+    TapPos tp;
+    tp.xa = min(max(x0, 0), Wt - 1), tp.xb = min(max(x0 + 1, 0), Wt - 1);
+    tp.ya = min(max(y0, 0), Ht - 1), tp.yb = min(max(y0 + 1, 0), Ht - 1);
+    tp.nw = x0in && y0in, tp.ne = x1in && y0in, tp.sw = x0in && y1in, tp.se = x1in && y1in;
+    return tp;
 }
+// the four texels of one channel as stored (a tap outside the texture reads the clamped border texel)
+template <typename TexT>
+__device__ __forceinline__ void load_taps(const TexT* __restrict__ ch, int64_t s_row, const TapPos& tp, float (&v)[4]) {
+    const int64_t oa = static_cast<int64_t>(tp.ya) * s_row, ob = static_cast<int64_t>(tp.yb) * s_row;
+    v[0] = to_f32(ch[oa + tp.xa]), v[1] = to_f32(ch[oa + tp.xb]), v[2] = to_f32(ch[ob + tp.xa]), v[3] = to_f32(ch[ob + tp.xb]);
+}
+// ... with zeros padding
+__device__ __forceinline__ void pad_taps(const TapPos& tp, const float (&v)[4], float (&t)[4]) {
+    t[0] = tp.nw ? v[0] : 0.0f, t[1] = tp.ne ? v[1] : 0.0f, t[2] = tp.sw ? v[2] : 0.0f, t[3] = tp.se ? v[3] : 0.0f;
+}
+template <typename TexT>
+__device__ __forceinline__ void gather_channel(const TexT* __restrict__ ch, int64_t s_row, const TapPos& tp, float (&t)[4]) {
+    float v[4];
+    load_taps<TexT>(ch, s_row, tp, v);
+    pad_taps(tp, v, t);
+}
+
+template <typename TexT>
+__device__ __forceinline__ void gather_taps(const TexT* __restrict__ pl, int64_t s_chan, int64_t s_row, int Ht, int Wt, float ix, float iy, Taps& q) {
+    const TapPos tp = tap_pos(Ht, Wt, ix, iy, q);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) gather_channel<TexT>(pl + c * s_chan, s_row, tp, q.t[c]);
+}
+
+// ---- the tap sources (see the header) ----------------------------------------------------------------------------------------------------------
+template <typename TexT>
+struct VolumeSource {
+    static constexpr bool kSkips = false;          // taps() never returns false
+    static constexpr bool kForwardAlpha = false;   // the alpha sample is the frame's fma chain in both modes
+    const TexT* __restrict__ vol;
+    __device__ __forceinline__ VolumeSource(const KParams& p, const BwdView& vw)
+        : vol(static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi) {}
+    template <bool AC, bool STRICT>
+    __device__ __forceinline__ void start(BwdPixel& bp, const KParams& p, const BwdView& vw, const BwdParams& b, int n, int px, int py, bool active) const {
+        bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    }
+    template <bool STRICT>
+    __device__ __forceinline__ bool taps(const KParams& p, int k, int Ht, int Wt, float ix, float iy, Taps& q) const {
+        gather_taps<TexT>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, q);
+        return true;
+    }
+};
+
+// the colour image of plane k of MPI m: rgb, or the background on the last plane (uniform per plane)
+template <typename TexT>
+struct ColourImages {
+    const TexT* __restrict__ rgb;
+    const TexT* __restrict__ bgi;
+    int64_t rs_chan, rs_row, bs_chan, bs_row;
+    __device__ __forceinline__ ColourImages(const SharedK& sh, int m)
+        : rgb(static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(m) * sh.rs_mpi),
+          bgi(sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(m) * sh.bs_mpi : nullptr),
+          rs_chan(sh.rs_chan), rs_row(sh.rs_row), bs_chan(sh.bs_chan), bs_row(sh.bs_row) {}
+    __device__ __forceinline__ void taps(int k, int D, const TapPos& tp, Taps& q) const {
+        const bool last_bg = bgi != nullptr && k == D - 1;
+        const TexT* __restrict__ col = last_bg ? bgi : rgb;
+        const int64_t c_chan = last_bg ? bs_chan : rs_chan, c_row = last_bg ? bs_row : rs_row;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gather_channel<TexT>(col + c * c_chan, c_row, tp, q.t[c]);
+    }
+};
+
+template <typename TexT>
+struct SharedSource {
+    static constexpr bool kSkips = false;
+    static constexpr bool kForwardAlpha = false;   // (the volume path's sweep exactly)
+    const TexT* __restrict__ alpha;   // KParams' volume fields: the alpha planes, s_chan = 0
+    ColourImages<TexT> col;
+    __device__ __forceinline__ SharedSource(const KParams& p, const BwdView& vw, const SharedK& sh)
+        : alpha(static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi), col(sh, vw.m) {}
+    template <bool AC, bool STRICT>
+    __device__ __forceinline__ void start(BwdPixel& bp, const KParams& p, const BwdView& vw, const BwdParams& b, int n, int px, int py, bool active) const {
+        bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, alpha);   // (the shared backward's setup)
+    }
+    template <bool STRICT>
+    __device__ __forceinline__ bool taps(const KParams& p, int k, int Ht, int Wt, float ix, float iy, Taps& q) const {
+        const TapPos tp = tap_pos(Ht, Wt, ix, iy, q);
+        col.taps(k, p.D, tp, q);
+        gather_channel<TexT>(alpha + static_cast<int64_t>(k) * p.s_plane, p.s_row, tp, q.t[3]);
+        return true;
+    }
+};
+
+template <typename TexT>
+struct DepthSource {
+    static constexpr bool kSkips = true;
+    static constexpr bool kForwardAlpha = true;    // strict-order mode: bilerp<true> of the ramp taps, as render_depth_kernel
+    const TexT* __restrict__ depth;   // KParams' volume fields: the depth image (s_plane, s_chan unused)
+    const float* __restrict__ pz;
+    DepthK dk;
+    ColourImages<TexT> col;
+    __device__ __forceinline__ DepthSource(const KParams& p, const BwdView& vw, const SharedK& sh, const DepthK& d)
+        : depth(static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi),
+          pz(d.plane_z + static_cast<int64_t>(vw.m) * d.pz_stride), dk(d), col(sh, vw.m) {}
+    template <bool AC, bool STRICT>
+    __device__ __forceinline__ void start(BwdPixel& bp, const KParams& p, const BwdView& vw, const BwdParams& b, int n, int px, int py, bool active) const {
+        bwd_pixel_setup_with<true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T,
+                                   [&](float t_fwd) { return depth_total_transmittance<TexT, AC, STRICT>(p, vw, bp, depth, pz, dk, t_fwd); });
+    }
+    template <bool STRICT>
+    __device__ __forceinline__ bool taps(const KParams& p, int k, int Ht, int Wt, float ix, float iy, Taps& q) const {
+        const TapPos tp = tap_pos(Ht, Wt, ix, iy, q);
+        float d[4], a[4];
+        load_taps<TexT>(depth, p.s_row, tp, d);
+        const float z = pz[k];
+        bool inside;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = depth_ramp<STRICT>(z, d[i], dk, inside);
+        pad_taps(tp, a, q.t[3]);
+        // (a NaN ramp value compares unequal to 0: such a plane is swept, as on the expanded volume)
+        if (q.t[3][0] == 0.0f && q.t[3][1] == 0.0f && q.t[3][2] == 0.0f && q.t[3][3] == 0.0f) return false;
+        col.taps(k, p.D, tp, q);
+        return true;
+    }
+};
+
+template <typename TexT, typename... Extra> struct SourceOf;
+template <typename TexT> struct SourceOf<TexT> { using type = VolumeSource<TexT>; };
+template <typename TexT> struct SourceOf<TexT, SharedK> { using type = SharedSource<TexT>; };
+template <typename TexT> struct SourceOf<TexT, SharedK, DepthK> { using type = DepthSource<TexT>; };
 
 // Slab layout (floats): component j of tile t of view n at ws[(j * N + n) * T + t];  j = 0..2 eye, 3..5 z_dir, 6 + 3k + (0, 1, 2) = plane k's
 // (d, h, w).  Every slot is written by exactly one workgroup.
-template <typename TexT, bool AC, bool STRICT, bool DHW>
+//
+// The frame.  Extra: the layout's structs -- none: the RGBA volume; SharedK: the shared-colour layout; SharedK, DepthK: the depth-alpha layout -- which
+// select the tap source (SourceOf).
+template <typename TexT, bool AC, bool STRICT, bool DHW, typename... Extra>
 __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, const BwdParams b, float* __restrict__ g_ray, float* __restrict__ slab,
-                                                             const int tiles_x, const int n_tiles) {
+                                                             const int tiles_x, const int n_tiles, const Extra... extra) {
+    using Src = typename SourceOf<TexT, Extra...>::type;
     __shared__ float4 pcA[kGChunk];                    // zdiff, w, h, RN(2/w)
     __shared__ float pcB[kGChunk];                     // RN(2/h)
     __shared__ float red[DHW ? kGWaves * kGChunk * 3 : 1];   // per wave and plane: (d, h, w) partial sums
@@ -91,9 +230,9 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
     const int64_t HW = vw.HW;
     const int Ht = p.Ht, Wt = p.Wt;
     const float rWt = 1.0f / static_cast<float>(Wt), rHt = 1.0f / static_cast<float>(Ht);
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const Src src(p, vw, extra...);
     BwdPixel bp;
-    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    src.template start<AC, STRICT>(bp, p, vw, b, n, px, py, active);
     const float rx = bp.rx, ry = bp.ry, rz = bp.rz, rrz = bp.rrz, dot = bp.dot;
     float sx = 0.0f, sy = 0.0f, ss = 0.0f;      // sum_k g_x, g_y, g_s
     float srx = 0.0f, sry = 0.0f, srz = 0.0f;   // sum_k g_x s, g_y s, g_s s
@@ -121,45 +260,52 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
                 plane_coord_recip<AC>(a.x, a.y * 0.5f, a.z * 0.5f, rw, rh, ex, ey, rx, ry, rz, rrz, cx, cy, ix, iy, s);
             }
             Taps q;
-            gather_taps<TexT>(vol + static_cast<int64_t>(kc + t) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, q);
-            const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
-            float smp[4], dix[4], diy[4];
+            float vd = 0.0f, vh = 0.0f, vw_ = 0.0f;   // this pixel's share of the plane's (d, h, w) sums
+            const bool live = src.template taps<STRICT>(p, kc + t, Ht, Wt, ix, iy, q);
+            if (!Src::kSkips || live) {   // (false: the plane is the identity of this pixel's sweep)
+                const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
+                float smp[4], dix[4], diy[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float acc = q.t[c][0] * w00;
-                acc = __builtin_fmaf(q.t[c][1], w01, acc);
-                acc = __builtin_fmaf(q.t[c][2], w10, acc);
-                smp[c] = __builtin_fmaf(q.t[c][3], w11, acc);
-                dix[c] = __builtin_fmaf(q.t[c][3] - q.t[c][2], q.wy1, (q.t[c][1] - q.t[c][0]) * q.wy0);
-                diy[c] = __builtin_fmaf(q.t[c][3] - q.t[c][1], q.wx1, (q.t[c][2] - q.t[c][0]) * q.wx0);
-            }
+                for (int c = 0; c < 4; ++c) {
+                    float acc = q.t[c][0] * w00;
+                    acc = __builtin_fmaf(q.t[c][1], w01, acc);
+                    acc = __builtin_fmaf(q.t[c][2], w10, acc);
+                    smp[c] = __builtin_fmaf(q.t[c][3], w11, acc);
+                    dix[c] = __builtin_fmaf(q.t[c][3] - q.t[c][2], q.wy1, (q.t[c][1] - q.t[c][0]) * q.wy0);
+                    diy[c] = __builtin_fmaf(q.t[c][3] - q.t[c][1], q.wx1, (q.t[c][2] - q.t[c][0]) * q.wx0);
+                }
+                // (the strict-order forward of this layout rounds its alpha sample once per op: the sweep divides T_out by THAT om)
+            if (STRICT && Src::kForwardAlpha) smp[3] = ((q.t[3][0] * w00 + q.t[3][1] * w01) + q.t[3][2] * w10) + q.t[3][3] * w11;
             // the sweep: T_k = T_{k+1} / om_k, sample gradients d_s
-            float d_s[4];
-            const float w = bp.plane_recip(smp, s, d_s);   // w_k = a_k T_k
-            const float d0 = d_s[0], d1 = d_s[1], d2 = d_s[2], d3 = d_s[3];
-            // position gradient
-            const float g_ix = d0 * dix[0] + d1 * dix[1] + d2 * dix[2] + d3 * dix[3];
-            const float g_iy = d0 * diy[0] + d1 * diy[1] + d2 * diy[2] + d3 * diy[3];
-            float kx = cx, ky = cy;   // dix/du' (AC: (Wt-1)/2; else Wt/2 times the narrowing factor c of u' = c u)
-            if (!AC) {
-                const float uu = (2.0f * ix + 1.0f) * rWt - 1.0f, vv = (2.0f * iy + 1.0f) * rHt - 1.0f;   // u' (|u'| <= 0.95 iff narrowed, else > 1)
-                kx = 0.5f * cx * (fabsf(uu) <= 0.975f ? kNarrowScale : 1.0f);
-                ky = 0.5f * cy * (fabsf(vv) <= 0.975f ? kNarrowScale : 1.0f);
+                float d_s[4];
+                const float w = bp.plane_recip(smp, s, d_s);   // w_k = a_k T_k
+                const float d0 = d_s[0], d1 = d_s[1], d2 = d_s[2], d3 = d_s[3];
+                // position gradient
+                const float g_ix = d0 * dix[0] + d1 * dix[1] + d2 * dix[2] + d3 * dix[3];
+                const float g_iy = d0 * diy[0] + d1 * diy[1] + d2 * diy[2] + d3 * diy[3];
+                float kx = cx, ky = cy;   // dix/du' (AC: (Wt-1)/2; else Wt/2 times the narrowing factor c of u' = c u)
+                if (!AC) {
+                    const float uu = (2.0f * ix + 1.0f) * rWt - 1.0f, vv = (2.0f * iy + 1.0f) * rHt - 1.0f;   // u' (|u'| <= 0.95 iff narrowed, else > 1)
+                    kx = 0.5f * cx * (fabsf(uu) <= 0.975f ? kNarrowScale : 1.0f);
+                    ky = 0.5f * cy * (fabsf(vv) <= 0.975f ? kNarrowScale : 1.0f);
+                }
+                const float g_x = g_ix * (kx * rw), g_y = g_iy * (ky * rh);   // du/dx = 2/w = rw
+                const float Gk = bp.gz * w;
+                const float g_s = g_x * rx + g_y * ry + Gk * dot;
+                sx += g_x, sy += g_y, ss += g_s;
+                srx += g_x * s, sry += g_y * s, srz += g_s * s;
+                sG += Gk * s;
+                if (DHW) {
+                    const float x = ex + rx * s, y = ey + ry * s;
+                    vd = g_s * rrz, vh = -0.5f * g_y * y * rh, vw_ = -0.5f * g_x * x * rw;   // d(2x/w)/dw = -(2/w)(x/w)
+                    vd = active ? vd : 0.0f, vh = active ? vh : 0.0f, vw_ = active ? vw_ : 0.0f;
+                }
             }
-            const float g_x = g_ix * (kx * rw), g_y = g_iy * (ky * rh);   // du/dx = 2/w = rw
-            const float Gk = bp.gz * w;
-            const float g_s = g_x * rx + g_y * ry + Gk * dot;
-            sx += g_x, sy += g_y, ss += g_s;
-            srx += g_x * s, sry += g_y * s, srz += g_s * s;
-            sG += Gk * s;
-            if (DHW) {
-                const float x = ex + rx * s, y = ey + ry * s;
-                float vd = g_s * rrz, vh = -0.5f * g_y * y * rh, vw = -0.5f * g_x * x * rw;   // d(2x/w)/dw = -(2/w)(x/w)
-                vd = active ? vd : 0.0f, vh = active ? vh : 0.0f, vw = active ? vw : 0.0f;
-                vd = wave_sum(vd), vh = wave_sum(vh), vw = wave_sum(vw);
+            if (DHW) {   // (every lane of the wave, skipped planes included: the wave sums are cross-lane)
+                vd = wave_sum(vd), vh = wave_sum(vh), vw_ = wave_sum(vw_);
                 if (lane == 0) {
                     float* o = red + (wave * kGChunk + t) * 3;
-                    o[0] = vd, o[1] = vh, o[2] = vw;
+                    o[0] = vd, o[1] = vh, o[2] = vw_;
                 }
             }
         }
@@ -243,33 +389,54 @@ uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw) {
 }
 
 // g_ray [N,3,H,W], g_eye / g_z [N,3], g_dhw [M,D,3]: overwritten; nullptr = not wanted.  p.ws must hold geometry_backward_workspace_bytes(p,
-// g_dhw != nullptr) bytes when any of g_eye, g_z, g_dhw is wanted (checked by the caller).
-hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
-                                    float* g_z, float* g_dhw, hipStream_t stream) {
+// g_dhw != nullptr) bytes when any of g_eye, g_z, g_dhw is wanted (checked by the caller).  pixel(type, AC, STRICT, DHW, grid, b, slab, tiles_x,
+// n_tiles) launches the layout's pixel kernel; the slab reducer is the same for all.
+template <typename Pixel>
+static hipError_t launch_geometry_passes(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_eye, float* g_z,
+                                         float* g_dhw, hipStream_t stream, Pixel&& pixel) {
+    using namespace bwgeo;
     BwdParams b{};
     b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T;
     const bool want_dhw = g_dhw != nullptr;
     float* slab = (g_eye || g_z || g_dhw) ? static_cast<float*>(p.ws) : nullptr;
-    {
-        using namespace bwgeo;
-        const int tx = tiles_x_of(p), nt = tiles_of(p);
-        const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
-        dispatch_dtype(dtype, [&](auto t) {
-            dispatch_bool(p.flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) {
-                dispatch_bool(p.flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) {
-                    dispatch_bool(want_dhw, [&](auto DHW) {
-                        hipLaunchKernelGGL((geometry_pixel_kernel<typename decltype(t)::type, decltype(AC)::value, decltype(STRICT)::value, decltype(DHW)::value>),
-                                           grid, dim3(kGT), 0, stream, p, b, g_ray, slab, tx, nt);
-                    });
-                });
+    const int tx = tiles_x_of(p), nt = tiles_of(p);
+    const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
+    dispatch_dtype(dtype, [&](auto t) {
+        dispatch_bool(p.flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) {
+            dispatch_bool(p.flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) {
+                dispatch_bool(want_dhw, [&](auto DHW) { pixel(t, AC, STRICT, DHW, grid, b, slab, tx, nt); });
             });
         });
-    }
+    });
     if (slab != nullptr) {
-        const dim3 grid(6 + (want_dhw ? 3 * p.D : 0), std::max(p.N, p.M));
-        hipLaunchKernelGGL(bwgeo::geometry_reduce_kernel, grid, dim3(bwgeo::kGRed), 0, stream, p, slab, bwgeo::tiles_of(p), g_eye, g_z, g_dhw);
+        const dim3 rgrid(6 + (want_dhw ? 3 * p.D : 0), std::max(p.N, p.M));
+        hipLaunchKernelGGL(geometry_reduce_kernel, rgrid, dim3(kGRed), 0, stream, p, slab, nt, g_eye, g_z, g_dhw);
     }
     return hipGetLastError();
 }
+#define GMPI_GEOMETRY_INSTANCE(kernel, ...) kernel<typename decltype(t)::type, decltype(AC)::value, decltype(STRICT)::value, decltype(DHW)::value, ##__VA_ARGS__>
+
+hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
+                                    float* g_z, float* g_dhw, hipStream_t stream) {
+    return launch_geometry_passes(p, dtype, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream,
+                                  [&](auto t, auto AC, auto STRICT, auto DHW, dim3 grid, const BwdParams& b, float* slab, int tx, int nt) {
+        hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt);
+    });
+}
+
+// The same passes over the shared-colour layout (dk == nullptr; p carries the alpha planes, s_chan = 0) and the depth-alpha layout (p carries the
+// depth image).
+hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
+                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, hipStream_t stream) {
+    return launch_geometry_passes(p, dtype, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream,
+                                  [&](auto t, auto AC, auto STRICT, auto DHW, dim3 grid, const BwdParams& b, float* slab, int tx, int nt) {
+        if (dk != nullptr) {
+            hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel, SharedK, DepthK)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt, sh, *dk);
+        } else {
+            hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel, SharedK)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt, sh);
+        }
+    });
+}
+#undef GMPI_GEOMETRY_INSTANCE
 
 }  // namespace gmpi

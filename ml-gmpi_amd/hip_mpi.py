@@ -503,7 +503,11 @@ class MPI(nn.Module):
                      align_corners=True and uniform views per MPI, other launches silently take the atomic path)
       geometry_grad  False (default: the reference's behaviour -- no gradient reaches the plane geometry or the camera tensors) | True: the
                      gradient also flows to dhw, ray_dir, eye_pos and z_dir (gmpi_mpi_render_geometry_backward_launch, render_backward_geometry.hip:
-                     an extension, the reference builds its grid under torch.no_grad(), mpi.py:65).
+                     an extension, the reference builds its grid under torch.no_grad(), mpi.py:65) on the volume entry, `render_views`; the
+                     two layout entries raise NotImplementedError for such tensors | "all": everything True gives, and the gradient reaches the
+                     four tensors on `render_views_shared` and `render_views_depth` too (gmpi_mpi_render_shared_geometry_backward_launch /
+                     gmpi_mpi_render_depth_geometry_backward_launch: the same pass with the layout's taps, nothing is expanded).  Any other
+                     string: ValueError.  `mpi.geometry_grad` stays a bool; `mpi.geometry_grad_layouts` says whether the layouts are included.
 
     The transmittance output T (want_transmittance=True) is differentiable like colour and depth: a loss on it (`color + T * bg`, a coverage
     loss on 1 - T) reaches the volume and, with geometry_grad=True, the geometry (gmpi_mpi_render_backward_ex_launch: dT/da_k = -T / om_k).
@@ -512,9 +516,13 @@ class MPI(nn.Module):
     DEFAULT_RANGE_CHECK = "touched"
 
     def __init__(self, align_corners=True, variant: str = "auto", strict_order: bool = False,
-                 range_check: Optional[str] = None, on_out_of_plane: str = "exit", backward: str = "atomic", geometry_grad: bool = False):
+                 range_check: Optional[str] = None, on_out_of_plane: str = "exit", backward: str = "atomic",
+                 geometry_grad: Union[bool, str] = False):
         super().__init__()
+        if isinstance(geometry_grad, str) and geometry_grad != "all":
+            raise ValueError(f'geometry_grad is False, True or "all", not {geometry_grad!r}')
         self.geometry_grad = bool(geometry_grad)
+        self.geometry_grad_layouts = geometry_grad == "all"   # the shared-colour and depth-alpha entries too
         self._align_corners = align_corners
         if range_check is None:
             range_check = type(self).DEFAULT_RANGE_CHECK   # (a class attribute: `install()` swaps in a subclass that overrides it)
@@ -758,11 +766,12 @@ class MPI(nn.Module):
             return (_RenderFunction, (rgba,)) if rgba.requires_grad or geometry else None
         # shared-colour layout (render_views_shared): rgba is the alpha tensor, shared = (rgb, background or None); depth-alpha layout
         # (render_views_depth): rgba is the depth image, depth = (plane_z, z_lo, z_hi)
-        if geometry:
+        if geometry and not self.geometry_grad_layouts:
             what, expand = ("shared-colour", "expand_shared_color") if depth is None else ("depth-alpha", "expand_depth_alpha")
-            raise NotImplementedError(f"the {what} render has no gradient w.r.t. the plane geometry or the camera tensors "
-                                      f"(geometry_grad=True): render the expanded volume ({expand}) with render_views for that")
-        if rgba.requires_grad or any(t is not None and t.requires_grad for t in shared):
+            raise NotImplementedError(f"the {what} render has no gradient w.r.t. the plane geometry or the camera tensors under "
+                                      f'geometry_grad=True: build the module with geometry_grad="all" for that (or render the expanded '
+                                      f"volume, {expand}, with render_views)")
+        if geometry or rgba.requires_grad or any(t is not None and t.requires_grad for t in shared):
             return _SharedRenderFunction if depth is None else _DepthRenderFunction, (shared[0], rgba, shared[1])
         return None
 
@@ -795,8 +804,9 @@ class MPI(nn.Module):
         (gmpi_mpi_render_shared_backward_launch: the colour gradient is summed over the planes on the chip).  `variant` (None: the module's own):
         "gather" forces the one-pixel-per-lane kernels; "lds" selects the staged forward (render_shared_forward.hip: texel boxes of 32 x 16 pixel
         tiles through LDS) when gmpi_render_shared_supports says it can take the three tensors (base pointers and outer strides multiples of 4
-        texels) and AUTO's kernel otherwise -- the backward is the tile backward either way; every other variant lets the library choose.  No gradient w.r.t. the geometry (NotImplementedError with
-        geometry_grad=True and a camera / dhw tensor that requires grad).  The three tensors must have ONE dtype (TypeError otherwise: nothing is
+        texels) and AUTO's kernel otherwise -- the backward is the tile backward either way; every other variant lets the library choose.  Gradient w.r.t. dhw and the camera
+        tensors: with geometry_grad="all" (one extra launch after the image backward; the image backward is skipped when no image needs a
+        gradient); geometry_grad=True and a camera / dhw tensor that requires grad raise NotImplementedError.  The three tensors must have ONE dtype (TypeError otherwise: nothing is
         cast behind the caller's back).  range_check="full" runs the exhaustive pass over the three tensors in EVERY call (the volume path's
         "unchanged volume" cache is not kept for three tensors), and that pass reads contiguous memory: a strided alpha view such as
         `rgba[:, :, 3:]` is copied for it, D planes per call -- use the default "touched" where the no-copy property matters.  The tile
@@ -816,8 +826,9 @@ class MPI(nn.Module):
         arguments, returned dict and status handling as `render_views_shared`.  One kernel: `variant=` takes None, "auto" or "gather" (any other name:
         ValueError); the module's own variant is read as `render_views_shared` reads it ("gather" as such, every other one is the library's choice).  Under autograd the gradient
         reaches rgb, depth and background in their own dtypes (gmpi_mpi_render_depth_backward_launch: the gradient of all D alpha planes lands in
-        the one depth image); none w.r.t. plane_z or the geometry (NotImplementedError with geometry_grad=True and a camera / dhw tensor that
-        requires grad).  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
+        the one depth image); w.r.t. dhw and the camera tensors with geometry_grad="all" (one extra launch after the image backward, which is
+        skipped when no image needs a gradient; geometry_grad=True and a camera / dhw tensor that requires grad raise NotImplementedError);
+        never w.r.t. plane_z or the ramp's bounds.  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
         background (a depth image is no [0, 1] tensor); "touched" also sets the range bit for a NaN depth some pixel samples.
         `depth_backward`: "pixel" (the default) back-propagates with the one-pixel-per-lane kernel; "tile" with
         gmpi_mpi_render_depth_backward_tile_launch -- one workgroup per 32 x 16 pixel tile, the gradients of rgb and depth summed in LDS across
@@ -926,6 +937,53 @@ def _upstream(ctx, dev, g_color, g_depth, g_T):
     return g_color, g_depth, g_T
 
 
+def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream):
+    """The gradient w.r.t. the sample positions (render_backward_geometry.hip) for the inputs (dhw, ray_dir, eye_pos, z_dir) flagged in `want`, in
+    each input's own dtype and device (ctx.geo_meta): every output overwritten, NULL = not wanted; the per-view and per-plane sums go through
+    slabs in a workspace lent for this call (no atomics: bit-reproducible).  entry: the C entry; structs: what it takes between the parameter
+    struct and the upstream gradients (the layout's structs)."""
+    p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved tensors
+    shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
+    out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+    ws = None   # (held until this call returns: the launch that uses it is on the stream by then)
+    if want[0] or want[2] or want[3]:
+        need = int(_lib.load_library().gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _lend(p, ws)
+    _call(entry, dev, ctypes.byref(p), *structs, *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), stream=stream)
+    return [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
+
+
+def _layout_backward(ctx, g_color, g_depth, g_T, keep, T, image_shapes, image_call, geometry_entry, structs):
+    """The backward of both layout bridges.  Image gradients: zero-filled fp32 tensors of `image_shapes` for the inputs that need one, handed to
+    image_call(p, upstream, grads) -- skipped when no image needs a gradient.  Then, for a module with geometry_grad="all", the geometry pass
+    (`geometry_entry` with the layout's `structs`) when dhw, ray_dir, eye_pos or z_dir needs one: one extra launch."""
+    dev = keep.rgba.device
+    want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
+    geo_want = [ctx.geometry and ctx.needs_input_grad[i] for i in (4, 5, 6, 7)]   # dhw, ray_dir, eye_pos, z_dir
+    if not (any(want) or any(geo_want)) or (g_color is None and g_depth is None and g_T is None):
+        return (None,) * 9
+    g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
+    upstream = (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T))
+    out = [None] * 3
+    if any(want):
+        p = _render_params(ctx.scalars, keep, T=T)
+        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(image_shapes(p), want)]
+        image_call(p, upstream, grads)
+        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
+    geo = [None] * 4
+    if any(geo_want):
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        geo = _geometry_pass(ctx, keep, T, dev, stream, geo_want, geometry_entry, structs, upstream)
+    return out[0], out[1], out[2], None, geo[0], geo[1], geo[2], geo[3], None
+
+
+def _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir) -> None:
+    """What a layout bridge keeps for the geometry pass: whether the module includes the layouts, and each camera / dhw input's dtype and device."""
+    ctx.geometry = mpi.geometry_grad_layouts
+    ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]
+
+
 class _RenderFunction(torch.autograd.Function):
     """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba) and, for an MPI with
     geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir); their _ex forms when the loss
@@ -983,26 +1041,16 @@ class _RenderFunction(torch.autograd.Function):
         geo = [None] * 4   # dhw, ray_dir, eye_pos, z_dir
         want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
         if any(want):
-            # gradient w.r.t. the sample positions (render_backward_geometry.hip): every output overwritten, NULL = not wanted; the per-view and
-            # per-plane sums go through slabs in a workspace (no atomics: bit-reproducible)
-            p = _render_params(ctx.scalars, keep, T=T)
-            shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
-            out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
-            ws = None   # (held until this call returns: the launch that uses it is on the stream by then)
-            if want[0] or want[2] or want[3]:
-                need = int(lib.gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
-                ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-                _lend(p, ws)
-            _call("gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch", dev,
-                  ctypes.byref(p), *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), stream=stream)
-            geo = [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
+            entry = "gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch"
+            geo = _geometry_pass(ctx, keep, T, dev, stream, want, entry, (), upstream)
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
 
 
 class _SharedRenderFunction(torch.autograd.Function):
     """autograd bridge of the shared-colour render, built like `_RenderFunction`: forward = gmpi_mpi_render_shared_launch, backward =
     gmpi_mpi_render_shared_backward_launch into zero-filled fp32 gradients of the inputs that need one (the others are passed as NULL and
-    skipped by the kernel).  Saved tensors, private T buffer, unused outputs as None: as there."""
+    skipped by the kernel).  Saved tensors, private T buffer, unused outputs as None: as there.  For a module with geometry_grad="all" the node is
+    also recorded when only dhw or a camera tensor requires grad, and its backward ends with gmpi_mpi_render_shared_geometry_backward_launch."""
 
     @staticmethod
     def forward(ctx, rgb, alpha, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
@@ -1010,6 +1058,7 @@ class _SharedRenderFunction(torch.autograd.Function):
         ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
         ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, alpha, background)]
+        _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir)
         return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
@@ -1019,23 +1068,18 @@ class _SharedRenderFunction(torch.autograd.Function):
         rest = saved[7:]
         bg = rest.pop(0) if ctx.has_bg else None
         keep = _Keep(alpha, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
-        dev = alpha.device
-        want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
-        if not any(want) or (g_color is None and g_depth is None and g_T is None):
-            return (None,) * 9
-        p = _render_params(ctx.scalars, keep, T=T)
-        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
-        shapes = [(p.M, 3, p.Ht, p.Wt), (p.M, p.D, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)]
-        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+        sc = _shared_color(rgb, bg)
 
         def ptr_stride(t, dims):
             if t is None:
                 return None, None
             return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
-        _call("gmpi_mpi_render_shared_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
-              g_color.data_ptr(), _ptr(g_depth), _ptr(g_T), *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
-        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
-        return out[0], out[1], out[2], None, None, None, None, None, None
+
+        def image_call(p, upstream, grads):
+            _call("gmpi_mpi_render_shared_backward_launch", alpha.device, ctypes.byref(p), ctypes.byref(sc), *upstream,
+                  *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
+        return _layout_backward(ctx, g_color, g_depth, g_T, keep, T, lambda p: [(p.M, 3, p.Ht, p.Wt), (p.M, p.D, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)],
+                                image_call, "gmpi_mpi_render_shared_geometry_backward_launch", (ctypes.byref(sc),))
 
 
 # render_views_depth(depth_forward=...): None reads as "pixel"; anything but the two names is refused before any call
@@ -1054,7 +1098,8 @@ _DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "ti
 class _DepthRenderFunction(torch.autograd.Function):
     """autograd bridge of the depth-alpha render, built like `_SharedRenderFunction`: forward = gmpi_mpi_render_depth_launch, backward =
     gmpi_mpi_render_depth_backward_launch (depth_backward="tile": gmpi_mpi_render_depth_backward_tile_launch) into zero-filled fp32 gradients of
-    rgb, the depth image and the background."""
+    rgb, the depth image and the background; with geometry_grad="all" the node is also recorded when only dhw or a camera tensor requires grad, and
+    its backward ends with gmpi_mpi_render_depth_geometry_backward_launch."""
 
     @staticmethod
     def forward(ctx, rgb, depth, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
@@ -1064,6 +1109,7 @@ class _DepthRenderFunction(torch.autograd.Function):
         plane_z, ctx.z_lo, ctx.z_hi = kwargs["_depth"]
         ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], plane_z, *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, depth, background)]
+        _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir)
         return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
@@ -1073,24 +1119,18 @@ class _DepthRenderFunction(torch.autograd.Function):
         rest = saved[8:]
         bg = rest.pop(0) if ctx.has_bg else None
         keep = _Keep(depth, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
-        dev = depth.device
-        want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
-        if not any(want) or (g_color is None and g_depth is None and g_T is None):
-            return (None,) * 9
-        p = _render_params(ctx.scalars, keep, T=T)
-        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
-        shapes = [(p.M, 3, p.Ht, p.Wt), (p.M, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)]
-        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+        sc, da = _shared_color(rgb, bg), _depth_alpha(plane_z, ctx.z_lo, ctx.z_hi)
+        structs = (ctypes.byref(sc), ctypes.byref(da))
 
         def ptr_stride(t):
             if t is None:
                 return None, None
             return t.data_ptr(), (ctypes.c_int64 * 3)(*t.stride()[:3])
-        _call(ctx.backward_entry, dev, ctypes.byref(p), ctypes.byref(_shared_color(rgb, bg)),
-              ctypes.byref(_depth_alpha(plane_z, ctx.z_lo, ctx.z_hi)), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T),
-              *ptr_stride(grads[0]), *ptr_stride(grads[1]), *ptr_stride(grads[2]))
-        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
-        return out[0], out[1], out[2], None, None, None, None, None, None
+
+        def image_call(p, upstream, grads):
+            _call(ctx.backward_entry, depth.device, ctypes.byref(p), *structs, *upstream, *ptr_stride(grads[0]), *ptr_stride(grads[1]), *ptr_stride(grads[2]))
+        return _layout_backward(ctx, g_color, g_depth, g_T, keep, T, lambda p: [(p.M, 3, p.Ht, p.Wt), (p.M, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)],
+                                image_call, "gmpi_mpi_render_depth_geometry_backward_launch", structs)
 
 
 HipMPI = MPI
