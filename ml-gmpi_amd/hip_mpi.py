@@ -24,7 +24,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, depth_alpha, shared_color
 from .quantized import is_interleaved
 
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16, torch.uint8: _lib.DTYPE_U8}
@@ -355,28 +355,110 @@ def _shared_color(rgb: torch.Tensor, background: Optional[torch.Tensor]) -> _lib
 def _depth_alpha(plane_z: torch.Tensor, z_lo: float, z_hi: float) -> _lib.GmpiDepthAlpha:
     """The one builder of GmpiDepthAlpha: plane_z fp32 [D] or [M,D] on the device (innermost stride 1), the ramp's constants rounded as
     `depth_alpha.ramp_constants` rounds them."""
-    from .depth_alpha import ramp_constants
     da = _lib.GmpiDepthAlpha()
     da.struct_size = ctypes.sizeof(_lib.GmpiDepthAlpha)
     da.plane_z = plane_z.data_ptr()
     da.plane_z_stride = plane_z.stride(0) if plane_z.ndim == 2 else 0
-    da.z_lo, da.z_hi, da.z_den = ramp_constants(z_lo, z_hi)
+    da.z_lo, da.z_hi, da.z_den = depth_alpha.ramp_constants(z_lo, z_hi)
     return da
 
 
-def _depth_operands(rgb, depth, plane_z, z_bounds, background, n_planes: int):
-    """What `render_views` takes for the depth-alpha layout: (the depth image as the view [M,1,1,Ht,Wt], _shared = (rgb, background), _depth =
-    (plane_z as contiguous fp32 on the device, z_lo, z_hi)); the checks that need no launch."""
-    from .depth_alpha import _check
-    _check(rgb, depth, plane_z, background)
-    _refuse_uint8("the depth-alpha render", rgb, depth, background)
+# What differs between the two layouts and is no tensor or option: the words messages use (`first`: the name of `render_views`' first argument),
+# the expand function they quote, the entry of the geometry backward.
+_Kind = collections.namedtuple("_Kind", "name expand first geometry_entry")
+_SHARED_COLOUR = _Kind("shared-colour", "expand_shared_color", "alpha", "gmpi_mpi_render_shared_geometry_backward_launch")
+_DEPTH_ALPHA = _Kind("depth-alpha", "expand_depth_alpha", "depth", "gmpi_mpi_render_depth_geometry_backward_launch")
+# render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
+_DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch"}
+
+
+class _Layout:
+    """An input layout that is not the RGBA volume, as `render_views(_layout=...)` and the autograd bridge take it (the volume is `_layout=None`):
+    shared-colour (`render_views`' first argument is then the alpha tensor [M,D,1,Ht,Wt]) or, with a `plane_z`, depth-alpha (the depth image as
+    [M,1,1,Ht,Wt]; the planes are dhw's).  Built by `_shared_layout` / `_depth_layout` alone, which check what they put in: rgb, background: the
+    caller's tensors; variant: the kernel asked for by name, or None = the module's own; backward_entry: the C entry of the image backward;
+    depth-alpha only: plane_z (detached fp32 on the device, [D] or [M,D]), ramp = (z_lo, z_hi), depth_forward ("pixel", "window" or None)."""
+
+    def __init__(self, kind, rgb, background, variant, backward_entry, plane_z=None, ramp=None, depth_forward=None):
+        self.kind, self.rgb, self.background, self.variant, self.backward_entry = kind, rgb, background, variant, backward_entry
+        self.plane_z, self.ramp, self.depth_forward = plane_z, ramp, depth_forward
+
+    @property
+    def requires_grad(self) -> bool:
+        return self.rgb.requires_grad or (self.background is not None and self.background.requires_grad)
+
+    def operands(self, mpi, first, dhw):
+        """(plane count, GMPI_VARIANT_* of the launch, (rgb, background) as the kernels read them) next to `first`, the first argument as the
+        kernels read it.  The entries know AUTO and GATHER (and, shared-colour, LDS: asked for in `launch`, once the structs exist)."""
+        variant = mpi.variant if self.variant is None else self.variant
+        assert variant in _lib.VARIANTS, variant
+        # (a dtype the kernels do not store -- float64 -- becomes fp32 with the first argument)
+        rgb = _kernel_operand(self.rgb.to(first.device, first.dtype), 3)
+        bg = None if self.background is None else _kernel_operand(self.background.to(first.device, first.dtype), 3)
+        return (first if self.plane_z is None else dhw).shape[1], _lib.VARIANT_GATHER if variant == "gather" else _lib.VARIANT_AUTO, (rgb, bg)
+
+    def launch(self, mpi, p, first, images, dev, stream) -> None:
+        """The forward.  range_check="full": the exhaustive pass over the layout's [0, 1] tensors in every call (never cached: three identities to
+        track; a depth image is none).  A staged forward asked for by name -- variant "lds", depth_forward "window" -- runs where its loader can
+        take these tensors (alignment), else the one-pixel-per-lane kernel does, counted on `mpi` and warned of once per process."""
+        tensors = (first,) + images
+        if mpi.range_check == "full":
+            _range_pass(tensors if self.plane_z is None else images, p, dev, stream)
+        sc = _shared_color(*images)
+        if self.plane_z is None:
+            if (mpi.variant if self.variant is None else self.variant) == "lds" and first.is_cuda:
+                p.variant = _lib.VARIANT_LDS
+                if not _forward_takes("gmpi_render_shared_supports", (p, sc), tensors):
+                    p.variant = _lib.VARIANT_AUTO
+                    mpi.shared_lds_fallbacks += 1
+                    _warn_lds_fallback()
+            return _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
+        da = _depth_alpha(self.plane_z, *self.ramp)
+        entry = "gmpi_mpi_render_depth_launch"
+        if self.depth_forward == "window":
+            if _forward_takes("gmpi_render_depth_window_supports", (p, sc, da), tensors):
+                entry = "gmpi_mpi_render_depth_window_launch"
+            else:
+                mpi.depth_window_fallbacks += 1
+                _warn_window_fallback()
+        _call(entry, dev, ctypes.byref(p), ctypes.byref(sc), ctypes.byref(da), stream=stream)
+
+
+def _one_dtype(kind: _Kind, rgb, first, background) -> None:
+    """The three tensors of a layout have one storage dtype -- no quiet cast: an fp32 colour image next to bf16 alphas would be rounded unseen --
+    and it is not uint8 (that refusal comes first, also among mixed dtypes)."""
     for t in (rgb, background):
-        if t is not None and t.dtype != depth.dtype:   # (no quiet cast, as in the shared-colour render)
-            raise TypeError(f"depth-alpha render: rgb, depth and background must have one storage dtype, got {t.dtype} next to depth in {depth.dtype}")
+        if t is not None and t.dtype != first.dtype:
+            _refuse_uint8(f"the {kind.name} render", rgb, first, background)
+            raise TypeError(f"{kind.name} render: rgb, {kind.first} and background must have one storage dtype, got {t.dtype} next to {kind.first} in {first.dtype}")
+    if first.dtype is torch.uint8:
+        _refuse_uint8(f"the {kind.name} render", first)
+
+
+def _shared_layout(rgb, alpha, background, variant):
+    """`MPI.render_views_shared` / `MPIRenderer.render_shared`: (`render_views`' first argument, its `_layout`); the checks that need no launch."""
+    shared_color._check(rgb, alpha, background)
+    _one_dtype(_SHARED_COLOUR, rgb, alpha, background)
+    return alpha, _Layout(_SHARED_COLOUR, rgb, background, variant, "gmpi_mpi_render_shared_backward_launch")
+
+
+def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, variant, depth_backward, depth_forward):
+    """`MPI.render_views_depth` / `MPIRenderer.render_depth`: (the depth image as the view [M,1,1,Ht,Wt], `render_views`' `_layout`); the option
+    names and the checks that need no launch.  depth_forward None reads as "pixel"."""
+    if variant not in (None, "auto", "gather"):
+        raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
+    if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
+        raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
+    if depth_forward not in (None, "pixel", "window"):
+        raise ValueError(f'depth_forward is "pixel" or "window", not {depth_forward!r}')
+    depth_alpha._check(rgb, depth, plane_z, background)
+    _one_dtype(_DEPTH_ALPHA, rgb, depth, background)
     assert plane_z.shape[-1] == n_planes, f"plane_z holds {plane_z.shape[-1]} planes, dhw {n_planes}"
-    z_lo, z_hi = (float(v) for v in z_bounds)
+    z_lo, z_hi = z_bounds
+    z_lo, z_hi = float(z_lo), float(z_hi)
     assert z_lo < z_hi, (z_lo, z_hi)
-    return depth.unsqueeze(1), (rgb, background), (_f32_on(plane_z.detach(), depth.device), z_lo, z_hi)
+    return depth.unsqueeze(1), _Layout(_DEPTH_ALPHA, rgb, background, variant, _DEPTH_BACKWARD_ENTRIES[depth_backward],
+                                       _f32_on(plane_z.detach(), depth.device), (z_lo, z_hi), depth_forward)
 
 
 def _lend(p: _lib.GmpiRenderParams, ws: torch.Tensor) -> None:
@@ -401,26 +483,25 @@ def _readable_past_last_row(t: torch.Tensor, extra: int) -> bool:
     return (last + 1 + extra) * t.element_size() <= t.untyped_storage().nbytes()
 
 
-def _staged_forward_takes(p, sc, tensors) -> bool:
-    """Whether GMPI_VARIANT_LDS of the shared-colour forward can run this launch: gmpi_render_shared_supports (alignment of the three tensors), and,
-    for a texture width that is no multiple of 4, that the padding its loader reads behind the LAST row of each tensor is allocated (behind every
-    other row it is the row stride's).  Errors the launch would raise are raised here, under the query's name."""
-    rc = _lib.load_library().gmpi_render_shared_supports(ctypes.byref(p), ctypes.byref(sc))
+def _forward_takes(query: str, structs, tensors) -> bool:
+    """Whether a staged forward can run this launch: the library's `query` over the launch's structs -- gmpi_render_shared_supports for
+    GMPI_VARIANT_LDS of the shared-colour forward (base pointers and outer strides multiples of 4 texels), gmpi_render_depth_window_supports for the
+    window forward of the depth-alpha layout (multiples of 16 bytes) -- and, for a texture width that is no multiple of 4, that the padding the
+    loader reads behind the LAST row of each tensor is allocated (behind every other row it is the row stride's).  Errors the launch would raise
+    are raised here, under the query's name."""
+    rc = getattr(_lib.load_library(), query)(*map(ctypes.byref, structs))
     if rc < 0:
-        _lib.check(rc, "gmpi_render_shared_supports")
-    pad = -p.Wt % 4
+        _lib.check(rc, query)
+    pad = -structs[0].Wt % 4
     return rc == 1 and all(t is None or _readable_past_last_row(t, pad) for t in tensors)
 
 
-def _window_forward_takes(p, sc, da, tensors) -> bool:
-    """Whether the window forward of the depth-alpha layout can run this launch: gmpi_render_depth_window_supports (16-byte alignment of the three
-    images) and, as for the staged shared-colour forward, allocated padding behind the LAST row of each tensor when the texture width is no
-    multiple of 4.  Errors the launch would raise are raised here, under the query's name."""
-    rc = _lib.load_library().gmpi_render_depth_window_supports(ctypes.byref(p), ctypes.byref(sc), ctypes.byref(da))
-    if rc < 0:
-        _lib.check(rc, "gmpi_render_depth_window_supports")
-    pad = -p.Wt % 4
-    return rc == 1 and all(t is None or _readable_past_last_row(t, pad) for t in tensors)
+def _range_pass(tensors, p, dev, stream) -> None:
+    """range_check="full": the exhaustive pass over each tensor, into the status words of launch `p`.  It reads contiguous memory."""
+    for t in tensors:
+        if t is not None:
+            t = t if t.is_contiguous() else t.contiguous()
+            _call("gmpi_rgba_range_check_launch", dev, t.data_ptr(), p.rgba_dtype, t.numel(), p.status, stream=stream)
 
 
 _LDS_FALLBACK_WARNED = False
@@ -435,7 +516,7 @@ def _warn_window_fallback() -> None:
         _WINDOW_FALLBACK_WARNED = True
         warnings.warn('depth-alpha render: depth_forward="window" cannot take these tensors (base pointers and outer strides must be multiples of '
                       "16 bytes); the one-pixel-per-lane kernel runs instead (counted in MPI.depth_window_fallbacks; this warning is given once)",
-                      RuntimeWarning, stacklevel=4)
+                      RuntimeWarning, stacklevel=5)
 
 
 def _warn_lds_fallback() -> None:
@@ -445,7 +526,7 @@ def _warn_lds_fallback() -> None:
     if not _LDS_FALLBACK_WARNED:
         _LDS_FALLBACK_WARNED = True
         warnings.warn('shared-colour render: variant="lds" cannot take these tensors (base pointers and outer strides must be multiples of 4 texels); '
-                      "the one-pixel-per-lane kernel runs instead (counted in MPI.shared_lds_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
+                      "the one-pixel-per-lane kernel runs instead (counted in MPI.shared_lds_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=5)
 
 
 def _f32_on(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
@@ -621,8 +702,7 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _shared=None, _shared_variant: Optional[str] = None, _depth=None, _depth_backward: str = "pixel",
-                     _depth_forward: str = "pixel"):
+                     _layout: Optional[_Layout] = None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -641,25 +721,17 @@ class MPI(nn.Module):
         if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
-        if _shared is not None:
-            _refuse_uint8("the shared-colour render", rgba, *_shared)
         if torch.is_grad_enabled() and not _in_autograd_fn:
             if rgba.dtype is torch.uint8 and self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
                 raise NotImplementedError("no gradient flows through a uint8 volume, w.r.t. the plane geometry and the camera tensors included "
                                           "(geometry_grad=True): render dequantize_volume(q) (ml_gmpi_amd.quantized) for that, or detach the "
                                           "camera and dhw tensors")
-            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _shared, _depth)
+            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _layout)
             if bridge is not None:
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
-                              status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint)
-                if _shared is not None:
-                    kwargs["_shared_variant"] = _shared_variant
-                if _depth is not None:
-                    kwargs["_depth"] = _depth
-                    kwargs["_depth_backward"] = _depth_backward   # (read by _DepthRenderFunction; the forward does not depend on it)
-                    if _depth_forward != "pixel":
-                        kwargs["_depth_forward"] = _depth_forward
+                              status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint,
+                              _layout=_layout)
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -673,15 +745,9 @@ class MPI(nn.Module):
         rgba_in = rgba   # (as the caller passed it: the identity the full-range-check cache is keyed on)
         rgba = _volume_operand(rgba)
         M, D, _, Ht, Wt = rgba.shape
-        if _depth is not None:   # (the depth-alpha layout: rgba is the depth image [M,1,1,Ht,Wt]; the planes are dhw's and plane_z's)
-            D = dhw.shape[1]
-        sh_rgb = sh_bg = None
-        if _shared is not None:   # one storage dtype for the three tensors
-            for t in _shared:
-                if t is not None and t.dtype != rgba_in.dtype:   # (no quiet cast: an fp32 colour image next to bf16 alphas would be rounded unseen)
-                    raise TypeError(f"shared-colour render: rgb, alpha and background must have one storage dtype, got {t.dtype} next to alpha in {rgba_in.dtype}")
-            # (a dtype the kernels do not store -- float64 -- becomes fp32 with the alpha tensor)
-            sh_rgb, sh_bg = (None if t is None else _kernel_operand(t.to(dev, rgba.dtype), 3) for t in _shared)
+        variant, images = _lib.VARIANTS[self.variant], None
+        if _layout is not None:   # (rgba is the layout's first argument: the alpha tensor, or the depth image -- the planes are then dhw's)
+            D, variant, images = _layout.operands(self, rgba, dhw)
         ray_dir, eye_pos, z_dir, dhw = (_f32_on(t, dev) for t in (ray_dir, eye_pos, z_dir, dhw))
         N, _, H, W = ray_dir.shape
         assert eye_pos.shape == (N, 3) and z_dir.shape == (N, 3), (eye_pos.shape, z_dir.shape, N)
@@ -697,11 +763,6 @@ class MPI(nn.Module):
             depth = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
         if T is None and want_transmittance:
             T = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
-        variant = _lib.VARIANTS[self.variant]
-        if _shared is not None:   # (the shared-colour entries know AUTO, GATHER and LDS; LDS is asked for below, once the struct exists)
-            shared_variant = self.variant if _shared_variant is None else _shared_variant
-            assert shared_variant in _lib.VARIANTS, shared_variant
-            variant = _lib.VARIANT_GATHER if shared_variant == "gather" else _lib.VARIANT_AUTO
         scalars = _Scalars(self._flags(out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint), variant, _DTYPES[rgba.dtype],
                            N, M, D, Ht, Wt, H, W, max(uniform, 1))
         current = torch.cuda.current_stream(dev) if on_device else None
@@ -710,69 +771,45 @@ class MPI(nn.Module):
         with _stream_lock(dev, stream) if on_device else contextlib.nullcontext():
             status, defer_status, ring, slot = _status_target(dev, stream, status, defer_status, on_device and not _in_autograd_fn)
             p = _render_params(scalars, keep, color, depth, T, status)
-            if on_device and _shared is None:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
-                need = int(_lib.load_library().gmpi_render_workspace_bytes(ctypes.byref(p)))
-                if need:
-                    _lend(p, _workspace(dev, stream, need))
-            # range_check="full": the exhaustive pass, over the volume unless it is the one that passed last, over the three shared-colour
-            # tensors in every call (never cached: three identities to track)
-            checked = ()
-            if self.range_check == "full" and rgba.dtype is not torch.uint8:   # (8-bit codes are in [0, 1] by construction: nothing to pass over)
-                # (a depth image is no [0, 1] tensor: the pass covers the two colour images)
-                checked = (sh_rgb, sh_bg) if _depth is not None else (rgba, sh_rgb, sh_bg) if _shared is not None else (rgba,) if self._full_check_needed(rgba_in) else ()
-            for t in checked:
-                if t is not None:
-                    t = t if t.is_contiguous() else t.contiguous()
-                    _call("gmpi_rgba_range_check_launch", dev, t.data_ptr(), p.rgba_dtype, t.numel(), status.data_ptr(), stream=stream)
-            if _shared is not None:
-                sc = _shared_color(sh_rgb, sh_bg)
-                if shared_variant == "lds" and on_device and _depth is None:   # the staged forward where it can take these tensors (alignment), else AUTO's kernel
-                    p.variant = _lib.VARIANT_LDS
-                    if not _staged_forward_takes(p, sc, (rgba, sh_rgb, sh_bg)):
-                        p.variant = _lib.VARIANT_AUTO
-                        self.shared_lds_fallbacks += 1
-                        _warn_lds_fallback()
-                if _depth is not None:
-                    da = _depth_alpha(*_depth)
-                    entry = "gmpi_mpi_render_depth_launch"
-                    if _depth_forward == "window":   # the window forward where its loader can take these tensors (alignment), else today's entry
-                        if _window_forward_takes(p, sc, da, (rgba, sh_rgb, sh_bg)):
-                            entry = "gmpi_mpi_render_depth_window_launch"
-                        else:
-                            self.depth_window_fallbacks += 1
-                            _warn_window_fallback()
-                    _call(entry, dev, ctypes.byref(p), ctypes.byref(sc), ctypes.byref(da), stream=stream)
-                else:
-                    _call("gmpi_mpi_render_shared_launch", dev, ctypes.byref(p), ctypes.byref(sc), stream=stream)
-            else:
+            fully_checked = None   # the volume whose exhaustive range pass this call ran
+            if _layout is None:
+                if on_device:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
+                    need = int(_lib.load_library().gmpi_render_workspace_bytes(ctypes.byref(p)))
+                    if need:
+                        _lend(p, _workspace(dev, stream, need))
+                # range_check="full": the exhaustive pass over the volume, unless it is the one that passed last (8-bit codes are in [0, 1] by
+                # construction: nothing to pass over)
+                if self.range_check == "full" and rgba.dtype is not torch.uint8 and self._full_check_needed(rgba_in):
+                    _range_pass((rgba,), p, dev, stream)
+                    fully_checked = rgba_in
                 _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
+            else:
+                _layout.launch(self, p, rgba, images, dev, stream)
             res = dict(color=color, depth=depth, T=T, status=status)
             if _in_autograd_fn:  # what the backward needs to rebuild the launch
-                res["_bwd"] = (p, keep) if _shared is None else (p, keep, (sh_rgb, sh_bg))
+                res["_bwd"] = (p, keep) if images is None else (p, keep, images)
             if ring is not None:
                 ring.host_words[slot].copy_(status, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(current)
                 ring.pending.append((slot, ev, self, p, keep, c2w_mat, sphere_c))
             elif not defer_status:
-                self._settle(status, p, keep, c2w_mat, sphere_c, rgba_in if _shared is None and checked else None)
+                self._settle(status, p, keep, c2w_mat, sphere_c, fully_checked)
             return res
 
-    def _autograd_bridge(self, rgba, dhw, ray_dir, eye_pos, z_dir, shared, depth=None):
+    def _autograd_bridge(self, rgba, dhw, ray_dir, eye_pos, z_dir, layout):
         """(autograd.Function, its leading tensor arguments) when this call has to be recorded, else None."""
         geometry = self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir))
-        if shared is None:
+        if layout is None:
             # G-step of the reference (train.py:740-779): gradient w.r.t. the RGBA volume through the fused backward
             return (_RenderFunction, (rgba,)) if rgba.requires_grad or geometry else None
-        # shared-colour layout (render_views_shared): rgba is the alpha tensor, shared = (rgb, background or None); depth-alpha layout
-        # (render_views_depth): rgba is the depth image, depth = (plane_z, z_lo, z_hi)
+        # a layout: rgba is its first argument (the alpha tensor, the depth image)
         if geometry and not self.geometry_grad_layouts:
-            what, expand = ("shared-colour", "expand_shared_color") if depth is None else ("depth-alpha", "expand_depth_alpha")
-            raise NotImplementedError(f"the {what} render has no gradient w.r.t. the plane geometry or the camera tensors under "
+            raise NotImplementedError(f"the {layout.kind.name} render has no gradient w.r.t. the plane geometry or the camera tensors under "
                                       f'geometry_grad=True: build the module with geometry_grad="all" for that (or render the expanded '
-                                      f"volume, {expand}, with render_views)")
-        if geometry or rgba.requires_grad or any(t is not None and t.requires_grad for t in shared):
-            return _SharedRenderFunction if depth is None else _DepthRenderFunction, (shared[0], rgba, shared[1])
+                                      f"volume, {layout.kind.expand}, with render_views)")
+        if geometry or rgba.requires_grad or layout.requires_grad:
+            return _LayoutRenderFunction, (layout.rgb, rgba, layout.background)
         return None
 
     def _flags(self, out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint) -> int:
@@ -812,10 +849,8 @@ class MPI(nn.Module):
         `rgba[:, :, 3:]` is copied for it, D planes per call -- use the default "touched" where the no-copy property matters.  The tile
         backward (every variant but "gather", D <= 128) assumes a pinhole ray field like the other staged kernels; D > 128 takes the
         one-pixel-per-lane backward, which is several times slower."""
-        from .shared_color import _check
-        _check(rgb, alpha, background)
-        assert "_shared" not in kwargs
-        return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _shared=(rgb, background), _shared_variant=variant, **kwargs)
+        alpha, layout = _shared_layout(rgb, alpha, background, variant)
+        return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _layout=layout, **kwargs)
 
     # -- depth-alpha layout ------------------------------------------------------------------------------------------------------------
     def render_views_depth(self, rgb: torch.Tensor, depth: torch.Tensor, plane_z: torch.Tensor, z_bounds, dhw: torch.Tensor, ray_dir: torch.Tensor,
@@ -841,20 +876,10 @@ class MPI(nn.Module):
         same status words.  Its loader needs base pointers and outer strides that are multiples of 16 bytes (and, for a width that is no multiple
         of 4, allocated padding behind the last row): tensors it cannot take render with the one-pixel kernel, counted in
         `depth_window_fallbacks`, one RuntimeWarning per process.  Any other name: ValueError.  The backward does not depend on it."""
-        assert "_shared" not in kwargs and "_depth" not in kwargs and "_depth_backward" not in kwargs and "_depth_forward" not in kwargs
-        variant = kwargs.pop("variant", None)   # (None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
-        if variant not in (None, "auto", "gather"):
-            raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
-        depth_backward = kwargs.pop("depth_backward", "pixel")
-        if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
-            raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
-        if depth_backward != "pixel":   # (the default: exactly the call without the argument)
-            kwargs["_depth_backward"] = depth_backward
-        depth_forward = _depth_forward_name(kwargs.pop("depth_forward", "pixel"))
-        if depth_forward != "pixel":
-            kwargs["_depth_forward"] = depth_forward
-        depth5, shared, depth_alpha = _depth_operands(rgb, depth, plane_z, z_bounds, background, dhw.shape[1])
-        return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _shared=shared, _shared_variant=variant, _depth=depth_alpha, **kwargs)
+        # (variant None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
+        depth5, layout = _depth_layout(rgb, depth, plane_z, z_bounds, background, dhw.shape[1], kwargs.pop("variant", None),
+                                       kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"))
+        return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _layout=layout, **kwargs)
 
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
     def raise_on_status(self, status: torch.Tensor, params=None, keep=None, c2w_mat=None, sphere_c=None):
@@ -902,27 +927,25 @@ class MPI(nn.Module):
             raise RuntimeError(msg)
 
 
-def _bridge_forward(ctx, mpi, volume, geometry, kwargs, shared=None):
+def _bridge_forward(ctx, mpi, volume, geometry, kwargs):
     """The forward of both autograd bridges: the render with a transmittance buffer private to the node (never a caller-supplied `out["T"]`,
     which a batch driver reuses across launches; the caller's gets a copy), the scalar fields of its struct kept for the backward.  Returns
-    the result dict, the kept tensors and, for the shared-colour render, its (rgb, background)."""
+    the result dict, the kept tensors and, for a layout (`kwargs["_layout"]`), its (rgb, background) as the kernels read them."""
     kw = dict(kwargs, want_transmittance=True)
     user_out = kw.get("out") or {}
     kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # private T
-    if shared is not None:
-        kw["_shared"] = tuple(None if t is None else t.detach() for t in shared)
     res = mpi.render_views(volume.detach(), *geometry, _in_autograd_fn=True, **kw)
     bwd = res.pop("_bwd")   # (p, keep) or (p, keep, (rgb, background))
-    p = bwd[0]
+    p, images = bwd[0], bwd[2] if len(bwd) == 3 else None
     if kwargs.get("want_transmittance") and user_out.get("T") is not None:
         user_out["T"].copy_(res["T"])
     # (the staged shared-colour forward is a forward variant only: its backward is AUTO's, the tile backward)
-    bwd_variant = _lib.VARIANT_AUTO if shared is not None and p.variant == _lib.VARIANT_LDS else p.variant
+    bwd_variant = _lib.VARIANT_AUTO if images is not None and p.variant == _lib.VARIANT_LDS else p.variant
     ctx.scalars = _Scalars(p.flags, bwd_variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi)
     ctx.mark_non_differentiable(res["status"])
     # (an output nobody used arrives as None, not as a zero tensor: "T unused" -> today's launch, told apart from gT = 0 without a reduction)
     ctx.set_materialize_grads(False)
-    return res, bwd[1], bwd[2] if shared is not None else None
+    return res, bwd[1], images
 
 
 def _upstream(ctx, dev, g_color, g_depth, g_T):
@@ -952,36 +975,6 @@ def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream):
         _lend(p, ws)
     _call(entry, dev, ctypes.byref(p), *structs, *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), stream=stream)
     return [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)]
-
-
-def _layout_backward(ctx, g_color, g_depth, g_T, keep, T, image_shapes, image_call, geometry_entry, structs):
-    """The backward of both layout bridges.  Image gradients: zero-filled fp32 tensors of `image_shapes` for the inputs that need one, handed to
-    image_call(p, upstream, grads) -- skipped when no image needs a gradient.  Then, for a module with geometry_grad="all", the geometry pass
-    (`geometry_entry` with the layout's `structs`) when dhw, ray_dir, eye_pos or z_dir needs one: one extra launch."""
-    dev = keep.rgba.device
-    want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
-    geo_want = [ctx.geometry and ctx.needs_input_grad[i] for i in (4, 5, 6, 7)]   # dhw, ray_dir, eye_pos, z_dir
-    if not (any(want) or any(geo_want)) or (g_color is None and g_depth is None and g_T is None):
-        return (None,) * 9
-    g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
-    upstream = (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T))
-    out = [None] * 3
-    if any(want):
-        p = _render_params(ctx.scalars, keep, T=T)
-        grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(image_shapes(p), want)]
-        image_call(p, upstream, grads)
-        out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
-    geo = [None] * 4
-    if any(geo_want):
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        geo = _geometry_pass(ctx, keep, T, dev, stream, geo_want, geometry_entry, structs, upstream)
-    return out[0], out[1], out[2], None, geo[0], geo[1], geo[2], geo[3], None
-
-
-def _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir) -> None:
-    """What a layout bridge keeps for the geometry pass: whether the module includes the layouts, and each camera / dhw input's dtype and device."""
-    ctx.geometry = mpi.geometry_grad_layouts
-    ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]
 
 
 class _RenderFunction(torch.autograd.Function):
@@ -1046,91 +1039,58 @@ class _RenderFunction(torch.autograd.Function):
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
 
 
-class _SharedRenderFunction(torch.autograd.Function):
-    """autograd bridge of the shared-colour render, built like `_RenderFunction`: forward = gmpi_mpi_render_shared_launch, backward =
-    gmpi_mpi_render_shared_backward_launch into zero-filled fp32 gradients of the inputs that need one (the others are passed as NULL and
-    skipped by the kernel).  Saved tensors, private T buffer, unused outputs as None: as there.  For a module with geometry_grad="all" the node is
-    also recorded when only dhw or a camera tensor requires grad, and its backward ends with gmpi_mpi_render_shared_geometry_backward_launch."""
+def _ptr_stride(t: Optional[torch.Tensor], dims):
+    """(pointer, strides along `dims`) of a gradient tensor as the image entries take it; (NULL, NULL) for one that is not wanted."""
+    if t is None:
+        return None, None
+    return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
+
+
+class _LayoutRenderFunction(torch.autograd.Function):
+    """autograd bridge of the shared-colour and depth-alpha renders (`kwargs["_layout"]` says which), built like `_RenderFunction`: forward = the
+    layout's forward entry, backward = its image entry (gmpi_mpi_render_shared_backward_launch; gmpi_mpi_render_depth_backward_launch or, with
+    depth_backward="tile", gmpi_mpi_render_depth_backward_tile_launch) into zero-filled fp32 gradients of rgb, the alpha tensor / depth image and
+    the background -- those that need one: the others are passed as NULL and skipped by the kernel, and the launch is skipped when none does.
+    Saved tensors (plane_z among them), private T buffer, unused outputs as None: as there.  For a module with geometry_grad="all" the node is
+    also recorded when only dhw or a camera tensor requires grad, and its backward ends with the layout's geometry entry: one extra launch."""
 
     @staticmethod
-    def forward(ctx, rgb, alpha, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
-        res, keep, (rgb_d, bg_d) = _bridge_forward(ctx, mpi, alpha, (dhw, ray_dir, eye_pos, z_dir), kwargs, shared=(rgb, background))
-        ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
-        ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
-        ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, alpha, background)]
-        _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir)
+    def forward(ctx, rgb, mid, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+        layout = kwargs["_layout"]
+        res, keep, (rgb_k, bg_k) = _bridge_forward(ctx, mpi, mid, (dhw, ray_dir, eye_pos, z_dir), kwargs)
+        ctx.save_for_backward(keep.rgba, rgb_k, *keep[1:5], res["T"], bg_k, keep.view_to_mpi, layout.plane_z)   # (None where there is none)
+        ctx.backward_entry, ctx.geometry_entry, ctx.ramp = layout.backward_entry, layout.kind.geometry_entry, layout.ramp
+        ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, mid, background)]
+        ctx.geometry = mpi.geometry_grad_layouts
+        ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
         return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_T, g_status):
-        saved = list(ctx.saved_tensors)
-        alpha, rgb, dhw, ray_dir, eye_pos, z_dir, T = saved[:7]
-        rest = saved[7:]
-        bg = rest.pop(0) if ctx.has_bg else None
-        keep = _Keep(alpha, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
-        sc = _shared_color(rgb, bg)
-
-        def ptr_stride(t, dims):
-            if t is None:
-                return None, None
-            return t.data_ptr(), (ctypes.c_int64 * 3)(*[t.stride(d) for d in dims])
-
-        def image_call(p, upstream, grads):
-            _call("gmpi_mpi_render_shared_backward_launch", alpha.device, ctypes.byref(p), ctypes.byref(sc), *upstream,
-                  *ptr_stride(grads[0], (0, 1, 2)), *ptr_stride(grads[1], (0, 1, 3)), *ptr_stride(grads[2], (0, 1, 2)))
-        return _layout_backward(ctx, g_color, g_depth, g_T, keep, T, lambda p: [(p.M, 3, p.Ht, p.Wt), (p.M, p.D, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)],
-                                image_call, "gmpi_mpi_render_shared_geometry_backward_launch", (ctypes.byref(sc),))
-
-
-# render_views_depth(depth_forward=...): None reads as "pixel"; anything but the two names is refused before any call
-def _depth_forward_name(depth_forward) -> str:
-    if depth_forward is None:
-        return "pixel"
-    if depth_forward not in ("pixel", "window"):
-        raise ValueError(f'depth_forward is "pixel" or "window", not {depth_forward!r}')
-    return depth_forward
-
-
-# render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
-_DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch"}
-
-
-class _DepthRenderFunction(torch.autograd.Function):
-    """autograd bridge of the depth-alpha render, built like `_SharedRenderFunction`: forward = gmpi_mpi_render_depth_launch, backward =
-    gmpi_mpi_render_depth_backward_launch (depth_backward="tile": gmpi_mpi_render_depth_backward_tile_launch) into zero-filled fp32 gradients of
-    rgb, the depth image and the background; with geometry_grad="all" the node is also recorded when only dhw or a camera tensor requires grad, and
-    its backward ends with gmpi_mpi_render_depth_geometry_backward_launch."""
-
-    @staticmethod
-    def forward(ctx, rgb, depth, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
-        ctx.backward_entry = _DEPTH_BACKWARD_ENTRIES[kwargs.get("_depth_backward", "pixel")]
-        res, keep, (rgb_d, bg_d) = _bridge_forward(ctx, mpi, depth, (dhw, ray_dir, eye_pos, z_dir), kwargs, shared=(rgb, background))
-        ctx.has_bg, ctx.has_v2m = bg_d is not None, keep.view_to_mpi is not None
-        plane_z, ctx.z_lo, ctx.z_hi = kwargs["_depth"]
-        ctx.save_for_backward(keep.rgba, rgb_d, *keep[1:5], res["T"], plane_z, *([bg_d] if ctx.has_bg else []), *([keep.view_to_mpi] if ctx.has_v2m else []))
-        ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, depth, background)]
-        _remember_geometry(ctx, mpi, dhw, ray_dir, eye_pos, z_dir)
-        return res["color"], res["depth"], res["T"], res["status"]
-
-    @staticmethod
-    def backward(ctx, g_color, g_depth, g_T, g_status):
-        saved = list(ctx.saved_tensors)
-        depth, rgb, dhw, ray_dir, eye_pos, z_dir, T, plane_z = saved[:8]
-        rest = saved[8:]
-        bg = rest.pop(0) if ctx.has_bg else None
-        keep = _Keep(depth, dhw, ray_dir, eye_pos, z_dir, rest.pop(0) if ctx.has_v2m else None)
-        sc, da = _shared_color(rgb, bg), _depth_alpha(plane_z, ctx.z_lo, ctx.z_hi)
-        structs = (ctypes.byref(sc), ctypes.byref(da))
-
-        def ptr_stride(t):
-            if t is None:
-                return None, None
-            return t.data_ptr(), (ctypes.c_int64 * 3)(*t.stride()[:3])
-
-        def image_call(p, upstream, grads):
-            _call(ctx.backward_entry, depth.device, ctypes.byref(p), *structs, *upstream, *ptr_stride(grads[0]), *ptr_stride(grads[1]), *ptr_stride(grads[2]))
-        return _layout_backward(ctx, g_color, g_depth, g_T, keep, T, lambda p: [(p.M, 3, p.Ht, p.Wt), (p.M, 1, p.Ht, p.Wt), (p.M, 3, p.Ht, p.Wt)],
-                                image_call, "gmpi_mpi_render_depth_geometry_backward_launch", structs)
+        mid, rgb, dhw, ray_dir, eye_pos, z_dir, T, bg, view_to_mpi, plane_z = ctx.saved_tensors
+        keep, dev = _Keep(mid, dhw, ray_dir, eye_pos, z_dir, view_to_mpi), mid.device
+        want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
+        geo_want = [ctx.geometry and ctx.needs_input_grad[i] for i in (4, 5, 6, 7)]   # dhw, ray_dir, eye_pos, z_dir
+        if not (any(want) or any(geo_want)) or (g_color is None and g_depth is None and g_T is None):
+            return (None,) * 9
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
+        upstream = (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T))
+        sc = _shared_color(rgb, bg)   # the forward's structs, rebuilt from the saved tensors
+        structs = (ctypes.byref(sc),) if plane_z is None else (ctypes.byref(sc), ctypes.byref(_depth_alpha(plane_z, *ctx.ramp)))
+        out = [None] * 3
+        if any(want):   # zero-filled fp32 gradients of the images that need one; the launch is skipped when none does
+            p = _render_params(ctx.scalars, keep, T=T)
+            image = (p.M, 3, p.Ht, p.Wt)
+            mid_shape, mid_dims = ((p.M, p.D, 1, p.Ht, p.Wt), (0, 1, 3)) if plane_z is None else ((p.M, 1, p.Ht, p.Wt), (0, 1, 2))   # alpha planes | depth image
+            grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip((image, mid_shape, image), want)]
+            _call(ctx.backward_entry, dev, ctypes.byref(p), *structs, *upstream,
+                  *_ptr_stride(grads[0], (0, 1, 2)), *_ptr_stride(grads[1], mid_dims), *_ptr_stride(grads[2], (0, 1, 2)))
+            out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
+        geo = [None] * 4
+        if any(geo_want):   # a module with geometry_grad="all": the geometry pass with the layout's structs
+            stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+            geo = _geometry_pass(ctx, keep, T, dev, stream, geo_want, ctx.geometry_entry, structs, upstream)
+        return out[0], out[1], out[2], None, geo[0], geo[1], geo[2], geo[3], None
 
 
 HipMPI = MPI

@@ -17,7 +17,7 @@ import logging
 import numpy as np
 import torch
 
-from .hip_mpi import MPI, _call, _cat
+from .hip_mpi import MPI, _call, _cat, _depth_layout, _shared_layout
 from .pinhole import gen_cam
 from .plane_geometry import compute_plane_dhws, sample_distance
 from .poses import draw_angle_noise, gen_sphere_path, gen_sphere_paths_ahead, host_math
@@ -418,11 +418,7 @@ class MPIRenderer:
         vertical_std = self.vertical_std if vertical_std is None else vertical_std
         views_per_mpi = int(ext.pop("views_per_mpi", 1))
         want_T = bool(ext.pop("want_transmittance", False))
-        shared = ext.pop("_shared", None)   # render_shared: (rgb, background or None); batch_mpi_rgbas is then the alpha tensor
-        shared_variant = ext.pop("_shared_variant", None)
-        depth_alpha = ext.pop("_depth", None)   # render_depth: (plane_z, z_lo, z_hi); batch_mpi_rgbas is then the depth image [B,1,1,Ht,Wt]
-        depth_backward = ext.pop("_depth_backward", None)   # render_depth(depth_backward="tile")
-        depth_forward = ext.pop("_depth_forward", None)     # render_depth(depth_forward="window")
+        layout = ext.pop("_layout", None)   # render_shared / render_depth: batch_mpi_rgbas is then the alpha tensor / the depth image [B,1,1,Ht,Wt]
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -441,7 +437,7 @@ class MPIRenderer:
             #  backward, and the next render() of this shape would overwrite them through a raw pointer -- no version counter sees that)
             # (nor when the status check lags: the pending entry of this call keeps its camera tensors for the diagnostics of a tripped
             #  assertion -- "pos / dir / min val" of THIS call, printed one or more calls later -- so a later call must not overwrite them)
-            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or any(t is not None and t.requires_grad for t in (shared or ())) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad))
+            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad))
             ray_t, eye_t, zd_t = self._generate_rays_hip(c2w, reuse=not recording and defer != "lag")
         else:
             if given_cam_infos is None:
@@ -465,9 +461,7 @@ class MPIRenderer:
             batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
             check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
             c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-            **({} if shared is None else {"_shared": shared, "_shared_variant": shared_variant}), **({} if depth_alpha is None else {"_depth": depth_alpha}),
-            **({} if depth_backward is None else {"_depth_backward": depth_backward}),
-            **({} if depth_forward is None else {"_depth_forward": depth_forward}))
+            _layout=layout)
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
@@ -481,10 +475,8 @@ class MPIRenderer:
         background_rgb [B,3,Ht,Wt] or None = the last plane's own colour.  Keyword arguments, return tuple, pose sampling and the consumption of
         the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the expanded volume.  `variant`: the kernel, as
         in `MPI.render_views_shared` (None: the renderer's own; "lds": the staged forward)."""
-        from .shared_color import _check
-        _check(batch_mpi_rgb, batch_mpi_alpha, background_rgb)
-        assert "_shared" not in kwargs
-        return self.render(batch_mpi_alpha, render_h, render_w, _shared=(batch_mpi_rgb, background_rgb), _shared_variant=variant, **kwargs)
+        alpha, layout = _shared_layout(batch_mpi_rgb, batch_mpi_alpha, background_rgb, variant)
+        return self.render(alpha, render_h, render_w, _layout=layout, **kwargs)
 
 
     def render_depth(self, batch_rgb, batch_depth, render_h, render_w, *, z_range, n_z_bins, plane_z=None, background_rgb=None, **kwargs):
@@ -497,23 +489,11 @@ class MPIRenderer:
         one-pixel-per-lane kernel runs; any other name is a ValueError before anything is launched.  `depth_forward`: "pixel" (default) or
         "window", as in `MPI.render_views_depth` -- the window forward gives the same bits."""
         from .depth_alpha import depth_alpha_bounds
-        from .hip_mpi import _DEPTH_BACKWARD_ENTRIES, _depth_forward_name, _depth_operands
-        depth_forward = _depth_forward_name(kwargs.pop("depth_forward", "pixel"))
-        assert "_depth_forward" not in kwargs
-        if depth_forward != "pixel":
-            kwargs["_depth_forward"] = depth_forward
-        depth_backward = kwargs.pop("depth_backward", "pixel")
-        if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
-            raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
-        assert "_depth_backward" not in kwargs
-        if depth_backward != "pixel":
-            kwargs["_depth_backward"] = depth_backward
         if plane_z is None:
             plane_z = self.get_xyz_single_res(batch_depth.shape[-2], batch_depth.shape[-1], only_z=True)[1].reshape(-1)
-        assert "_shared" not in kwargs and "_depth" not in kwargs
-        depth5, shared, depth_alpha = _depth_operands(batch_rgb, batch_depth, plane_z, depth_alpha_bounds(z_range, n_z_bins), background_rgb,
-                                                      self.dynamic_mpi_plane_dhws.shape[0])
-        return self.render(depth5, render_h, render_w, _shared=shared, _depth=depth_alpha, **kwargs)
+        depth5, layout = _depth_layout(batch_rgb, batch_depth, plane_z, depth_alpha_bounds(z_range, n_z_bins), background_rgb,
+                                       self.dynamic_mpi_plane_dhws.shape[0], None, kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"))
+        return self.render(depth5, render_h, render_w, _layout=layout, **kwargs)
 
 
 class _RaysFromC2W(torch.autograd.Function):

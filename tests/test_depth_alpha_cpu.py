@@ -283,8 +283,8 @@ def test_renderer_render_depth_takes_the_normalised_plane_depths(rec):
     c = rec.named("gmpi_mpi_render_depth_launch")[0]
     da = c.args[2]
     want = r.get_xyz_single_res(S, S, only_z=True)[1].reshape(-1)
-    assert want.shape == (4,) and torch.equal(seen["_depth"][0], want.float())
-    assert da.plane_z == seen["_depth"][0].data_ptr() and da.plane_z_stride == 0
+    assert want.shape == (4,) and torch.equal(seen["_layout"].plane_z, want.float())
+    assert da.plane_z == seen["_layout"].plane_z.data_ptr() and da.plane_z_stride == 0
     lo, hi = depth_alpha_bounds(1, 4)
     assert (da.z_lo, da.z_hi) == (lo, hi) and c.args[0].D == 4 and c.args[0].flags & 2   # (OUT_PM1: render()'s colour range)
 

@@ -6,12 +6,17 @@ import torch
 
 from ml_gmpi_amd import _lib
 from ml_gmpi_amd.hip_mpi import MPI
+from test_depth_alpha_cpu import depth_inputs
 from test_marshal_cpu import (BACKWARD_ENTRIES, FORWARD_ENTRIES, GEOMETRY_BACKWARD, VOLUME_BACKWARD, H, W, Recorder, check_backward_struct,
                               loss_of, make_inputs, shared_inputs)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ENTRIES = tuple(e for e in FORWARD_ENTRIES + BACKWARD_ENTRIES if e.startswith("gmpi_mpi_render"))
+DEPTH_FORWARD = {"pixel": "gmpi_mpi_render_depth_launch", "window": "gmpi_mpi_render_depth_window_launch"}
+DEPTH_BACKWARD = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch"}
+DEPTH_SUPPORTS = "gmpi_render_depth_window_supports"
+ENTRIES = (tuple(e for e in FORWARD_ENTRIES + BACKWARD_ENTRIES if e.startswith("gmpi_mpi_render")) + tuple(DEPTH_FORWARD.values())
+           + tuple(DEPTH_BACKWARD.values()) + (DEPTH_SUPPORTS,))
 
 
 @pytest.fixture
@@ -77,3 +82,34 @@ def test_shared_backward_rebuilds_the_forward_structs(rec, dtype, background, us
     assert bytes(bwd.args[1]) == bytes(fwd.args[1])   # GmpiSharedColor: the same struct
     assert (bwd.args[4] is not None) == uses_T
     assert rgb.grad.shape == rgb.shape and alpha.grad.shape == alpha.shape and (bg is None or bg.grad.shape == bg.shape)
+
+
+@pytest.mark.parametrize("depth_forward", ["pixel", "window"])
+@pytest.mark.parametrize("depth_backward", ["pixel", "tile"])
+@pytest.mark.parametrize("uses_T", [False, True])
+@pytest.mark.parametrize("background", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_depth_backward_rebuilds_the_forward_structs(rec, dtype, background, uses_T, depth_backward, depth_forward):
+    rgb, depth, pz, bg, geo = depth_inputs(dtype, background, per_mpi_table=True)
+    rgb, depth, pz, bg = (None if t is None else t.to(DEV) for t in (rgb, depth, pz, bg))
+    geo = tuple(t.to(DEV) for t in geo)
+    for t in (rgb, depth, bg):
+        if t is not None:
+            t.requires_grad_(True)
+    mpi = MPI(on_out_of_plane="raise")
+    res = mpi.render_views_depth(rgb, depth, pz, (-2 / 10, 2 / 10), *geo, background=bg, want_transmittance=True, depth_backward=depth_backward,
+                                 depth_forward=depth_forward)
+    loss_of(res, uses_T).backward()
+    torch.cuda.synchronize()
+    *query, fwd, bwd = rec.calls
+    # "window": the support query, then the window entry or -- tensors its loader cannot take -- the one-pixel entry, counted as a fallback
+    assert [c.name for c in query] == ([DEPTH_SUPPORTS] if depth_forward == "window" else [])
+    assert fwd.name in (DEPTH_FORWARD[depth_forward], DEPTH_FORWARD["pixel"]) and bwd.name == DEPTH_BACKWARD[depth_backward]
+    assert mpi.depth_window_fallbacks == int(fwd.name != DEPTH_FORWARD[depth_forward])
+    check_backward_struct(bwd, fwd, uses_T)
+    assert bytes(bwd.args[1]) == bytes(fwd.args[1]) and bytes(bwd.args[2]) == bytes(fwd.args[2])   # GmpiSharedColor, GmpiDepthAlpha: the same structs
+    for q in query:
+        assert all(bytes(q.args[i]) == bytes(fwd.args[i]) for i in range(3))
+    assert (bwd.args[5] is not None) == uses_T
+    for t in (rgb, depth, bg):
+        assert t is None or (t.grad.shape == t.shape and t.grad.dtype == dtype and bool(torch.isfinite(t.grad.float()).all()))

@@ -330,13 +330,15 @@ def test_shared_colour_full_range_check_covers_the_three_tensors(rec):
 VOLUME_BACKWARD = ("gmpi_mpi_render_backward_launch", "gmpi_mpi_render_backward_ex_launch")
 GEOMETRY_BACKWARD = ("gmpi_mpi_render_geometry_backward_launch", "gmpi_mpi_render_geometry_backward_ex_launch")
 SAME_POINTERS = ("view_to_mpi", "dhw", "ray_dir", "eye_pos", "z_dir", "rgba")
+# the image backwards of the two layouts: one entry each for a loss with and without T (the T gradient is an argument, NULL when unused)
+LAYOUT_BACKWARD = ("gmpi_mpi_render_shared_backward_launch", "gmpi_mpi_render_depth_backward_launch", "gmpi_mpi_render_depth_backward_tile_launch")
 
 
 def check_backward_struct(bwd: Call, fwd: Call, uses_T: bool, overwrite: bool = False, user_T=None):
     """`bwd`: a recorded backward call; `fwd`: the forward call of the same node.  overwrite: FLAG_GRAD_OVERWRITE is expected (the
     backward="gather" path of the volume gradient, with a workspace)."""
     b, f = bwd.args[0], fwd.args[0]
-    assert bwd.name.endswith("_ex_launch") == uses_T or bwd.name == "gmpi_mpi_render_shared_backward_launch", bwd.name
+    assert bwd.name.endswith("_ex_launch") == uses_T or bwd.name in LAYOUT_BACKWARD, bwd.name
     got, want = scalars_of(b), scalars_of(f)
     assert got.pop("workspace_bytes") == (b.workspace_bytes if b.workspace else 0)
     want.pop("workspace_bytes")

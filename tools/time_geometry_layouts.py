@@ -28,7 +28,7 @@ def one(layout, S, B, D, n_z_bins, reps):
     sys.path.insert(0, ROOT)
     import ml_gmpi_amd
     from ml_gmpi_amd import _lib, depth_alpha_bounds, expand_depth_alpha, expand_shared_color
-    from ml_gmpi_amd.hip_mpi import _depth_alpha, _shared_color
+    from ml_gmpi_amd.hip_mpi import _depth_alpha, _depth_layout, _shared_color, _shared_layout
     lib = _lib.load_library()
     dev = torch.device("cuda:0")
     cs = torch.cuda.current_stream(dev).cuda_stream
@@ -82,9 +82,11 @@ def one(layout, S, B, D, n_z_bins, reps):
     torch.cuda.reset_peak_memory_stats(dev)
     with torch.no_grad():
         if layout == "shared":
-            res = r.mpi.render_views(mid, dhw, ray, eye, zd, _shared=(rgb, bg), _in_autograd_fn=True, **kw)
+            first, lay = _shared_layout(rgb, mid, bg, None)
         else:
-            res = r.mpi.render_views(mid.unsqueeze(1), dhw, ray, eye, zd, _shared=(rgb, bg), _depth=(plane_z, *zb), _in_autograd_fn=True, **kw)
+            first, lay = _depth_layout(rgb, mid, plane_z, zb, bg, D, None, "pixel", "pixel")
+        res = r.mpi.render_views(first, dhw, ray, eye, zd, _layout=lay, _in_autograd_fn=True, **kw)
+        del first, lay
     p = res.pop("_bwd")[0]
     row["frac_T_underflow"] = float((res["T"] < 1e-30).float().mean())
     q, ws = backward_struct(p)
