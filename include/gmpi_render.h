@@ -203,7 +203,9 @@ int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
  * Round 6: when params->workspace holds at least gmpi_render_backward_workspace_bytes(params) bytes (256-byte aligned; N D H W 24 bytes for the
  * sample gradients and sample positions of every pixel and plane, plus one homography record per view and plane), the launch runs WITHOUT atomics: a pixel pass writes the sample gradients, a texel pass gathers them
  * through each plane's homography and writes every cell of grad_rgba once (deterministic; += without GMPI_FLAG_GRAD_OVERWRITE, = with it: then no
- * zero-fill is needed).  align_corners = True, uniform views_per_mpi (no view_to_mpi); other launches take the tile kernels whatever the workspace.
+ * zero-fill is needed).  align_corners = True, uniform views_per_mpi (no view_to_mpi), Wt >= 2 and a volume whose offsets inside one plane fit 32 bits,
+ * (3 rgba_stride[2] + Ht rgba_stride[3] + Wt) * sizeof(element) < 2^31 (the pixel pass addresses its taps so; grad_rgba may have any strides); other
+ * launches take the tile kernels whatever the workspace, and the workspace query answers 0 for them.
  * `ray_dir` must be a pinhole ray field (straight pixel lines map to straight lines on every plane -- what `Camera.generate_rays` /
  * gmpi_generate_rays_launch produce) for the tile kernels' texel boxes and for the gather's candidate windows; GMPI_VARIANT_GATHER (one pixel per lane,
  * 16 atomics per pixel and plane: the cross-check) makes no such assumption and takes no workspace.

@@ -23,7 +23,7 @@ bool band_variant_supports(const KParams& p, int dtype);                    // r
 uint64_t band_workspace_bytes(const KParams& p, int dtype);                 // render_band.hip
 uint32_t* band_gate_words(const KParams& p, int dtype);                     // render_band.hip
 int band_pixels_wide(int dtype);                                            // render_band.hip
-uint64_t backward_gather_workspace_bytes(const KParams& p);                 // render_backward_gather.hip
+uint64_t backward_gather_workspace_bytes(const KParams& p, int dtype);      // render_backward_gather.hip
 uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
 hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared.hip
 hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream);   // render_shared.hip
@@ -465,7 +465,7 @@ uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams* params) {
     KParams p;
     if (to_kparams(params, p, false, true) != GMPI_OK || p.N == 0) return 0;
     if (params->variant == GMPI_VARIANT_GATHER) return 0;   // the all-atomic cross-check kernel
-    return backward_gather_workspace_bytes(p);
+    return backward_gather_workspace_bytes(p, params->rgba_dtype);
 }
 
 int gmpi_mpi_render_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,

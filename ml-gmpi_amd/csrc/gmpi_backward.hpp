@@ -163,8 +163,17 @@ template <> __device__ __forceinline__ void load_pair<float>(const unsigned char
     a = v[0], b = v[1];
 }
 
+// Host side: do all offsets inside one plane of a [.., 4, Ht, Wt] tensor -- 3 channels + Ht rows + Wt items of `es` bytes -- fit 31 bits?  The ONE test of
+// every launcher whose kernel forms in-plane offsets in 32 bits (fetch_pair_taps; the 64 x 8 tile backward's gradient offsets, es = 1: they count items).
+inline bool plane_offsets_fit_32(int64_t s_chan, int64_t s_row, int Ht, int Wt, int es) {
+    if (s_chan < 0 || s_row < 0) return false;
+    const int64_t lim = (int64_t(1) << 31) / es;   // (each term is compared on its own first: no product or sum below can overflow 64 bits)
+    if (s_chan >= lim || s_row >= lim) return false;
+    return 3 * s_chan + static_cast<int64_t>(Ht) * s_row + Wt < lim;
+}
+
 // ---- taps fetched as (x, x + 1) pairs: 8 loads of 8 bytes instead of 16 of 4 for fp32 volumes, at 32-bit offsets from a uniform base (the launcher
-// checks Wt >= 2 and that a plane's byte offsets fit 32 bits).  What a plane keeps between the issue of its taps and their use:
+// checks Wt >= 2 and plane_offsets_fit_32).  What a plane keeps between the issue of its taps and their use:
 struct PairTaps {
     float s, wx1, wy1;   // depth factor; ix - floor(ix), iy - floor(iy)
     int x0, y0;          // floor(ix), floor(iy); -2 = out of range (NaN / huge coordinates: all weights 0)

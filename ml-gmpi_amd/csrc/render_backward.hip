@@ -567,8 +567,7 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
         const dim3 grid(tiles_x * tiles_y, p.N), block(kBwdThreads), block2(kB2Threads);
         // the round-5 kernel wants two columns (pair loads) and a plane's offsets -- volume and gradient -- in 32 bits
         const int es = static_cast<int>(sizeof(TexT));
-        bool v1 = p.Wt < 2 || (3 * p.s_chan + static_cast<int64_t>(p.Ht) * p.s_row + p.Wt) * es >= (int64_t(1) << 31) ||
-                  (3 * b.gs_chan + static_cast<int64_t>(p.Ht) * b.gs_row + p.Wt) >= (int64_t(1) << 31) || p.s_chan < 0 || p.s_row < 0;
+        bool v1 = p.Wt < 2 || !plane_offsets_fit_32(p.s_chan, p.s_row, p.Ht, p.Wt, es) || !plane_offsets_fit_32(b.gs_chan, b.gs_row, p.Ht, p.Wt, 1);
 #ifdef GMPI_TUNE
         v1 = v1 || (p.flags & (1u << 22)) != 0;  // GMPI_TUNE_SKIP=64: the round-1 tile kernel (A/B)
 #endif
@@ -599,8 +598,8 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
 
 // `tiles`: stage the scatter per pixel tile in LDS (default); false = one pixel per lane, 16 global atomics each
 // (GMPI_VARIANT_GATHER: the simple kernel, kept as the cross-check)
-bool backward_gather_supports(const KParams& p);                                                          // render_backward_gather.hip
-uint64_t backward_gather_workspace_bytes(const KParams& p);                                                // render_backward_gather.hip
+bool backward_gather_supports(const KParams& p, int dtype);                                                   // render_backward_gather.hip
+uint64_t backward_gather_workspace_bytes(const KParams& p, int dtype);                                         // render_backward_gather.hip
 hipError_t launch_backward_gather(const KParams& p, int dtype, const BwdParams& b, bool overwrite, hipStream_t stream);   // render_backward_gather.hip
 
 hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
@@ -616,7 +615,7 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
     if (p.N > 65535) tiles = false;  // grid.y
     // Round 6: with a workspace for the sample gradients (gmpi_render_backward_workspace_bytes) the atomics-free pair -- pixel pass + texel gather,
     // render_backward_gather.hip -- takes the launch: every cell of the gradient is written once by its owner.
-    bool gather = tiles && p.ws != nullptr && backward_gather_supports(p) && p.ws_bytes >= backward_gather_workspace_bytes(p) &&
+    bool gather = tiles && p.ws != nullptr && backward_gather_supports(p, dtype) && p.ws_bytes >= backward_gather_workspace_bytes(p, dtype) &&
                   reinterpret_cast<uintptr_t>(p.ws) % 256 == 0;
 #ifdef GMPI_TUNE  // GMPI_TUNE_BWD = 1 | 2: the tile kernels even with a workspace
     {

@@ -394,16 +394,17 @@ static uint64_t recs_bytes(const KParams& p) { return align256(static_cast<uint6
 }  // namespace bwdg
 
 // Can the atomics-free pair run this launch (workspace aside)?
-bool backward_gather_supports(const KParams& p) {
+bool backward_gather_supports(const KParams& p, int dtype) {
     if (!(p.flags & GMPI_FLAG_ALIGN_CORNERS)) return false;                                   // align_corners = True only (see the head of this file)
     if (p.view_to_mpi != nullptr) return false;                          // uniform views per MPI
     if (p.N > 65535 || p.M > 65535 || p.D > 65535) return false;         // grid.y / grid.z
     if (p.Wt < 2) return false;                                          // pair loads
+    if (!plane_offsets_fit_32(p.s_chan, p.s_row, p.Ht, p.Wt, dtype == GMPI_DTYPE_F32 ? 4 : 2)) return false;   // ... at 32-bit byte offsets inside a plane
     if (static_cast<int64_t>(p.H) * p.W >= (int64_t(1) << 31)) return false;
     return true;
 }
-uint64_t backward_gather_workspace_bytes(const KParams& p) {
-    if (!backward_gather_supports(p)) return 0;
+uint64_t backward_gather_workspace_bytes(const KParams& p, int dtype) {
+    if (!backward_gather_supports(p, dtype)) return 0;
     return bwdg::recs_bytes(p) + static_cast<uint64_t>(p.N) * p.D * p.H * p.W * 24u;   // sample gradients 16 B + sample positions 8 B per pixel and plane
 }
 

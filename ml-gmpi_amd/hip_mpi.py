@@ -581,7 +581,8 @@ class MPI(nn.Module):
                      into a zero-filled volume -- fastest, 2.12 + 0.32 ms at 1024^2 x 32 x 4; the order of the adds, hence the last bits, differs from
                      run to run) | "gather" (round 6: pixel pass + texel gather, render_backward_gather.hip -- no atomics, no zero-fill, every cell
                      written once in a fixed order: bit-reproducible gradients; 3.3 ms and 24 bytes of scratch per pixel and plane;
-                     align_corners=True and uniform views per MPI, other launches silently take the atomic path)
+                     align_corners=True, uniform views per MPI and a volume whose offsets inside one plane fit 32 bits --
+                     (3 s_chan + Ht s_row + Wt) itemsize < 2^31, which every contiguous volume meets; other launches silently take the atomic path)
       geometry_grad  False (default: the reference's behaviour -- no gradient reaches the plane geometry or the camera tensors) | True: the
                      gradient also flows to dhw, ray_dir, eye_pos and z_dir (gmpi_mpi_render_geometry_backward_launch, render_backward_geometry.hip:
                      an extension, the reference builds its grid under torch.no_grad(), mpi.py:65) on the volume entry, `render_views`; the
