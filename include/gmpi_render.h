@@ -348,8 +348,8 @@ typedef struct GmpiDepthAlpha {
  * it, any other variant is GMPI_E_VARIANT.  z_lo >= z_hi or z_den <= 0 (or a NaN among them): GMPI_E_SHAPE; a negative plane_z_stride:
  * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
  * never synchronises.  A window forward has an entry of its own (gmpi_mpi_render_depth_window_launch, below: this entry keeps its one kernel and
- * still refuses GMPI_VARIANT_LDS).  Gradients w.r.t. the geometry: gmpi_mpi_render_depth_geometry_backward_launch (gmpi_query(30)).  Not built: 8-bit
- * storage, gradients w.r.t. plane_z and the ramp's bounds (gmpi_query(22) says whether the layout itself is built in).
+ * still refuses GMPI_VARIANT_LDS).  Gradients w.r.t. the geometry: gmpi_mpi_render_depth_geometry_backward_launch (gmpi_query(30)).  The expected depth of the un-warped stack, for the
+ * shading augmentation (LightRenderer): gmpi_ramp_depth_launch (gmpi_query(32)).  Not built: 8-bit storage, gradients w.r.t. plane_z and the ramp's bounds (gmpi_query(22) says whether the layout itself is built in).
  */
 int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
 
@@ -535,6 +535,33 @@ int gmpi_alpha_depth_backward_ex_launch(const void *alpha, int32_t alpha_dtype, 
                                         int32_t H, int32_t W, void *stream);
 
 /*
+ * gmpi_alpha_depth_launch and gmpi_alpha_depth_backward_ex_launch for a depth-alpha MPI, WITHOUT the alpha planes (what the shading augmentation
+ * needs of this layout: LightRenderer.render_depth in the Python package).  By definition gmpi_ramp_depth_launch equals gmpi_alpha_depth_launch on
+ *     a_k = (min(max(plane_z[k] - depth, z_lo), z_hi) - z_lo) / z_den       (GmpiDepthAlpha above: fp32, one rounding per step, the IEEE quotient),
+ * bit for bit in depth_out and transmittance_out ([B,1,H,W] fp32; transmittance_out may be NULL); the planes are never materialised: one thread
+ * holds one depth texel in a register and walks the planes there.  depth_image: [B,1,H,W] in fp32 / bf16 / fp16 (GMPI_DTYPE_U8: GMPI_E_DTYPE),
+ * innermost stride 1, stride_row >= W, stride_b >= 0 (an expanded batch, the channel view of an RGB-D tensor).  ramp->plane_z is [D] or [B,D]
+ * through plane_z_stride; plane_ds [D] are the metric plane distances (another table than plane_z).
+ * The backward gives the gradient w.r.t. the depth image through both outputs (grad_depth, grad_transmittance: [B,1,H,W] fp32, each may be NULL;
+ * both NULL: nothing is added): dL/da_k as gmpi_alpha_depth_backward_ex_launch computes it (same numerics; `transmittance` is the forward's
+ * transmittance_out or NULL), and plane k contributes -dL/da_k / z_den to its texel where z_lo <= plane_z[k] - depth <= z_hi, bounds included,
+ * nothing elsewhere.  The sum is ADDED to grad_depth_image (fp32 [B,1,H,W] view: gstride_b > 0, gstride_row >= W, innermost stride 1; zeroed by
+ * the caller) with a plain load, add and store: one thread owns a texel, there are no atomics.
+ * Errors, all before any launch: D, H, W <= 0, B < 0, B or H > 65535: GMPI_E_SHAPE; B == 0: GMPI_OK; a NULL depth_image, ramp, ramp->plane_z,
+ * plane_ds, depth_out / grad_depth_image: GMPI_E_NULL; ramp->struct_size: GMPI_E_ABI; z_lo >= z_hi or z_den <= 0 (or a NaN among them):
+ * GMPI_E_SHAPE; a stride outside the above: GMPI_E_STRIDE.  Stream-ordered, allocate nothing, never synchronise.  gmpi_query(32) == 1 says that
+ * both entries are built in.
+ */
+int gmpi_ramp_depth_launch(const void *depth_image, int32_t depth_dtype, int64_t stride_b, int64_t stride_row,
+                           const GmpiDepthAlpha *ramp, const float *plane_ds, int32_t B, int32_t D, int32_t H, int32_t W,
+                           float *depth_out, float *transmittance_out, void *stream);
+int gmpi_ramp_depth_backward_launch(const void *depth_image, int32_t depth_dtype, int64_t stride_b, int64_t stride_row,
+                                    const GmpiDepthAlpha *ramp, const float *plane_ds, const float *transmittance,
+                                    const float *grad_depth, const float *grad_transmittance, float *grad_depth_image,
+                                    int64_t gstride_b, int64_t gstride_row, int32_t B, int32_t D, int32_t H, int32_t W,
+                                    void *stream);
+
+/*
  * Self-test of the default mode's division: the coordinate chain (mpi.py:76, 89-90) divides through correctly rounded
  * reciprocals hoisted out of the plane loop (q0 = n*r, e = fma(-d, q0, n), q = fma(e, r, q0) with r = RN(1/d)); this entry
  * compares that against the IEEE division on `pairs` pseudo-random operand pairs (classes: 0 zdiff/ray_z, 1 x/(w/2),
@@ -563,7 +590,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * (gmpi_mpi_render_depth_backward_tile_launch) takes: more go to the one-pixel-per-lane kernel; 24 is unused (-1); the depth-alpha window forward
  * (gmpi_mpi_render_depth_window_launch): 25 whether it is built in, 26 / 27 the width / height of its window in texels, 28 the planes per refill of
  * its box table; 29 is unused (-1); 30 whether the geometry backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_shared_geometry_backward_launch,
- * gmpi_mpi_render_depth_geometry_backward_launch) is built in.  Unknown -> -1.                                                          */
+ * gmpi_mpi_render_depth_geometry_backward_launch) is built in; 31 is unused (-1); 32 whether compute_depth of the depth-alpha layout
+ * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in.  Unknown -> -1.                                                */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -4,7 +4,7 @@ from .hip_mpi import MPI, HipMPI, flush_status
 from .renderer import MPIRenderer, PRESETS, make_renderer, rays_from_c2w
 from .driver import ViewBatchDriver, shard_views, render_views_sharded, frames_to_uint8, dump_frames
 from .install import install, uninstall
-from .light import LightRenderer, compute_depth
+from .light import LightRenderer, compute_depth, compute_depth_ramp
 from .shared_color import expand_shared_color, split_shared_color
 from .depth_alpha import depth_alpha_bounds, depth_alpha_planes, expand_depth_alpha
 from .quantized import quantize_volume, dequantize_volume, layers_as_volume, volume_as_layers
@@ -13,7 +13,7 @@ __all__ = [
     "GmpiError", "build_extension", "library_path", "load_library",
     "MPI", "HipMPI", "flush_status", "MPIRenderer", "PRESETS", "make_renderer", "rays_from_c2w",
     "ViewBatchDriver", "shard_views", "render_views_sharded", "frames_to_uint8", "dump_frames",
-    "install", "uninstall", "compute_depth", "LightRenderer", "expand_shared_color", "split_shared_color",
+    "install", "uninstall", "compute_depth", "compute_depth_ramp", "LightRenderer", "expand_shared_color", "split_shared_color",
     "depth_alpha_bounds", "depth_alpha_planes", "expand_depth_alpha",
     "quantize_volume", "dequantize_volume", "layers_as_volume", "volume_as_layers",
 ]

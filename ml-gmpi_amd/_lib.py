@@ -53,6 +53,8 @@ EXPORTS = (
     "gmpi_light_apply_backward_launch",
     "gmpi_alpha_depth_backward_launch",
     "gmpi_alpha_depth_backward_ex_launch",
+    "gmpi_ramp_depth_launch",
+    "gmpi_ramp_depth_backward_launch",
     "gmpi_selftest_division_launch",
     "gmpi_stream_probe_launch",
     "gmpi_query",
@@ -260,6 +262,13 @@ def load_library():
     lib.gmpi_alpha_depth_backward_ex_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                                                         vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
+    lib.gmpi_ramp_depth_launch.restype = ctypes.c_int
+    lib.gmpi_ramp_depth_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(GmpiDepthAlpha), vp,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
+    lib.gmpi_ramp_depth_backward_launch.restype = ctypes.c_int
+    lib.gmpi_ramp_depth_backward_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(GmpiDepthAlpha), vp, vp, vp, vp,
+                                                    vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, vp]
     lib.gmpi_stream_probe_launch.restype = ctypes.c_int
     lib.gmpi_stream_probe_launch.argtypes = [vp, ctypes.c_uint64, vp, vp]
     lib.gmpi_selftest_division_launch.restype = ctypes.c_int

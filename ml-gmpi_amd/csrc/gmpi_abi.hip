@@ -195,16 +195,7 @@ __global__ __launch_bounds__(256) void alpha_depth_kernel(const T* __restrict__ 
     if (x >= W) return;
     const T* a = alpha + b * sb + y * sr + x;
     float Tr = 1.0f, Z = 0.0f;
-#pragma unroll 4
-    for (int k = 0; k < D; ++k) {
-        const float al = to_f32(a[k * sd]);
-        const float w = al * Tr;           // weights = alpha * cumprod[:-1]
-        const float wd = w * ds[k];
-        Z = Z + wd;                        // torch.sum(weights * plane_ds, dim=1)
-        float om = 1.0f - al;
-        om = om + 1e-10f;
-        Tr = Tr * om;
-    }
+    alpha_depth_composite(D, ds, [&](int k) { return to_f32(a[k * sd]); }, Tr, Z);   // (gmpi_shared.hpp: one text with ramp_depth_kernel)
     const int64_t o = (static_cast<int64_t>(b) * H + y) * W + x;
     depth[o] = Z;
     if (tout) tout[o] = Tr;
@@ -868,6 +859,7 @@ int gmpi_query(int32_t what) {
         case 25: return 1;  // the depth-alpha window forward (gmpi_mpi_render_depth_window_launch) is built in  (24: unused)
         case 26: case 27: case 28: return depth_window_query(what);
         case 30: return 1;  // the geometry backward of the shared-colour and depth-alpha layouts is built in  (29: unused)
+        case 32: return 1;  // compute_depth of the depth-alpha layout (gmpi_ramp_depth_launch, light_kernels.hip) is built in  (31: unused)
         default: return -1;
     }
 }

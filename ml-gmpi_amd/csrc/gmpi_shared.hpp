@@ -210,4 +210,54 @@ __device__ __forceinline__ XT depth_total_transmittance(const KParams& p, const 
     return t;
 }
 
+// ---- LightRenderer.compute_depth for one texel: the composite and its back-to-front sweep, ONE text each ------------------------------------------
+// Instances: alpha_depth_kernel (gmpi_abi.hip) and alpha_depth_backward_kernel (light_kernels.hip) hand in loads of alpha planes and a store per
+// plane; ramp_depth_kernel and ramp_depth_backward_kernel (light_kernels.hip) hand in the ramp of one depth texel held in a register and a masked
+// running sum.  alpha(k): the alpha of plane k; sink(k, v): what to do with dL/da_k.  ds: plane distances [D], wave-uniform.
+// Op order (with -ffp-contract=off, what the bit-equality with the oracle rests on): w = a T; Z += w d; om = (1 - a) + 1e-10; T *= om.
+template <typename AlphaF>
+__device__ __forceinline__ void alpha_depth_composite(int D, const float* __restrict__ ds, AlphaF alpha, float& Tr, float& Z) {
+#pragma unroll 4
+    for (int k = 0; k < D; ++k) {
+        const float al = alpha(k);
+        const float w = al * Tr;           // weights = alpha * cumprod[:-1]
+        const float wd = w * ds[k];
+        Z = Z + wd;                        // torch.sum(weights * plane_ds, dim=1)
+        float om = 1.0f - al;
+        om = om + 1e-10f;
+        Tr = Tr * om;
+    }
+}
+// dL/da_k = T_k q_k - S_k / om_k, q_k = g d_k, S_k = gT T_out + sum_{j>k} a_j T_j q_j, back to front from the forward's final transmittance (same
+// scheme as render_backward.hip: no cancellation behind opaque planes; T carried as mantissa x 2^exponent).  o: the texel's index in the three
+// [B,1,H,W] images t_final, g_depth, g_T, each of which may be nullptr.
+template <typename AlphaF, typename SinkF>
+__device__ __forceinline__ void alpha_depth_sweep(int D, const float* __restrict__ ds, const float* __restrict__ t_final, const float* __restrict__ g_depth,
+                                                  const float* __restrict__ g_T, int64_t o, AlphaF alpha, SinkF sink) {
+    const float g = g_depth ? g_depth[o] : 0.0f;
+    float tm = t_final ? t_final[o] : 0.0f;
+    int te = 0;
+    if (!(tm >= 1e-30f)) {  // missing or underflowed: rebuild front to back in the extended representation
+        tm = 1.0f;
+        for (int k = 0; k < D; ++k) {
+            tm *= (1.0f - alpha(k)) + 1e-10f;
+            te += __builtin_amdgcn_frexp_expf(tm);
+            tm = __builtin_amdgcn_frexp_mantf(tm);
+        }
+    }
+    float S = 0.0f;
+    if (g_T) S = g_T[o] * __builtin_amdgcn_ldexpf(tm, te);   // (below 1e-30 * |gT| the term flushes: T_out itself underflows)
+    for (int k = D - 1; k >= 0; --k) {
+        const float al = alpha(k);
+        const float om = (1.0f - al) + 1e-10f;
+        tm = tm / om;
+        te += __builtin_amdgcn_frexp_expf(tm);
+        tm = __builtin_amdgcn_frexp_mantf(tm);
+        const float Tk = __builtin_amdgcn_ldexpf(tm, te);
+        const float q = g * ds[k];
+        sink(k, Tk * q - S / om);
+        S += al * Tk * q;
+    }
+}
+
 }  // namespace gmpi

@@ -7,6 +7,7 @@
 //   light_apply_kernel    = clip(rgb * shading, 0, 1), alpha passed through, over the whole volume (:193-198).
 // The first two work on B*H*W images (tiny); the third streams the RGBA volume once (read + write).
 #include "gmpi_device.hpp"
+#include "gmpi_shared.hpp"
 
 #include "../../include/gmpi_render.h"
 
@@ -165,30 +166,45 @@ __global__ __launch_bounds__(256) void alpha_depth_backward_kernel(const T* __re
     const T* __restrict__ a = alpha + b * sb + static_cast<int64_t>(y) * sr + x;
     float* __restrict__ ga = g_alpha + b * gb + static_cast<int64_t>(y) * gr + x;
     const int64_t o = (static_cast<int64_t>(b) * H + y) * W + x;
-    const float g = g_depth ? g_depth[o] : 0.0f;
-    float tm = t_final ? t_final[o] : 0.0f;
-    int te = 0;
-    if (!(tm >= 1e-30f)) {  // missing or underflowed: rebuild front to back in the extended representation
-        tm = 1.0f;
-        for (int k = 0; k < D; ++k) {
-            tm *= (1.0f - to_f32(a[k * sd])) + 1e-10f;
-            te += __builtin_amdgcn_frexp_expf(tm);
-            tm = __builtin_amdgcn_frexp_mantf(tm);
-        }
-    }
-    float S = 0.0f;
-    if (g_T) S = g_T[o] * __builtin_amdgcn_ldexpf(tm, te);   // (below 1e-30 * |gT| the term flushes: T_out itself underflows)
-    for (int k = D - 1; k >= 0; --k) {
-        const float al = to_f32(a[k * sd]);
-        const float om = (1.0f - al) + 1e-10f;
-        tm = tm / om;
-        te += __builtin_amdgcn_frexp_expf(tm);
-        tm = __builtin_amdgcn_frexp_mantf(tm);
-        const float Tk = __builtin_amdgcn_ldexpf(tm, te);
-        const float q = g * ds[k];
-        ga[k * gd] += Tk * q - S / om;
-        S += al * Tk * q;
-    }
+    alpha_depth_sweep(D, ds, t_final, g_depth, g_T, o, [&](int k) { return to_f32(a[k * sd]); }, [&](int k, float v) { ga[k * gd] += v; });
+}
+
+// ---- the same two passes for a depth-alpha MPI (GmpiDepthAlpha; depth_alpha.py): a_k is the ramp of plane_z[k] minus ONE depth texel, so the alpha
+// planes are never read or written -- the texel sits in a register and the plane loop is register work (plane_z, plane_ds: wave-uniform reads).
+// The ramp is depth_ramp (gmpi_shared.hpp) through the rounded reciprocal, which gives the IEEE quotient: the bits of alpha_depth_kernel on
+// depth_alpha_planes(...).
+template <typename T>
+__global__ __launch_bounds__(256) void ramp_depth_kernel(const T* __restrict__ image, int64_t sb, int64_t sr, DepthK dk, const float* __restrict__ ds,
+                                                         int D, int H, int W, float* __restrict__ depth, float* __restrict__ tout) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= W) return;
+    const float d = to_f32(image[b * sb + static_cast<int64_t>(y) * sr + x]);
+    const float* __restrict__ pz = dk.plane_z + b * dk.pz_stride;
+    float Tr = 1.0f, Z = 0.0f;
+    alpha_depth_composite(D, ds, [&](int k) { bool inside; return depth_ramp<false>(pz[k], d, dk, inside); }, Tr, Z);
+    const int64_t o = (static_cast<int64_t>(b) * H + y) * W + x;
+    depth[o] = Z;
+    if (tout) tout[o] = Tr;
+}
+
+// d a_k / d depth = -1 / den where lo <= plane_z[k] - depth <= hi (bounds included: where torch.clamp passes a gradient), 0 elsewhere -- a NaN texel
+// included.  One thread owns its texel: the sum over the planes is a register, ADDED to g_image by a plain load, add and store.
+template <typename T>
+__global__ __launch_bounds__(256) void ramp_depth_backward_kernel(const T* __restrict__ image, int64_t sb, int64_t sr, DepthK dk,
+                                                                  const float* __restrict__ ds, const float* __restrict__ t_final,
+                                                                  const float* __restrict__ g_depth, const float* __restrict__ g_T,
+                                                                  float* __restrict__ g_image, int64_t gb, int64_t gr, int D, int H, int W) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= W) return;
+    const float d = to_f32(image[b * sb + static_cast<int64_t>(y) * sr + x]);
+    const float* __restrict__ pz = dk.plane_z + b * dk.pz_stride;
+    const int64_t o = (static_cast<int64_t>(b) * H + y) * W + x;
+    bool inside = false;
+    float acc = 0.0f;
+    alpha_depth_sweep(D, ds, t_final, g_depth, g_T, o, [&](int k) { return depth_ramp<false>(pz[k], d, dk, inside); },
+                      [&](int, float v) { acc += inside ? v : 0.0f; });
+    float* __restrict__ gi = g_image + b * gb + static_cast<int64_t>(y) * gr + x;
+    *gi += -acc / dk.den;
 }
 
 static int rc_of(hipError_t e) { return e == hipSuccess ? GMPI_OK : GMPI_E_LAUNCH - static_cast<int>(e); }
@@ -284,6 +300,60 @@ int gmpi_alpha_depth_backward_launch(const void* alpha, int32_t alpha_dtype, int
     if (B > 0 && D > 0 && H > 0 && W > 0 && !grad_depth) return GMPI_E_NULL;
     return gmpi_alpha_depth_backward_ex_launch(alpha, alpha_dtype, stride_b, stride_d, stride_row, plane_ds, transmittance, grad_depth, nullptr,
                                                grad_alpha, gstride_b, gstride_d, gstride_row, B, D, H, W, stream);
+}
+
+// The checks the two ramp entries share, all before any launch; fills DepthK as the depth-alpha launchers fill it (to_depth, gmpi_abi.hip).
+// GMPI_OK with B == 0 means: nothing to do.
+static int to_ramp(const void* depth_image, int32_t depth_dtype, int64_t stride_b, int64_t stride_row, const GmpiDepthAlpha* ramp, const float* plane_ds,
+                   int32_t B, int32_t D, int32_t H, int32_t W, DepthK& dk) {
+    if (B < 0 || D <= 0 || H <= 0 || W <= 0 || B > 65535 || H > 65535) return GMPI_E_SHAPE;   // (rows and images are grid.y and grid.z)
+    if (B == 0) return GMPI_OK;
+    if (!depth_image || !ramp || !plane_ds) return GMPI_E_NULL;
+    if (ramp->struct_size != sizeof(GmpiDepthAlpha)) return GMPI_E_ABI;
+    if (!ramp->plane_z) return GMPI_E_NULL;
+    if (depth_dtype < GMPI_DTYPE_F32 || depth_dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
+    if (ramp->plane_z_stride < 0 || stride_b < 0 || stride_row < W) return GMPI_E_STRIDE;
+    if (!(ramp->z_lo < ramp->z_hi) || !(ramp->z_den > 0.0f)) return GMPI_E_SHAPE;
+    dk.plane_z = ramp->plane_z, dk.pz_stride = ramp->plane_z_stride;
+    dk.lo = ramp->z_lo, dk.hi = ramp->z_hi, dk.den = ramp->z_den, dk.rden = 1.0f / ramp->z_den;
+    return GMPI_OK;
+}
+
+int gmpi_ramp_depth_launch(const void* depth_image, int32_t depth_dtype, int64_t stride_b, int64_t stride_row, const GmpiDepthAlpha* ramp,
+                           const float* plane_ds, int32_t B, int32_t D, int32_t H, int32_t W, float* depth_out, float* transmittance_out,
+                           void* stream) {
+    DepthK dk;
+    const int rc = to_ramp(depth_image, depth_dtype, stride_b, stride_row, ramp, plane_ds, B, D, H, W, dk);
+    if (rc != GMPI_OK || B == 0) return rc;
+    if (!depth_out) return GMPI_E_NULL;
+    const dim3 grid((W + 255) / 256, H, B), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    dispatch_dtype(depth_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(ramp_depth_kernel<T>, grid, block, 0, st, static_cast<const T*>(depth_image), stride_b, stride_row, dk, plane_ds, D, H, W, depth_out,
+                           transmittance_out);
+    });
+    return rc_of(hipGetLastError());
+}
+
+int gmpi_ramp_depth_backward_launch(const void* depth_image, int32_t depth_dtype, int64_t stride_b, int64_t stride_row, const GmpiDepthAlpha* ramp,
+                                    const float* plane_ds, const float* transmittance, const float* grad_depth, const float* grad_transmittance,
+                                    float* grad_depth_image, int64_t gstride_b, int64_t gstride_row, int32_t B, int32_t D, int32_t H, int32_t W,
+                                    void* stream) {
+    DepthK dk;
+    const int rc = to_ramp(depth_image, depth_dtype, stride_b, stride_row, ramp, plane_ds, B, D, H, W, dk);
+    if (rc != GMPI_OK || B == 0) return rc;
+    if (!grad_depth_image) return GMPI_E_NULL;
+    if (gstride_b <= 0 || gstride_row < W) return GMPI_E_STRIDE;
+    if (!grad_depth && !grad_transmittance) return GMPI_OK;   // (nothing to add)
+    const dim3 grid((W + 255) / 256, H, B), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    dispatch_dtype(depth_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(ramp_depth_backward_kernel<T>, grid, block, 0, st, static_cast<const T*>(depth_image), stride_b, stride_row, dk, plane_ds, transmittance,
+                           grad_depth, grad_transmittance, grad_depth_image, gstride_b, gstride_row, D, H, W);
+    });
+    return rc_of(hipGetLastError());
 }
 
 }  // extern "C"

@@ -23,11 +23,16 @@ def ramp_constants(z_lo: float, z_hi: float) -> Tuple[float, float, float]:
     return float(np.float32(z_lo)), float(np.float32(z_hi)), float(np.float32(float(z_hi) - float(z_lo) + 1e-8))
 
 
-def _check(rgb: torch.Tensor, depth: torch.Tensor, plane_z: torch.Tensor, background: Optional[torch.Tensor]) -> None:
+def _check_depth(depth: torch.Tensor, plane_z: torch.Tensor) -> None:
     assert depth.ndim == 4 and depth.shape[1] == 1, f"Expected depth of shape (#mpi, 1, h, w), got {tuple(depth.shape)}"
+    M = depth.shape[0]
+    assert plane_z.ndim == 1 or (plane_z.ndim == 2 and plane_z.shape[0] == M), f"Expected plane_z of shape (#planes,) or ({M}, #planes), got {tuple(plane_z.shape)}"
+
+
+def _check(rgb: torch.Tensor, depth: torch.Tensor, plane_z: torch.Tensor, background: Optional[torch.Tensor]) -> None:
+    _check_depth(depth, plane_z)
     M, _, Ht, Wt = depth.shape
     assert tuple(rgb.shape) == (M, 3, Ht, Wt), f"Expected rgb of shape {(M, 3, Ht, Wt)}, got {tuple(rgb.shape)}"
-    assert plane_z.ndim == 1 or (plane_z.ndim == 2 and plane_z.shape[0] == M), f"Expected plane_z of shape (#planes,) or ({M}, #planes), got {tuple(plane_z.shape)}"
     if background is not None:
         assert tuple(background.shape) == (M, 3, Ht, Wt), f"Expected background of shape {(M, 3, Ht, Wt)}, got {tuple(background.shape)}"
 

@@ -9,6 +9,9 @@ point cloud -> normals -> Lambert shading per texel, and `clip(rgb * shading, 0,
 The reference applies the augmentation inside the G-step (train.py:535-541): when the volume requires grad the same
 kernels run under a `torch.autograd.Function` whose backward uses two more streaming kernels for the volume-sized ops
 (clip(rgb*shading) and the alpha compositing of the depth) and torch autograd for the B*H*W middle (blur, normals, Lambert).
+
+`render_shared` and `render_depth` are the augmentation for the shared-colour and the depth-alpha layout: there the shaded MPI is an MPI of
+the same layout, and only the expected depth needs a kernel (`compute_depth`; `compute_depth_ramp`, which reads one depth image and no planes).
 """
 import ctypes
 
@@ -17,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, poses
-from .hip_mpi import _DTYPES, _call, _ptr, _refuse_uint8
+from .hip_mpi import _DTYPES, _call, _depth_alpha, _ptr, _refuse_uint8
 
 EPS = 1e-8  # light_renderer.py:8
 
@@ -95,6 +98,89 @@ class _DepthFunction(torch.autograd.Function):
               alpha.stride(3), ds.data_ptr(), T.data_ptr(), _ptr(g_depth), _ptr(g_T), grad.data_ptr(), grad.stride(0), grad.stride(1),
               grad.stride(3), B, D, H, W)
         return grad.to(ctx.in_dtype), None
+
+
+def compute_depth_ramp(depth: torch.Tensor, plane_z: torch.Tensor, z_lo: float, z_hi: float, plane_ds: torch.Tensor,
+                       want_transmittance: bool = False):
+    """`compute_depth` for a depth-alpha MPI, without the alpha planes: depth [B,1,H,W] (any float storage dtype; may be a strided view such as
+    channel 3 of an RGB-D tensor or an expanded batch), plane_z [D] or [B,D], the ramp's bounds as `depth_alpha_planes` takes them, plane_ds [D]
+    or [D,1] metric plane distances -> expected depth [B,1,H,W] (float32) [, transmittance [B,1,H,W]].
+
+    By definition `compute_depth(depth_alpha_planes(depth, plane_z, z_lo, z_hi), plane_ds, ...)`, bit for bit (gmpi_ramp_depth_launch: the texel
+    is held in a register, the [B,D,1,H,W] planes are never built).  Differentiable w.r.t. depth through both outputs
+    (gmpi_ramp_depth_backward_launch); plane_z, plane_ds and the bounds get no gradient."""
+    from .depth_alpha import _check_depth
+    _refuse_uint8("compute_depth_ramp", depth)
+    _check_depth(depth, plane_z)
+    if torch.is_grad_enabled():
+        for name, v in (("plane_z", plane_z), ("plane_ds", plane_ds), ("z_lo", z_lo), ("z_hi", z_hi)):
+            if isinstance(v, torch.Tensor) and v.requires_grad:
+                raise NotImplementedError(f"compute_depth_ramp provides no gradient w.r.t. {name}")
+    if not depth.is_cuda:
+        raise _lib.GmpiError("compute_depth_ramp needs tensors on a ROCm device (no CPU path)")
+    z_lo, z_hi = float(z_lo), float(z_hi)
+    if torch.is_grad_enabled() and depth.requires_grad:
+        out, T = _RampDepthFunction.apply(depth, plane_z, plane_ds, z_lo, z_hi)
+    else:
+        with torch.no_grad():
+            out, T = _ramp_depth(_ramp_operands(depth, plane_z, plane_ds), z_lo, z_hi, want_transmittance)
+    return (out, T) if want_transmittance else out
+
+
+def _ramp_operands(depth: torch.Tensor, plane_z: torch.Tensor, plane_ds: torch.Tensor):
+    """What the ramp entries read: the depth image in a storage dtype they take (innermost stride 1, rows that do not overlap, no negative stride:
+    such views are passed as they are), plane_z [D] or [B,D] and plane_ds [D] in fp32 on its device."""
+    if depth.dtype not in _DTYPES:
+        depth = depth.float()
+    if depth.stride(3) != 1 or depth.stride(0) < 0 or depth.stride(2) < depth.shape[3]:
+        depth = depth.contiguous()
+    pz = plane_z.detach().to(depth.device, torch.float32).contiguous()
+    ds = plane_ds.detach().reshape(-1).to(depth.device, torch.float32).contiguous()
+    assert ds.numel() == pz.shape[-1], f"{tuple(ds.shape)}, {tuple(pz.shape)}"
+    return depth, pz, ds
+
+
+def _ramp_depth(operands, z_lo: float, z_hi: float, want_transmittance: bool):
+    """gmpi_ramp_depth_launch -> (depth, T or None), both float32 [B,1,H,W]."""
+    image, pz, ds = operands
+    B, _, H, W = image.shape
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device)
+    T = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device) if want_transmittance else None
+    ramp = _depth_alpha(pz, z_lo, z_hi)
+    _call("gmpi_ramp_depth_launch", image.device, image.data_ptr(), _DTYPES[image.dtype], image.stride(0), image.stride(2), ctypes.byref(ramp),
+          ds.data_ptr(), B, pz.shape[-1], H, W, out.data_ptr(), _ptr(T))
+    return out, T
+
+
+class _RampDepthFunction(torch.autograd.Function):
+    """autograd bridge of compute_depth_ramp, as _DepthFunction: forward = gmpi_ramp_depth_launch (T always, kept for the backward's sweep),
+    backward = gmpi_ramp_depth_backward_launch into a zero-filled fp32 image.  An output the loss does not use arrives as None and is passed as
+    NULL."""
+
+    @staticmethod
+    def forward(ctx, depth, plane_z, plane_ds, z_lo, z_hi):
+        operands = _ramp_operands(depth.detach(), plane_z, plane_ds)
+        out, T = _ramp_depth(operands, z_lo, z_hi, True)
+        ctx.save_for_backward(*operands, T)
+        ctx.misc = (z_lo, z_hi, depth.dtype)
+        ctx.set_materialize_grads(False)
+        return out, T
+
+    @staticmethod
+    def backward(ctx, g_depth, g_T):
+        image, pz, ds, T = ctx.saved_tensors
+        z_lo, z_hi, in_dtype = ctx.misc
+        if not ctx.needs_input_grad[0] or (g_depth is None and g_T is None):
+            return None, None, None, None, None
+        B, _, H, W = image.shape
+        dev = image.device
+        g_depth = None if g_depth is None else g_depth.to(torch.float32).contiguous()
+        g_T = None if g_T is None else g_T.to(torch.float32).contiguous()
+        grad = torch.zeros((B, 1, H, W), dtype=torch.float32, device=dev)
+        ramp = _depth_alpha(pz, z_lo, z_hi)
+        _call("gmpi_ramp_depth_backward_launch", dev, image.data_ptr(), _DTYPES[image.dtype], image.stride(0), image.stride(2), ctypes.byref(ramp),
+              ds.data_ptr(), T.data_ptr(), _ptr(g_depth), _ptr(g_T), grad.data_ptr(), grad.stride(0), grad.stride(2), B, pz.shape[-1], H, W)
+        return grad.to(in_dtype), None, None, None, None
 
 
 def gaussian_kernel1d(ksize: int, sigma: float) -> torch.Tensor:
@@ -260,13 +346,39 @@ class LightRenderer:
         dev = alpha.device
         light_direction = self._next_light(alpha.shape[0])
         plane_ds = mpi_plane_dhws[:, :1].detach().to(dev)
-        xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach().to(dev, torch.float32)
-        H, W = alpha.shape[-2:]
         depth = compute_depth(alpha, plane_ds)                                                      # [B,1,H,W] float32
+        shade = self._shade_images(depth, mpi_tex_pix_xyz, light_direction)
+        return shade(rgb), alpha, (None if background is None else shade(background))
+
+    def render_depth(self, rgb: torch.Tensor, depth: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, *,
+                     plane_z: torch.Tensor, z_range: float, n_z_bins: int, background: torch.Tensor = None):
+        """`render` for a depth-alpha MPI (rgb [B,3,H,W], depth [B,1,H,W], plane_z [D] or [B,D], background [B,3,H,W] or None; the ramp's bounds
+        are `depth_alpha_bounds(z_range, n_z_bins)`): the shading is one value per texel and multiplies the colour images, so the shaded MPI is a
+        depth-alpha MPI again -- (clip(rgb * shading, 0, 1), depth, clip(background * shading, 0, 1) or None), colours in float32, the depth
+        image as it was handed in.  Equal to `render(expand_depth_alpha(rgb, depth, plane_z, z_lo, z_hi, background))` read back as such an MPI;
+        the step counter, cur_ka / cur_kd and the torch RNG advance as in `render`.  The expected depth comes from the differentiable
+        `compute_depth_ramp` kernel (no alpha planes), the rest is image-sized torch: differentiable w.r.t. rgb, depth and background."""
+        from .depth_alpha import _check, depth_alpha_bounds
+        _refuse_uint8("LightRenderer.render_depth", rgb, depth, background)
+        if not depth.is_cuda:
+            raise _lib.GmpiError("LightRenderer.render_depth needs tensors on a ROCm device (no CPU path)")
+        _check(rgb, depth, plane_z, background)
+        z_lo, z_hi = depth_alpha_bounds(z_range, n_z_bins)
+        light_direction = self._next_light(depth.shape[0])
+        plane_ds = mpi_plane_dhws[:, :1].detach().to(depth.device)
+        z = compute_depth_ramp(depth, plane_z, z_lo, z_hi, plane_ds)                                # [B,1,H,W] float32
+        shade = self._shade_images(z, mpi_tex_pix_xyz, light_direction)
+        return shade(rgb), depth, (None if background is None else shade(background))
+
+    def _shade_images(self, depth: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, light_direction: torch.Tensor):
+        """The image-sized middle of the augmentation in torch (blur, point cloud, normals, Lambert), shared by `render_shared` and
+        `render_depth`: expected depth [B,1,H,W] fp32 -> the function colour image -> clip(image * shading, 0, 1) in float32."""
+        dev = depth.device
+        H, W = depth.shape[-2:]
+        xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach().to(dev, torch.float32)
         blurred = _blur_torch(depth, _blur_matrix(H, self._k1d, dev), _blur_matrix(W, self._k1d, dev))
         shading = _shading_torch(blurred, xyz_last, light_direction.to(dev, torch.float32), self.cur_ka, self.cur_kd).unsqueeze(1)   # [B,1,H,W]
-        shade = lambda c: torch.clip(c.to(torch.float32) * shading, min=0.0, max=1.0)
-        return shade(rgb), alpha, (None if background is None else shade(background))
+        return lambda c: torch.clip(c.to(torch.float32) * shading, min=0.0, max=1.0)
 
     def _next_light(self, B: int) -> torch.Tensor:
         """One step of the augmentation's schedule: advances `step`, draws the light position on the sphere (consumes the torch RNG exactly as
