@@ -7,11 +7,11 @@
 //   BwdPixel / bwd_pixel_setup(_with)   the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
-//   tile_box                        texel box of a pixel tile on one plane, from its four corner pixels
 //   cvt_rpi_i32, fix_split, to_fix, abs_bits, lds_barrier, wave_max_u32, wave_max_bits     the fixed-point and wave primitives of the staged scatters
 //   the cross-plane tile frame      what shared_tile and depth_tile stage their cross-plane sums with: the tile constants (kTileW .. kTilePlanes, kCW, kCH),
 //                                   TileFrame / tile_frame / tile_frame_box / tile_grid, FixScale / fix_scale, lds_add_taps, MovingWindow and its flush
-//                                   (their tap prefetch, fetch_taps, knows the shared-colour structs and lives in gmpi_shared.hpp)
+//                                   (their tap prefetch, fetch_taps, knows the shared-colour structs and lives in gmpi_shared.hpp; this lane's pixel, the
+//                                   corner pixels and tile_box are the forward's, gmpi_device.hpp; render_depth_window.hip, a forward, borrows the constants)
 // A change to the sweep or to the frame is made here, never in a kernel.
 #pragma once
 #include "gmpi_device.hpp"
@@ -224,40 +224,6 @@ __device__ __forceinline__ void pair_samples(const PairTaps& q, int Ht, int Wt, 
     }
 }
 
-// ---- texel box of a pixel tile on one plane ---------------------------------------------------------------------------------------------------
-// The tile's corner pixels (cx0, cy0), (cx1, cy0), (cx0, cy1), (cx1, cy1) map to (cix, ciy)[0..3] (the forward's chain; rdv = the view's rays); a
-// pinhole ray field maps pixel lines to lines, so every tap of the tile lies in the box of those images grown by 1/64 texel + the 2 x 2 support.
-// Returns (bx0, by0, nx, ny); nx = 0: not staged -- the images are not finite (all four fields 0) or the box exceeds pitch x rows.
-template <bool AC>
-__device__ __forceinline__ int4 tile_box(const KParams& p, const BwdView& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0,
-                                         int cx1, int cy0, int cy1, int pitch, int rows, float (&cix)[4], float (&ciy)[4]) {
-    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-    bool finite = true;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * p.W + ((c & 1) ? cx1 : cx0);
-        float ix, iy, s, u, v;
-        plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[vw.HW + q], rdv[2 * vw.HW + q], vw.cx, vw.cy, ix, iy, s, u, v);
-        finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);
-        mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-        cix[c] = ix, ciy[c] = iy;
-    }
-    int4 bb = make_int4(0, 0, 0, 0);
-    if (finite) {
-        const float eps = 1.0f / 64;
-        bb.x = static_cast<int>(floorf(mnx - eps)), bb.y = static_cast<int>(floorf(mny - eps));
-        bb.z = static_cast<int>(floorf(mxx + eps)) + 2 - bb.x, bb.w = static_cast<int>(floorf(mxy + eps)) + 2 - bb.y;
-        if (bb.z > pitch || bb.w > rows) bb.z = 0;
-    }
-    return bb;
-}
-template <bool AC>
-__device__ __forceinline__ int4 tile_box(const KParams& p, const BwdView& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0,
-                                         int cx1, int cy0, int cy1, int pitch, int rows) {
-    float cix[4], ciy[4];
-    return tile_box<AC>(p, vw, rdv, zdiff, ph, pw, cx0, cx1, cy0, cy1, pitch, rows, cix, ciy);
-}
-
 // ---- primitives of the staged (fixed-point, LDS) scatters ---------------------------------------------------------------------------------------
 // round to nearest (floor(x + 0.5)) in one instruction: the staged sums must not be biased -- with a texture much coarser than the image a hundred
 // taps meet in one texel, and a truncating conversion adds up to half a unit of the fixed-point grid PER TAP in one direction
@@ -320,24 +286,14 @@ constexpr int kFixBits = 40;           // a staged term is scaled to below 2^41 
 inline bool tile_planes_fit(const KParams& p) { return p.D <= kTilePlanes; }
 
 // The tile and the pixel of this lane.  tile < 0: the workgroup is one of the grid's padding (the grid is a multiple of 8) and returns as a whole.
-struct TileFrame {
+struct TileFrame : TileLane, TileCorners {   // this lane's pixel and the tile's corner pixels (gmpi_device.hpp: the forward's)
     int tile, txi, tyi;
-    int px, py;               // this lane's pixel
-    bool active;              // ... lies inside the image
-    int cx0, cx1, cy0, cy1;   // the tile's corner pixels, clamped into the image
 };
 __device__ __forceinline__ TileFrame tile_frame(const KParams& p, int tiles_x) {
-    TileFrame t;
-    const int tid = threadIdx.x;
     const int n_tiles = tiles_x * ((p.H + kTileH - 1) / kTileH);
     const int tile = xcd_item_per_group(static_cast<int>(blockIdx.x), n_tiles, n_tiles);
-    t.tile = tile >= n_tiles ? -1 : tile;
-    t.tyi = tile / tiles_x, t.txi = tile - t.tyi * tiles_x;
-    t.px = t.txi * kTileW + (tid % kTileW), t.py = t.tyi * kTileH + (tid / kTileW);
-    t.active = t.px < p.W && t.py < p.H;
-    t.cx0 = t.txi * kTileW, t.cx1 = min(t.cx0 + kTileW - 1, p.W - 1);
-    t.cy0 = t.tyi * kTileH, t.cy1 = min(t.cy0 + kTileH - 1, p.H - 1);
-    return t;
+    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+    return TileFrame{tile_lane<kTileW, kTileH>(txi, tyi, threadIdx.x, p.W, p.H), tile_corners<kTileW, kTileH>(txi, tyi, p.W, p.H), tile >= n_tiles ? -1 : tile, txi, tyi};
 }
 // the tile's texel box on plane k of the view; staged (nx > 0) when it fits pitch x rows
 template <bool AC>

@@ -385,7 +385,9 @@ __device__ __forceinline__ void gather_sample(const TexT* __restrict__ pl, int64
 }
 
 // ---- the forward's frame: what every render kernel does around its plane loop.  A change here reaches all of them, and
-//      the backward sweeps (gmpi_backward.hpp), which read the same view constants and the same dot product. -----------------------------------
+//      the backward sweeps (gmpi_backward.hpp), which read the same view constants and the same dot product.  View / view_setup, check_camera_behind,
+//      ray_dot, last_plane / leaves_last_plane, gather_plane, store_pixel; then the tile frame of the staged tile kernels: view_group_items, fwd_tile_id /
+//      fwd_tile / fwd_tile_grid, tile_lane / tile_corners, corner_extent / item_box / tile_box, origin_words / origin_rsrc. ---------------------------
 // What is uniform over view n.  Everything is forced inline: a field a kernel does not read costs it nothing.
 struct View {
     int m;                          // the MPI the view samples
@@ -480,6 +482,118 @@ __device__ __forceinline__ void store_pixel(const KParams& p, int n, int64_t HW,
         p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
         if (p.T_out) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
     }
+}
+
+// ---- the tile frame: a workgroup of TW x TH lanes owns a TW x TH pixel tile, one pixel per lane, and stages per plane the texel box spanned by the
+//      tile's four corner pixels (render_lds.hip has the why).  ONE text for the four forward tile kernels (render_lds, render_u8, render_shared_forward,
+//      render_depth_window) and, through tile_lane / tile_corners / tile_box, for the tile backwards (gmpi_backward.hpp, render_backward.hip). ---------
+// Work items of one group of views that share an MPI (xcd_item_per_group's group_items), `per_view` items per view.
+inline __host__ __device__ int view_group_items(const KParams& p, int per_view) { return per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1); }
+
+// blockIdx -> tile id: every XCD gets a contiguous run of the tiles of every group of views that share an MPI; n_tiles and above: a padding workgroup.
+__device__ __forceinline__ int fwd_tile_id(const KParams& p, int block, int tiles_x, int tiles_y, int n_tiles, int rot = 0, int split = 1) {
+    return xcd_item_per_group(block, view_group_items(p, tiles_x * tiles_y), n_tiles, rot, split);
+}
+// tile id -> view n, position `rem` inside the view (0: the tile that runs check_camera_behind), tile column and row; views that share one MPI are
+// interleaved per tile position (item_to_view).  false: a padding workgroup, which returns as a whole.
+struct FwdTile { int n, rem, txi, tyi; };
+__device__ __forceinline__ bool fwd_tile(const KParams& p, int tile_id, int tiles_x, int tiles_y, int n_tiles, FwdTile& t) {
+    if (tile_id >= n_tiles) return false;
+    item_to_view(p, tile_id, tiles_x * tiles_y, t.n, t.rem);
+    t.tyi = t.rem / tiles_x, t.txi = t.rem - t.tyi * tiles_x;
+    return true;
+}
+// host side: what fwd_tile_id expects of the launch
+struct FwdTileGrid { int tiles_x, tiles_y, n_tiles; dim3 grid; };
+template <int TW, int TH>
+inline FwdTileGrid fwd_tile_grid(const KParams& p) {
+    const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH, n_tiles = tiles_x * tiles_y * p.N;
+    return FwdTileGrid{tiles_x, tiles_y, n_tiles, dim3(xcd_grid_per_group(view_group_items(p, tiles_x * tiles_y), n_tiles))};
+}
+
+// The pixel of lane `lane` of tile (txi, tyi): lanes outside the image shadow the last row / column (pix is clamped, `active` says so).
+struct TileLane { int px, py; bool active; int64_t pix; };
+template <int TW, int TH>
+__device__ __forceinline__ TileLane tile_lane(int txi, int tyi, int lane, int W, int H) {
+    TileLane l;
+    l.px = txi * TW + (lane % TW), l.py = tyi * TH + (lane / TW);
+    l.active = l.px < W && l.py < H;
+    l.pix = static_cast<int64_t>(min(l.py, H - 1)) * W + min(l.px, W - 1);
+    return l;
+}
+// The tile's corner pixels, clamped into the image.
+struct TileCorners { int cx0, cx1, cy0, cy1; };
+template <int TW, int TH>
+__device__ __forceinline__ TileCorners tile_corners(int txi, int tyi, int W, int H) {
+    const int cx0 = txi * TW, cy0 = tyi * TH;
+    return TileCorners{cx0, min(cx0 + TW - 1, W - 1), cy0, min(cy0 + TH - 1, H - 1)};
+}
+
+// The pixels (cx0, cy0), (cx1, cy0), (cx0, cy1), (cx1, cy1) map to (cix, ciy)[0..3] on one plane (the exact chain; rdv = the view's rays): their extent,
+// and whether all of them are finite (below 1e6: false for NaN too).  A pinhole ray field maps pixel lines to lines, so every tap of the pixel rectangle
+// lies in that extent grown by the 2 x 2 support.
+struct CornerExtent { float mnx, mxx, mny, mxy; bool finite; };
+template <bool AC>
+__device__ __forceinline__ CornerExtent corner_extent(const View& vw, const float* __restrict__ rdv, int W, float zdiff, float ph, float pw, int cx0, int cx1,
+                                                      int cy0, int cy1, float (&cix)[4], float (&ciy)[4]) {
+    CornerExtent e{__builtin_inff(), -__builtin_inff(), __builtin_inff(), -__builtin_inff(), true};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * W + ((c & 1) ? cx1 : cx0);
+        float s, u, v;
+        plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[vw.HW + q], rdv[2 * vw.HW + q], vw.cx, vw.cy, cix[c], ciy[c], s, u, v);
+        e.finite = e.finite && (fabsf(cix[c]) < 1e6f) && (fabsf(ciy[c]) < 1e6f);
+        e.mnx = fminf(e.mnx, cix[c]), e.mxx = fmaxf(e.mxx, cix[c]), e.mny = fminf(e.mny, ciy[c]), e.mxy = fmaxf(e.mxy, ciy[c]);
+    }
+    return e;
+}
+template <bool AC>
+__device__ __forceinline__ CornerExtent corner_extent(const View& vw, const float* __restrict__ rdv, int W, float zdiff, float ph, float pw, int cx0, int cx1,
+                                                      int cy0, int cy1) {
+    float cix[4], ciy[4];
+    return corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, cx0, cx1, cy0, cy1, cix, ciy);
+}
+// Extent -> staged box (x0, y0, items per row, rows) in loader items of TPI texels: grown by kBoxSlack (the fp32 error of ix is < 1e-3 texel) and the
+// 2 x 2 support, x0 aligned down to an item.  `fits`: within max_cols items x max_rows rows; how "not staged" is written is the caller's.  An extent
+// that is not finite gives four zeros and does not fit.
+constexpr float kBoxSlack = 1.0f / 64;
+template <int TPI>
+__device__ __forceinline__ int4 item_box(const CornerExtent& e, int max_cols, int max_rows, bool& fits) {
+    int4 bb = make_int4(0, 0, 0, 0);
+    fits = false;
+    if (e.finite) {
+        const int bx0 = static_cast<int>(floorf(e.mnx - kBoxSlack)), bx1 = static_cast<int>(floorf(e.mxx + kBoxSlack)) + 1;   // first and last texel column
+        const int by0 = static_cast<int>(floorf(e.mny - kBoxSlack)), by1 = static_cast<int>(floorf(e.mxy + kBoxSlack)) + 1;
+        bb.x = bx0 & ~(TPI - 1), bb.y = by0;
+        bb.z = (bx1 - bb.x) / TPI + 1, bb.w = by1 - by0 + 1;
+        fits = bb.z <= max_cols && bb.w <= max_rows;
+    }
+    return bb;
+}
+// Texel box of a pixel tile on one plane, in texels: (bx0, by0, nx, ny); nx = 0: not staged -- the corner images are not finite (all four fields 0) or
+// the box exceeds pitch x rows.
+template <bool AC>
+__device__ __forceinline__ int4 tile_box(const KParams& p, const View& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0, int cx1,
+                                         int cy0, int cy1, int pitch, int rows, float (&cix)[4], float (&ciy)[4]) {
+    bool fits;
+    int4 bb = item_box<1>(corner_extent<AC>(vw, rdv, p.W, zdiff, ph, pw, cx0, cx1, cy0, cy1, cix, ciy), pitch, rows, fits);
+    if (!fits) bb.z = 0;
+    return bb;
+}
+template <bool AC>
+__device__ __forceinline__ int4 tile_box(const KParams& p, const View& vw, const float* __restrict__ rdv, float zdiff, float ph, float pw, int cx0, int cx1,
+                                         int cy0, int cy1, int pitch, int rows) {
+    float cix[4], ciy[4];
+    return tile_box<AC>(p, vw, rdv, zdiff, ph, pw, cx0, cx1, cy0, cy1, pitch, rows, cix, ciy);
+}
+
+// A box origin's address in the per-plane table: two words (48 bits) = words 0, 1 of the plane's raw-buffer descriptor; and the descriptor rebuilt from
+// them.  It must be PROVABLY wave-uniform or hipcc wraps every buffer op in a waterfall loop: its inputs go through readfirstlane.  num_records 2^31:
+// only the explicit out-of-range offset 0x80000000 is rejected (reads as zero without touching memory).
+__device__ __forceinline__ int2 origin_words(uint64_t a) { return make_int2(static_cast<int>(a & 0xffffffffu), static_cast<int>((a >> 32) & 0xffffu)); }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t origin_rsrc(int lo, int hi) {
+    const uint32_t b_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(lo)), b_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(hi));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((static_cast<uint64_t>(b_hi) << 32) | b_lo), 0, static_cast<int>(0x80000000u), 0x00020000);
 }
 
 // floor(x) as an integer in one instruction (v_cvt_flr_i32_f32); NaN -> 0, saturating

@@ -5,7 +5,7 @@
 //
 // The arithmetic is render_depth_kernel's (render_depth.hip), term for term: plane_coord, the last-plane test, make_taps, depth_ramp on the four depth
 // taps, bilerp, the `a != 0` skip, three colour samples, blend, store_pixel, report_status.  What differs is where the taps come from.  In this layout
-// all four channels are single images shared by every plane, so nothing new has to be read per plane: a tile's texel boxes (tile_box, gmpi_backward.hpp)
+// all four channels are single images shared by every plane, so nothing new has to be read per plane: a tile's texel boxes (tile_box, gmpi_device.hpp)
 // only drift by parallax, and one window of kCW x kCH texels (the tile backward's, here fp32 texels [row][channel][x]: 32 KiB) serves many planes.
 //
 // WINDOW.  When the next staged plane's box is not inside the window, the window is re-anchored with that box at the end it drifts away from (the
@@ -52,18 +52,15 @@ __global__ __launch_bounds__(kTileThreads) void render_depth_window_kernel(const
     __shared__ int wave_nan[kTileThreads / 64];
     __shared__ __attribute__((aligned(16))) float win[kCH * kWLine];
 
-    // ---- blockIdx -> tile, as render_shared_forward_kernel ----------------------------------------------------------------------------------------
+    // ---- blockIdx -> tile, this lane's pixel, the tile's corner pixels: the tile frame of gmpi_device.hpp -----------------------------------------
     const int tid = threadIdx.x;
-    const int tiles_per_view = tiles_x * tiles_y;
-    const int tile_id = xcd_item_per_group(static_cast<int>(blockIdx.x), tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles);
-    if (tile_id >= n_tiles) return;
-    int n, trem;
-    item_to_view(p, tile_id, tiles_per_view, n, trem);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
+    FwdTile ft;
+    if (!fwd_tile(p, fwd_tile_id(p, blockIdx.x, tiles_x, tiles_y, n_tiles), tiles_x, tiles_y, n_tiles, ft)) return;
+    const int n = ft.n;
 
     uint32_t bad = 0;
     const View vw = view_setup<AC>(p, n, bad);
-    check_camera_behind(p, vw, trem == 0 && tid == 0);   // once per view
+    check_camera_behind(p, vw, ft.rem == 0 && tid == 0);   // once per view
     const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
     const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
     const bool check_last = (p.flags & GMPI_FLAG_CHECK_LAST_PLANE) != 0;
@@ -74,14 +71,12 @@ __global__ __launch_bounds__(kTileThreads) void render_depth_window_kernel(const
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(vw.m) * sh.bs_mpi : nullptr;
     const float* __restrict__ pz = dk.plane_z + static_cast<int64_t>(vw.m) * dk.pz_stride;
 
-    // ---- this thread's pixel (out-of-image lanes shadow the last row / column) --------------------------------------------------------------------
-    const int px = txi * kTileW + (tid % kTileW), py = tyi * kTileH + (tid / kTileW);
-    const bool active = px < W && py < H;
-    const int64_t pix = static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
+    const TileLane tl = tile_lane<kTileW, kTileH>(ft.txi, ft.tyi, tid, W, H);
+    const int64_t pix = tl.pix;
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
-    const int cx0 = txi * kTileW, cx1 = min(cx0 + kTileW - 1, W - 1);
-    const int cy0 = tyi * kTileH, cy1 = min(cy0 + kTileH - 1, H - 1);
+    const TileCorners tc = tile_corners<kTileW, kTileH>(ft.txi, ft.tyi, W, H);
+    const int cx0 = tc.cx0, cx1 = tc.cx1, cy0 = tc.cy0, cy1 = tc.cy1;
     // tame: the ray's slopes lie between the four corner pixels' (a few ulp of tolerance: far below the box's 1/64 texel); false for NaN
     bool tame;
     {
@@ -255,7 +250,7 @@ __global__ __launch_bounds__(kTileThreads) void render_depth_window_kernel(const
             }
         }
     }
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active);
     report_status(p.status, bad);
 }
 
@@ -285,12 +280,10 @@ int depth_window_query(int what) {
 
 template <typename TexT>
 static hipError_t launch_depth_window_t(const KParams& p, const SharedK& sh, const DepthK& dk, hipStream_t stream) {
-    const int tiles_x = (p.W + kTileW - 1) / kTileW, tiles_y = (p.H + kTileH - 1) / kTileH;
-    const int n_tiles = tiles_x * tiles_y * p.N;
-    const dim3 grid(xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)), block(kTileThreads);
+    const FwdTileGrid tg = fwd_tile_grid<kTileW, kTileH>(p);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        hipLaunchKernelGGL((render_depth_window_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, sh, dk, tiles_x,
-                           tiles_y, n_tiles);
+        hipLaunchKernelGGL((render_depth_window_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), tg.grid, dim3(kTileThreads), 0, stream, p, sh, dk, tg.tiles_x,
+                           tg.tiles_y, tg.n_tiles);
     });
     return hipGetLastError();
 }

@@ -38,6 +38,7 @@
 // HBM traffic: each texel of the volume is read once per view (halo rows/columns are shared with the
 // neighbouring tiles through the XCD's L2: the blockIdx -> tile map gives every XCD a contiguous run
 // of tiles).  Algorithmic bytes: 16 B (fp32) / 8 B (bf16) per pixel*plane + 28-32 B per pixel.
+// The frame shared with the other tile forwards (tile -> view, pixel, corner box, origin words) is gmpi_device.hpp's.
 #include "gmpi_device.hpp"
 
 #include <cstdlib>
@@ -52,7 +53,6 @@ constexpr int kNT = 512;              // threads per workgroup (8 wavefronts)
 constexpr int kChunk = 96;            // planes per geometry-table refill
 constexpr int kRecBytes = 48;         // per-plane record: three 16-byte LDS broadcasts
 constexpr int kMaxStagedItems = 4;    // 16-byte items (4 VGPRs each) a thread may hold in flight: 80 VGPRs at 6 waves/SIMD
-constexpr float kBoxEps = 1.0f / 64;  // slack on the corner-derived box (fp32 error of ix is < 1e-3 texel)
 
 // Staging-buffer geometry per tile shape.  kPitch = floats per (row,channel) line in LDS (a multiple of 8: the texel-row
 // stride 4*kPitch floats is then a multiple of the 32 LDS banks, so taps of lanes on neighbouring texel rows do not
@@ -169,7 +169,6 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
 
     // ---- blockIdx -> tile: XCD x (blockIdx % 8) gets the contiguous run [x*per, (x+1)*per) of tiles, so
     //      neighbouring tiles (shared halo texels) meet in one L2 ------------------------------------------
-    const int tiles_per_view = tiles_x * tiles_y;
     const int per_xcd = (n_tiles + 7) / 8;
     int tile_id = (vblock % 8) * per_xcd + vblock / 8;
     if (vblock >= static_cast<unsigned>(per_xcd * 8)) tile_id = n_tiles;
@@ -179,19 +178,19 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
     //  * fp32 volumes: measured 1.5 % (config 3 shape) to 3.7 % (config 5) faster than one run per XCD, 16-bit volumes 1 % slower
     //    (profiles/r03_xcd_order.txt) -- so 16-bit volumes keep the run per XCD.
     if (p.gate != nullptr || sizeof(TexT) == 4)
-        tile_id = xcd_item_per_group(vblock, tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles, p.band_rot, p.band_split);
+        tile_id = fwd_tile_id(p, vblock, tiles_x, tiles_y, n_tiles, p.band_rot, p.band_split);
 #ifdef GMPI_TUNE  // (experiment: flag bit 19 flips the order)
     if (p.flags & (1u << 19)) {
         tile_id = (p.gate != nullptr || sizeof(TexT) == 4) ? (vblock % 8) * per_xcd + vblock / 8
-                                                           : xcd_item_per_group(vblock, tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles);
+                                                           : fwd_tile_id(p, vblock, tiles_x, tiles_y, n_tiles);
         if (vblock >= static_cast<unsigned>(per_xcd * 8) && (p.gate != nullptr || sizeof(TexT) == 4)) tile_id = n_tiles;
     }
 #endif
-    if (tile_id >= n_tiles) return;
-    int n, trem;
-    item_to_view(p, tile_id, tiles_per_view, n, trem);  // (views that share one MPI are interleaved per tile position)
+    // ---- the common tail: the tile frame of gmpi_device.hpp (tile -> view and position, this lane's pixel, the corner pixels) ----------------------
+    FwdTile ft;
+    if (!fwd_tile(p, tile_id, tiles_x, tiles_y, n_tiles, ft)) return;
+    const int n = ft.n;
     if (view_bits != nullptr ? ((view_bits[n >> 5] >> (n & 31)) & 1u) == 0u : view_gated_out(p, n)) return;  // (AUTO: this view is the band kernel's)
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
 
     const int tid = threadIdx.x;
     uint32_t bad = 0;
@@ -205,20 +204,17 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
     const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
     const int64_t s_chan = p.s_chan, s_row = p.s_row, s_plane = p.s_plane;
 
-    check_camera_behind(p, vw, trem == 0 && tid == 0);  // once per view
+    check_camera_behind(p, vw, ft.rem == 0 && tid == 0);  // once per view
 
-    // ---- this thread's pixel (out-of-image lanes shadow the last row/column) ---------------------------------
-    const int px = txi * TW + (tid % TW), py = tyi * TH + (tid / TW);
-    const bool active = px < W && py < H;
-    const int64_t pix = static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
+    const TileLane tl = tile_lane<TW, TH>(ft.txi, ft.tyi, tid, W, H);
+    const int64_t pix = tl.pix;
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
     const float rcp_rz = 1.0f / rz;  // correctly rounded; hoisted out of the plane loop (see div_by_recip)
     Accum A;
 
-    // ---- tile corner pixels (for the per-plane texel box) ----------------------------------------------------
-    const int cx0 = txi * TW, cx1 = min(cx0 + TW - 1, W - 1);
-    const int cy0 = tyi * TH, cy1 = min(cy0 + TH - 1, H - 1);
+    const TileCorners tc = tile_corners<TW, TH>(ft.txi, ft.tyi, W, H);
+    const int cy0 = tc.cy0, cy1 = tc.cy1;
 
     // ---- loader role, re-derived per chunk from the widest / tallest box of the chunk (set_loader_map below):
     //      thread -> item column `lcol` of the (row,channel) lines lrowc + perpass*r, r < npass <= kNL.  A frontal
@@ -258,39 +254,22 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
                 const int k = kc + t;
                 const float d = dhw[3 * k + 0], ph = dhw[3 * k + 1], pw = dhw[3 * k + 2];
                 const float zdiff = d - ez;
-                float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-                bool finite = true;
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int64_t q = static_cast<int64_t>((c & 2) ? y_hi : y_lo) * W + ((c & 1) ? cx1 : cx0);
-                    float ix, iy, s, u, v;
-                    plane_coord<AC>(zdiff, ph, pw, ex, ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], cx, cy, ix, iy, s, u, v);
-                    finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);  // false for NaN too
-                    mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-                }
-                int4 ri = make_int4(0, 0, -1, 0);  // qx0, by0, nq (< 0: does not fit), nrows
+                bool fits;
+                int4 ri = item_box<TPI>(corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, tc.cx0, tc.cx1, y_lo, y_hi), kCols, kMaxRows, fits);  // qx0, by0, nq, nrows
                 int cols = 0, lines = 0;
-                if (finite) {
-                    const int bx0 = static_cast<int>(floorf(mnx - kBoxEps)), bx1 = static_cast<int>(floorf(mxx + kBoxEps)) + 1;
-                    const int by0 = static_cast<int>(floorf(mny - kBoxEps)), by1 = static_cast<int>(floorf(mxy + kBoxEps)) + 1;
-                    ri.x = bx0 & ~(TPI - 1);
-                    ri.y = by0;
-                    ri.z = (bx1 - ri.x) / TPI + 1;
-                    ri.w = by1 - by0 + 1;
-                    if (ri.z > kCols || ri.w > kMaxRows) {
-                        ri.z = -1;
-                    } else {  // (qx0 and Wt are multiples of the item width)
-                        const int clo = min(max(-ri.x / TPI, 0), ri.z), chi = min(max((Wt - ri.x) / TPI, 0), ri.z);
-                        const int rlo = min(max(-by0, 0), ri.w), rhi = min(max(Ht - by0, 0), ri.w);
-                        cols = ri.z | clo << 8 | (chi - clo) << 16;
-                        lines = LPR * ri.w | LPR * rlo << 8 | LPR * (rhi - rlo) << 16;
-                    }
+                if (!fits) {
+                    ri.z = -1;  // (< 0: does not fit)
+                } else {  // (qx0 and Wt are multiples of the item width)
+                    const int clo = min(max(-ri.x / TPI, 0), ri.z), chi = min(max((Wt - ri.x) / TPI, 0), ri.z);
+                    const int rlo = min(max(-ri.y, 0), ri.w), rhi = min(max(Ht - ri.y, 0), ri.w);
+                    cols = ri.z | clo << 8 | (chi - clo) << 16;
+                    lines = LPR * ri.w | LPR * rlo << 8 | LPR * (rhi - rlo) << 16;
                 }
                 nq_max = max(nq_max, ri.z < 0 ? 1 << 20 : ri.z);
                 row_max = max(row_max, ri.w);
                 const float hw = pw * 0.5f, hh = ph * 0.5f;  // exact halves: (2x)/w == x/(w/2)
-                const uint64_t origin = reinterpret_cast<uint64_t>(vol + (static_cast<int64_t>(k) * s_plane + static_cast<int64_t>(ri.y) * s_row + ri.x));
-                tabL[t] = make_int4(static_cast<int>(origin & 0xffffffffu), static_cast<int>((origin >> 32) & 0xffffu), cols, lines);
+                const int2 origin = origin_words(reinterpret_cast<uint64_t>(vol + (static_cast<int64_t>(k) * s_plane + static_cast<int64_t>(ri.y) * s_row + ri.x)));
+                tabL[t] = make_int4(origin.x, origin.y, cols, lines);
                 tabF[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
                 tabG[t] = make_int4(__float_as_int(1.0f / hh), ri.x, ri.y, 0);
             }
@@ -331,15 +310,10 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
             // integer masks (not bools): keeps the uniform liveness logic on the scalar unit
             const int live = t < kn ? load_mask : 0, live_store = t < kn ? store_mask : 0;
             const int4 rl = tabL[min(t, kn - 1)];
-            // the descriptor must be PROVABLY wave-uniform or hipcc wraps every buffer op in a waterfall loop
-            // (cdna_hip_programming.md T20): pass its inputs through readfirstlane.  Base = the box origin, so the
-            // per-lane offsets are the chunk-invariant g_off[]; num_records 2^31: only the explicit out-of-range
-            // offset below is rejected (every other lane is inside the texture by the range tests)
-            const uint32_t b_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(rl.x));
-            const uint32_t b_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(rl.y));
+            // base = the box origin, so the per-lane offsets are the chunk-invariant g_off[] (every lane that is not rejected explicitly below is
+            // inside the texture by the range tests)
+            const __amdgpu_buffer_rsrc_t rsrc = origin_rsrc(rl.x, rl.y);
             const int cols = __builtin_amdgcn_readfirstlane(rl.z), lines = __builtin_amdgcn_readfirstlane(rl.w);
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<void*>((static_cast<uint64_t>(b_hi) << 32) | b_lo), 0, static_cast<int>(0x80000000u), 0x00020000);
             // item columns [clo, clo+ncol) and lines [llo, llo+nline) of the box lie inside the texture (one unsigned
             // compare each); everything else reads as zero ("zeros" padding) without touching memory
             // (a plane that is not live gets empty ranges: the uniform flags stay on the scalar unit)
@@ -576,7 +550,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
 
     const LastPlane lp = last_plane(p, vw);
     if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active);
     report_status(p.status, bad);
 }
 
@@ -649,10 +623,9 @@ int lds_variant_query(int what) {
 template <typename TexT, int TW, int MINW, int PF, int LAYOUT>
 static hipError_t launch_lds_t(const KParams& p, hipStream_t stream) {
     constexpr int TH = kNT / TW;
-    const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH;
-    const int n_tiles = tiles_x * tiles_y * p.N;
-    const unsigned grid_x = (p.gate != nullptr || sizeof(TexT) == 4 || (p.flags & (1u << 19))) ? xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)
-                                              : static_cast<unsigned>(((n_tiles + 7) / 8) * 8);
+    const FwdTileGrid tg = fwd_tile_grid<TW, TH>(p);
+    const int tiles_x = tg.tiles_x, tiles_y = tg.tiles_y, n_tiles = tg.n_tiles;
+    const unsigned grid_x = (p.gate != nullptr || sizeof(TexT) == 4 || (p.flags & (1u << 19))) ? tg.grid.x : static_cast<unsigned>(((n_tiles + 7) / 8) * 8);  // (16-bit: one run per XCD)
     const dim3 grid(grid_x), block(kNT);
     if (p.gate != nullptr) {
         unsigned gg = std::min(grid_x, gated_grid<TexT>(p.view_to_mpi == nullptr && p.views_per_mpi > 1));

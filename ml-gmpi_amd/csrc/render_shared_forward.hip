@@ -1,5 +1,5 @@
 // render_shared_forward.hip -- GMPI_VARIANT_LDS of the shared-colour forward (gmpi_mpi_render_shared_launch): render_lds.hip's pixel tiles for the
-// layout of render_shared.hip.
+// layout of render_shared.hip.  Tile decode, pixel, corner box and origin words are the tile frame of gmpi_device.hpp.
 //
 // One workgroup of 512 threads owns a 32 x 16 pixel tile (one pixel per thread) and walks the D planes front to back.  Per plane the texel box
 // spanned by the tile's four corner pixels is copied to LDS as fp32 planes [row][channel][x] (56 texels x 27 rows, the tile kernel's buffer) and
@@ -32,7 +32,6 @@ constexpr int kFPitch = 56, kFRows = 27;                   // staging buffer: te
 constexpr int kFTPI = 4, kFCols = kFPitch / kFTPI;         // texels per loader item, items per line
 constexpr int kFBufFloats = kFRows * 4 * kFPitch;          // 6048 floats = 24 192 bytes
 constexpr int kFChunk = 64;                                // planes per box-table refill
-constexpr float kFBoxEps = 1.0f / 64;                      // slack on the corner-derived box (fp32 error of ix is < 1e-3 texel)
 static_assert(kFRows * kFCols <= kFThreads, "one loader item per thread and channel");
 static_assert(2 * kFBufFloats * 4 + kFChunk * 16 <= 53 * 1024, "3 workgroups per CU");
 
@@ -52,18 +51,15 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
     __shared__ int4 org[kFChunk][2];
     __shared__ __attribute__((aligned(16))) float stage[2][kFBufFloats];
 
-    // ---- blockIdx -> tile: every XCD gets a contiguous run of the tiles of every group of views that share an MPI (gmpi_device.hpp) -------------
+    // ---- blockIdx -> tile, this lane's pixel, the tile's corner pixels: the tile frame of gmpi_device.hpp -----------------------------------------
     const int tid = threadIdx.x;
-    const int tiles_per_view = tiles_x * tiles_y;
-    const int tile_id = xcd_item_per_group(static_cast<int>(blockIdx.x), tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles);
-    if (tile_id >= n_tiles) return;
-    int n, trem;
-    item_to_view(p, tile_id, tiles_per_view, n, trem);   // (views that share one MPI are neighbours per tile position)
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
+    FwdTile ft;
+    if (!fwd_tile(p, fwd_tile_id(p, blockIdx.x, tiles_x, tiles_y, n_tiles), tiles_x, tiles_y, n_tiles, ft)) return;
+    const int n = ft.n;
 
     uint32_t bad = 0;
     const View vw = view_setup<AC>(p, n, bad);
-    check_camera_behind(p, vw, trem == 0 && tid == 0);   // once per view
+    check_camera_behind(p, vw, ft.rem == 0 && tid == 0);   // once per view
     const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
     const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
     const bool check_last = (p.flags & GMPI_FLAG_CHECK_LAST_PLANE) != 0;
@@ -73,25 +69,20 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
     const TexT* __restrict__ rgb = static_cast<const TexT*>(sh.rgb) + static_cast<int64_t>(vw.m) * sh.rs_mpi;
     const TexT* __restrict__ bgi = sh.bg ? static_cast<const TexT*>(sh.bg) + static_cast<int64_t>(vw.m) * sh.bs_mpi : nullptr;
 
-    // ---- this thread's pixel (out-of-image lanes shadow the last row / column) --------------------------------------------------------------------
-    // (px, py, pix are formed again for the epilogue: nothing of them stays in a register across the plane loop)
-    auto pixel_of = [&](bool& active) {
+    // (this lane's pixel is formed again for the epilogue: nothing of it stays in a register across the plane loop)
+    auto pixel_of = [&]() {
         int lane = tid;
         asm volatile("" : "+v"(lane));   // (opaque: or the two evaluations are merged and the first one's results kept)
-        const int px = txi * kFW + (lane % kFW), py = tyi * kFH + (lane / kFW);
-        active = px < W && py < H;
-        return static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
+        return tile_lane<kFW, kFH>(ft.txi, ft.tyi, lane, W, H);
     };
     float rx, ry, rz;
     {
-        bool unused;
-        const int64_t pix = pixel_of(unused);
+        const int64_t pix = pixel_of().pix;
         rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     }
     const float dot = ray_dot(vw, rx, ry, rz);
     Accum A;
-    const int cx0 = txi * kFW, cx1 = min(cx0 + kFW - 1, W - 1);
-    const int cy0 = tyi * kFH, cy1 = min(cy0 + kFH - 1, H - 1);
+    const TileCorners tc = tile_corners<kFW, kFH>(ft.txi, ft.tyi, W, H);
 
     // ---- loader role: item column lcol of box row lrow, the same for the four channels; byte offsets from the box origin per row stride ---------
     const int lrow = tid / kFCols, lcol = tid - lrow * kFCols;
@@ -106,24 +97,9 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
         for (int t = tid; t < kn; t += kFThreads) {
             const int k = kc + t;
             const float zdiff = vw.dhw[3 * k] - vw.ez, ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
-            float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-            bool finite = true;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * W + ((c & 1) ? cx1 : cx0);
-                float ix, iy, s, u, v;
-                plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], vw.cx, vw.cy, ix, iy, s, u, v);
-                finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);   // false for NaN too
-                mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-            }
-            int4 bb = make_int4(0, 0, 0, 0);
-            if (finite) {
-                const int bx0 = static_cast<int>(floorf(mnx - kFBoxEps)), bx1 = static_cast<int>(floorf(mxx + kFBoxEps)) + 1;   // first and last texel column
-                const int by0 = static_cast<int>(floorf(mny - kFBoxEps)), by1 = static_cast<int>(floorf(mxy + kFBoxEps)) + 1;
-                bb.x = bx0 & ~(kFTPI - 1), bb.y = by0;
-                bb.z = (bx1 - bb.x) / kFTPI + 1, bb.w = by1 - by0 + 1;
-                if (bb.z > kFCols || bb.w > kFRows) bb.z = 0;
-            }
+            bool fits;
+            int4 bb = item_box<kFTPI>(corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, tc.cx0, tc.cx1, tc.cy0, tc.cy1), kFCols, kFRows, fits);
+            if (!fits) bb.z = 0;
             box[t] = bb;
             const bool last_bg = bgi != nullptr && k == D - 1;
             const TexT* col = last_bg ? bgi : rgb;
@@ -132,10 +108,9 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             const uint64_t oc = static_cast<uint64_t>(c_chan * static_cast<int64_t>(kEs));
             const uint64_t o1 = o0 + oc, o2 = o1 + oc;
             const uint64_t o3 = reinterpret_cast<uint64_t>(alpha) + static_cast<uint64_t>((static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + bb.x) * static_cast<int64_t>(kEs));
-            auto lo = [](uint64_t a) { return static_cast<int>(a & 0xffffffffu); };
-            auto hi = [](uint64_t a) { return static_cast<int>((a >> 32) & 0xffffu); };
-            org[t][0] = make_int4(lo(o0), hi(o0), lo(o1), hi(o1));
-            org[t][1] = make_int4(lo(o2), hi(o2), lo(o3), hi(o3));
+            const int2 w0 = origin_words(o0), w1 = origin_words(o1), w2 = origin_words(o2), w3 = origin_words(o3);
+            org[t][0] = make_int4(w0.x, w0.y, w1.x, w1.y);
+            org[t][1] = make_int4(w2.x, w2.y, w3.x, w3.y);
         }
         __syncthreads();   // table published
 
@@ -155,14 +130,7 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             if (last_bg) off_col = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(sh.bs_row) + kFTPI * lcol) * kEs;
             const uint32_t oc = ok ? off_col : 0x80000000u, oa = ok ? off_a : 0x80000000u;   // == num_records: rejected
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                // the descriptor must be provably wave-uniform, or every buffer load is wrapped in a waterfall loop
-                const uint32_t b_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ow[2 * c]));
-                const uint32_t b_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ow[2 * c + 1]));
-                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((static_cast<uint64_t>(b_hi) << 32) | b_lo), 0,
-                                                                                      static_cast<int>(0x80000000u), 0x00020000);
-                L[c] = I4::load(rsrc, c < 3 ? oc : oa);
-            }
+            for (int c = 0; c < 4; ++c) L[c] = I4::load(origin_rsrc(ow[2 * c], ow[2 * c + 1]), c < 3 ? oc : oa);
         };
         // registers -> LDS: the box itself (texels of it outside the texture are the zeros the loads returned); lanes outside the box stay idle
         auto store_box = [&](int t, float* buf, const Raw (&L)[4]) {
@@ -236,9 +204,8 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             composite(t, buf);
         }
     }
-    bool active;
-    const int64_t pix = pixel_of(active);
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    const TileLane tl = pixel_of();
+    store_pixel<STRICT>(p, n, HW, tl.pix, A, dot, tl.active);
     report_status(p.status, bad);
 }
 
@@ -267,12 +234,10 @@ int shared_forward_query(int what) {
 
 template <typename TexT>
 static hipError_t launch_shared_forward_t(const KParams& p, const SharedK& sh, hipStream_t stream) {
-    const int tiles_x = (p.W + kFW - 1) / kFW, tiles_y = (p.H + kFH - 1) / kFH;
-    const int n_tiles = tiles_x * tiles_y * p.N;
-    const dim3 grid(xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)), block(kFThreads);
+    const FwdTileGrid tg = fwd_tile_grid<kFW, kFH>(p);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        hipLaunchKernelGGL((render_shared_forward_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, sh, tiles_x, tiles_y,
-                           n_tiles);
+        hipLaunchKernelGGL((render_shared_forward_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), tg.grid, dim3(kFThreads), 0, stream, p, sh, tg.tiles_x,
+                           tg.tiles_y, tg.n_tiles);
     });
     return hipGetLastError();
 }

@@ -3,7 +3,7 @@
 // A code c in 0..255 stands for the fp32 value c / 255 (to_f32(u8_t), gmpi_device.hpp): rendering the volume is by definition rendering that fp32
 // volume.  One workgroup of 512 threads owns a 32 x 16 pixel tile (one pixel per thread) and walks the D planes front to back; per plane the texel
 // box spanned by the tile's four corner pixels is staged in LDS, two buffers, one barrier per plane, the loads of plane k + 1 in flight while
-// plane k is composited (render_lds.hip has the why of all that).
+// plane k is composited (render_lds.hip has the why of all that; tile decode, pixel, corner box and origin words are the tile frame of gmpi_device.hpp).
 //
 // What is new is the LDS image: the RAW texels, interleaved, one dword (R | G << 8 | B << 16 | A << 24) per texel, 64 texels x 32 rows.
 //  * A pixel's 2 x 2 footprint is two ds_read2_b32 (texels x, x + 1 of rows y and y + 1) instead of the fp32 planes' eight.
@@ -38,7 +38,6 @@ constexpr int kUPitch = 64, kURows = 32;                   // staging buffer: te
 constexpr int kUTPI = 4, kUCols = kUPitch / kUTPI;         // texels per loader item, items per row
 constexpr int kUBufWords = kURows * kUPitch;               // 2048 dwords = 8 KB
 constexpr int kUChunk = 64;                                // planes per table refill
-constexpr float kUBoxEps = 1.0f / 64;                      // slack on the corner-derived box (fp32 error of ix is < 1e-3 texel)
 static_assert(kURows * kUCols == kUThreads, "one loader item per thread");
 static_assert(kUPitch % 32 == 0, "row pitch: a multiple of the 32 banks of ds_read2_b32");
 static_assert(2 * kUBufWords * 4 + kUChunk * 48 <= 40 * 1024, "4 workgroups per CU");
@@ -59,18 +58,15 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     __shared__ float4 geo[kUChunk];
     __shared__ __attribute__((aligned(16))) uint32_t stage[2][kUBufWords];
 
-    // ---- blockIdx -> tile: every XCD gets a contiguous run of the tiles of every group of views that share an MPI (gmpi_device.hpp) -------------
+    // ---- blockIdx -> tile, this lane's pixel, the tile's corner pixels: the tile frame of gmpi_device.hpp -----------------------------------------
     const int tid = threadIdx.x;
-    const int tiles_per_view = tiles_x * tiles_y;
-    const int tile_id = xcd_item_per_group(static_cast<int>(blockIdx.x), tiles_per_view * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles);
-    if (tile_id >= n_tiles) return;
-    int n, trem;
-    item_to_view(p, tile_id, tiles_per_view, n, trem);   // (views that share one MPI are interleaved per tile position)
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
+    FwdTile ft;
+    if (!fwd_tile(p, fwd_tile_id(p, blockIdx.x, tiles_x, tiles_y, n_tiles), tiles_x, tiles_y, n_tiles, ft)) return;
+    const int n = ft.n;
 
     uint32_t bad = 0;
     const View vw = view_setup<AC>(p, n, bad);
-    check_camera_behind(p, vw, trem == 0 && tid == 0);   // once per view
+    check_camera_behind(p, vw, ft.rem == 0 && tid == 0);   // once per view
     const int D = p.D, Ht = p.Ht, Wt = p.Wt, H = p.H, W = p.W;
     const int64_t HW = vw.HW;
     const float* __restrict__ rdv = vw.rays;
@@ -78,16 +74,13 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     constexpr int kTexelBytes = kPacked ? 4 : 1;   // bytes from one texel of a row to the next
     const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
 
-    // ---- this thread's pixel (out-of-image lanes shadow the last row / column) --------------------------------------------------------------------
-    const int px = txi * kUW + (tid % kUW), py = tyi * kUH + (tid / kUW);
-    const bool active = px < W && py < H;
-    const int64_t pix = static_cast<int64_t>(min(py, H - 1)) * W + min(px, W - 1);
+    const TileLane tl = tile_lane<kUW, kUH>(ft.txi, ft.tyi, tid, W, H);
+    const int64_t pix = tl.pix;
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
     const float rcp_rz = 1.0f / rz;   // correctly rounded; hoisted out of the plane loop (div_by_recip)
     Accum A;
-    const int cx0 = txi * kUW, cx1 = min(cx0 + kUW - 1, W - 1);
-    const int cy0 = tyi * kUH, cy1 = min(cy0 + kUH - 1, H - 1);
+    const TileCorners tc = tile_corners<kUW, kUH>(ft.txi, ft.tyi, W, H);
 
     // ---- loader role: item column lcol of box row lrow; byte offset from the box origin (one byte per texel and channel) ---------------------------
     const int lrow = tid / kUCols, lcol = tid - lrow * kUCols;
@@ -100,28 +93,13 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
         for (int t = tid; t < kn; t += kUThreads) {
             const int k = kc + t;
             const float zdiff = vw.dhw[3 * k] - vw.ez, ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
-            float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = mnx, mxy = mxx;
-            bool finite = true;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int64_t q = static_cast<int64_t>((c & 2) ? cy1 : cy0) * W + ((c & 1) ? cx1 : cx0);
-                float ix, iy, s, u, v;
-                plane_coord<AC>(zdiff, ph, pw, vw.ex, vw.ey, rdv[q], rdv[HW + q], rdv[2 * HW + q], vw.cx, vw.cy, ix, iy, s, u, v);
-                finite = finite && (fabsf(ix) < 1e6f) && (fabsf(iy) < 1e6f);   // false for NaN too
-                mnx = fminf(mnx, ix), mxx = fmaxf(mxx, ix), mny = fminf(mny, iy), mxy = fmaxf(mxy, iy);
-            }
-            int4 bb = make_int4(0, 0, 0, 0);
-            if (finite) {
-                const int bx0 = static_cast<int>(floorf(mnx - kUBoxEps)), bx1 = static_cast<int>(floorf(mxx + kUBoxEps)) + 1;   // first and last texel column
-                const int by0 = static_cast<int>(floorf(mny - kUBoxEps)), by1 = static_cast<int>(floorf(mxy + kUBoxEps)) + 1;
-                bb.x = bx0 & ~(kUTPI - 1), bb.y = by0;
-                bb.z = (bx1 - bb.x) / kUTPI + 1, bb.w = by1 - by0 + 1;
-                if (bb.z > kUCols || bb.w > kURows) bb = make_int4(0, 0, 0, 0);
-            }
+            bool fits;
+            int4 bb = item_box<kUTPI>(corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, tc.cx0, tc.cx1, tc.cy0, tc.cy1), kUCols, kURows, fits);
+            if (!fits) bb = make_int4(0, 0, 0, 0);
             box[t] = bb;
             const float hw = pw * 0.5f, hh = ph * 0.5f;   // exact halves: (2x) / w == x / (w / 2)
-            const uint64_t o = reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + kTexelBytes * bb.x);
-            org[t] = make_int4(static_cast<int>(o & 0xffffffffu), static_cast<int>((o >> 32) & 0xffffu), __float_as_int(1.0f / hh), 0);
+            const int2 o = origin_words(reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + kTexelBytes * bb.x));
+            org[t] = make_int4(o.x, o.y, __float_as_int(1.0f / hh), 0);
             geo[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
         }
         __syncthreads();   // table published
@@ -133,11 +111,7 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
             const int4 oo = org[min(t, kn - 1)];
             const int qx0 = __builtin_amdgcn_readfirstlane(bb.x), by0 = __builtin_amdgcn_readfirstlane(bb.y);
             const int nq = t < kn ? __builtin_amdgcn_readfirstlane(bb.z) : 0, nrows = __builtin_amdgcn_readfirstlane(bb.w);
-            // the descriptor must be provably wave-uniform, or every buffer load is wrapped in a waterfall loop
-            const uint32_t b_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(oo.x));
-            const uint32_t b_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(oo.y));
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((static_cast<uint64_t>(b_hi) << 32) | b_lo), 0,
-                                                                                  static_cast<int>(0x80000000u), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsrc = origin_rsrc(oo.x, oo.y);
             const int gx = qx0 + kUTPI * lcol, gy = by0 + lrow;   // (Wt is a multiple of 4: an item lies inside the texture row or outside it)
             // (bitwise on purpose: `&&` would be lowered to exec-mask control flow)
             const bool ok = (lcol < nq) & (lrow < nrows) & (gx >= 0) & (gx < Wt) & (gy >= 0) & (gy < Ht);
@@ -231,7 +205,7 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     }
     const LastPlane lp = last_plane(p, vw);
     if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active);
     report_status(p.status, bad);
 }
 
@@ -272,13 +246,12 @@ int u8_variant_query(int what) {
 }
 
 hipError_t launch_u8(const KParams& p, hipStream_t stream) {
-    const int tiles_x = (p.W + kUW - 1) / kUW, tiles_y = (p.H + kUH - 1) / kUH;
-    const int n_tiles = tiles_x * tiles_y * p.N;
-    const dim3 grid(xcd_grid_per_group(tiles_x * tiles_y * (p.view_to_mpi == nullptr ? p.views_per_mpi : 1), n_tiles)), block(kUThreads);
+    const FwdTileGrid tg = fwd_tile_grid<kUW, kUH>(p);
+    const dim3 block(kUThreads);
     const bool packed = u8_interleaved(p);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        if (packed) hipLaunchKernelGGL((render_rgba8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
-        else hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, tiles_x, tiles_y, n_tiles);
+        if (packed) hipLaunchKernelGGL((render_rgba8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+        else hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
     });
     return hipGetLastError();
 }

@@ -58,7 +58,6 @@ constexpr int wave_lds(int waves_per_simd) { return waves_per_simd >= 4 ? 10240 
 // texel slots of a wave's box: 16 bytes (fp32 RGBA) or 8 bytes (fp16 RGBA, HALF); 16 bytes of front padding
 constexpr int box_slots(int waves_per_simd, int slot_bytes) { return (wave_lds(waves_per_simd) - kRing * kEntry - 16) / slot_bytes; }
 constexpr int kMaxNP = 3;
-constexpr float kBoxSlack = 1.0f / 64;  // slack on the corner-derived box (fp32 error of ix is < 1e-3 texel)
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
