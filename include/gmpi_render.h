@@ -71,7 +71,8 @@ enum {
                                             small launch ~18 us of table kernel and empty launches); launches of up to 512 strips stay with the
                                             strip kernel whatever the hint (its 6-way plane split still wins there).  Like
                                             GMPI_FLAG_HINT_FRONTAL it never changes a result.                                                */
-    GMPI_FLAG_GRAD_OVERWRITE = 1 << 7,   /* gmpi_mpi_render_backward_launch only (round 6): the caller does not need what grad_rgba holds.
+    GMPI_FLAG_GRAD_OVERWRITE = 1 << 7,   /* gmpi_mpi_render_backward_launch (round 6; and the layouts' _backward_gather_launch entries, which say what it
+                                            means there): the caller does not need what grad_rgba holds.
                                             With the workspace gmpi_render_backward_workspace_bytes asks for, the launch then WRITES every element
                                             of grad_rgba (no zero-fill needed); without the flag it reads, adds and writes back.  On the tile-kernel
                                             path (no workspace, or a launch the gather path does not take) the flag changes nothing: that path only
@@ -415,6 +416,49 @@ int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams *params, c
                                                const int64_t *grad_background_stride, void *stream);
 
 /*
+ * The image backward of the two layouts WITHOUT atomics: gmpi_mpi_render_shared_backward_launch / gmpi_mpi_render_depth_backward_launch as the pair of
+ * gmpi_mpi_render_backward_launch's workspace path -- a pixel pass that writes one record per view, plane and pixel (the exact sample position from the
+ * forward's coordinate chain and dL/d(r, g, b, alpha sample): 24 bytes; the sweep is the layout's one-pixel-per-lane kernel's, term for term), then a
+ * texel gather through each plane's inverse homography in which every gradient cell has ONE owner and is written once, in a fixed order: two launches
+ * give the same bits.  The colour sums run ACROSS the planes that use rgb (plane D-1's go to grad_background when there is one); grad_alpha is stored per
+ * plane; the depth-alpha layout adds plane k's sum to a cell's depth gradient where z_lo <= plane_z[k] - depth <= z_hi for that texel and divides by
+ * -z_den once per cell.  A workgroup owns a 64 x 16 texel tile of one MPI over a RUN of planes: one run when that fills the chip (at least 1024
+ * workgroups), else the planes per run are halved until it does, each run writes its partial colour / depth sums to a slab of the workspace and a small
+ * kernel adds the runs up in run order.  The number of runs is a function of M, D, Ht and Wt alone.
+ * Arguments, checks and error codes: those of the layout's image backward, except
+ *   - params->workspace must hold gmpi_render_layout_backward_gather_workspace_bytes(params, shared, depth_alpha) bytes, 256-byte aligned:
+ *     GMPI_E_WORKSPACE otherwise;
+ *   - the pair takes GMPI_FLAG_ALIGN_CORNERS launches with uniform views_per_mpi (no view_to_mpi), Wt >= 2, N, M, D <= 65535 and H W < 2^31; any D, any
+ *     stride, fp32 / bf16 / fp16 storage.  Every other launch, and every variant but GMPI_VARIANT_AUTO, is GMPI_E_VARIANT: these entries run the pair or
+ *     return an error, they never fall back to the atomic kernels (which have entries of their own);
+ *   - with GMPI_FLAG_GRAD_OVERWRITE every cell inside [Ht, Wt] of each wanted gradient is WRITTEN (no zero-fill needed); without it every such cell is
+ *     read, added to and written back by its owner.  Cells of the padding between rows, channels or MPIs are never touched.
+ * A term is added only where its bilinear weight is not zero: a pixel whose upstream gradient is not finite reaches the cells of its own footprints
+ * only.  The candidate windows assume a pinhole ray field (see ray_dir above); a (view, plane) without a usable homography looks at every pixel.
+ * gmpi_query(34) == 1 says that the entries are built in.
+ */
+int gmpi_mpi_render_shared_backward_gather_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const float *grad_rgb_out,
+                                                  const float *grad_depth, const float *grad_transmittance, float *grad_shared_rgb,
+                                                  const int64_t *grad_shared_rgb_stride, float *grad_alpha, const int64_t *grad_alpha_stride,
+                                                  float *grad_background, const int64_t *grad_background_stride, void *stream);
+int gmpi_mpi_render_depth_backward_gather_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                                 const float *grad_rgb_out, const float *grad_depth, const float *grad_transmittance,
+                                                 float *grad_shared_rgb, const int64_t *grad_shared_rgb_stride, float *grad_depth_image,
+                                                 const int64_t *grad_depth_image_stride, float *grad_background,
+                                                 const int64_t *grad_background_stride, void *stream);
+
+/* Bytes of workspace the two entries above want for this launch (depth_alpha NULL: the shared-colour entry): the homography records, 24 bytes per view,
+ * plane and pixel, and the run slabs, rounded to 256.  0: the pair cannot take the launch -- exactly where the launch returns GMPI_E_VARIANT or an
+ * argument error.  Launches nothing. */
+uint64_t gmpi_render_layout_backward_gather_workspace_bytes(const GmpiRenderParams *params, const GmpiSharedColor *shared,
+                                                            const GmpiDepthAlpha *depth_alpha);
+
+/* The plane runs per texel tile the pair uses for this launch (0 where the query above answers 0), and a hook for tests: a positive `runs` replaces the
+ * rule for every later launch and query of this process (rounded to what D allows: ceil(D / ceil(D / runs)) runs), 0 restores it. */
+int gmpi_render_layout_backward_gather_runs(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha);
+void gmpi_render_layout_backward_gather_set_runs(int32_t runs);
+
+/*
  * gmpi_mpi_render_geometry_backward_ex_launch over the two layouts: the gradient of gmpi_mpi_render_shared_launch / gmpi_mpi_render_depth_launch w.r.t.
  * the sample POSITIONS -- by definition that of the volume entry on the expanded volume, which is never materialised.  `params`, `shared` and
  * `depth_alpha` as for the layout's image backward (params->rgba = the alpha planes, resp. the depth image; AUTO and GATHER run the same kernel, any
@@ -591,7 +635,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * (gmpi_mpi_render_depth_window_launch): 25 whether it is built in, 26 / 27 the width / height of its window in texels, 28 the planes per refill of
  * its box table; 29 is unused (-1); 30 whether the geometry backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_shared_geometry_backward_launch,
  * gmpi_mpi_render_depth_geometry_backward_launch) is built in; 31 is unused (-1); 32 whether compute_depth of the depth-alpha layout
- * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in.  Unknown -> -1.                                                */
+ * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in; 33 is unused (-1); 34 whether the atomics-free backward of the shared-colour
+ * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

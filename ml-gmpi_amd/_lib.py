@@ -40,6 +40,11 @@ EXPORTS = (
     "gmpi_render_depth_window_supports",
     "gmpi_mpi_render_depth_backward_launch",
     "gmpi_mpi_render_depth_backward_tile_launch",
+    "gmpi_render_layout_backward_gather_workspace_bytes",
+    "gmpi_render_layout_backward_gather_runs",
+    "gmpi_render_layout_backward_gather_set_runs",
+    "gmpi_mpi_render_shared_backward_gather_launch",
+    "gmpi_mpi_render_depth_backward_gather_launch",
     "gmpi_mpi_render_shared_geometry_backward_launch",
     "gmpi_mpi_render_depth_geometry_backward_launch",
     "gmpi_last_plane_uv_minmax_launch",
@@ -226,6 +231,17 @@ def load_library():
                                                           vp, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp]
     lib.gmpi_mpi_render_depth_backward_tile_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_backward_tile_launch.argtypes = list(lib.gmpi_mpi_render_depth_backward_launch.argtypes)   # (the same signature)
+    # the atomics-free pair of the two layouts: the signatures of their image backwards; the query takes the three structs (GmpiDepthAlpha NULL: shared-colour)
+    lib.gmpi_mpi_render_shared_backward_gather_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shared_backward_gather_launch.argtypes = list(lib.gmpi_mpi_render_shared_backward_launch.argtypes)
+    lib.gmpi_mpi_render_depth_backward_gather_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_depth_backward_gather_launch.argtypes = list(lib.gmpi_mpi_render_depth_backward_launch.argtypes)
+    lib.gmpi_render_layout_backward_gather_workspace_bytes.restype = ctypes.c_uint64
+    lib.gmpi_render_layout_backward_gather_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha)]
+    lib.gmpi_render_layout_backward_gather_runs.restype = ctypes.c_int
+    lib.gmpi_render_layout_backward_gather_runs.argtypes = list(lib.gmpi_render_layout_backward_gather_workspace_bytes.argtypes)
+    lib.gmpi_render_layout_backward_gather_set_runs.restype = None
+    lib.gmpi_render_layout_backward_gather_set_runs.argtypes = [ctypes.c_int32]
     lib.gmpi_mpi_render_shared_geometry_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gmpi_mpi_render_depth_geometry_backward_launch.restype = ctypes.c_int

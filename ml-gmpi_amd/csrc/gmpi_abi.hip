@@ -25,6 +25,11 @@ uint32_t* band_gate_words(const KParams& p, int dtype);                     // r
 int band_pixels_wide(int dtype);                                            // render_band.hip
 uint64_t backward_gather_workspace_bytes(const KParams& p, int dtype);      // render_backward_gather.hip
 uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
+uint64_t layout_gather_workspace_bytes(const KParams& p, bool depth);       // render_backward_gather.hip
+int layout_gather_runs(const KParams& p);                                   // render_backward_gather.hip
+void layout_gather_force_runs(int runs);                                    // render_backward_gather.hip
+hipError_t launch_layout_backward_gather(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const SharedG& g, bool overwrite,
+                                         hipStream_t stream);               // render_backward_gather.hip
 hipError_t launch_shared(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared.hip
 hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh, const SharedG& g, bool tiles, hipStream_t stream);   // render_shared.hip
 hipError_t launch_shared_forward(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared_forward.hip
@@ -706,6 +711,77 @@ int gmpi_mpi_render_depth_backward_tile_launch(const GmpiRenderParams* params, c
                           grad_depth_image, grad_depth_image_stride, grad_background, grad_background_stride, stream, true);
 }
 
+// The atomics-free pair over the two layouts (render_backward_gather.hip).  ONE predicate for the query and the launches: the layout's struct checks
+// pass, the variant is AUTO and layout_gather_workspace_bytes is not 0 (the caller allocates on the strength of the query).  depth_alpha NULL:
+// shared-colour.
+static int to_layout(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, bool depth, KParams& p, SharedK& sh,
+                     DepthK& dk) {
+    return depth ? to_depth(params, shared, depth_alpha, false, p, sh, dk) : to_shared(params, shared, false, p, sh);
+}
+
+uint64_t gmpi_render_layout_backward_gather_workspace_bytes(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    if (to_layout(params, shared, depth_alpha, depth_alpha != nullptr, p, sh, dk) != GMPI_OK || p.N == 0) return 0;
+    if (params->variant != GMPI_VARIANT_AUTO) return 0;
+    return layout_gather_workspace_bytes(p, depth_alpha != nullptr);
+}
+
+int gmpi_render_layout_backward_gather_runs(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha) {
+    if (gmpi_render_layout_backward_gather_workspace_bytes(params, shared, depth_alpha) == 0) return 0;
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    to_layout(params, shared, depth_alpha, depth_alpha != nullptr, p, sh, dk);
+    return layout_gather_runs(p);
+}
+
+void gmpi_render_layout_backward_gather_set_runs(int32_t runs) { layout_gather_force_runs(runs); }
+
+static int layout_backward_gather(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha, bool depth,
+                                  const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
+                                  const int64_t* grad_shared_rgb_stride, float* grad_mid, const int64_t* grad_mid_stride, float* grad_background,
+                                  const int64_t* grad_background_stride, void* stream) {
+    KParams p;
+    SharedK sh;
+    DepthK dk;
+    int rc = to_layout(params, shared, depth_alpha, depth, p, sh, dk);
+    if (rc != GMPI_OK) return rc;
+    int64_t gd_stride[3] = {0, 1, 0};   // (depth-alpha: the depth image's channel stride is ignored)
+    if (depth && grad_mid != nullptr && grad_mid_stride != nullptr) {
+        gd_stride[0] = grad_mid_stride[0], gd_stride[2] = grad_mid_stride[2];
+        grad_mid_stride = gd_stride;
+    }
+    SharedG g{};
+    rc = to_shared_grads(params, p, sh, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride, grad_mid, grad_mid_stride,
+                         grad_background, grad_background_stride, g);
+    if (rc != GMPI_OK || p.N == 0) return rc;
+    if (params->variant != GMPI_VARIANT_AUTO) return GMPI_E_VARIANT;   // the pair has one form; the atomic kernels have entries of their own
+    const uint64_t need = layout_gather_workspace_bytes(p, depth);
+    if (need == 0) return GMPI_E_VARIANT;                              // a launch the pair does not take: never a quiet fall-back to atomics
+    if (p.ws == nullptr || p.ws_bytes < need || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return GMPI_E_WORKSPACE;
+    return hip_rc(launch_layout_backward_gather(p, params->rgba_dtype, sh, depth ? &dk : nullptr, g, (p.flags & GMPI_FLAG_GRAD_OVERWRITE) != 0,
+                                                static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_shared_backward_gather_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb_out,
+                                                  const float* grad_depth, const float* grad_transmittance, float* grad_shared_rgb,
+                                                  const int64_t* grad_shared_rgb_stride, float* grad_alpha, const int64_t* grad_alpha_stride,
+                                                  float* grad_background, const int64_t* grad_background_stride, void* stream) {
+    return layout_backward_gather(params, shared, nullptr, false, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride,
+                                  grad_alpha, grad_alpha_stride, grad_background, grad_background_stride, stream);
+}
+
+int gmpi_mpi_render_depth_backward_gather_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                                 const float* grad_rgb_out, const float* grad_depth, const float* grad_transmittance,
+                                                 float* grad_shared_rgb, const int64_t* grad_shared_rgb_stride, float* grad_depth_image,
+                                                 const int64_t* grad_depth_image_stride, float* grad_background, const int64_t* grad_background_stride,
+                                                 void* stream) {
+    return layout_backward_gather(params, shared, depth_alpha, true, grad_rgb_out, grad_depth, grad_transmittance, grad_shared_rgb, grad_shared_rgb_stride,
+                                  grad_depth_image, grad_depth_image_stride, grad_background, grad_background_stride, stream);
+}
+
 // The geometry backward over the two layouts: the layout's own struct checks (to_shared / to_depth, as its image backward), then the volume entry's.
 int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const float* grad_rgb, const float* grad_depth,
                                                     const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
@@ -860,6 +936,7 @@ int gmpi_query(int32_t what) {
         case 26: case 27: case 28: return depth_window_query(what);
         case 30: return 1;  // the geometry backward of the shared-colour and depth-alpha layouts is built in  (29: unused)
         case 32: return 1;  // compute_depth of the depth-alpha layout (gmpi_ramp_depth_launch, light_kernels.hip) is built in  (31: unused)
+        case 34: return 1;  // the atomics-free backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_*_backward_gather_launch) is built in  (33: unused)
         default: return -1;
     }
 }

@@ -369,7 +369,11 @@ _Kind = collections.namedtuple("_Kind", "name expand first geometry_entry")
 _SHARED_COLOUR = _Kind("shared-colour", "expand_shared_color", "alpha", "gmpi_mpi_render_shared_geometry_backward_launch")
 _DEPTH_ALPHA = _Kind("depth-alpha", "expand_depth_alpha", "depth", "gmpi_mpi_render_depth_geometry_backward_launch")
 # render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
-_DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch"}
+_DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch",
+                           "gather": "gmpi_mpi_render_depth_backward_launch"}
+# render_views_shared(shared_backward=...): likewise.  "gather" (both layouts): the atomics-free pair where it can take the launch, else the entry named here
+_SHARED_BACKWARD_ENTRIES = {"tile": "gmpi_mpi_render_shared_backward_launch", "gather": "gmpi_mpi_render_shared_backward_launch"}
+_GATHER_ENTRIES = {"shared-colour": "gmpi_mpi_render_shared_backward_gather_launch", "depth-alpha": "gmpi_mpi_render_depth_backward_gather_launch"}
 
 
 class _Layout:
@@ -377,11 +381,14 @@ class _Layout:
     shared-colour (`render_views`' first argument is then the alpha tensor [M,D,1,Ht,Wt]) or, with a `plane_z`, depth-alpha (the depth image as
     [M,1,1,Ht,Wt]; the planes are dhw's).  Built by `_shared_layout` / `_depth_layout` alone, which check what they put in: rgb, background: the
     caller's tensors; variant: the kernel asked for by name, or None = the module's own; backward_entry: the C entry of the image backward;
+    gather: the backward was asked for as "gather" -- the atomics-free pair (`_GATHER_ENTRIES`) where the library can take the launch, backward_entry
+    otherwise; gather_runs: a test-only override of the pair's plane runs per texel tile (None: the library's rule);
     depth-alpha only: plane_z (detached fp32 on the device, [D] or [M,D]), ramp = (z_lo, z_hi), depth_forward ("pixel", "window" or None)."""
 
-    def __init__(self, kind, rgb, background, variant, backward_entry, plane_z=None, ramp=None, depth_forward=None):
+    def __init__(self, kind, rgb, background, variant, backward_entry, plane_z=None, ramp=None, depth_forward=None, gather=False, gather_runs=None):
         self.kind, self.rgb, self.background, self.variant, self.backward_entry = kind, rgb, background, variant, backward_entry
         self.plane_z, self.ramp, self.depth_forward = plane_z, ramp, depth_forward
+        self.gather, self.gather_runs = gather, gather_runs
 
     @property
     def requires_grad(self) -> bool:
@@ -435,20 +442,24 @@ def _one_dtype(kind: _Kind, rgb, first, background) -> None:
         _refuse_uint8(f"the {kind.name} render", first)
 
 
-def _shared_layout(rgb, alpha, background, variant):
-    """`MPI.render_views_shared` / `MPIRenderer.render_shared`: (`render_views`' first argument, its `_layout`); the checks that need no launch."""
+def _shared_layout(rgb, alpha, background, variant, shared_backward="tile", gather_runs=None):
+    """`MPI.render_views_shared` / `MPIRenderer.render_shared`: (`render_views`' first argument, its `_layout`); the option name and the checks
+    that need no launch."""
+    if not isinstance(shared_backward, str) or shared_backward not in _SHARED_BACKWARD_ENTRIES:
+        raise ValueError(f'shared_backward is "tile" or "gather", not {shared_backward!r}')
     shared_color._check(rgb, alpha, background)
     _one_dtype(_SHARED_COLOUR, rgb, alpha, background)
-    return alpha, _Layout(_SHARED_COLOUR, rgb, background, variant, "gmpi_mpi_render_shared_backward_launch")
+    return alpha, _Layout(_SHARED_COLOUR, rgb, background, variant, _SHARED_BACKWARD_ENTRIES[shared_backward], gather=shared_backward == "gather",
+                          gather_runs=gather_runs)
 
 
-def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, variant, depth_backward, depth_forward):
+def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, variant, depth_backward, depth_forward, gather_runs=None):
     """`MPI.render_views_depth` / `MPIRenderer.render_depth`: (the depth image as the view [M,1,1,Ht,Wt], `render_views`' `_layout`); the option
     names and the checks that need no launch.  depth_forward None reads as "pixel"."""
     if variant not in (None, "auto", "gather"):
         raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
-    if depth_backward not in _DEPTH_BACKWARD_ENTRIES:
-        raise ValueError(f'depth_backward is "pixel" or "tile", not {depth_backward!r}')
+    if not isinstance(depth_backward, str) or depth_backward not in _DEPTH_BACKWARD_ENTRIES:
+        raise ValueError(f'depth_backward is "pixel", "tile" or "gather", not {depth_backward!r}')
     if depth_forward not in (None, "pixel", "window"):
         raise ValueError(f'depth_forward is "pixel" or "window", not {depth_forward!r}')
     depth_alpha._check(rgb, depth, plane_z, background)
@@ -458,7 +469,8 @@ def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, vari
     z_lo, z_hi = float(z_lo), float(z_hi)
     assert z_lo < z_hi, (z_lo, z_hi)
     return depth.unsqueeze(1), _Layout(_DEPTH_ALPHA, rgb, background, variant, _DEPTH_BACKWARD_ENTRIES[depth_backward],
-                                       _f32_on(plane_z.detach(), depth.device), (z_lo, z_hi), depth_forward)
+                                       _f32_on(plane_z.detach(), depth.device), (z_lo, z_hi), depth_forward, gather=depth_backward == "gather",
+                                       gather_runs=gather_runs)
 
 
 def _lend(p: _lib.GmpiRenderParams, ws: torch.Tensor) -> None:
@@ -517,6 +529,20 @@ def _warn_window_fallback() -> None:
         warnings.warn('depth-alpha render: depth_forward="window" cannot take these tensors (base pointers and outer strides must be multiples of '
                       "16 bytes); the one-pixel-per-lane kernel runs instead (counted in MPI.depth_window_fallbacks; this warning is given once)",
                       RuntimeWarning, stacklevel=5)
+
+
+_GATHER_FALLBACK_WARNED = False
+
+
+def _warn_gather_fallback(kind: _Kind) -> None:
+    """Once per process: a layout's backward was asked for as "gather" and the atomic kernels ran (every such backward is counted in
+    `MPI.layout_gather_fallbacks`)."""
+    global _GATHER_FALLBACK_WARNED
+    if not _GATHER_FALLBACK_WARNED:
+        _GATHER_FALLBACK_WARNED = True
+        warnings.warn(f'{kind.name} render: the "gather" backward cannot take this launch (it needs align_corners=True, uniform views per MPI and '
+                      "room for its scratch memory); the atomic kernels run instead and the gradients are not bit-reproducible (counted in "
+                      "MPI.layout_gather_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=2)
 
 
 def _warn_lds_fallback() -> None:
@@ -620,6 +646,7 @@ class MPI(nn.Module):
         self._full_check_passed = None   # (weakref to the volume's base tensor, fingerprint): see _volume_fingerprint
         self.shared_lds_fallbacks = 0    # shared-colour launches that asked for "lds" and ran AUTO's kernel instead (a debug counter)
         self.depth_window_fallbacks = 0  # depth-alpha launches that asked for depth_forward="window" and ran the one-pixel kernel instead
+        self.layout_gather_fallbacks = 0   # shared-colour / depth-alpha backwards that asked for "gather" and ran the atomic kernels instead
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -849,8 +876,15 @@ class MPI(nn.Module):
         "unchanged volume" cache is not kept for three tensors), and that pass reads contiguous memory: a strided alpha view such as
         `rgba[:, :, 3:]` is copied for it, D planes per call -- use the default "touched" where the no-copy property matters.  The tile
         backward (every variant but "gather", D <= 128) assumes a pinhole ray field like the other staged kernels; D > 128 takes the
-        one-pixel-per-lane backward, which is several times slower."""
-        alpha, layout = _shared_layout(rgb, alpha, background, variant)
+        one-pixel-per-lane backward, which is several times slower.
+        `shared_backward`: "tile" (the default) is the backward described above, which ends in global atomics; "gather" back-propagates with
+        gmpi_mpi_render_shared_backward_gather_launch -- a pixel pass that writes one record per pixel and plane into scratch memory (N D H W 24
+        bytes, allocated for the call), then a texel gather in which every gradient cell is written once by its one owner, the colour sums running
+        across the planes: no atomics, no zero-fill, the same bits in every run, the same gradients up to the order of the adds.  It takes
+        align_corners=True and uniform views per MPI; any other launch, and one whose scratch cannot be allocated, takes the "tile" path, counted
+        in `layout_gather_fallbacks`, one RuntimeWarning per process.  Any other name: ValueError.  `MPI(backward="gather")` names the volume
+        entry's backward only: it does not change this argument's default.  The forward does not depend on it."""
+        alpha, layout = _shared_layout(rgb, alpha, background, variant, kwargs.pop("shared_backward", "tile"), kwargs.pop("_gather_runs", None))
         return self.render_views(alpha, dhw, ray_dir, eye_pos, z_dir, _layout=layout, **kwargs)
 
     # -- depth-alpha layout ------------------------------------------------------------------------------------------------------------
@@ -870,7 +904,10 @@ class MPI(nn.Module):
         gmpi_mpi_render_depth_backward_tile_launch -- one workgroup per 32 x 16 pixel tile, the gradients of rgb and depth summed in LDS across
         the planes: the same gradients up to the order of the adds.  The tile backward assumes a pinhole ray field like the other staged kernels
         (any other gives correct gradients at the one-pixel kernel's speed) and takes D <= 128; with more planes, or with the "gather" variant,
-        the entry launches the one-pixel-per-lane kernel.  Any other name: ValueError.  The forward does not depend on it.
+        the entry launches the one-pixel-per-lane kernel.  "gather": gmpi_mpi_render_depth_backward_gather_launch, the atomics-free pair as
+        `render_views_shared(shared_backward="gather")` describes it (the depth gradient of all planes is one sum per texel, divided once): bit-
+        reproducible; launches it cannot take (align_corners=False, a ragged view_to_mpi, no room for the scratch) take the "pixel" path, counted
+        in `layout_gather_fallbacks`, one RuntimeWarning per process.  Any other name: ValueError.  The forward does not depend on it.
         `depth_forward`: "pixel" (the default, also None) renders with the one-pixel-per-lane kernel; "window" with
         gmpi_mpi_render_depth_window_launch -- one workgroup per 32 x 16 pixel tile, every tap read from one window of rgb and depth texels in LDS
         that moves with the tile's texel boxes, planes in front of the window's nearest depth skipped per tile: the same bits in both modes, the
@@ -879,7 +916,7 @@ class MPI(nn.Module):
         `depth_window_fallbacks`, one RuntimeWarning per process.  Any other name: ValueError.  The backward does not depend on it."""
         # (variant None: the module's own, read as render_views_shared reads it -- "gather", or the library's choice)
         depth5, layout = _depth_layout(rgb, depth, plane_z, z_bounds, background, dhw.shape[1], kwargs.pop("variant", None),
-                                       kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"))
+                                       kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"), kwargs.pop("_gather_runs", None))
         return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _layout=layout, **kwargs)
 
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
@@ -1050,7 +1087,8 @@ def _ptr_stride(t: Optional[torch.Tensor], dims):
 class _LayoutRenderFunction(torch.autograd.Function):
     """autograd bridge of the shared-colour and depth-alpha renders (`kwargs["_layout"]` says which), built like `_RenderFunction`: forward = the
     layout's forward entry, backward = its image entry (gmpi_mpi_render_shared_backward_launch; gmpi_mpi_render_depth_backward_launch or, with
-    depth_backward="tile", gmpi_mpi_render_depth_backward_tile_launch) into zero-filled fp32 gradients of rgb, the alpha tensor / depth image and
+    depth_backward="tile", gmpi_mpi_render_depth_backward_tile_launch; with "gather" the layout's _backward_gather_launch entry into gradients it
+    overwrites, where the library can take the launch) into zero-filled fp32 gradients of rgb, the alpha tensor / depth image and
     the background -- those that need one: the others are passed as NULL and skipped by the kernel, and the launch is skipped when none does.
     Saved tensors (plane_z among them), private T buffer, unused outputs as None: as there.  For a module with geometry_grad="all" the node is
     also recorded when only dhw or a camera tensor requires grad, and its backward ends with the layout's geometry entry: one extra launch."""
@@ -1061,6 +1099,7 @@ class _LayoutRenderFunction(torch.autograd.Function):
         res, keep, (rgb_k, bg_k) = _bridge_forward(ctx, mpi, mid, (dhw, ray_dir, eye_pos, z_dir), kwargs)
         ctx.save_for_backward(keep.rgba, rgb_k, *keep[1:5], res["T"], bg_k, keep.view_to_mpi, layout.plane_z)   # (None where there is none)
         ctx.backward_entry, ctx.geometry_entry, ctx.ramp = layout.backward_entry, layout.kind.geometry_entry, layout.ramp
+        ctx.gather, ctx.gather_runs, ctx.kind, ctx.mpi = layout.gather, layout.gather_runs, layout.kind, mpi
         ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, mid, background)]
         ctx.geometry = mpi.geometry_grad_layouts
         ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
@@ -1083,9 +1122,35 @@ class _LayoutRenderFunction(torch.autograd.Function):
             p = _render_params(ctx.scalars, keep, T=T)
             image = (p.M, 3, p.Ht, p.Wt)
             mid_shape, mid_dims = ((p.M, p.D, 1, p.Ht, p.Wt), (0, 1, 3)) if plane_z is None else ((p.M, 1, p.Ht, p.Wt), (0, 1, 2))   # alpha planes | depth image
-            grads = [torch.zeros(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip((image, mid_shape, image), want)]
-            _call(ctx.backward_entry, dev, ctypes.byref(p), *structs, *upstream,
-                  *_ptr_stride(grads[0], (0, 1, 2)), *_ptr_stride(grads[1], mid_dims), *_ptr_stride(grads[2], (0, 1, 2)))
+            # "gather": with the scratch memory the library asks for, the atomics-free pair WRITES every element of the wanted gradients -- no
+            # zero-fill, bit-reproducible (render_backward_gather.hip).  A launch it cannot take (the query answers 0: align_corners=False, a ragged
+            # view list) or whose scratch cannot be allocated takes the layout's atomic entry into zero-filled gradients, counted and warned of once.
+            entry, ws, lib = ctx.backward_entry, None, _lib.load_library()
+            forced = ctx.gather and ctx.gather_runs is not None   # (tests: a fixed number of plane runs for the query and the launch below)
+            if forced:
+                lib.gmpi_render_layout_backward_gather_set_runs(int(ctx.gather_runs))
+            try:
+                if ctx.gather:
+                    need = int(lib.gmpi_render_layout_backward_gather_workspace_bytes(ctypes.byref(p), *structs, *((None,) if plane_z is None else ())))
+                    if need:
+                        try:
+                            ws = torch.empty(need, dtype=torch.uint8, device=dev)   # (512-byte aligned blocks; freed with this call)
+                        except torch.cuda.OutOfMemoryError:
+                            ws = None                                                # (no room for the scratch: the atomic path needs none)
+                    if ws is None:
+                        ctx.mpi.layout_gather_fallbacks += 1
+                        _warn_gather_fallback(ctx.kind)
+                    else:
+                        _lend(p, ws)
+                        p.flags |= _lib.FLAG_GRAD_OVERWRITE
+                        entry = _GATHER_ENTRIES[ctx.kind.name]
+                alloc = torch.zeros if ws is None else torch.empty
+                grads = [alloc(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip((image, mid_shape, image), want)]
+                _call(entry, dev, ctypes.byref(p), *structs, *upstream,
+                      *_ptr_stride(grads[0], (0, 1, 2)), *_ptr_stride(grads[1], mid_dims), *_ptr_stride(grads[2], (0, 1, 2)))
+            finally:
+                if forced:
+                    lib.gmpi_render_layout_backward_gather_set_runs(0)
             out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
         geo = [None] * 4
         if any(geo_want):   # a module with geometry_grad="all": the geometry pass with the layout's structs

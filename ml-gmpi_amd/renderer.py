@@ -474,8 +474,11 @@ class MPIRenderer:
         generator holds before it concatenates): batch_mpi_rgb [B,3,Ht,Wt], batch_mpi_alpha [B,D,1,Ht,Wt] (may be the view `rgba[:, :, 3:]`),
         background_rgb [B,3,Ht,Wt] or None = the last plane's own colour.  Keyword arguments, return tuple, pose sampling and the consumption of
         the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the expanded volume.  `variant`: the kernel, as
-        in `MPI.render_views_shared` (None: the renderer's own; "lds": the staged forward)."""
-        alpha, layout = _shared_layout(batch_mpi_rgb, batch_mpi_alpha, background_rgb, variant)
+        in `MPI.render_views_shared` (None: the renderer's own; "lds": the staged forward).  `shared_backward`: "tile" (default) or "gather", as
+        in `MPI.render_views_shared` -- "gather" back-propagates without atomics (bit-reproducible gradients); any other name is a ValueError
+        before anything is launched."""
+        alpha, layout = _shared_layout(batch_mpi_rgb, batch_mpi_alpha, background_rgb, variant, kwargs.pop("shared_backward", "tile"),
+                                       kwargs.pop("_gather_runs", None))
         return self.render(alpha, render_h, render_w, _layout=layout, **kwargs)
 
 
@@ -484,15 +487,17 @@ class MPIRenderer:
         without building it (the output of GMPI's "depth2alpha" generator): batch_rgb [B,3,Ht,Wt], batch_depth [B,1,Ht,Wt], background_rgb
         [B,3,Ht,Wt] or None = the last plane's own colour.  plane_z [D] or [B,D]: None takes this renderer's normalised plane depths,
         `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with.  Keyword arguments, return tuple, pose
-        sampling and the consumption of the torch RNG are `render`'s.  `depth_backward`: "pixel" (default) or "tile", as in
+        sampling and the consumption of the torch RNG are `render`'s.  `depth_backward`: "pixel" (default), "tile" or "gather", as in
         `MPI.render_views_depth` -- the tile backward assumes a pinhole ray field (this renderer's rays are one) and takes D <= 128, else the
-        one-pixel-per-lane kernel runs; any other name is a ValueError before anything is launched.  `depth_forward`: "pixel" (default) or
+        one-pixel-per-lane kernel runs; "gather" back-propagates without atomics (bit-reproducible gradients); any other name is a ValueError
+        before anything is launched.  `depth_forward`: "pixel" (default) or
         "window", as in `MPI.render_views_depth` -- the window forward gives the same bits."""
         from .depth_alpha import depth_alpha_bounds
         if plane_z is None:
             plane_z = self.get_xyz_single_res(batch_depth.shape[-2], batch_depth.shape[-1], only_z=True)[1].reshape(-1)
         depth5, layout = _depth_layout(batch_rgb, batch_depth, plane_z, depth_alpha_bounds(z_range, n_z_bins), background_rgb,
-                                       self.dynamic_mpi_plane_dhws.shape[0], None, kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"))
+                                       self.dynamic_mpi_plane_dhws.shape[0], None, kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"),
+                                       kwargs.pop("_gather_runs", None))
         return self.render(depth5, render_h, render_w, _layout=layout, **kwargs)
 
 

@@ -8,6 +8,11 @@ several planes wide) and 256 (a step).
            32 x 16 pixel tile, one LDS window for all planes): columns `depth_bwd_tile`, `depth_total_tile`.  The two depth backwards are timed
            ALTERNATELY in the same child (pixel, tile, pixel, tile, ...), and their gradients are compared per image (`tile_check`: the largest
            |tile - pixel| / (1e-5 max|pixel| + 1e-7) over the three images, <= 1 passes; a failure ends the run)
+  depth, atomics-free pair    the same forward with gmpi_mpi_render_depth_backward_gather_launch (render_backward_gather.hip: pixel pass + texel gather,
+           every gradient cell written once: no zero-fill): columns `depth_bwd_pair`, `depth_total_pair` (forward + pair), `pair_ws_mb` (the scratch it is
+           lent), `pair_peak_mb` (peak memory of one pass, scratch included), `pair_runs` (plane runs per texel tile).  `pair_check`: the largest
+           |pair - pixel| / (1e-5 max|pixel| + 1e-7) over the three images (<= 1 passes), `pair_repro`: 1 when two launches give the same bits; anything
+           else ends the run
   volume   expand_depth_alpha (the ramp + the generator's expand and two cat), forward (variant auto), zero-fill of the volume gradient, volume backward
            (tile kernels), autograd through the expand (plane sums of the colour gradient, the clamp's mask and the plane sum for the depth)
   shared   the alpha planes materialised (depth_alpha_planes), render_views_shared (variant auto: one pixel per lane), zero-fill of the three gradients,
@@ -20,7 +25,8 @@ several planes wide) and 256 (a step).
            A last shape is the 8-view camera path of ONE 512^2 x 96 MPI (views_per_mpi = 8), forward only.
 
 and the peak device memory of one pass of each above the inputs (torch.cuda.max_memory_allocated).  Every shape runs in a child process of its own under a
-time limit; the first failure ends the run.  usage: python tools/time_depth_alpha.py [--forward] [reps] [passes]   (--forward: no backward at any shape)"""
+time limit; the first failure ends the run.  usage: python tools/time_depth_alpha.py [--forward | --backward] [reps] [passes]   (--forward: no backward at
+any shape; --backward: only the shapes with a backward)"""
 import ctypes
 import os
 import subprocess
@@ -183,6 +189,35 @@ def one(S, B, D, n_z_bins, with_backward, reps, views=1):
         del want
     torch.cuda.synchronize()
     row["depth_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    if with_backward:
+        # the atomics-free pair: its scratch, one pass's peak memory, twice the same bits, and its results at the timed size against the one-pixel kernel's
+        pg = backward_struct(p)
+        pg.variant = _lib.VARIANT_AUTO
+        need = int(lib.gmpi_render_layout_backward_gather_workspace_bytes(ctypes.byref(pg), ctypes.byref(sc), ctypes.byref(da)))
+        assert need > 0, "the pair does not take this launch"
+        row["pair_runs"] = int(lib.gmpi_render_layout_backward_gather_runs(ctypes.byref(pg), ctypes.byref(sc), ctypes.byref(da)))
+        torch.cuda.reset_peak_memory_stats(dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        pg.workspace, pg.workspace_bytes = ws.data_ptr(), need
+        pg.flags |= _lib.FLAG_GRAD_OVERWRITE
+        dbwd_pair = lambda: _lib.check(lib.gmpi_mpi_render_depth_backward_gather_launch(
+            ctypes.byref(pg), ctypes.byref(sc), ctypes.byref(da), gc.data_ptr(), gd.data_ptr(), None, d_rgb.data_ptr(), st[0], d_dep.data_ptr(), st[1],
+            d_bg.data_ptr(), st[2], cs), "depth backward, atomics-free pair")
+        for t in (d_rgb, d_dep, d_bg):
+            t.fill_(float("nan"))
+        dbwd_pair()
+        torch.cuda.synchronize()
+        row["pair_ws_mb"] = need / 2 ** 20
+        row["pair_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20   # outputs, gradients and the scratch: depth_peak_mb + pair_ws_mb
+        first = [t.clone() for t in (d_rgb, d_dep, d_bg)]
+        dbwd_pair()
+        row["pair_repro"] = int(all(torch.equal(t, f) for t, f in zip((d_rgb, d_dep, d_bg), first)))
+        for t in (d_rgb, d_dep, d_bg):
+            t.zero_()
+        dbwd()
+        row["pair_check"] = max(float((f - w).abs().max()) / (1e-5 * float(w.abs().max()) + 1e-7) for f, w in zip(first, (d_rgb, d_dep, d_bg)))
+        assert row["pair_check"] <= 1.0 and row["pair_repro"] == 1, ("the pair against the one-pixel backward", row["pair_check"], row["pair_repro"])
+        del first
     with torch.no_grad():
         # the two forwards at the timed size: the window kernel must give the one-pixel kernel's bits
         fwd = lambda how: lambda: r.mpi.render_views_depth(rgb, depth, plane_z, zb, dhw, ray, eye, zd, background=bg, out=out, depth_forward=how, **kw)
@@ -205,6 +240,10 @@ def one(S, B, D, n_z_bins, with_backward, reps, views=1):
         row["shared_total"] = row["shared_planes"] + row["shared_fwd"] + row["shared_fill"] + row["shared_bwd"] + row["shared_planes_bwd"]
         row["depth_total"] = row["depth_fwd"] + row["depth_fill"] + row["depth_bwd"]
         row["depth_total_tile"] = row["depth_fwd"] + row["depth_fill"] + row["depth_bwd_tile"]
+        row["depth_bwd_pair"] = timed(dbwd_pair)
+        row["depth_total_pair"] = row["depth_fwd"] + row["depth_bwd_pair"]   # (no zero-fill: every cell is written)
+        row["pair_vs_fill_plus_pixel"] = row["depth_bwd_pair"] / (row["depth_fill"] + row["depth_bwd"])
+        row["pair_vs_fill_plus_tile"] = row["depth_bwd_pair"] / (row["depth_fill"] + row["depth_bwd_tile"])
     row["fwd_vs_volume"] = row["depth_fwd"] / (row["volume_expand"] + row["volume_fwd"])
     row["fwd_vs_shared"] = row["depth_fwd"] / (row["shared_planes"] + row["shared_fwd"])
     row["fwd_vs_auto_on_existing_volume"] = row["depth_fwd"] / row["volume_fwd"]
@@ -222,14 +261,16 @@ if __name__ == "__main__":
         S, B, D, n, bw, reps, views = sys.argv[2:9]
         one(int(S), int(B), int(D), int(n), int(bw), int(reps), int(views))
         sys.exit(0)
-    argv = [a for a in sys.argv[1:] if a != "--forward"]
-    forward_only = len(argv) != len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if a not in ("--forward", "--backward")]
+    forward_only, backward_only = "--forward" in sys.argv[1:], "--backward" in sys.argv[1:]
     reps = argv[0] if len(argv) > 0 else "15"
     passes = int(argv[1]) if len(argv) > 1 else 3
     print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape;", passes, "passes")
     for k in range(passes):
         print(f"== pass {k + 1} ==", flush=True)
         for S, B, D, bw, views in SHAPES:
+            if backward_only and not bw:
+                continue
             for n in N_Z_BINS:
                 try:
                     rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), str(n), str(0 if forward_only else bw), reps, str(views)], timeout=240).returncode

@@ -6,9 +6,14 @@ The shared forward is timed twice: the one-pixel-per-lane kernel ("shared_fwd": 
   baseline  materialise the expanded volume as the generator does (expand + two cat), forward (variant auto), zero-fill of the volume gradient,
             volume backward (tile kernels), plane sum of the colour gradient (the backward of the generator's expand)
   shared    forward, zero-fill of the three gradients, shared backward: one-pixel-per-lane kernel ("gather") and tile kernel separately
+  shared, atomics-free pair    the same forward with gmpi_mpi_render_shared_backward_gather_launch (render_backward_gather.hip: pixel pass + texel gather,
+            every gradient cell written once: no zero-fill): columns `shared_bwd_pair`, `shared_total_pair` (forward + pair), `pair_ws_mb` (the scratch
+            it is lent), `pair_peak_mb` (peak memory of one pass, scratch included), `pair_runs` (plane runs per texel tile).  `pair_check`: the largest
+            |pair - tile| / (1e-5 max|tile| + 1e-7) over the three gradients (<= 1 passes), `pair_repro`: 1 when two launches give the same bits;
+            anything else ends the run
 
 and the peak device memory of one pass of each (torch.cuda.max_memory_allocated).  Every shape runs in a child process of its own under a time
-limit; the first failure ends the run.  usage: python tools/time_shared_color.py [reps]"""
+limit; the first failure ends the run.  usage: python tools/time_shared_color.py [--backward] [reps] [passes]   (--backward: only the shapes with a backward)"""
 import ctypes
 import os
 import subprocess
@@ -116,6 +121,36 @@ def one(S, B, D, dtype_name, with_backward, reps, V=1):
         tile()
     torch.cuda.synchronize()
     row["shared_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20
+    if with_backward:
+        # the atomics-free pair: its scratch, one pass's peak memory, twice the same bits, and its results at the timed size against the tile kernel's
+        qp = _lib.GmpiRenderParams.from_buffer_copy(p)
+        qp.rgb_out = qp.depth_out = qp.status = None
+        qp.variant = _lib.VARIANT_AUTO
+        need = int(lib.gmpi_render_layout_backward_gather_workspace_bytes(ctypes.byref(qp), ctypes.byref(sc), None))
+        assert need > 0, "the pair does not take this launch"
+        row["pair_runs"] = int(lib.gmpi_render_layout_backward_gather_runs(ctypes.byref(qp), ctypes.byref(sc), None))
+        torch.cuda.reset_peak_memory_stats(dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        qp.workspace, qp.workspace_bytes = ws.data_ptr(), need
+        qp.flags |= _lib.FLAG_GRAD_OVERWRITE
+        pair = lambda: _lib.check(lib.gmpi_mpi_render_shared_backward_gather_launch(
+            ctypes.byref(qp), ctypes.byref(sc), gc.data_ptr(), gd.data_ptr(), None, g_rgb.data_ptr(), strides[0], g_alpha.data_ptr(), strides[1],
+            g_bg.data_ptr(), strides[2], cs), "shared backward, atomics-free pair")
+        for t in (g_rgb, g_alpha, g_bg):
+            t.fill_(float("nan"))
+        pair()
+        torch.cuda.synchronize()
+        row["pair_ws_mb"] = need / 2 ** 20
+        row["pair_peak_mb"] = (torch.cuda.max_memory_allocated(dev) - base_mem) / 2 ** 20   # outputs, gradients and the scratch: shared_peak_mb + pair_ws_mb
+        first = [t.clone() for t in (g_rgb, g_alpha, g_bg)]
+        pair()
+        row["pair_repro"] = int(all(torch.equal(t, f) for t, f in zip((g_rgb, g_alpha, g_bg), first)))
+        for t in (g_rgb, g_alpha, g_bg):
+            t.zero_()
+        tile()
+        row["pair_check"] = max(float((f - w).abs().max()) / (1e-5 * float(w.abs().max()) + 1e-7) for f, w in zip(first, (g_rgb, g_alpha, g_bg)))
+        assert row["pair_check"] <= 1.0 and row["pair_repro"] == 1, ("the pair against the tile backward", row["pair_check"], row["pair_repro"])
+        del first
     with torch.no_grad():
         row["shared_fwd"] = timed(lambda: r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, **kw))
         staged = r.mpi.render_views_shared(rgb, alpha, dhw, ray, eye, zd, background=bg, out=out, variant="lds", _in_autograd_fn=True, **kw)
@@ -128,6 +163,9 @@ def one(S, B, D, dtype_name, with_backward, reps, V=1):
         row["shared_fill"] = timed(lambda: (g_rgb.zero_(), g_alpha.zero_(), g_bg.zero_()))
         row["shared_bwd_tile"] = timed(tile)
         row["shared_bwd_gather"] = timed(gather)
+        row["shared_bwd_pair"] = timed(pair)
+        row["shared_total_pair"] = row["shared_fwd"] + row["shared_bwd_pair"]   # (no zero-fill: every cell is written)
+        row["pair_vs_fill_plus_tile"] = row["shared_bwd_pair"] / (row["shared_fill"] + row["shared_bwd_tile"])
         row["base_total"] = row["base_expand"] + row["base_fwd"] + row["base_fill"] + row["base_bwd"] + row["base_sum"]
         row["shared_total_tile"] = row["shared_fwd"] + row["shared_fill"] + row["shared_bwd_tile"]
         row["shared_total_gather"] = row["shared_fwd"] + row["shared_fill"] + row["shared_bwd_gather"]
@@ -144,13 +182,20 @@ if __name__ == "__main__":
         S, B, D, dt, bw, reps, V = sys.argv[2:9]
         one(int(S), int(B), int(D), dt, int(bw), int(reps), int(V))
         sys.exit(0)
-    reps = sys.argv[1] if len(sys.argv) > 1 else "15"
-    print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape")
-    for S, B, D, dt, bw, V in SHAPES:
-        try:
-            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), dt, str(bw), reps, str(V)], timeout=240).returncode
-        except subprocess.TimeoutExpired:   # (run() has killed the child)
-            rc = "time limit of 240 s"
-        if rc != 0:
-            print(f"shape {S} x {B} x {D} {dt}: exit status {rc}; stopping")
-            sys.exit(1)
+    argv = [a for a in sys.argv[1:] if a != "--backward"]
+    backward_only = len(argv) != len(sys.argv) - 1
+    reps = argv[0] if len(argv) > 0 else "15"
+    passes = int(argv[1]) if len(argv) > 1 else 1
+    print("times in ms (medians of", reps, "runs after 3 warm-up runs), memory in MiB above the inputs; one child process per shape;", passes, "pass(es)")
+    for k in range(passes):
+        print(f"== pass {k + 1} ==", flush=True)
+        for S, B, D, dt, bw, V in SHAPES:
+            if backward_only and not bw:
+                continue
+            try:
+                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", S, str(B), str(D), dt, str(bw), reps, str(V)], timeout=240).returncode
+            except subprocess.TimeoutExpired:   # (run() has killed the child)
+                rc = "time limit of 240 s"
+            if rc != 0:
+                print(f"shape {S} x {B} x {D} {dt}: exit status {rc}; stopping")
+                sys.exit(1)
