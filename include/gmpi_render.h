@@ -230,6 +230,56 @@ int gmpi_mpi_render_backward_ex_launch(const GmpiRenderParams *params, const flo
 uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams *params);
 
 /*
+ * The plane-chunked render: the stack [M, D, 4, Ht, Wt] never exists as one tensor (the reference's render_video.py:55-77 generates `chunk_n_planes` planes
+ * at a time and has to torch.cat them only because MPI.forward cannot composite a stack piece by piece).  The composite is associative over the plane
+ * axis: a partial (C, Z, T) per pixel is all that passes from one plane range to the next.  One launch renders ONE chunk, front chunks first.
+ *   params   describes the chunk: D, rgba (+ strides) and dhw are the chunk's own -- the chunk's tensor and the chunk's rows [M, D, 3] of the plane table.
+ *   carry    state_in: the state behind the planes in front of this chunk, [N, 5, H, W] fp32, or NULL: the stack starts here (T = 1, sums 0).
+ *            state_out: [N, 5, H, W] fp32, or NULL: not wanted (the last chunk).  state_in == state_out is allowed: a lane reads and writes its own pixel.
+ * The five channels are the kernels' raw accumulator after the planes so far: r, g, b, z, T.  Colour is in [0, 1] -- never GMPI_FLAG_OUT_PM1's form --, z is
+ * in the launch mode's own form: with GMPI_FLAG_STRICT_ORDER sum w_k depth_k, without it sum w_k s_k, BEFORE the per-pixel factor ray . z_dir.  The state is
+ * OPAQUE: do not interpret it, and consume a state in the mode (GMPI_FLAG_STRICT_ORDER set or not) that produced it.
+ * rgb_out, depth_out and transmittance_out may each be NULL here.  When given they receive the FINISHED images of the stack so far (the epilogue of
+ * gmpi_mpi_render_launch; GMPI_FLAG_OUT_PM1 applies only there): transmittance_out is the T behind the chunk, which the chunk backward wants.  state_out and all
+ * three outputs NULL: GMPI_E_NULL.  GMPI_FLAG_CHECK_LAST_PLANE refers to the last plane of THIS launch: set it on the final chunk only.  Status bits
+ * OR-accumulate as ever (GMPI_STATUS_CAMERA_BEHIND_PLANE looks at the chunk's planes).
+ * Kernels: GMPI_VARIANT_GATHER and GMPI_VARIANT_LDS for fp32 / bf16 / fp16 and for GMPI_DTYPE_U8, planar and channels-last (the kernels and conditions of
+ * gmpi_mpi_render_launch, in instances of their own); GMPI_VARIANT_AUTO is LDS where the tile kernel takes the tensors, else GATHER, whatever the launch
+ * size and the camera hints; WAVE and BAND are GMPI_E_VARIANT (the strip kernel splits the plane axis itself; the band kernel has no carry yet).  No
+ * workspace is read.  With GMPI_FLAG_STRICT_ORDER the chunked render has the bits of the one-shot render of the concatenation with the same variant, however
+ * the stack is cut; without it too, as long as the tile kernel stages the same planes.  gmpi_query(36) == 1 says the entries are built in.
+ */
+typedef struct GmpiCarry {
+    uint32_t struct_size;    /* = sizeof(GmpiCarry) */
+    uint32_t reserved;       /* 0 */
+    const float *state_in;   /* [N,5,H,W] fp32 or NULL: the stack starts here (T = 1, sums 0) */
+    float *state_out;        /* [N,5,H,W] fp32 or NULL: not wanted (the last chunk) */
+} GmpiCarry;
+int gmpi_mpi_render_chunk_launch(const GmpiRenderParams *params, const GmpiCarry *carry, void *stream);
+
+/*
+ * Gradient of a chunked render w.r.t. ONE chunk; chunks are swept from the last to the first.  `params` are the chunk's forward parameters;
+ * params->transmittance_out is T BEHIND the chunk as the forward launch wrote it (NULL: rebuilt from T_in by a walk of the chunk's alpha).  grad_rgb,
+ * grad_depth, grad_transmittance are the gradients w.r.t. the FINAL images (grad_depth NULL or given to every chunk; grad_transmittance to the LAST chunk
+ * only, NULL elsewhere; the GMPI_FLAG_OUT_PM1 factor is applied as in gmpi_mpi_render_backward_launch when the flag is set in params -- set it for every
+ * chunk of a stack whose final colour was written with it).
+ *   T_in   [N,1,H,W] T in front of the chunk (the transmittance_out of the chunk in front), or NULL = 1 (the first chunk)
+ *   S_in   [N,1,H,W] the suffix sum handed over by the chunk behind, or NULL = 0 (the last chunk)
+ *   S_out  [N,1,H,W] or NULL: the suffix sum in front of this chunk's first plane.  S_in == S_out is allowed.
+ * The sweep is gmpi_mpi_render_backward_ex_launch's, continued instead of started: T starts at the boundary value, S = S_in + gT T_behind, and
+ * dL/da_k = T_k q_k - S_k / om_k, dL/drgb_k = g w_k hold unchanged with the GLOBAL T_k and S_k (every later plane is linear in the T that reaches it).
+ * Underflow: where T behind the chunk is below 1e-30, T is rebuilt in mantissa x 2^exponent form by walking the chunk's alpha from T_in instead of from 1.
+ * Where T_in is below 1e-30 too (zero and denormals included) the pixel contributes nothing from this chunk: its volume gradients are zero and
+ * S_out = S_in.  The terms dropped are below 1e-20 D |q|.
+ * variant GATHER selects the one-pixel-per-lane all-atomic kernel, anything else the 64 x 8 tile kernel; grad_rgba [M,D,4,Ht,Wt] of the CHUNK, fp32, is
+ * accumulated into (the caller zero-fills it).  The atomics-free pair, the geometry backward and the two image layouts have no chunk form.
+ * GMPI_DTYPE_U8: GMPI_E_DTYPE.  N == 0: GMPI_OK.  N > 65535: GMPI_E_SHAPE.
+ */
+int gmpi_mpi_render_chunk_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                          const float *grad_transmittance, const float *T_in, const float *S_in, float *S_out,
+                                          float *grad_rgba, const int64_t *grad_rgba_stride, void *stream);
+
+/*
  * Gradient of the render w.r.t. the sample POSITIONS (an extension: the reference builds the grid under torch.no_grad(), mpi.py:65):
  * the rays, the eye positions, the optical axes and the plane geometry.  `params`, grad_rgb, grad_depth and transmittance_out as for
  * gmpi_mpi_render_backward_launch.  Per view n, pixel, plane k, with s = (d_k - ez)/rz, x = ex + rx s, y = ey + ry s, depth_k = s (r . z_dir),
@@ -636,7 +686,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * its box table; 29 is unused (-1); 30 whether the geometry backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_shared_geometry_backward_launch,
  * gmpi_mpi_render_depth_geometry_backward_launch) is built in; 31 is unused (-1); 32 whether compute_depth of the depth-alpha layout
  * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in; 33 is unused (-1); 34 whether the atomics-free backward of the shared-colour
- * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in.  Unknown -> -1.  */
+ * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in; 35 is unused (-1); 36 whether the plane-chunked render (gmpi_mpi_render_chunk_launch,
+ * gmpi_mpi_render_chunk_backward_launch) is built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

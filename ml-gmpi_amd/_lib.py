@@ -32,6 +32,8 @@ EXPORTS = (
     "gmpi_mpi_render_geometry_backward_launch",
     "gmpi_mpi_render_backward_ex_launch",
     "gmpi_mpi_render_geometry_backward_ex_launch",
+    "gmpi_mpi_render_chunk_launch",
+    "gmpi_mpi_render_chunk_backward_launch",
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
@@ -96,6 +98,14 @@ class GmpiRenderParams(ctypes.Structure):
         ("rgb_out", ctypes.c_void_p), ("depth_out", ctypes.c_void_p), ("transmittance_out", ctypes.c_void_p),
         ("status", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+class GmpiCarry(ctypes.Structure):
+    """Field-for-field mirror of `struct GmpiCarry` in include/gmpi_render.h: the per-pixel state a plane-chunked render hands from launch to launch."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p),
     ]
 
 
@@ -212,6 +222,11 @@ def load_library():
                                                        ctypes.POINTER(ctypes.c_int64), vp]
     lib.gmpi_mpi_render_geometry_backward_ex_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gmpi_mpi_render_chunk_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_chunk_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiCarry), vp]
+    lib.gmpi_mpi_render_chunk_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_chunk_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp,
+                                                          ctypes.POINTER(ctypes.c_int64), vp]
     lib.gmpi_mpi_render_shared_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp]
     i64p = ctypes.POINTER(ctypes.c_int64)

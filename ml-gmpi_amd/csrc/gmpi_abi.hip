@@ -12,6 +12,11 @@ namespace gmpi {
 
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream);  // render_gather.hip
 hipError_t launch_lds(const KParams& p, int dtype, int tune, hipStream_t stream);  // render_lds.hip
+hipError_t launch_gather_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream);   // render_gather.hip
+hipError_t launch_lds_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream);      // render_lds.hip
+hipError_t launch_u8_chunk(const KParams& p, const CarryK& carry, hipStream_t stream);                  // render_u8.hip
+hipError_t launch_backward_chunk(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, const float* T_in, const float* S_in,
+                                 float* S_out, float* g_rgba, const int64_t* gstride, bool tiles, hipStream_t stream);   // render_backward.hip
 hipError_t launch_backward(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
                            const int64_t* gstride, bool tiles, hipStream_t stream);  // render_backward.hip
 bool lds_variant_supports(const KParams& p, int dtype);                     // render_lds.hip
@@ -484,6 +489,47 @@ int gmpi_mpi_render_backward_ex_launch(const GmpiRenderParams* params, const flo
                                   params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the plane-chunked render: one chunk of the stack per launch, the per-pixel state (forward: Accum; backward: T and S) handed from launch to launch ----
+int gmpi_mpi_render_chunk_launch(const GmpiRenderParams* params, const GmpiCarry* carry, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;  // no views
+    KParams p;
+    const int rc = to_kparams(params, p, false, true, true);
+    if (rc != GMPI_OK) return rc;
+    if (carry == nullptr) return GMPI_E_NULL;
+    if (carry->struct_size != sizeof(GmpiCarry)) return GMPI_E_ABI;
+    int variant = params->variant;
+    if (variant == GMPI_VARIANT_WAVE || variant == GMPI_VARIANT_BAND) return GMPI_E_VARIANT;   // (the strip kernel splits the plane axis itself; the band kernel: a follow-up)
+    if (variant != GMPI_VARIANT_AUTO && variant != GMPI_VARIANT_GATHER && variant != GMPI_VARIANT_LDS) return GMPI_E_VARIANT;
+    if (carry->state_out == nullptr && p.rgb_out == nullptr && p.depth_out == nullptr && p.T_out == nullptr) return GMPI_E_NULL;   // nothing to write
+    const CarryK ck{carry->state_in, carry->state_out};
+    p.ws = nullptr, p.ws_bytes = 0;   // no kernel of this entry wants scratch
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool u8 = params->rgba_dtype == GMPI_DTYPE_U8;
+    const bool staged = u8 ? u8_variant_supports(p) : lds_variant_supports(p, params->rgba_dtype);
+    if (variant == GMPI_VARIANT_AUTO) variant = staged ? GMPI_VARIANT_LDS : GMPI_VARIANT_GATHER;
+    if (variant == GMPI_VARIANT_GATHER) {
+        if (p.N > 65535) return GMPI_E_SHAPE;  // the gather kernel puts the view index in grid.z
+        return hip_rc(launch_gather_chunk(p, ck, params->rgba_dtype, st));
+    }
+    if (!staged) return GMPI_E_VARIANT;   // LDS: these tensors are not aligned for its loader
+    return hip_rc(u8 ? launch_u8_chunk(p, ck, st) : launch_lds_chunk(p, ck, params->rgba_dtype, st));
+}
+
+int gmpi_mpi_render_chunk_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, const float* grad_transmittance,
+                                          const float* T_in, const float* S_in, float* S_out, float* grad_rgba, const int64_t* grad_rgba_stride, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;
+    KParams p;
+    const int rc = to_kparams(params, p, false, true);   // (GMPI_DTYPE_U8: GMPI_E_DTYPE)
+    if (rc != GMPI_OK) return rc;
+    if (grad_rgb == nullptr || grad_rgba == nullptr || grad_rgba_stride == nullptr) return GMPI_E_NULL;
+    if (p.N > 65535) return GMPI_E_SHAPE;  // both backward kernels put the view index in grid.y / grid.z: split the batch
+    if (grad_rgba_stride[4] != 1) return GMPI_E_STRIDE;
+    for (int i = 0; i < 4; ++i)
+        if (grad_rgba_stride[i] <= 0 && !(i == 0 && params->M == 1)) return GMPI_E_STRIDE;
+    return hip_rc(launch_backward_chunk(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, T_in, S_in, S_out, grad_rgba, grad_rgba_stride,
+                                        params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
+}
+
 uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams* params, int want_dhw) {
     KParams p;
     if (to_kparams(params, p, false, true) != GMPI_OK || p.N == 0) return 0;
@@ -937,6 +983,7 @@ int gmpi_query(int32_t what) {
         case 30: return 1;  // the geometry backward of the shared-colour and depth-alpha layouts is built in  (29: unused)
         case 32: return 1;  // compute_depth of the depth-alpha layout (gmpi_ramp_depth_launch, light_kernels.hip) is built in  (31: unused)
         case 34: return 1;  // the atomics-free backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_*_backward_gather_launch) is built in  (33: unused)
+        case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }
 }

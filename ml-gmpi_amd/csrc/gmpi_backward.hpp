@@ -4,7 +4,8 @@
 // section 3.3 -- the forward's quotients and texels, bit-reproducible gather and geometry passes, gT entering S in every sweep -- hold because they
 // all run THIS code:
 //   BwdView / bwd_view              what is uniform over a view: the forward's View / view_setup (gmpi_device.hpp)
-//   BwdPixel / bwd_pixel_setup(_with)   the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T
+//   BwdPixel / bwd_pixel_setup(_with)   the per-pixel state: ray, dot, upstream gradients (OUT_PM1 applied), T = T_out, S = gT T -- or, for one chunk of a
+//                                   plane-chunked stack, the sweep CONTINUED from T_in / S_in; bwd_store_suffix hands S to the chunk in front
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
 //   cvt_rpi_i32, fix_split, to_fix, abs_bits, lds_barrier, wave_max_u32, wave_max_bits     the fixed-point and wave primitives of the staged scatters
@@ -26,7 +27,13 @@ struct BwdParams {
     const float* g_T;      // [N,1,H,W] gradient w.r.t. the final transmittance, or nullptr: the sweep's S starts at gT * T_out
     float* g_rgba;        // [M,D,4,Ht,Wt] fp32, accumulated into (caller zero-fills)
     int64_t gs_mpi, gs_plane, gs_chan, gs_row;
+    // The hand-over of a plane-chunked sweep (gmpi_mpi_render_chunk_backward_launch; the chunk instances of render_backward.hip read them, nobody else):
+    const float* T_in = nullptr;   // [N,1,H,W] T in front of the chunk's first plane, or nullptr = 1
+    const float* S_in = nullptr;   // [N,1,H,W] the suffix sum behind the chunk's last plane, or nullptr = 0
+    float* S_out = nullptr;        // [N,1,H,W] or nullptr: the suffix sum in front of the chunk's first plane
 };
+
+constexpr float kTUsable = 1e-30f;   // a transmittance below this is rebuilt (XT) or, in front of a chunk, marks a pixel no plane behind it reaches
 
 // transmittance as mantissa (in [0.5,1)) x 2^exponent
 struct XT {
@@ -44,13 +51,14 @@ struct XT {
 template <typename TexT, bool AC>
 __device__ __forceinline__ XT total_transmittance(const KParams& p, const float* __restrict__ dhw, const TexT* __restrict__ vol,
                                                   float t_fwd, bool have_fwd, float ex, float ey, float ez, float rx, float ry,
-                                                  float rz, float cx, float cy) {
-    XT t{1.0f, 0};
+                                                  float rz, float cx, float cy, float t_front = 1.0f) {
+    XT t{t_front, 0};   // (t_front: T in front of plane 0 -- 1, or a chunk's T_in; the walk renormalises it with its first factor)
     if (have_fwd && t_fwd >= 1e-30f) {
         t.m = t_fwd;
         t.renorm();
         return t;
     }
+    if (t_front != 1.0f) t.renorm();   // (a chunk's T_in may be tiny: its product with an om of 1e-10 must not leave the normal range)
     uint32_t unused = 0;
     for (int k = 0; k < p.D; ++k) {
         float ix, iy, s, u, v;
@@ -119,7 +127,7 @@ struct BwdPixel {
 template <bool MASKED, typename Total>
 __device__ __forceinline__ void bwd_pixel_setup_with(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
                                                      const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
-                                                     Total&& total) {
+                                                     Total&& total, const float* S_in = nullptr) {
     if (!MASKED) active = true;
     const int64_t HW = vw.HW;
     const int64_t pix = MASKED ? static_cast<int64_t>(min(py, p.H - 1)) * p.W + min(px, p.W - 1) : static_cast<int64_t>(py) * p.W + px;
@@ -135,15 +143,38 @@ __device__ __forceinline__ void bwd_pixel_setup_with(BwdPixel& bp, const KParams
     const float t_fwd = (active && p.T_out) ? p.T_out[static_cast<int64_t>(n) * HW + pix] : (MASKED ? 1.0f : 0.0f);
     if (active) bp.T = total(t_fwd);
     if (active && g_T) bp.S = g_T[static_cast<int64_t>(n) * HW + pix] * bp.T.value();   // dT_out/da_k = -T_out / om_k: T_out acts as a background
+    // A sweep that is CONTINUED (the planes of this launch are a chunk of a longer stack): the suffix sum of the planes behind comes in, S = S_in + gT T.
+    if (S_in != nullptr && active) bp.S = S_in[static_cast<int64_t>(n) * HW + pix] + bp.S;
 }
 // vol: channel 0 of the view's MPI -- the RGBA volume, or the alpha planes of the shared-colour layout (s_chan = 0).
+// T_in, S_in (the chunk instances of render_backward.hip; nullptr, a compile-time constant, for everybody else): the planes of this launch are a chunk
+// of a longer stack.  p.T_out is then T BEHIND the chunk and T_in the one in front of it; dL/da_k = T_k q_k - S_k / om_k and dL/drgb_k = g w_k hold
+// unchanged with the GLOBAL T_k and S_k, so the sweep only starts elsewhere: T at the boundary value -- rebuilt, when that has underflowed, by the walk
+// over the chunk's alpha from T_in instead of from 1 -- and S at S_in (+ gT T for the last chunk).  Where T_in itself is below 1e-30 (zero, denormals
+// and NaN included) nothing behind reaches the pixel: it contributes nothing from this chunk (zero upstream gradients, T = 0, S = 0: every d_s is 0)
+// and hands S_in on unchanged (bwd_store_suffix); the terms dropped are below 1e-20 D |q|.
 template <typename TexT, bool AC, bool MASKED>
 __device__ __forceinline__ void bwd_pixel_setup(BwdPixel& bp, const KParams& p, const BwdView& vw, int n, int px, int py, bool active,
                                                 const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_T,
-                                                const TexT* __restrict__ vol) {
+                                                const TexT* __restrict__ vol, const float* T_in = nullptr, const float* S_in = nullptr) {
+    bool dead = false;
     bwd_pixel_setup_with<MASKED>(bp, p, vw, n, px, py, active, g_rgb, g_depth, g_T, [&](float t_fwd) {
-        return total_transmittance<TexT, AC>(p, vw.dhw, vol, t_fwd, p.T_out != nullptr, vw.ex, vw.ey, vw.ez, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy);
-    });
+        float t_front = 1.0f;
+        if (T_in != nullptr) {
+            t_front = T_in[static_cast<int64_t>(n) * vw.HW + bp.pix];
+            dead = !(t_front >= kTUsable);
+            if (dead) return XT{0.0f, 0};
+        }
+        return total_transmittance<TexT, AC>(p, vw.dhw, vol, t_fwd, p.T_out != nullptr, vw.ex, vw.ey, vw.ez, bp.rx, bp.ry, bp.rz, vw.cx, vw.cy, t_front);
+    }, S_in);
+    if (T_in != nullptr && dead) bp.gr = bp.gg = bp.gb = bp.gz = 0.0f, bp.S = 0.0f;
+}
+// The hand-over to the chunk in front: after plane 0 of the launch the lane stores its suffix sum.  S_in == S_out is fine: a lane touches its own pixel only.
+__device__ __forceinline__ void bwd_store_suffix(const BwdParams& b, const BwdPixel& bp, int n, int64_t HW, bool active) {
+    if (b.S_out == nullptr || !active) return;
+    const int64_t i = static_cast<int64_t>(n) * HW + bp.pix;
+    const bool dead = b.T_in != nullptr && !(b.T_in[i] >= kTUsable);
+    b.S_out[i] = dead ? (b.S_in != nullptr ? b.S_in[i] : 0.0f) : bp.S;
 }
 
 // Where the pixel's ray meets plane k of its view's MPI, by the forward's strict-order chain (compiler divisions).

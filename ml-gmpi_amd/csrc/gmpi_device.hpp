@@ -49,6 +49,14 @@ struct KParams {
     int32_t band_rot, band_split;   // band kernel: per-view rotation of the XCD <-> run assignment, pieces per run (xcd_item_per_group)
     int32_t band_tail;              // band kernel: the last band_tail bands of every XCD's last run are handed out by tickets (render_band.hip)
 };
+// The carry of a plane-chunked render (gmpi_mpi_render_chunk_launch; load_carry / store_carry below): the Accum of every pixel in front of this launch's
+// planes / behind them, [N, 5, H, W] fp32, either may be nullptr.  An argument of its own, of the carry instances of the gather, tile and 8-bit tile
+// kernels alone: as two more members of KParams the pointers moved the band kernel's range-checking instances into scratch.
+struct CarryK {
+    const float* state_in;
+    float* state_out;
+};
+struct NoCarry {};   // what the one-shot instances take in CarryK's place: nothing
 
 // blockIdx -> work item (pixel tile / band), "per view group" form: XCD x = blockIdx % 8 (workgroups are dealt round-robin to the 8 XCDs)
 // gets a contiguous run of the items of EVERY group of views that share an MPI, so that row-major neighbours meet in one L2 AND the XCDs walk
@@ -464,15 +472,49 @@ __device__ __forceinline__ void gather_plane(const KParams& p, const View& vw, c
     blend<STRICT>(A, smp[0], smp[1], smp[2], smp[3], s, dot);
 }
 
+// The carry of a plane-chunked render: the composite is associative over the plane axis, and the raw Accum of a pixel after the planes so far -- channels
+// r, g, b, z, T of state [N, 5, H, W]; colour in [0, 1], z in the mode's own form (STRICT: sum w depth_k; default: sum w s_k, before finish_depth's factor)
+// -- is all that passes from one plane range to the next.  A launch that starts from the loaded Accum and runs blend() over its planes performs, per
+// pixel, exactly the operations the one-shot launch performs over those planes: same bits.  A lane reads and writes only its own pixel, so state_in ==
+// state_out is fine (a lane outside the image shadows a neighbour's pixel and may see it half-written: its result is never stored).
+__device__ __forceinline__ Accum load_carry(NoCarry, int, int64_t, int64_t) { return Accum{}; }
+__device__ __forceinline__ void store_carry(NoCarry, int, int64_t, int64_t, const Accum&, bool) {}
+__device__ __forceinline__ Accum load_carry(const CarryK& c, int n, int64_t HW, int64_t pix) {
+    Accum A;
+    if (c.state_in != nullptr) {
+        const float* s = c.state_in + static_cast<int64_t>(n) * 5 * HW + pix;
+        A.r = s[0], A.g = s[HW], A.b = s[2 * HW], A.z = s[3 * HW], A.T = s[4 * HW];
+    }
+    return A;
+}
+__device__ __forceinline__ void store_carry(const CarryK& c, int n, int64_t HW, int64_t pix, const Accum& A, bool active) {
+    if (c.state_out != nullptr && active) {
+        float* s = c.state_out + static_cast<int64_t>(n) * 5 * HW + pix;
+        s[0] = A.r, s[HW] = A.g, s[2 * HW] = A.b, s[3 * HW] = A.z, s[4 * HW] = A.T;
+    }
+}
+
 // The pixel's results: colour ([0, 1], or 2 c - 1 with GMPI_FLAG_OUT_PM1: mpi_renderer.py:467), depth, transmittance if wanted.  (2 c - 1 is
 // formed before the `active` test on purpose: the 16-bit tile kernels sit at their register cap and the other order moves their spills.)
-template <bool STRICT>
-__device__ __forceinline__ void store_pixel(const KParams& p, int n, int64_t HW, int64_t pix, const Accum& A, float dot, bool active) {
+// With a CarryK (the carry instances): the state goes out first, and rgb_out / depth_out may each be nullptr -- a chunk that is not the last wants neither.
+template <bool STRICT, typename Carry = NoCarry>
+__device__ __forceinline__ void store_pixel(const KParams& p, int n, int64_t HW, int64_t pix, const Accum& A, float dot, bool active, const Carry& carry = Carry{}) {
+    constexpr bool CARRY = std::is_same_v<Carry, CarryK>;
     float r = A.r, g = A.g, b = A.b;
     if (p.flags & GMPI_FLAG_OUT_PM1) {
         r = 2.0f * r - 1.0f;
         g = 2.0f * g - 1.0f;
         b = 2.0f * b - 1.0f;
+    }
+    if constexpr (CARRY) {
+        store_carry(carry, n, HW, pix, A, active);
+        if (active && p.rgb_out != nullptr) {
+            float* out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;
+            out[0] = r, out[HW] = g, out[2 * HW] = b;
+        }
+        if (active && p.depth_out != nullptr) p.depth_out[static_cast<int64_t>(n) * HW + pix] = finish_depth<STRICT>(A, dot);
+        if (active && p.T_out != nullptr) p.T_out[static_cast<int64_t>(n) * HW + pix] = A.T;
+        return;
     }
     if (active) {
         float* __restrict__ out = p.rgb_out + static_cast<int64_t>(n) * 3 * HW + pix;

@@ -23,8 +23,11 @@
 
 namespace gmpi {
 
-template <typename TexT, bool AC>
-__global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, const BwdParams b) {
+// The three kernels below are bodies with two instances each: the whole stack (CHUNK = false: the kernels' names and code of old) and one chunk of a
+// plane-chunked stack (CHUNK = true, the *_chunk_kernel twins: the sweep is continued from BwdParams::T_in / S_in -- bwd_pixel_setup has the rule -- and
+// every pixel lane stores its suffix sum to S_out after plane 0 of the launch).
+template <typename TexT, bool AC, bool CHUNK>
+__device__ __forceinline__ void render_backward_pixel(const KParams& p, const BwdParams& b) {
     const int n = blockIdx.z;
     const int px = blockIdx.x * 64 + threadIdx.x;
     const int py = blockIdx.y * 4 + threadIdx.y;
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, c
     const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
     float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
     BwdPixel bp;
-    bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, b.g_rgb, b.g_depth, b.g_T, vol);
+    bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, b.g_rgb, b.g_depth, b.g_T, vol, CHUNK ? b.T_in : nullptr, CHUNK ? b.S_in : nullptr);
 
     // ---- back-to-front sweep: gradients, scattered with the bilinear weights --------------------------------------
     uint32_t unused = 0;
@@ -60,6 +63,15 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, c
             if (x1in && y1in) atomicAdd(gc + ob + 1, d * f.se);
         }
     }
+    if constexpr (CHUNK) bwd_store_suffix(b, bp, n, vw.HW, true);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, const BwdParams b) {
+    render_backward_pixel<TexT, AC, false>(p, b);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_backward_chunk_kernel(const KParams p, const BwdParams b) {
+    render_backward_pixel<TexT, AC, true>(p, b);
 }
 
 // ---- tile version: the scatter is staged in LDS ---------------------------------------------------------------------
@@ -79,8 +91,8 @@ constexpr int kBwdPitch = 56, kBwdRows = 27, kBwdCap = kBwdPitch * kBwdRows * 4;
 constexpr int kBwdChunk = 96;
 constexpr int kBwdFixBits = 48;
 
-template <typename TexT, bool AC>
-__global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+template <typename TexT, bool AC, bool CHUNK>
+__device__ __forceinline__ void render_backward_tile_body(const KParams& p, const BwdParams& b, const int tiles_x) {
     __shared__ int4 box[kBwdChunk];  // bx0, by0, nx (<= 0: not staged), ny
     __shared__ uint32_t gmax[kBwdChunk];  // per plane: largest |sample gradient| of the tile, as fp32 bits
     __shared__ unsigned long long acc[kBwdCap];
@@ -99,7 +111,7 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
     for (int i = tid; i < kBwdCap; i += kBwdThreads) acc[i] = 0ull;
 
     BwdPixel bp;
-    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol, CHUNK ? b.T_in : nullptr, CHUNK ? b.S_in : nullptr);
     uint32_t unused = 0;
 
     // ---- back-to-front sweep: gradients; scatter through the LDS boxes ------------------------------------------
@@ -187,6 +199,15 @@ __global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(co
             }
         }
     }
+    if constexpr (CHUNK) bwd_store_suffix(b, bp, n, vw.HW, active);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+    render_backward_tile_body<TexT, AC, false>(p, b, tiles_x);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(kBwdThreads, 6) void render_backward_tile_chunk_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+    render_backward_tile_body<TexT, AC, true>(p, b, tiles_x);
 }
 
 // ---- tile version, round 5: ONE barrier per plane, wave roles ------------------------------------------------------------
@@ -231,8 +252,8 @@ using B2Tall = B2Geo<32, 16, 56, 27>;   // 23.6 KB per box
 using B2Wide = B2Geo<64, 8, 80, 19>;    // 23.8 KB per box
 constexpr int kBwdDefaultGeo = 2;       // 1 = 32 x 16 tiles (round 5) | 2 = 64 x 8 tiles (profiles/r06_backward.txt)
 
-template <typename TexT, bool AC, typename G>
-__global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+template <typename TexT, bool AC, typename G, bool CHUNK>
+__device__ __forceinline__ void render_backward_tile2_body(const KParams& p, const BwdParams& b, const int tiles_x) {
     constexpr int kB2TW = G::TW, kB2TH = G::TH, kB2Pitch = G::Pitch, kB2Rows = G::Rows, kB2Cap = G::Cap;
     __shared__ int4 box[kB2Chunk];        // bx0, by0, nx (<= 0: not staged), ny
     __shared__ float4 pcA[kB2Chunk];      // zdiff, w/2, h/2, RN(2/w)
@@ -281,7 +302,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     // the pixel's own state: loaded by the PIXEL waves only (a load a flush wave issued and never used would stay "pending" for the
     // compiler's wait-count insertion, which then drains vmcnt -- the flush's own atomics -- in front of the first overwrite of its register)
     BwdPixel bp;
-    if (!flusher) bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    if (!flusher) bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol, CHUNK ? b.T_in : nullptr, CHUNK ? b.S_in : nullptr);
 
     // what a plane keeps between the issue of its taps and their use (PairTaps), and between its gradients and their scatter (Grad)
     struct Grad { float d[4]; float nw, ne, sw, se; int x0, y0; };   // (weights of taps outside the texture are 0)
@@ -547,6 +568,7 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
                 B2_STAMP(3);
             }
         }
+        if constexpr (CHUNK) bwd_store_suffix(b, bp, n, vw.HW, active);   // (the pixel lanes only: a flusher wave holds no pixel)
     }
 #ifdef GMPI_PROF
     if (p.status != nullptr && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && (tid == 192 || tid == kB2Pix + 64)) {
@@ -558,8 +580,16 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(co
     }
 #endif
 }
+template <typename TexT, bool AC, typename G>
+__global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+    render_backward_tile2_body<TexT, AC, G, false>(p, b, tiles_x);
+}
+template <typename TexT, bool AC, typename G>
+__global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_chunk_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+    render_backward_tile2_body<TexT, AC, G, true>(p, b, tiles_x);
+}
 
-template <typename TexT>
+template <typename TexT, bool CHUNK = false>
 static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool tiles, hipStream_t stream) {
     const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
     if (tiles) {
@@ -572,7 +602,10 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
         v1 = v1 || (p.flags & (1u << 22)) != 0;  // GMPI_TUNE_SKIP=64: the round-1 tile kernel (A/B)
 #endif
         if (v1) {
-            dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_tile_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, tiles_x); });
+            dispatch_bool(ac, [&](auto AC) {
+                if constexpr (CHUNK) hipLaunchKernelGGL((render_backward_tile_chunk_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, tiles_x);
+                else hipLaunchKernelGGL((render_backward_tile_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, tiles_x);
+            });
             return hipGetLastError();
         }
         // Round 6: 64 x 8 pixel tiles (32 x 16 in round 5)
@@ -585,14 +618,25 @@ static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool t
             using G = decltype(geo_tag);
             const int tx = (p.W + G::TW - 1) / G::TW, ty = (p.H + G::TH - 1) / G::TH;
             const dim3 grid2(xcd_grid_per_group(tx * ty, tx * ty), p.N);
-            dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_tile2_kernel<TexT, decltype(AC)::value, G>), grid2, block2, 0, stream, p, b, tx); });
+            dispatch_bool(ac, [&](auto AC) {
+                if constexpr (CHUNK) hipLaunchKernelGGL((render_backward_tile2_chunk_kernel<TexT, decltype(AC)::value, G>), grid2, block2, 0, stream, p, b, tx);
+                else hipLaunchKernelGGL((render_backward_tile2_kernel<TexT, decltype(AC)::value, G>), grid2, block2, 0, stream, p, b, tx);
+            });
         };
-        if (geo == 1) go(B2Tall{});
-        else go(B2Wide{});
+        if constexpr (CHUNK) {   // (the shipped geometry only)
+            (void)geo;
+            go(B2Wide{});
+        } else {
+            if (geo == 1) go(B2Tall{});
+            else go(B2Wide{});
+        }
         return hipGetLastError();
     }
     const dim3 block(64, 4), grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
-    dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b); });
+    dispatch_bool(ac, [&](auto AC) {
+        if constexpr (CHUNK) hipLaunchKernelGGL((render_backward_chunk_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b);
+        else hipLaunchKernelGGL((render_backward_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b);
+    });
     return hipGetLastError();
 }
 
@@ -625,6 +669,19 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
 #endif
     if (gather) return launch_backward_gather(p, dtype, b, (p.flags & GMPI_FLAG_GRAD_OVERWRITE) != 0, stream);
     return dispatch_dtype(dtype, [&](auto t) { return launch_backward_t<typename decltype(t)::type>(p, b, tiles, stream); });
+}
+
+// One chunk of a plane-chunked stack (gmpi_mpi_render_chunk_backward_launch): the tile kernel or the one-pixel kernel, continued from T_in / S_in.  Never
+// the atomics-free pair: it has no chunk form, and no workspace is read.
+hipError_t launch_backward_chunk(const KParams& p0, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, const float* T_in, const float* S_in,
+                                 float* S_out, float* g_rgba, const int64_t* gstride, bool tiles, hipStream_t stream) {
+    KParams p = p0;
+    p.ws = nullptr, p.ws_bytes = 0;
+    BwdParams b;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T, b.g_rgba = g_rgba;
+    b.gs_mpi = gstride[0], b.gs_plane = gstride[1], b.gs_chan = gstride[2], b.gs_row = gstride[3];
+    b.T_in = T_in, b.S_in = S_in, b.S_out = S_out;
+    return dispatch_dtype(dtype, [&](auto t) { return launch_backward_t<typename decltype(t)::type, true>(p, b, tiles, stream); });
 }
 
 }  // namespace gmpi

@@ -14,8 +14,10 @@ namespace gmpi {
 constexpr int kGatherTileW = 64;  // one wavefront = 64 consecutive pixels of a row
 constexpr int kGatherTileH = 4;   // 4 wavefronts per workgroup
 
-template <typename TexT, bool AC, bool STRICT>
-__global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kernel(const KParams p) {
+// The kernel body.  Carry = CarryK: the instance of a plane-chunked render (gmpi_mpi_render_chunk_launch) -- the Accum comes from state_in and goes to
+// state_out, the finished images are optional; everything between is the same text, so a pixel's bits do not depend on where the stack was cut.
+template <typename TexT, bool AC, bool STRICT, typename Carry>
+__device__ __forceinline__ void render_gather_pixel(const KParams& p, const Carry& carry) {
     const int n = blockIdx.z;
     const int px = blockIdx.x * kGatherTileW + threadIdx.x;
     const int py = blockIdx.y * kGatherTileH + threadIdx.y;
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kern
     const bool check_range = (p.flags & GMPI_FLAG_CHECK_RANGE) != 0;
     const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
 
-    Accum A;
+    Accum A = load_carry(carry, n, HW, pix);
 #pragma unroll 2
     for (int k = 0; k < p.D; ++k) {  // gather_plane's body, written out: through the helper one instance (fp16, align_corners, strict) takes 2 VGPRs more
         const float d = vw.dhw[3 * k + 0], ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
@@ -43,24 +45,37 @@ __global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kern
     }
     const LastPlane lp = last_plane(p, vw);
     if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, active, carry);
     report_status(p.status, bad);
 }
 
+template <typename TexT, bool AC, bool STRICT>
+__global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_kernel(const KParams p) {
+    render_gather_pixel<TexT, AC, STRICT>(p, NoCarry{});
+}
+template <typename TexT, bool AC, bool STRICT>
+__global__ __launch_bounds__(kGatherTileW* kGatherTileH) void render_gather_chunk_kernel(const KParams p, const CarryK carry) {
+    render_gather_pixel<TexT, AC, STRICT>(p, carry);
+}
+
 template <typename TexT>
-static hipError_t launch_gather_t(const KParams& p, hipStream_t stream) {
+static hipError_t launch_gather_t(const KParams& p, const CarryK* carry, hipStream_t stream) {
     const dim3 block(kGatherTileW, kGatherTileH);
     const dim3 grid((p.W + kGatherTileW - 1) / kGatherTileW, (p.H + kGatherTileH - 1) / kGatherTileH, p.N);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        hipLaunchKernelGGL((render_gather_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p);
+        if (carry != nullptr) hipLaunchKernelGGL((render_gather_chunk_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p, *carry);
+        else hipLaunchKernelGGL((render_gather_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p);
     });
     return hipGetLastError();
 }
 
-hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) {
-    if (dtype == GMPI_DTYPE_U8 && u8_interleaved(p)) return launch_gather_t<rgba8_t>(p, stream);  // (channels-last codes: one texel load per tap)
-    if (dtype == GMPI_DTYPE_U8) return launch_gather_t<u8_t>(p, stream);  // (8-bit codes: to_f32 is the division by 255; only the forward takes them)
-    return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, stream); });
+// carry: nullptr = the one-shot kernels, else their carry instances
+static hipError_t launch_gather_any(const KParams& p, const CarryK* carry, int dtype, hipStream_t stream) {
+    if (dtype == GMPI_DTYPE_U8 && u8_interleaved(p)) return launch_gather_t<rgba8_t>(p, carry, stream);  // (channels-last codes: one texel load per tap)
+    if (dtype == GMPI_DTYPE_U8) return launch_gather_t<u8_t>(p, carry, stream);  // (8-bit codes: to_f32 is the division by 255; only the forward takes them)
+    return dispatch_dtype(dtype, [&](auto t) { return launch_gather_t<typename decltype(t)::type>(p, carry, stream); });
 }
+hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) { return launch_gather_any(p, nullptr, dtype, stream); }
+hipError_t launch_gather_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream) { return launch_gather_any(p, &carry, dtype, stream); }
 
 }  // namespace gmpi

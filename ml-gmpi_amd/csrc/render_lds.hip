@@ -146,9 +146,10 @@ __device__ __forceinline__ bool quad_out_of_unit(const float4& q) {
 //   row only bites when a texel is skipped inside 8 pixels).
 // The body of one workgroup's tile, as a function of the (virtual) block index: the kernels below call it once (render_lds_kernel) or in a
 // loop over a small grid (render_lds_gated_kernel).
-template <typename TexT, bool AC, bool STRICT, int TW, int MINW, int PF, int LAYOUT>
+// Carry = CarryK: the instances of a plane-chunked render (gmpi_mpi_render_chunk_launch): the Accum enters from state_in and leaves to state_out.
+template <typename TexT, bool AC, bool STRICT, int TW, int MINW, int PF, int LAYOUT, typename Carry = NoCarry>
 __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles, const unsigned vblock,
-                                                const uint32_t* view_bits = nullptr) {  // view_bits: the gate, one bit per view, already in LDS
+                                                const uint32_t* view_bits = nullptr, const Carry& carry = Carry{}) {  // view_bits: the gate, one bit per view, already in LDS
     using Q = Quad<TexT>;
     constexpr int LPR = LAYOUT == 1 ? 1 : 4;
     constexpr int kTexelBytes = 4 * static_cast<int>(sizeof(TexT));  // interleaved layout: RGBA of one texel
@@ -211,7 +212,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
     const float rcp_rz = 1.0f / rz;  // correctly rounded; hoisted out of the plane loop (see div_by_recip)
-    Accum A;
+    Accum A = load_carry(carry, n, HW, pix);
 
     const TileCorners tc = tile_corners<TW, TH>(ft.txi, ft.tyi, W, H);
     const int cy0 = tc.cy0, cy1 = tc.cy1;
@@ -550,7 +551,7 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
 
     const LastPlane lp = last_plane(p, vw);
     if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active, carry);
     report_status(p.status, bad);
 }
 
@@ -558,6 +559,11 @@ __device__ __forceinline__ void render_lds_tile(const KParams& p, const int tile
 template <typename TexT, bool AC, bool STRICT, int TW, int MINW, int PF, int LAYOUT>
 __global__ __launch_bounds__(kNT, MINW) void render_lds_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
     render_lds_tile<TexT, AC, STRICT, TW, MINW, PF, LAYOUT>(p, tiles_x, tiles_y, n_tiles, blockIdx.x);
+}
+
+template <typename TexT, bool AC, bool STRICT, int TW, int MINW, int PF, int LAYOUT>
+__global__ __launch_bounds__(kNT, MINW) void render_lds_chunk_kernel(const KParams p, const CarryK carry, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_lds_tile<TexT, AC, STRICT, TW, MINW, PF, LAYOUT>(p, tiles_x, tiles_y, n_tiles, blockIdx.x, nullptr, carry);
 }
 
 // AUTO's fallback launch for the views the band kernel leaves (KParams::gate): usually NO view is left, and a grid of one workgroup per
@@ -668,6 +674,32 @@ hipError_t launch_lds(const KParams& p0, int dtype, int tune, hipStream_t stream
         using TexT = typename decltype(t)::type;
         constexpr bool k16 = sizeof(TexT) == 2;
         return launch_lds_t<TexT, kTileW, (k16 ? 8 : 6), 1, (k16 ? 1 : 0)>(p, stream);
+    });
+}
+
+// The carry instances: the shipped tile shape and layouts of launch_lds, never gated (a chunk launch is one kernel).  fp32: 6 waves per SIMD as the
+// one-shot kernel.  16-bit volumes: the one-shot instances sit at the 64 VGPRs of 8 waves per SIMD (store_pixel's comment), and with the state's
+// pointers and its optional outputs every one of the eight instances went 8 to 28 bytes into scratch there; asked for 7 they take 68-72 VGPRs, none.
+constexpr int kChunkMinWaves16 = 7;
+template <typename TexT, int TW, int MINW, int PF, int LAYOUT>
+static hipError_t launch_lds_chunk_t(const KParams& p, const CarryK& carry, hipStream_t stream) {
+    constexpr int TH = kNT / TW;
+    const FwdTileGrid tg = fwd_tile_grid<TW, TH>(p);
+    const unsigned grid_x = sizeof(TexT) == 4 ? tg.grid.x : static_cast<unsigned>(((tg.n_tiles + 7) / 8) * 8);  // (16-bit: one run per XCD, as launch_lds_t)
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_lds_chunk_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, TW, MINW, PF, LAYOUT>), dim3(grid_x), dim3(kNT), 0, stream, p,
+                           carry, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+    });
+    return hipGetLastError();
+}
+hipError_t launch_lds_chunk(const KParams& p0, const CarryK& carry, int dtype, hipStream_t stream) {
+    KParams p = p0;
+    p.band_rot = kTileViewRotation, p.band_split = kTileRunPieces;
+    p.gate = nullptr;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using TexT = typename decltype(t)::type;
+        constexpr bool k16 = sizeof(TexT) == 2;
+        return launch_lds_chunk_t<TexT, kTileW, (k16 ? kChunkMinWaves16 : 6), 1, (k16 ? 1 : 0)>(p, carry, stream);
     });
 }
 

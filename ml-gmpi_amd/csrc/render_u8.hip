@@ -46,8 +46,9 @@ static_assert(2 * kUBufWords * 4 + kUChunk * 48 <= 40 * 1024, "4 workgroups per 
 // image: one loader item = 4 texels = one 16-byte buffer load and one 16-byte LDS store, no v_perm; strides and offsets count bytes, a box row is one
 // run of 16 bytes per item.  The item's dword alignment is what u8_variant_supports asks for.  Everything behind the LDS image is the same code:
 // the kernel body is this one function, the two kernels below are its instances (the planar one keeps its name and its template arguments).
-template <typename TexT, bool AC, bool STRICT>
-__device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles) {
+// Carry = CarryK: the instances of a plane-chunked render (gmpi_mpi_render_chunk_launch): the Accum enters from state_in and leaves to state_out.
+template <typename TexT, bool AC, bool STRICT, typename Carry = NoCarry>
+__device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles, const Carry& carry = Carry{}) {
     // Per plane of the chunk, written once by one thread so that the 8 waves do not repeat the address arithmetic on their scalar units:
     //   box:  qx0 (a multiple of 4), by0, items per row (0: not staged), rows
     //   org:  byte address of the box origin (texel row by0, column qx0 of channel 0) = words 0, 1 of the plane's buffer descriptor, RN(1 / hh).
@@ -79,7 +80,7 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     const float rx = rdv[pix], ry = rdv[HW + pix], rz = rdv[2 * HW + pix];
     const float dot = ray_dot(vw, rx, ry, rz);
     const float rcp_rz = 1.0f / rz;   // correctly rounded; hoisted out of the plane loop (div_by_recip)
-    Accum A;
+    Accum A = load_carry(carry, n, HW, pix);
     const TileCorners tc = tile_corners<kUW, kUH>(ft.txi, ft.tyi, W, H);
 
     // ---- loader role: item column lcol of box row lrow; byte offset from the box origin (one byte per texel and channel) ---------------------------
@@ -205,7 +206,7 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     }
     const LastPlane lp = last_plane(p, vw);
     if (leaves_last_plane<AC>(vw, lp, rx, ry, rz)) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active);
+    store_pixel<STRICT>(p, n, HW, pix, A, dot, tl.active, carry);
     report_status(p.status, bad);
 }
 
@@ -219,6 +220,16 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_kernel(co
 template <bool AC, bool STRICT>
 __global__ __launch_bounds__(kUThreads, STRICT ? 7 : 8) void render_rgba8_kernel(const KParams p, const int tiles_x, const int tiles_y, const int n_tiles) {
     render_u8_tile<rgba8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles);
+}
+
+// (the carry instances: the state's five loads and stores lie outside the plane loop; same bounds as their one-shot twins)
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_chunk_kernel(const KParams p, const CarryK carry, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<u8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles, carry);
+}
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 7 : 8) void render_rgba8_chunk_kernel(const KParams p, const CarryK carry, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<rgba8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles, carry);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
@@ -252,6 +263,16 @@ hipError_t launch_u8(const KParams& p, hipStream_t stream) {
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
         if (packed) hipLaunchKernelGGL((render_rgba8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
         else hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+    });
+    return hipGetLastError();
+}
+hipError_t launch_u8_chunk(const KParams& p, const CarryK& carry, hipStream_t stream) {
+    const FwdTileGrid tg = fwd_tile_grid<kUW, kUH>(p);
+    const dim3 block(kUThreads);
+    const bool packed = u8_interleaved(p);
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        if (packed) hipLaunchKernelGGL((render_rgba8_chunk_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, carry, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+        else hipLaunchKernelGGL((render_u8_chunk_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, carry, tg.tiles_x, tg.tiles_y, tg.n_tiles);
     });
     return hipGetLastError();
 }

@@ -532,6 +532,18 @@ def _warn_window_fallback() -> None:
 
 
 _GATHER_FALLBACK_WARNED = False
+_CHUNK_VARIANT_WARNED = False
+
+
+def _warn_chunk_variant(name: str) -> None:
+    """Once per process: a plane-chunked render on a module built with variant "band" or "wave" (every such launch is counted in
+    `MPI.chunk_variant_fallbacks`)."""
+    global _CHUNK_VARIANT_WARNED
+    if not _CHUNK_VARIANT_WARNED:
+        _CHUNK_VARIANT_WARNED = True
+        warnings.warn(f'plane-chunked render: variant="{name}" has no kernel that takes a carried state (the strip kernel splits the plane axis '
+                      "itself, the band kernel is not built for it); the chunks render with the library's own choice, the tile kernel where it "
+                      "can take the tensors (counted in MPI.chunk_variant_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
 
 
 def _warn_gather_fallback(kind: _Kind) -> None:
@@ -647,6 +659,7 @@ class MPI(nn.Module):
         self.shared_lds_fallbacks = 0    # shared-colour launches that asked for "lds" and ran AUTO's kernel instead (a debug counter)
         self.depth_window_fallbacks = 0  # depth-alpha launches that asked for depth_forward="window" and ran the one-pixel kernel instead
         self.layout_gather_fallbacks = 0   # shared-colour / depth-alpha backwards that asked for "gather" and ran the atomic kernels instead
+        self.chunk_variant_fallbacks = 0   # chunk launches of a module built with variant "band" / "wave", which ran AUTO's chunk kernel instead
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -919,6 +932,43 @@ class MPI(nn.Module):
                                        kwargs.pop("depth_backward", "pixel"), kwargs.pop("depth_forward", "pixel"), kwargs.pop("_gather_runs", None))
         return self.render_views(depth5, dhw, ray_dir, eye_pos, z_dir, _layout=layout, **kwargs)
 
+    # -- plane-chunked render ----------------------------------------------------------------------------------------------------------
+    def chunked_render(self, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor, z_dir: torch.Tensor, **kwargs) -> "ChunkedRender":
+        """A `render_views` whose volume arrives a few planes at a time (gmpi_mpi_render_chunk_launch): returns a `ChunkedRender`; `.add(chunk)` takes
+        the next Dc planes [M, Dc, 4, Ht, Wt] -- the next Dc rows of dhw [M, D, 3] -- and launches at once, `.finish()` returns `render_views`' dict.
+        Between the launches only a per-pixel state [N, 5, H, W] lives on the device: the stack [M, D, 4, Ht, Wt] never exists as one tensor.  kwargs:
+        `render_views`' views_per_mpi, view_to_mpi, check_last_plane, out_pm1, want_transmittance, status, defer_status, out (and c2w_mat, sphere_c
+        for the diagnostics of a ray that leaves the last plane).  The no-gradient path: see `render_views_chunks` for chunks that require grad."""
+        return ChunkedRender(self, dhw, ray_dir, eye_pos, z_dir, **kwargs)
+
+    def render_views_chunks(self, chunks, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor, z_dir: torch.Tensor, **kwargs):
+        """`render_views` of `torch.cat(chunks, 1)` without the concatenation: `chunks` is a sequence or an iterator of [M, Dc, 4, Ht, Wt] tensors
+        (one M, Ht, Wt and dtype; Dc may differ) that hold dhw's D planes front to back.  With strict_order=True the result has the bits of that
+        one-shot render with the same variant.  Without gradients an iterator is consumed lazily, one chunk alive at a time (`chunked_render`).
+        When grad is enabled and a chunk of a SEQUENCE requires grad, one autograd node records the whole call: the forward keeps one
+        transmittance image [N,1,H,W] per chunk and nothing else, the backward runs the chunks from last to first with one suffix-sum image carried
+        in place (gmpi_mpi_render_chunk_backward_launch), and every chunk gets a gradient of ITS size in its dtype: no [M, D, ...] gradient volume.
+        (An iterator whose chunks require grad is refused by `ChunkedRender.add`: the backward needs every chunk again.)  `MPI(backward="gather")`
+        takes the atomic kernels here -- the atomics-free pair has no chunk form --, `MPI(variant="gather")` the one-pixel-per-lane kernels.  No
+        gradient reaches the camera tensors or dhw: with geometry_grad such tensors raise NotImplementedError."""
+        if torch.is_grad_enabled():
+            if any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)) and (self.geometry_grad or dhw.requires_grad):
+                raise NotImplementedError("the plane-chunked render has no gradient w.r.t. the plane geometry or the camera tensors: use render_views "
+                                          "on the concatenation, torch.cat(chunks, 1), with MPI(geometry_grad=True), or detach these tensors")
+            if isinstance(chunks, (list, tuple)) and any(c.requires_grad for c in chunks):
+                chunks = tuple(chunks)
+                color, depth, T, st = _ChunkedRenderFunction.apply(self, dhw, ray_dir, eye_pos, z_dir, kwargs, *chunks)
+                return dict(color=color, depth=depth, T=T if kwargs.get("want_transmittance") else None, status=st)
+        cr = self.chunked_render(dhw, ray_dir, eye_pos, z_dir, **kwargs)
+        it = iter(chunks)
+        while True:   # (no loop variable: the chunk just rendered must not live on while the iterator makes the next one)
+            chunk = next(it, None)
+            if chunk is None:
+                break
+            cr.add(chunk)
+            del chunk
+        return cr.finish()
+
     # -- status word -> the reference's assertion behaviour ------------------------------------------------------
     def raise_on_status(self, status: torch.Tensor, params=None, keep=None, c2w_mat=None, sphere_c=None):
         word = int(status[0].item())  # the only host sync of a render call
@@ -1075,6 +1125,183 @@ class _RenderFunction(torch.autograd.Function):
             entry = "gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch"
             geo = _geometry_pass(ctx, keep, T, dev, stream, want, entry, (), upstream)
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
+
+
+class ChunkedRender:
+    """`MPI.chunked_render`: the volume of a `render_views` call, a few planes at a time.  Every `add` is one gmpi_mpi_render_chunk_launch whose state
+    is read and written in place; the LAST chunk -- the one that reaches dhw's D planes -- alone carries GMPI_FLAG_CHECK_LAST_PLANE and
+    GMPI_FLAG_OUT_PM1 and alone gets output pointers.  No reference to a chunk is kept.  One status word serves the whole stack -- words of this
+    object's own unless the caller passes `status` -- and is settled once, in `finish()` (defer_status=True: not at all; "lag" reads back at once:
+    the ring's entries keep the tensors of ONE launch).  range_check="full" runs the exhaustive pass on every chunk (never cached).  Peak memory
+    above the inputs: one chunk, the state (five images per view) and the outputs."""
+
+    def __init__(self, mpi, dhw, ray_dir, eye_pos, z_dir, views_per_mpi=1, view_to_mpi=None, check_last_plane=False, out_pm1=False,
+                 want_transmittance=False, status=None, defer_status=False, out=None, c2w_mat=None, sphere_c=None):
+        assert dhw.ndim == 3 and dhw.shape[2] == 3, dhw.shape
+        self.mpi, self.geometry = mpi, (dhw, ray_dir, eye_pos, z_dir)
+        self.views = (views_per_mpi, view_to_mpi)
+        self.check_last_plane, self.out_pm1, self.want_T = check_last_plane, out_pm1, want_transmittance
+        self.status, self.defer_status, self.out = status, defer_status is True, out or {}
+        self.c2w_mat, self.sphere_c = c2w_mat, sphere_c
+        self.D, self.planes, self.n_chunks = dhw.shape[1], 0, 0
+        self.state = self.result = self._last = None
+        self._dev = None
+
+    def _setup(self, chunk: torch.Tensor) -> None:
+        """At the first chunk: the device is the chunk's; the camera and plane tensors as contiguous fp32 there; the view index; the status words."""
+        mpi, dev = self.mpi, chunk.device
+        if not chunk.is_cuda and not getattr(_lib.load_library(), "records_only", False):
+            raise _lib.GmpiError(f"MPI.chunked_render needs tensors on a ROCm device: this package has no CPU path (got a chunk on {dev})")
+        dhw, ray_dir, eye_pos, z_dir = (_f32_on(t.detach(), dev) for t in self.geometry)
+        self.M, _, _, self.Ht, self.Wt = chunk.shape
+        N, _, H, W = ray_dir.shape
+        assert eye_pos.shape == (N, 3) and z_dir.shape == (N, 3), (eye_pos.shape, z_dir.shape, N)
+        assert dhw.shape[0] == self.M, (dhw.shape, chunk.shape)
+        uniform, view_to_mpi = _view_index(*self.views, self.M, N, dev)
+        self._dev, self._dtype, self._uniform = dev, chunk.dtype, max(uniform, 1)
+        self._geo, self._v2m, self._NHW = (dhw, ray_dir, eye_pos, z_dir), view_to_mpi, (N, H, W)
+        if self.status is None:   # (never the stream's shared words: another render may settle -- and clear -- them between two chunks)
+            self.status = torch.zeros(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+        variant = mpi.variant
+        if variant in ("band", "wave"):
+            variant = "auto"
+            _warn_chunk_variant(mpi.variant)
+        self._fallback, self._variant = variant != mpi.variant, _lib.VARIANTS[variant]
+
+    def add(self, chunk: torch.Tensor, _T: Optional[torch.Tensor] = None):
+        """Renders the next chunk.shape[1] planes.  _T (the autograd node): an image [N,1,H,W] that receives T behind this chunk.  Returns (the launch's
+        struct, the tensors it read): what that node keeps for its backward."""
+        assert self.result is None, "finish() has been called"
+        assert chunk.ndim == 5 and chunk.shape[2] == 4, f"a chunk is [M, Dc, 4, Ht, Wt], got {tuple(chunk.shape)}"
+        if torch.is_grad_enabled() and chunk.requires_grad and _T is None:
+            raise RuntimeError("chunked_render is the no-gradient path: a chunk that requires grad is rendered by MPI.render_views_chunks, which "
+                               "takes the chunks as a list or tuple (its backward reads every chunk again); or detach the chunk")
+        chunk = _volume_operand(chunk.detach())
+        if self._dev is None:
+            self._setup(chunk)
+        mpi, dev = self.mpi, self._dev
+        Dc, (N, H, W) = chunk.shape[1], self._NHW
+        assert (chunk.shape[0], chunk.shape[3], chunk.shape[4]) == (self.M, self.Ht, self.Wt) and chunk.dtype == self._dtype and chunk.device == dev, \
+            f"chunks share M, Ht, Wt, dtype and device: {tuple(chunk.shape)} {chunk.dtype} after [{self.M}, ., 4, {self.Ht}, {self.Wt}] {self._dtype}"
+        k0, last = self.planes, self.planes + Dc == self.D
+        assert Dc >= 1 and k0 + Dc <= self.D, f"{k0} + {Dc} planes added, dhw holds {self.D}"
+        dhw, ray_dir, eye_pos, z_dir = self._geo
+        rows = dhw[:, k0:k0 + Dc]   # the chunk's rows of the plane table, [M, Dc, 3] contiguous: a view for one MPI, a small copy for more
+        rows = rows if rows.is_contiguous() else rows.contiguous()
+        keep = _Keep(chunk, rows, ray_dir, eye_pos, z_dir, self._v2m)
+        first = k0 == 0
+        if not last and self.state is None:
+            self.state = torch.empty((N, 5, H, W), dtype=torch.float32, device=dev)
+        color = depth = None
+        T = _T
+        if last:   # the outputs: the caller's, or fresh ones
+            color, depth = self.out.get("color"), self.out.get("depth")
+            if color is None:
+                color = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+            if depth is None:
+                depth = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+            if T is None and self.want_T:
+                T = self.out.get("T")
+                if T is None:
+                    T = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+        scalars = _Scalars(mpi._flags(self.out_pm1 and last, self.check_last_plane and last, False, False, False), self._variant,
+                           _DTYPES[chunk.dtype], N, self.M, Dc, self.Ht, self.Wt, H, W, self._uniform)
+        on_device = chunk.is_cuda
+        stream = torch.cuda.current_stream(dev).cuda_stream if on_device else 0
+        with _stream_lock(dev, stream) if on_device else contextlib.nullcontext():
+            p = _render_params(scalars, keep, T=T)
+            p.status = self.status.data_ptr()
+            if last:
+                p.rgb_out, p.depth_out = color.data_ptr(), depth.data_ptr()
+            carry = _lib.GmpiCarry()
+            carry.struct_size = ctypes.sizeof(_lib.GmpiCarry)
+            carry.state_in = None if first else self.state.data_ptr()
+            carry.state_out = None if last else self.state.data_ptr()
+            if mpi.range_check == "full" and chunk.dtype is not torch.uint8:
+                _range_pass((chunk,), p, dev, stream)
+            _call("gmpi_mpi_render_chunk_launch", dev, ctypes.byref(p), ctypes.byref(carry), stream=stream)
+        if self._fallback:
+            mpi.chunk_variant_fallbacks += 1
+        self.planes, self.n_chunks = k0 + Dc, self.n_chunks + 1
+        if last:
+            # (what a tripped assertion's diagnostics read: the last chunk's struct and camera tensors -- not the chunk, which is not kept)
+            q = _lib.GmpiRenderParams.from_buffer_copy(p)
+            q.rgba = None
+            self._last = (q, _Keep(rows, rows, ray_dir, eye_pos, z_dir, self._v2m))
+            self.state = None
+            self.result = dict(color=color, depth=depth, T=T if self.want_T else None, status=self.status)
+        return p, keep
+
+    def finish(self) -> dict:
+        """`render_views`' dict, once exactly D planes have been added; settles the status word of the whole stack (unless defer_status=True)."""
+        assert self.planes == self.D and self.result is not None, f"{self.planes} of {self.D} planes were added"
+        if not self.defer_status:
+            self.mpi._settle(self.status, *self._last, self.c2w_mat, self.sphere_c, None)
+        return self.result
+
+
+class _ChunkedRenderFunction(torch.autograd.Function):
+    """autograd bridge of `MPI.render_views_chunks`: ONE node over all chunks.  forward = the chain of gmpi_mpi_render_chunk_launch, which keeps
+    the transmittance image behind every chunk -- [N,1,H,W] each, nothing else; backward = gmpi_mpi_render_chunk_backward_launch from the last chunk to
+    the first, one suffix-sum image carried in place: gT goes to the last chunk only, T_in is the kept image of the chunk in front (NULL for the
+    first), and every chunk that requires grad gets a zero-filled fp32 buffer of ITS size, cast to its dtype as `_RenderFunction` casts.  A chunk
+    that does not require grad still runs when a chunk in front of it does -- the hand-over of S needs it -- into a buffer that is dropped; chunks in
+    front of the first one that requires grad do not run.  Saved tensors and unused outputs as None: as `_RenderFunction`."""
+
+    @staticmethod
+    def forward(ctx, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs, *chunks):
+        kw = dict(kwargs, want_transmittance=True)
+        user_out = kw.get("out") or {}
+        kw["out"] = {k: v for k, v in user_out.items() if k != "T"}   # a T private to the node, as _bridge_forward
+        cr = ChunkedRender(mpi, dhw, ray_dir, eye_pos, z_dir, **kw)
+        N, _, H, W = ray_dir.shape
+        kept, Ts, scalars = [], [], []
+        for c in chunks:
+            T = torch.empty((N, 1, H, W), dtype=torch.float32, device=c.device)
+            p, keep = cr.add(c, _T=T)
+            Ts.append(T)
+            kept.append(keep)
+            # the backward's struct: the chunk's forward launch; GMPI_FLAG_OUT_PM1 on every chunk when the FINAL colour was written with it
+            flags = (p.flags & ~(_lib.FLAG_CHECK_LAST_PLANE | _lib.FLAG_OUT_PM1)) | (_lib.FLAG_OUT_PM1 if cr.out_pm1 else 0)
+            scalars.append(_Scalars(flags, p.variant, p.rgba_dtype, p.N, p.M, p.D, p.Ht, p.Wt, p.H, p.W, p.views_per_mpi))
+        res = cr.finish()
+        if kwargs.get("want_transmittance") and user_out.get("T") is not None:
+            user_out["T"].copy_(res["T"])
+        ctx.n, ctx.scalars_of, ctx.has_v2m = len(chunks), scalars, kept[0].view_to_mpi is not None
+        ctx.meta = [(c.dtype, tuple(c.shape)) for c in chunks]
+        ctx.save_for_backward(*kept[0][2:5], *([kept[0].view_to_mpi] if ctx.has_v2m else []), *[k.rgba for k in kept], *[k.dhw for k in kept], *Ts)
+        ctx.mark_non_differentiable(res["status"])
+        ctx.set_materialize_grads(False)
+        return res["color"], res["depth"], res["T"], res["status"]
+
+    @staticmethod
+    def backward(ctx, g_color, g_depth, g_T, g_status):
+        n, saved = ctx.n, ctx.saved_tensors
+        ray_dir, eye_pos, z_dir = saved[:3]
+        o = 4 if ctx.has_v2m else 3
+        view_to_mpi = saved[3] if ctx.has_v2m else None
+        vols, rows, Ts = saved[o:o + n], saved[o + n:o + 2 * n], saved[o + 2 * n:o + 3 * n]
+        needs = ctx.needs_input_grad[6:]
+        grads = [None] * n
+        if not any(needs) or (g_color is None and g_depth is None and g_T is None):
+            return (None,) * 6 + tuple(grads)
+        dev = vols[0].device
+        ctx.scalars = ctx.scalars_of[0]   # (_upstream reads N, H, W)
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        front = min(i for i in range(n) if needs[i])   # chunks in front of it hand S to nobody
+        S = torch.empty_like(Ts[0]) if n - 1 > front else None   # the one suffix-sum image, read and written in place
+        for c in range(n - 1, front - 1, -1):
+            last = c == n - 1
+            p = _render_params(ctx.scalars_of[c], _Keep(vols[c], rows[c], ray_dir, eye_pos, z_dir, view_to_mpi), T=Ts[c])
+            grad = torch.zeros(ctx.meta[c][1], dtype=torch.float32, device=dev)   # (a chunk that does not require grad: dropped below)
+            _call("gmpi_mpi_render_chunk_backward_launch", dev, ctypes.byref(p), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T) if last else None,
+                  _ptr(Ts[c - 1]) if c > 0 else None, None if last else _ptr(S), _ptr(S) if c > front else None,
+                  grad.data_ptr(), (ctypes.c_int64 * 5)(*grad.stride()), stream=stream)
+            if needs[c]:
+                grads[c] = grad.to(ctx.meta[c][0])
+            del grad
+        return (None,) * 6 + tuple(grads)
 
 
 def _ptr_stride(t: Optional[torch.Tensor], dims):

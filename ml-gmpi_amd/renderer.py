@@ -419,6 +419,7 @@ class MPIRenderer:
         views_per_mpi = int(ext.pop("views_per_mpi", 1))
         want_T = bool(ext.pop("want_transmittance", False))
         layout = ext.pop("_layout", None)   # render_shared / render_depth: batch_mpi_rgbas is then the alpha tensor / the depth image [B,1,1,Ht,Wt]
+        chunks = ext.pop("_chunks", None)   # render_chunks: the stack's chunks (batch_mpi_rgbas is then the first of them, looked at for its shape alone)
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -437,7 +438,8 @@ class MPIRenderer:
             #  backward, and the next render() of this shape would overwrite them through a raw pointer -- no version counter sees that)
             # (nor when the status check lags: the pending entry of this call keeps its camera tensors for the diagnostics of a tripped
             #  assertion -- "pos / dir / min val" of THIS call, printed one or more calls later -- so a later call must not overwrite them)
-            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad))
+            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad)
+                                                     or (isinstance(chunks, (list, tuple)) and any(c.requires_grad for c in chunks)))
             ray_t, eye_t, zd_t = self._generate_rays_hip(c2w, reuse=not recording and defer != "lag")
         else:
             if given_cam_infos is None:
@@ -457,17 +459,44 @@ class MPIRenderer:
         assert ray_t.shape[0] == batch_size, f"{ray_t.shape[0]}, {batch_size}"
 
         dhw = self._dhw_for(n_mpis)
-        res = self.mpi.render_views(
-            batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
-            check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
-            c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-            _layout=layout)
+        if chunks is not None:   # (no camera hints: a chunk launch has one kernel per variant, whatever the pose)
+            res = self.mpi.render_views_chunks(
+                chunks, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi, check_last_plane=assert_not_out_of_last_plane, out_pm1=True,
+                want_transmittance=want_T, c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer)
+        else:
+            res = self.mpi.render_views(
+                batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
+                check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
+                c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
+                _layout=layout)
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
             return res["color"], res["depth"], c2w, cam_angles, res["T"]
         return res["color"], res["depth"], c2w, cam_angles
 
+
+    def render_chunks(self, chunks, render_h, render_w, **kwargs):
+        """`render` of `torch.cat(chunks, 1)` without the concatenation (`MPI.render_views_chunks`): chunks is a sequence or an iterator of
+        [B, Dc, 4, Ht, Wt] tensors that hold this renderer's planes front to back -- the loop of the reference's render_video.py:55-77, which
+        generates `chunk_n_planes` planes at a time, without its torch.cat.  An iterator is consumed lazily, one chunk alive at a time (no
+        gradients); a list or tuple whose chunks require grad is recorded by one autograd node.  Keyword arguments and the return tuple are
+        `render`'s (T fifth under want_transmittance=True); the poses are sampled once, before the first chunk is rendered, exactly as `render`
+        samples them: a seeded call returns `render`'s c2w and angles.  A status check that lags ("lag") is read back at once here."""
+        if isinstance(chunks, (list, tuple)):
+            assert len(chunks) > 0, "no chunks"
+            return self.render(chunks[0], render_h, render_w, _chunks=chunks, **kwargs)
+        it = iter(chunks)
+        first = next(it)
+
+        def rest():   # the first chunk again, then the iterator's own: nothing is kept behind a chunk that has been handed on
+            nonlocal first
+            chunk, first = first, None
+            yield chunk
+            del chunk
+            yield from it
+        shape_only = first.new_empty((first.shape[0], 0))   # (render reads the number of MPIs off it; no view of the chunk: that would keep its storage)
+        return self.render(shape_only, render_h, render_w, _chunks=rest(), **kwargs)
 
     def render_shared(self, batch_mpi_rgb, batch_mpi_alpha, render_h, render_w, *, background_rgb=None, variant=None, **kwargs):
         """`render` of the volume `expand_shared_color(batch_mpi_rgb, batch_mpi_alpha, background_rgb)` without building it (the layout GMPI's
