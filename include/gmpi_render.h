@@ -535,6 +535,51 @@ int gmpi_mpi_render_depth_geometry_backward_launch(const GmpiRenderParams *param
                                                    float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw, void *stream);
 
 /*
+ * ---- the shaded render of an RGBA volume ---------------------------------------------------------------------------------------------------------
+ * The shading augmentation (LightRenderer: gmpi_light_apply_launch) multiplies the colour of every plane by ONE factor per texel and clips:
+ *     shaded[m,k,c] = clip(rgba[m,k,c] * shading[m,0], 0, 1) for c < 3 (fp32, one rounding for the product),  shaded[m,k,3] = rgba[m,k,3].
+ * By definition these entries render / back-propagate through THAT volume (apply_shading in the Python package is the executable definition)
+ * without building it: the multiply and the clip happen on the taps.  A NaN colour texel is shaded to 0, as gmpi_light_apply_launch's
+ * fminf(fmaxf(.)) makes it.  shading: fp32 [M,1,Ht,Wt]; shading_stride = {MPI stride, row stride} in elements, innermost stride 1, row stride >= Wt,
+ * an MPI stride of 0 only for M == 1.
+ */
+typedef struct GmpiShading {
+    uint32_t struct_size;         /* = sizeof(GmpiShading)                                             */
+    const float *shading;         /* [M,1,Ht,Wt] fp32                                                  */
+    int64_t shading_stride[2];    /* MPI, row                                                          */
+} GmpiShading;
+
+/*
+ * Forward.  params as for gmpi_mpi_render_launch (same outputs, flags and status bits; GMPI_FLAG_CHECK_RANGE tests the alpha taps raw -- the shaded
+ * colour is in [0, 1] by construction).  Variants: GMPI_VARIANT_GATHER = the one-pixel-per-lane kernel (render_shaded.hip: any shape, stride, ray
+ * field); GMPI_VARIANT_AUTO = the staged kernel where gmpi_render_shaded_supports says 1, else the one-pixel kernel; GMPI_VARIANT_LDS = the staged
+ * kernel, GMPI_E_VARIANT where it cannot run; WAVE / BAND: GMPI_E_VARIANT.  GMPI_DTYPE_U8: GMPI_E_DTYPE.  The staged kernel is the shared-colour
+ * forward's frame (32 x 16 pixel tiles, texel boxes through LDS) with a fifth loader item per plane for the shading box; gmpi_render_shaded_supports
+ * says 1 when its loader can take the tensors: the volume's base pointer and outer strides multiples of 4 texels, the shading's base pointer a
+ * multiple of 16 bytes and its strides multiples of 4 (0, or a negative error code the launch would return, otherwise).  For a texture width that is
+ * no multiple of 4 the loader reads up to 3 elements past the end of a row: behind the LAST row of each tensor they must be allocated.  In
+ * strict-order mode the result is bit-identical to gmpi_mpi_render_launch on the shaded volume, whatever the kernel.  N == 0: GMPI_OK.
+ */
+int gmpi_mpi_render_shaded_launch(const GmpiRenderParams *params, const GmpiShading *shading, void *stream);
+int gmpi_render_shaded_supports(const GmpiRenderParams *params, const GmpiShading *shading);
+
+/*
+ * Backward.  As gmpi_mpi_render_backward_ex_launch (grad_depth, grad_transmittance may be NULL; transmittance_out is the forward's T), followed on the
+ * same stream by the per-texel chain rule through clip(rgb * s) IN PLACE on grad_rgba:
+ *     g_rgb = g * s * [0 <= rgb * s <= 1],   grad_shading[m,0,y,x] = sum over planes and colour channels of g * rgb * [0 <= rgb * s <= 1],
+ * alpha untouched (the closed mask: where torch.clip passes a gradient).  grad_rgba: fp32 [M,D,4,Ht,Wt], zero-filled by the caller and added into
+ * (grad_rgba_stride: 5 element strides, innermost 1); it first holds the gradient w.r.t. the SHADED texels, and after the call the gradient w.r.t.
+ * rgba.  grad_shading: fp32 [M,1,Ht,Wt], WRITTEN (grad_shading_stride: MPI and row stride).  Either of the two may be NULL when the other is not (both
+ * NULL: GMPI_E_NULL).  With grad_rgba NULL no volume-sized buffer is involved: the entry zero-fills grad_shading and the one-pixel-per-lane kernel adds
+ * the chain rule's terms per tap (4 atomics per pixel and plane; whatever the variant).  Otherwise the kernels are: the one-pixel-per-lane backward (GMPI_VARIANT_GATHER, and every launch the 64 x 8 tile backward's guards refuse: Wt < 2, plane offsets beyond 32 bits)
+ * or the 64 x 8 tile backward, both with the taps shaded as the forward shades them.  Never the atomics-free pair; no workspace is read.
+ * gmpi_query(38) == 1 says these entries are built in.
+ */
+int gmpi_mpi_render_shaded_backward_launch(const GmpiRenderParams *params, const GmpiShading *shading, const float *grad_rgb, const float *grad_depth,
+                                           const float *grad_transmittance, float *grad_rgba, const int64_t *grad_rgba_stride, float *grad_shading,
+                                           const int64_t *grad_shading_stride, void *stream);
+
+/*
  * Diagnostics for a tripped GMPI_STATUS_OUT_OF_LAST_PLANE: min_u, max_u, min_v, max_v of the
  * normalised grid on the LAST plane per view (what mpi.py:106-109 print).  uv_minmax: [N,4] float.
  * Uses N, M, D, H, W, flags(ALIGN_CORNERS), view_to_mpi/views_per_mpi, dhw, ray_dir, eye_pos.
@@ -687,7 +732,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * gmpi_mpi_render_depth_geometry_backward_launch) is built in; 31 is unused (-1); 32 whether compute_depth of the depth-alpha layout
  * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in; 33 is unused (-1); 34 whether the atomics-free backward of the shared-colour
  * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in; 35 is unused (-1); 36 whether the plane-chunked render (gmpi_mpi_render_chunk_launch,
- * gmpi_mpi_render_chunk_backward_launch) is built in.  Unknown -> -1.  */
+ * gmpi_mpi_render_chunk_backward_launch) is built in; 37 is unused (-1); 38 whether the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch,
+ * gmpi_mpi_render_shaded_backward_launch) is built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

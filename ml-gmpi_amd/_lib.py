@@ -37,6 +37,9 @@ EXPORTS = (
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
+    "gmpi_mpi_render_shaded_launch",
+    "gmpi_render_shaded_supports",
+    "gmpi_mpi_render_shaded_backward_launch",
     "gmpi_mpi_render_depth_launch",
     "gmpi_mpi_render_depth_window_launch",
     "gmpi_render_depth_window_supports",
@@ -115,6 +118,14 @@ class GmpiSharedColor(ctypes.Structure):
         ("struct_size", ctypes.c_uint32),
         ("rgb", ctypes.c_void_p), ("rgb_stride", ctypes.c_int64 * 3),
         ("background", ctypes.c_void_p), ("background_stride", ctypes.c_int64 * 3),
+    ]
+
+
+class GmpiShading(ctypes.Structure):
+    """Field-for-field mirror of `struct GmpiShading` in include/gmpi_render.h."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("shading", ctypes.c_void_p), ("shading_stride", ctypes.c_int64 * 2),
     ]
 
 
@@ -235,6 +246,12 @@ def load_library():
     lib.gmpi_mpi_render_shared_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp, vp, vp,
                                                            vp, i64p, vp, i64p, vp, i64p, vp]
+    lib.gmpi_mpi_render_shaded_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shaded_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiShading), vp]
+    lib.gmpi_render_shaded_supports.restype = ctypes.c_int
+    lib.gmpi_render_shaded_supports.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiShading)]
+    lib.gmpi_mpi_render_shaded_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_shaded_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiShading), vp, vp, vp, vp, i64p, vp, i64p, vp]
     lib.gmpi_mpi_render_depth_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha), vp]
     lib.gmpi_mpi_render_depth_window_launch.restype = ctypes.c_int

@@ -40,6 +40,16 @@ hipError_t launch_shared_backward(const KParams& p, int dtype, const SharedK& sh
 hipError_t launch_shared_forward(const KParams& p, int dtype, const SharedK& sh, hipStream_t stream);   // render_shared_forward.hip
 bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh);   // render_shared_forward.hip
 int shared_forward_query(int what);                                         // render_shared_forward.hip
+hipError_t launch_shaded(const KParams& p, int dtype, const ShadeK& sh, hipStream_t stream);   // render_shaded.hip
+bool shaded_forward_supports(const KParams& p, int dtype, const ShadeK& sh);   // render_shaded.hip
+hipError_t launch_shaded_forward(const KParams& p, int dtype, const ShadeK& sh, hipStream_t stream);   // render_shaded.hip
+hipError_t launch_shaded_chain_rule(const KParams& p, int dtype, const ShadeK& sh, float* g, const int64_t* gst, float* g_shading, const int64_t* qst,
+                                    hipStream_t stream);   // render_shaded.hip
+hipError_t launch_zero_image(float* img, const int64_t* st, int M, int Ht, int Wt, hipStream_t stream);   // render_shaded.hip
+hipError_t launch_backward_shading_only(const KParams& p, int dtype, const ShadeK& sh, const float* g_rgb, const float* g_depth, const float* g_T, float* g_shading,
+                                        const int64_t* qst, hipStream_t stream);   // render_backward.hip
+hipError_t launch_backward_shaded(const KParams& p, int dtype, const ShadeK& sh, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
+                                  const int64_t* gstride, bool tiles, hipStream_t stream);   // render_backward.hip
 hipError_t launch_depth(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, hipStream_t stream);   // render_depth.hip
 hipError_t launch_depth_backward(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth.hip
 hipError_t launch_depth_backward_tile(const KParams& p, int dtype, const SharedK& sh, const DepthK& dk, const SharedG& g, hipStream_t stream);   // render_depth_tile.hip
@@ -663,6 +673,77 @@ int gmpi_mpi_render_shared_backward_launch(const GmpiRenderParams* params, const
     return hip_rc(launch_shared_backward(p, params->rgba_dtype, sh, g, params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the shaded render of an RGBA volume: the checks of the volume entries (to_kparams; GMPI_DTYPE_U8 refused) + the GmpiShading struct --------------
+static int to_shaded(const GmpiRenderParams* params, const GmpiShading* shading, bool forward, KParams& p, ShadeK& sh) {
+    if (params == nullptr || shading == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams) || shading->struct_size != sizeof(GmpiShading)) return GMPI_E_ABI;
+    p.N = 0;
+    if (params->N == 0) return GMPI_OK;   // no views: the callers return at once
+    const int rc = to_kparams(params, p, forward, true);
+    if (rc != GMPI_OK) return rc;
+    if (shading->shading == nullptr) return GMPI_E_NULL;
+    if (shading->shading_stride[1] < p.Wt || shading->shading_stride[0] < 0 || (shading->shading_stride[0] == 0 && p.M != 1)) return GMPI_E_STRIDE;
+    sh.s = shading->shading, sh.s_mpi = shading->shading_stride[0], sh.s_row = shading->shading_stride[1];
+    p.ws = nullptr, p.ws_bytes = 0;   // no kernel of these entries wants scratch
+    return GMPI_OK;
+}
+
+int gmpi_mpi_render_shaded_launch(const GmpiRenderParams* params, const GmpiShading* shading, void* stream) {
+    KParams p;
+    ShadeK sh;
+    const int rc = to_shaded(params, shading, true, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return GMPI_OK;
+    int variant = params->variant;
+    if (variant != GMPI_VARIANT_AUTO && variant != GMPI_VARIANT_GATHER && variant != GMPI_VARIANT_LDS) return GMPI_E_VARIANT;
+    const bool staged = shaded_forward_supports(p, params->rgba_dtype, sh);
+    if (variant == GMPI_VARIANT_AUTO) variant = staged ? GMPI_VARIANT_LDS : GMPI_VARIANT_GATHER;
+    if (variant == GMPI_VARIANT_LDS) {
+        if (!staged) return GMPI_E_VARIANT;   // these tensors are not aligned for its loader
+        return hip_rc(launch_shaded_forward(p, params->rgba_dtype, sh, static_cast<hipStream_t>(stream)));
+    }
+    if (p.N > 65535) return GMPI_E_SHAPE;  // the one-pixel kernel puts the view index in grid.z
+    return hip_rc(launch_shaded(p, params->rgba_dtype, sh, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_render_shaded_supports(const GmpiRenderParams* params, const GmpiShading* shading) {
+    KParams p;
+    ShadeK sh;
+    const int rc = to_shaded(params, shading, true, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return 0;
+    return shaded_forward_supports(p, params->rgba_dtype, sh) ? 1 : 0;
+}
+
+int gmpi_mpi_render_shaded_backward_launch(const GmpiRenderParams* params, const GmpiShading* shading, const float* grad_rgb, const float* grad_depth,
+                                           const float* grad_transmittance, float* grad_rgba, const int64_t* grad_rgba_stride, float* grad_shading,
+                                           const int64_t* grad_shading_stride, void* stream) {
+    KParams p;
+    ShadeK sh;
+    const int rc = to_shaded(params, shading, false, p, sh);
+    if (rc != GMPI_OK) return rc;
+    if (p.N == 0) return GMPI_OK;
+    if (grad_rgb == nullptr || (grad_rgba == nullptr && grad_shading == nullptr)) return GMPI_E_NULL;   // either gradient may be NULL when the other is not
+    if ((grad_rgba != nullptr && grad_rgba_stride == nullptr) || (grad_shading != nullptr && grad_shading_stride == nullptr)) return GMPI_E_NULL;
+    if (p.N > 65535 || p.M > 65535 || p.Ht > 65535) return GMPI_E_SHAPE;  // the view index is grid.y / grid.z; the chain rule's grid is (columns, Ht, M)
+    if (grad_rgba != nullptr) {
+        if (grad_rgba_stride[4] != 1 || grad_rgba_stride[3] < p.Wt) return GMPI_E_STRIDE;
+        for (int i = 0; i < 4; ++i)
+            if (grad_rgba_stride[i] <= 0 && !(i == 0 && params->M == 1)) return GMPI_E_STRIDE;
+    }
+    if (grad_shading != nullptr && (grad_shading_stride[1] < p.Wt || grad_shading_stride[0] < 0 || (grad_shading_stride[0] == 0 && p.M != 1))) return GMPI_E_STRIDE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (grad_rgba == nullptr) {   // the shading's gradient alone: no volume buffer -- zero-fill, then the one-pixel kernel adds the chain rule's terms per tap
+        const hipError_t z = launch_zero_image(grad_shading, grad_shading_stride, p.M, p.Ht, p.Wt, st);
+        if (z != hipSuccess) return hip_rc(z);
+        return hip_rc(launch_backward_shading_only(p, params->rgba_dtype, sh, grad_rgb, grad_depth, grad_transmittance, grad_shading, grad_shading_stride, st));
+    }
+    const hipError_t e = launch_backward_shaded(p, params->rgba_dtype, sh, grad_rgb, grad_depth, grad_transmittance, grad_rgba, grad_rgba_stride,
+                                                params->variant != GMPI_VARIANT_GATHER, st);
+    if (e != hipSuccess) return hip_rc(e);
+    return hip_rc(launch_shaded_chain_rule(p, params->rgba_dtype, sh, grad_rgba, grad_rgba_stride, grad_shading, grad_shading_stride, st));
+}
+
 // depth-alpha entries: params->rgba = the depth image (rgba_stride[1], [2] ignored); the checks of to_shared (AUTO and GATHER only) + the GmpiDepthAlpha struct.
 static int to_depth(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* da, bool forward, KParams& p, SharedK& sh, DepthK& dk) {
     if (params == nullptr || shared == nullptr || da == nullptr) return GMPI_E_NULL;
@@ -983,6 +1064,7 @@ int gmpi_query(int32_t what) {
         case 30: return 1;  // the geometry backward of the shared-colour and depth-alpha layouts is built in  (29: unused)
         case 32: return 1;  // compute_depth of the depth-alpha layout (gmpi_ramp_depth_launch, light_kernels.hip) is built in  (31: unused)
         case 34: return 1;  // the atomics-free backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_*_backward_gather_launch) is built in  (33: unused)
+        case 38: return 1;  // the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch, gmpi_mpi_render_shaded_backward_launch) is built in  (37: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -26,8 +26,12 @@ namespace gmpi {
 // The three kernels below are bodies with two instances each: the whole stack (CHUNK = false: the kernels' names and code of old) and one chunk of a
 // plane-chunked stack (CHUNK = true, the *_chunk_kernel twins: the sweep is continued from BwdParams::T_in / S_in -- bwd_pixel_setup has the rule -- and
 // every pixel lane stores its suffix sum to S_out after plane 0 of the launch).
-template <typename TexT, bool AC, bool CHUNK>
-__device__ __forceinline__ void render_backward_pixel(const KParams& p, const BwdParams& b) {
+// A third instance of the one-pixel body and of the 64 x 8 tile body: Shade = ShadeK (gmpi_backward.hpp), the *_shaded_kernel twins of the shaded render
+// (gmpi_mpi_render_shaded_backward_launch) -- the colour taps are shaded as its forward shades them, so what is scattered is the gradient w.r.t. the
+// SHADED texels; the chain rule through the clip follows in place (render_shaded.hip).  NoShade, the default, compiles to the kernels of old.
+template <typename TexT, bool AC, bool CHUNK, typename Shade = NoShade>
+__device__ __forceinline__ void render_backward_pixel(const KParams& p, const BwdParams& b, const Shade& shade = Shade{}) {
+    constexpr bool SHADED = !std::is_same_v<Shade, NoShade>;
     const int n = blockIdx.z;
     const int px = blockIdx.x * 64 + threadIdx.x;
     const int py = blockIdx.y * 4 + threadIdx.y;
@@ -45,7 +49,11 @@ __device__ __forceinline__ void render_backward_pixel(const KParams& p, const Bw
         float ix, iy, s;
         pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
         float smp[4], d_s[4];
-        gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
+        if constexpr (SHADED)
+            shaded_gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, shade.s + static_cast<int64_t>(vw.m) * shade.s_mpi,
+                                              shade.s_row, Ht, Wt, ix, iy, false, unused, smp);
+        else
+            gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
         bp.plane(smp, s, d_s);
 
         Footprint f = footprint(ix, iy, Ht, Wt);
@@ -72,6 +80,75 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const KParams p, c
 template <typename TexT, bool AC>
 __global__ __launch_bounds__(256) void render_backward_chunk_kernel(const KParams p, const BwdParams b) {
     render_backward_pixel<TexT, AC, true>(p, b);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_backward_shaded_kernel(const KParams p, const BwdParams b, const ShadeK shade) {
+    render_backward_pixel<TexT, AC, false>(p, b, shade);
+}
+
+// The shaded render's backward when ONLY the shading wants a gradient (gmpi_mpi_render_shaded_backward_launch with grad_rgba == NULL): no volume-sized
+// buffer exists to hold dL/d shaded, so the chain rule through clip(rgb * s) runs per TAP -- the term a pixel would scatter to texel (k, c, y, x),
+// d_s[c] * weight, times rgb * [0 <= rgb s <= 1] of that texel, summed over the three colour channels and added to grad_shading[m, 0, y, x] (zero-filled
+// by the entry): the sum over pixels, planes and channels that light_apply_backward_inplace_kernel forms from the volume, in another order.  One pixel
+// per lane, render_backward_kernel's sweep; 4 global atomics per pixel and plane.
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_backward_shading_only_kernel(const KParams p, const BwdParams b, const ShadeK shade, float* __restrict__ g_shading,
+                                                                           const int64_t q_mpi, const int64_t q_row) {
+    const int n = blockIdx.z;
+    const int px = blockIdx.x * 64 + threadIdx.x;
+    const int py = blockIdx.y * 4 + threadIdx.y;
+    if (px >= p.W || py >= p.H) return;
+    const BwdView vw = bwd_view<AC>(p, n);
+    const int Ht = p.Ht, Wt = p.Wt;
+    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const float* __restrict__ sh = shade.s + static_cast<int64_t>(vw.m) * shade.s_mpi;
+    float* __restrict__ gs = g_shading + static_cast<int64_t>(vw.m) * q_mpi;
+    BwdPixel bp;
+    bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, b.g_rgb, b.g_depth, b.g_T, vol);
+    for (int k = p.D - 1; k >= 0; --k) {
+        float ix, iy, s;
+        pixel_plane_coord<AC>(vw, bp, k, ix, iy, s);
+        // shaded_gather_sample's footprint, addresses and zeroed weights, with the raw colour taps kept
+        Footprint f = footprint(ix, iy, Ht, Wt);
+        const bool x0in = f.x0 >= 0 && f.x0 <= Wt - 1, x1in = f.x0 >= -1 && f.x0 <= Wt - 2;
+        const bool y0in = f.y0 >= 0 && f.y0 <= Ht - 1, y1in = f.y0 >= -1 && f.y0 <= Ht - 2;
+        if (!(x0in && y0in)) f.nw = 0.0f;
+        if (!(x1in && y0in)) f.ne = 0.0f;
+        if (!(x0in && y1in)) f.sw = 0.0f;
+        if (!(x1in && y1in)) f.se = 0.0f;
+        const int xa = min(max(f.x0, 0), Wt - 1), xb = min(max(f.x0 + 1, 0), Wt - 1);
+        const int ya = min(max(f.y0, 0), Ht - 1), yb = min(max(f.y0 + 1, 0), Ht - 1);
+        const int xs[4] = {xa, xb, xa, xb}, ys[4] = {ya, ya, yb, yb};
+        const float w[4] = {f.nw, f.ne, f.sw, f.se};
+        const TexT* __restrict__ pl = vol + static_cast<int64_t>(k) * p.s_plane;
+        float raw[3][4], st[4], smp[4], d_s[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) st[i] = sh[static_cast<int64_t>(ys[i]) * shade.s_row + xs[i]];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float t[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t[i] = to_f32(pl[c * p.s_chan + static_cast<int64_t>(ys[i]) * p.s_row + xs[i]]);
+            if (c < 3) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) raw[c][i] = t[i], t[i] = shade_texel(t[i], st[i]);
+            }
+            smp[c] = bilerp<false>(t[0], t[1], t[2], t[3], f);
+        }
+        bp.plane(smp, s, d_s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float prod = raw[c][i] * st[i];
+                v += (prod >= 0.0f && prod <= 1.0f) ? d_s[c] * raw[c][i] : 0.0f;
+            }
+            v *= w[i];
+            // (the weight gates the address's meaning: a tap outside the texture has weight 0; the clamped address is inside it either way)
+            if (w[i] != 0.0f && v != 0.0f) atomicAdd(gs + static_cast<int64_t>(ys[i]) * q_row + xs[i], v);
+        }
+    }
 }
 
 // ---- tile version: the scatter is staged in LDS ---------------------------------------------------------------------
@@ -252,8 +329,9 @@ using B2Tall = B2Geo<32, 16, 56, 27>;   // 23.6 KB per box
 using B2Wide = B2Geo<64, 8, 80, 19>;    // 23.8 KB per box
 constexpr int kBwdDefaultGeo = 2;       // 1 = 32 x 16 tiles (round 5) | 2 = 64 x 8 tiles (profiles/r06_backward.txt)
 
-template <typename TexT, bool AC, typename G, bool CHUNK>
-__device__ __forceinline__ void render_backward_tile2_body(const KParams& p, const BwdParams& b, const int tiles_x) {
+template <typename TexT, bool AC, typename G, bool CHUNK, typename Shade = NoShade>
+__device__ __forceinline__ void render_backward_tile2_body(const KParams& p, const BwdParams& b, const int tiles_x, const Shade& shade = Shade{}) {
+    constexpr bool SHADED = !std::is_same_v<Shade, NoShade>;
     constexpr int kB2TW = G::TW, kB2TH = G::TH, kB2Pitch = G::Pitch, kB2Rows = G::Rows, kB2Cap = G::Cap;
     __shared__ int4 box[kB2Chunk];        // bx0, by0, nx (<= 0: not staged), ny
     __shared__ float4 pcA[kB2Chunk];      // zdiff, w/2, h/2, RN(2/w)
@@ -315,8 +393,12 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
         fetch_pair_taps<TexT>(q, vol + static_cast<int64_t>(k) * p.s_plane, s_chan_b, s_row_b, Ht, Wt);
     };
     // the taps have landed: bilinear samples, the plane's gradients, the tile maximum
-    auto grads = [&](int t, const PairTaps& q, Grad& gq) -> uint2 {
+    auto grads = [&](int t, PairTaps& q, Grad& gq) -> uint2 {
         float smp[4];
+        // The shading pairs are loaded HERE, not a plane ahead with the taps: four more registers in flight across the scatter put the align_corners
+        // instances over the 80 the launch bounds leave (12 bytes of scratch); the image is one per MPI and comes from the caches.  (q is refilled by
+        // the next fetch.)
+        if constexpr (SHADED) shade_pair_taps(q, shade.s + static_cast<int64_t>(vw.m) * shade.s_mpi, static_cast<uint32_t>(shade.s_row) * 4u, Ht, Wt);
         pair_samples(q, Ht, Wt, smp);
         bp.plane_recip(smp, q.s, gq.d);
         {   // the scatter weights of the true taps (x0, y0) .. (x0 + 1, y0 + 1)
@@ -588,6 +670,10 @@ template <typename TexT, bool AC, typename G>
 __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_chunk_kernel(const KParams p, const BwdParams b, const int tiles_x) {
     render_backward_tile2_body<TexT, AC, G, true>(p, b, tiles_x);
 }
+template <typename TexT, bool AC, typename G>
+__global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_shaded_kernel(const KParams p, const BwdParams b, const int tiles_x, const ShadeK shade) {
+    render_backward_tile2_body<TexT, AC, G, false>(p, b, tiles_x, shade);
+}
 
 template <typename TexT, bool CHUNK = false>
 static hipError_t launch_backward_t(const KParams& p, const BwdParams& b, bool tiles, hipStream_t stream) {
@@ -669,6 +755,57 @@ hipError_t launch_backward(const KParams& p0, int dtype, const float* g_rgb, con
 #endif
     if (gather) return launch_backward_gather(p, dtype, b, (p.flags & GMPI_FLAG_GRAD_OVERWRITE) != 0, stream);
     return dispatch_dtype(dtype, [&](auto t) { return launch_backward_t<typename decltype(t)::type>(p, b, tiles, stream); });
+}
+
+// The shaded render's backward (gmpi_mpi_render_shaded_backward_launch): the 64 x 8 tile kernel's shaded twin, or -- GATHER, and every launch that kernel's
+// guards refuse (two columns for the pair loads; a plane's offsets in 32 bits for the volume, its gradient and the shading image) -- the one-pixel
+// kernel's.  The v1 tile kernel has no twin; never the atomics-free pair: no workspace is read.
+template <typename TexT>
+static hipError_t launch_backward_shaded_t(const KParams& p, const BwdParams& b, const ShadeK& sh, bool tiles, hipStream_t stream) {
+    const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
+    const int es = static_cast<int>(sizeof(TexT));
+    tiles = tiles && p.N <= 65535 && p.Wt >= 2 && plane_offsets_fit_32(p.s_chan, p.s_row, p.Ht, p.Wt, es) && plane_offsets_fit_32(b.gs_chan, b.gs_row, p.Ht, p.Wt, 1) &&
+            plane_offsets_fit_32(0, sh.s_row, p.Ht, p.Wt, 4);
+    if (tiles) {
+        using G = B2Wide;
+        const int tx = (p.W + G::TW - 1) / G::TW, ty = (p.H + G::TH - 1) / G::TH;
+        const dim3 grid2(xcd_grid_per_group(tx * ty, tx * ty), p.N);
+        dispatch_bool(ac, [&](auto AC) {
+            hipLaunchKernelGGL((render_backward_tile2_shaded_kernel<TexT, decltype(AC)::value, G>), grid2, dim3(kB2Threads), 0, stream, p, b, tx, sh);
+        });
+        return hipGetLastError();
+    }
+    const dim3 block(64, 4), grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
+    dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_shaded_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, sh); });
+    return hipGetLastError();
+}
+// grad_rgba == NULL: the shading's gradient alone, added into g_shading (the caller has zero-filled it).  N <= 65535 (grid.z).
+hipError_t launch_backward_shading_only(const KParams& p0, int dtype, const ShadeK& sh, const float* g_rgb, const float* g_depth, const float* g_T, float* g_shading,
+                                        const int64_t* qst, hipStream_t stream) {
+    KParams p = p0;
+    p.ws = nullptr, p.ws_bytes = 0;
+    BwdParams b;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T, b.g_rgba = nullptr;
+    b.gs_mpi = b.gs_plane = b.gs_chan = b.gs_row = 0;
+    const dim3 block(64, 4), grid((p.W + 63) / 64, (p.H + 3) / 4, p.N);
+    const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using TexT = typename decltype(t)::type;
+        dispatch_bool(ac, [&](auto AC) {
+            hipLaunchKernelGGL((render_backward_shading_only_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, sh, g_shading, qst[0], qst[1]);
+        });
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_backward_shaded(const KParams& p0, int dtype, const ShadeK& sh, const float* g_rgb, const float* g_depth, const float* g_T, float* g_rgba,
+                                  const int64_t* gstride, bool tiles, hipStream_t stream) {
+    KParams p = p0;
+    p.ws = nullptr, p.ws_bytes = 0;
+    BwdParams b;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T, b.g_rgba = g_rgba;
+    b.gs_mpi = gstride[0], b.gs_plane = gstride[1], b.gs_chan = gstride[2], b.gs_row = gstride[3];
+    return dispatch_dtype(dtype, [&](auto t) { return launch_backward_shaded_t<typename decltype(t)::type>(p, b, sh, tiles, stream); });
 }
 
 // One chunk of a plane-chunked stack (gmpi_mpi_render_chunk_backward_launch): the tile kernel or the one-pixel kernel, continued from T_in / S_in.  Never

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, depth_alpha, shared_color
+from . import _lib, depth_alpha, shaded, shared_color
 from .quantized import is_interleaved
 
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16, torch.uint8: _lib.DTYPE_U8}
@@ -352,6 +352,24 @@ def _shared_color(rgb: torch.Tensor, background: Optional[torch.Tensor]) -> _lib
     return sc
 
 
+def _shading_struct(shading: torch.Tensor) -> _lib.GmpiShading:
+    """The one builder of GmpiShading: shading fp32 [M,1,Ht,Wt], innermost stride 1 (`_shading_operand`)."""
+    sh = _lib.GmpiShading()
+    sh.struct_size = ctypes.sizeof(_lib.GmpiShading)
+    sh.shading = shading.data_ptr()
+    sh.shading_stride[:] = (shading.stride(0), shading.stride(2))
+    return sh
+
+
+def _shading_operand(shading: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    """The shading image as the kernels read it: fp32 on dev, innermost stride 1, row stride >= Wt, no negative stride; an MPI stride of 0 (an
+    `expand`ed image) only for one MPI.  The tensor itself when it is all that (a row-padded view, an expanded single image), else a contiguous copy."""
+    shading = shading.to(dev, torch.float32)
+    M, _, _, Wt = shading.shape
+    ok = shading.stride(3) == 1 and shading.stride(2) >= Wt and (shading.stride(0) > 0 or (shading.stride(0) == 0 and M == 1))
+    return shading if ok else shading.contiguous()
+
+
 def _depth_alpha(plane_z: torch.Tensor, z_lo: float, z_hi: float) -> _lib.GmpiDepthAlpha:
     """The one builder of GmpiDepthAlpha: plane_z fp32 [D] or [M,D] on the device (innermost stride 1), the ramp's constants rounded as
     `depth_alpha.ramp_constants` rounds them."""
@@ -533,6 +551,32 @@ def _warn_window_fallback() -> None:
 
 _GATHER_FALLBACK_WARNED = False
 _CHUNK_VARIANT_WARNED = False
+_SHADED_BACKWARD_WARNED = False
+
+
+_SHADED_LDS_WARNED = False
+
+
+def _warn_shaded_lds_fallback() -> None:
+    """Once per process: a shaded render on a module built with variant="lds" ran the one-pixel-per-lane kernel (every such launch is counted in
+    `MPI.shaded_lds_fallbacks`)."""
+    global _SHADED_LDS_WARNED
+    if not _SHADED_LDS_WARNED:
+        _SHADED_LDS_WARNED = True
+        warnings.warn('shaded render: variant="lds" cannot take these tensors (the volume\'s base pointer and outer strides must be multiples of 4 texels, '
+                      "the shading's of 16 bytes / 4 elements, and a width that is no multiple of 4 needs allocated padding behind the last row); the "
+                      "one-pixel-per-lane kernel runs instead (counted in MPI.shaded_lds_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
+
+
+def _warn_shaded_backward() -> None:
+    """Once per process: a shaded render on a module built with backward="gather" (every such backward is counted in
+    `MPI.shaded_backward_fallbacks`)."""
+    global _SHADED_BACKWARD_WARNED
+    if not _SHADED_BACKWARD_WARNED:
+        _SHADED_BACKWARD_WARNED = True
+        warnings.warn('shaded render: backward="gather" (the atomics-free pair) has no shaded form; the default backward, which ends in atomic adds, '
+                      "runs instead and the gradients are not bit-reproducible (counted in MPI.shaded_backward_fallbacks; this warning is given once)",
+                      RuntimeWarning, stacklevel=2)
 
 
 def _warn_chunk_variant(name: str) -> None:
@@ -660,6 +704,8 @@ class MPI(nn.Module):
         self.depth_window_fallbacks = 0  # depth-alpha launches that asked for depth_forward="window" and ran the one-pixel kernel instead
         self.layout_gather_fallbacks = 0   # shared-colour / depth-alpha backwards that asked for "gather" and ran the atomic kernels instead
         self.chunk_variant_fallbacks = 0   # chunk launches of a module built with variant "band" / "wave", which ran AUTO's chunk kernel instead
+        self.shaded_lds_fallbacks = 0    # shaded launches of a module built with variant "lds" that ran the one-pixel kernel instead
+        self.shaded_backward_fallbacks = 0   # shaded backwards of a module built with backward="gather", which ran the default backward instead
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -743,7 +789,7 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _layout: Optional[_Layout] = None):
+                     _layout: Optional[_Layout] = None, _shading: Optional[torch.Tensor] = None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -767,12 +813,13 @@ class MPI(nn.Module):
                 raise NotImplementedError("no gradient flows through a uint8 volume, w.r.t. the plane geometry and the camera tensors included "
                                           "(geometry_grad=True): render dequantize_volume(q) (ml_gmpi_amd.quantized) for that, or detach the "
                                           "camera and dhw tensors")
-            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _layout)
+            bridge = self._autograd_bridge(rgba, dhw, ray_dir, eye_pos, z_dir, _layout) if _shading is None else self._shaded_bridge(
+                rgba, _shading, dhw, ray_dir, eye_pos, z_dir)
             if bridge is not None:
                 kwargs = dict(views_per_mpi=views_per_mpi, view_to_mpi=view_to_mpi, check_last_plane=check_last_plane,
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint,
-                              _layout=_layout)
+                              _layout=_layout, _shading=_shading)
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -787,6 +834,8 @@ class MPI(nn.Module):
         rgba = _volume_operand(rgba)
         M, D, _, Ht, Wt = rgba.shape
         variant, images = _lib.VARIANTS[self.variant], None
+        if _shading is not None:   # (the shaded entries know AUTO, GATHER and LDS: "lds" is asked for below, once the structs exist)
+            variant, images = _lib.VARIANT_GATHER if self.variant == "gather" else _lib.VARIANT_AUTO, (_shading_operand(_shading, dev),)
         if _layout is not None:   # (rgba is the layout's first argument: the alpha tensor, or the depth image -- the planes are then dhw's)
             D, variant, images = _layout.operands(self, rgba, dhw)
         ray_dir, eye_pos, z_dir, dhw = (_f32_on(t, dev) for t in (ray_dir, eye_pos, z_dir, dhw))
@@ -813,7 +862,22 @@ class MPI(nn.Module):
             status, defer_status, ring, slot = _status_target(dev, stream, status, defer_status, on_device and not _in_autograd_fn)
             p = _render_params(scalars, keep, color, depth, T, status)
             fully_checked = None   # the volume whose exhaustive range pass this call ran
-            if _layout is None:
+            if _shading is not None:
+                # range_check="full": the exhaustive pass over the alpha channel in every call (the shaded colour is in [0, 1] by construction)
+                if self.range_check == "full":
+                    _range_pass((rgba[:, :, 3:],), p, dev, stream)
+                sh = _shading_struct(images[0])
+                # the staged forward where its loader can take the two tensors, padding behind the last row of a ragged width included (which the
+                # library cannot see: AUTO is resolved here), else the one-pixel-per-lane kernel
+                if self.variant != "gather" and on_device:
+                    p.variant = _lib.VARIANT_LDS
+                    if not _forward_takes("gmpi_render_shaded_supports", (p, sh), (rgba, images[0])):
+                        p.variant = _lib.VARIANT_GATHER
+                        if self.variant == "lds":   # asked for by name: counted and warned of once, as the other staged forwards
+                            self.shaded_lds_fallbacks += 1
+                            _warn_shaded_lds_fallback()
+                _call("gmpi_mpi_render_shaded_launch", dev, ctypes.byref(p), ctypes.byref(sh), stream=stream)
+            elif _layout is None:
                 if on_device:  # scratch for the kernels that want some (the band kernel's geometry table): 0 bytes for most launches
                     need = int(_lib.load_library().gmpi_render_workspace_bytes(ctypes.byref(p)))
                     if need:
@@ -853,6 +917,13 @@ class MPI(nn.Module):
             return _LayoutRenderFunction, (layout.rgb, rgba, layout.background)
         return None
 
+    def _shaded_bridge(self, rgba, shading, dhw, ray_dir, eye_pos, z_dir):
+        """`_autograd_bridge` for the shaded render: the gradient reaches the volume and the shading image, never the geometry."""
+        if self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
+            raise NotImplementedError("the shaded render has no gradient w.r.t. the plane geometry or the camera tensors: render "
+                                      "apply_shading(rgba, shading) with render_views for that, or detach the camera and dhw tensors")
+        return (_ShadedRenderFunction, (rgba, shading)) if rgba.requires_grad or shading.requires_grad else None
+
     def _flags(self, out_pm1, check_last_plane, frontal_hint, tilted_hint, oblique_hint) -> int:
         return ((_lib.FLAG_ALIGN_CORNERS if self._align_corners else 0) | (_lib.FLAG_OUT_PM1 if out_pm1 else 0)
                 | (_lib.FLAG_CHECK_LAST_PLANE if check_last_plane else 0) | (_lib.FLAG_CHECK_RANGE if self.range_check != "off" else 0)
@@ -872,6 +943,32 @@ class MPI(nn.Module):
             raise
         if fully_checked is not None:
             self._full_check_record(fully_checked)   # (read back and clean: the whole volume is in [0, 1])
+
+    # -- shaded RGBA volume ------------------------------------------------------------------------------------------------------------
+    def render_views_shaded(self, rgba: torch.Tensor, shading: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
+                            z_dir: torch.Tensor, **kwargs):
+        """`render_views` of the volume `apply_shading(rgba, shading)` (shaded.py) without building it: rgba [M,D,4,Ht,Wt] (fp32 / bf16 / fp16, any
+        outer strides), shading [M,1,Ht,Wt] (one factor per texel: `LightRenderer.shading_image`; converted with .float() when it is not fp32; a
+        row-padded view or, for one MPI, an expanded image is read as it is).  The multiply and the clip happen on the taps
+        (gmpi_mpi_render_shaded_launch): the forward allocates the output images only.  Same keyword arguments, returned dict, status bits and status
+        handling as `render_views`; strict-order mode is bit-identical to the render of the shaded volume.  A NaN colour texel is shaded to 0, as
+        `gmpi_light_apply_launch` shades it (torch.clip in `apply_shading` would keep the NaN).  Under autograd the gradient reaches rgba (in its
+        dtype) and shading: ONE fp32 gradient volume is zero-filled, filled by one backward launch with the gradient w.r.t. the shaded texels, and
+        turned into the gradient w.r.t. rgba in place by the per-texel chain rule through the clip, which also writes the shading's gradient
+        (gmpi_mpi_render_shaded_backward_launch); for an fp32 volume that buffer is rgba.grad.  What requires no grad gets no buffer: when only the
+        shading does, no volume is allocated (the one-pixel backward applies the chain rule per tap and adds into the shading's gradient).  The module's variant: "gather" forces the
+        one-pixel-per-lane kernels, forward and backward; every other one takes the staged forward (render_shaded.hip: texel boxes of 32 x 16 pixel
+        tiles through LDS, shaded once per staged texel) when gmpi_render_shaded_supports says it can take the two tensors -- the volume's base
+        pointer and outer strides multiples of 4 texels, the shading's of 16 bytes / 4 elements, allocated padding behind the last row of a width
+        that is no multiple of 4 -- and the one-pixel kernel otherwise (the same bits in strict-order mode; for a module built with variant "lds" counted in `shaded_lds_fallbacks`,
+        one RuntimeWarning per process), and the 64 x 8 tile backward.  range_check="full" passes over the alpha channel only (a strided view:
+        copied for the pass); "touched" tests the alpha taps.  Refused: a uint8 volume (TypeError), a shading that is not [M,1,Ht,Wt] (ValueError),
+        geometry_grad with a camera or dhw tensor that requires grad (NotImplementedError).  `MPI(backward="gather")` has no shaded form: such a
+        module runs the default backward here, counted in `shaded_backward_fallbacks`, one RuntimeWarning per process."""
+        if rgba.dtype is torch.uint8:
+            raise TypeError("the shaded render takes fp32, bf16 or fp16 volumes, not uint8 codes: render dequantize_volume(q) (ml_gmpi_amd.quantized)")
+        shaded._check(rgba, shading)
+        return self.render_views(rgba, dhw, ray_dir, eye_pos, z_dir, _shading=shading, **kwargs)
 
     # -- shared-colour layout ----------------------------------------------------------------------------------------------------------
     def render_views_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
@@ -1125,6 +1222,50 @@ class _RenderFunction(torch.autograd.Function):
             entry = "gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch"
             geo = _geometry_pass(ctx, keep, T, dev, stream, want, entry, (), upstream)
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
+
+
+class _ShadedRenderFunction(torch.autograd.Function):
+    """autograd bridge of `MPI.render_views_shaded`: forward = gmpi_mpi_render_shaded_launch, backward = gmpi_mpi_render_shaded_backward_launch -- one
+    zero-filled fp32 gradient volume, one backward launch, the chain rule through the clip in place (d/d rgba, d/d shading); when only the shading
+    requires grad, no volume at all (grad_rgba NULL: the chain rule per tap).  Saved tensors and the
+    private transmittance buffer as `_RenderFunction`."""
+
+    @staticmethod
+    def forward(ctx, rgba, shading, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+        res, keep, images = _bridge_forward(ctx, mpi, rgba, (dhw, ray_dir, eye_pos, z_dir), kwargs)
+        # (the forward's kernel is a forward variant only: the backward is the one-pixel kernel for "gather", the library's choice otherwise)
+        ctx.scalars = ctx.scalars._replace(variant=_lib.VARIANT_GATHER if mpi.variant == "gather" else _lib.VARIANT_AUTO)
+        ctx.has_v2m = keep.view_to_mpi is not None
+        ctx.save_for_backward(*keep[:5], res["T"], images[0], *([keep.view_to_mpi] if ctx.has_v2m else []))
+        ctx.mpi = mpi
+        ctx.in_dtype, ctx.in_shape = rgba.dtype, tuple(rgba.shape)
+        ctx.shading_meta = (shading.dtype, shading.device, tuple(shading.shape))
+        return res["color"], res["depth"], res["T"], res["status"]
+
+    @staticmethod
+    def backward(ctx, g_color, g_depth, g_T, g_status):
+        saved = ctx.saved_tensors
+        keep, T, sh = _Keep(*saved[:5], saved[7] if ctx.has_v2m else None), saved[5], saved[6]
+        dev = keep.rgba.device
+        want_rgba, want_shading = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_rgba or want_shading):
+            return (None,) * 8
+        if ctx.mpi.backward == "gather":
+            ctx.mpi.shaded_backward_fallbacks += 1
+            _warn_shaded_backward()
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved tensors
+        # (what needs no gradient gets no buffer: NULL.  Without the volume's buffer the entry forms the shading's gradient per tap, image-sized memory only)
+        grad = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dev) if want_rgba else None
+        g_sh = torch.empty(ctx.shading_meta[2], dtype=torch.float32, device=dev) if want_shading else None
+        _call("gmpi_mpi_render_shaded_backward_launch", dev, ctypes.byref(p), ctypes.byref(_shading_struct(sh)), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T),
+              _ptr(grad), None if grad is None else (ctypes.c_int64 * 5)(*grad.stride()), _ptr(g_sh),
+              None if g_sh is None else (ctypes.c_int64 * 2)(g_sh.stride(0), g_sh.stride(2)), stream=stream)
+        grad = grad.to(ctx.in_dtype) if want_rgba else None
+        if g_sh is not None:
+            g_sh = g_sh.to(device=ctx.shading_meta[1], dtype=ctx.shading_meta[0])
+        return grad, g_sh, None, None, None, None, None, None
 
 
 class ChunkedRender:

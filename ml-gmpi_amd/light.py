@@ -234,6 +234,16 @@ def _shading_torch(depth_blurred: torch.Tensor, xyz_last: torch.Tensor, light_di
     return ka + diffuse * kd
 
 
+def _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading):
+    """dL/d depth [B,1,H,W] from dL/d shading [B,H,W] through the image-sized middle (blur, point cloud, normals, Lambert): torch autograd over
+    the torch restatement of the two kernels.  The ONE backward of the middle: `_LightFunction` and `_ShadingFunction` both call it."""
+    with torch.enable_grad():
+        d = depth.detach().requires_grad_(True)
+        s = _shading_torch(_blur_torch(d, my, mx), xyz_last, light_dir, ka, kd)
+        (g_depth,) = torch.autograd.grad(s, d, g_shading)
+    return g_depth
+
+
 class _LightFunction(torch.autograd.Function):
     """LightRenderer.render as one autograd node: forward = the four kernels, backward = apply-backward kernel, torch
     autograd through the B*H*W middle, alpha-depth-backward kernel (adds into the alpha channel of the gradient)."""
@@ -264,17 +274,35 @@ class _LightFunction(torch.autograd.Function):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _call("gmpi_light_apply_backward_launch", dev, vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(), g_out.data_ptr(),
               g_rgba.data_ptr(), g_shading.data_ptr(), B, D, H, W, stream=stream)
-        with torch.enable_grad():
-            d = depth.detach().requires_grad_(True)
-            s = _shading_torch(_blur_torch(d, my, mx), xyz_last, light_dir, ka, kd)
-            (g_depth,) = torch.autograd.grad(s, d, g_shading)
-        g_depth = g_depth.contiguous()
+        g_depth = _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading).contiguous()
         alpha = vol[:, :, 3:]
         plane = H * W
         _call("gmpi_alpha_depth_backward_launch", dev, alpha.data_ptr(), _DTYPES[vol.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3),
               ds.data_ptr(), T.data_ptr(), g_depth.data_ptr(), g_rgba.data_ptr() + 3 * plane * 4, D * 4 * plane, 4 * plane, W, B, D, H, W,
               stream=stream)
         return g_rgba.to(in_dtype), None, None, None, None, None, None
+
+
+class _ShadingFunction(torch.autograd.Function):
+    """The image-sized middle of `LightRenderer.shading_image` as one autograd node: forward = the blur and shading kernels `render` runs (the
+    same bits), backward = torch autograd through their torch restatements, as in `_LightFunction.backward`."""
+
+    @staticmethod
+    def forward(ctx, depth, renderer, xyz_last, light_dir, ka, kd):
+        dev = depth.device
+        H, W = depth.shape[-2:]
+        d = depth.detach()
+        shading = renderer.shading(renderer.blurrer_func(d), xyz_last, light_dir, ka, kd).unsqueeze(1)
+        ctx.save_for_backward(d, _blur_matrix(H, renderer._k1d, dev), _blur_matrix(W, renderer._k1d, dev), xyz_last.to(dev, torch.float32),
+                              light_dir.to(dev, torch.float32))
+        ctx.misc = (ka, kd)
+        return shading
+
+    @staticmethod
+    def backward(ctx, g_shading):
+        depth, my, mx, xyz_last, light_dir = ctx.saved_tensors
+        ka, kd = ctx.misc
+        return _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading[:, 0].to(torch.float32)), None, None, None, None, None
 
 
 class LightRenderer:
@@ -369,6 +397,25 @@ class LightRenderer:
         z = compute_depth_ramp(depth, plane_z, z_lo, z_hi, plane_ds)                                # [B,1,H,W] float32
         shade = self._shade_images(z, mpi_tex_pix_xyz, light_direction)
         return shade(rgb), depth, (None if background is None else shade(background))
+
+    def shading_image(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
+        """The shading `render` multiplies the colours by, as an image: batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3]
+        -> [B,1,H,W] float32, for `MPI.render_views_shaded` / `MPIRenderer.render_shaded`, which shade on the taps: `render(mpi)` equals
+        `apply_shading(mpi, shading_image(mpi))` bit for bit (the depth, blur and shading kernels are `render`'s).  One step of the schedule: the
+        step counter, cur_ka / cur_kd and the torch RNG advance exactly as in `render` -- call one or the other per step.  Nothing volume-sized is
+        allocated in the forward.  Differentiable w.r.t. the alpha channel of batch_mpi: the expected depth comes from the differentiable
+        `compute_depth`, the image-sized middle back-propagates through its torch restatement (the one `_shade_images` runs)."""
+        _refuse_uint8("LightRenderer.shading_image", batch_mpi)
+        if not batch_mpi.is_cuda:
+            raise _lib.GmpiError("LightRenderer.shading_image needs tensors on a ROCm device (no CPU path)")
+        assert batch_mpi.ndim == 5 and batch_mpi.shape[2] == 4, f"Expected an RGBA volume (#mpi, #planes, 4, h, w), got {tuple(batch_mpi.shape)}"
+        light_direction = self._next_light(batch_mpi.shape[0])
+        plane_ds = mpi_plane_dhws[:, :1].detach().to(batch_mpi.device)
+        xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach()
+        depth = compute_depth(batch_mpi[:, :, 3:], plane_ds)                                        # [B,1,H,W] float32
+        if torch.is_grad_enabled() and depth.requires_grad:
+            return _ShadingFunction.apply(depth, self, xyz_last, light_direction, self.cur_ka, self.cur_kd)
+        return self.shading(self.blurrer_func(depth), xyz_last, light_direction, self.cur_ka, self.cur_kd).unsqueeze(1)
 
     def _shade_images(self, depth: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, light_direction: torch.Tensor):
         """The image-sized middle of the augmentation in torch (blur, point cloud, normals, Lambert), shared by `render_shared` and

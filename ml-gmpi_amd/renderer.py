@@ -419,6 +419,7 @@ class MPIRenderer:
         views_per_mpi = int(ext.pop("views_per_mpi", 1))
         want_T = bool(ext.pop("want_transmittance", False))
         layout = ext.pop("_layout", None)   # render_shared / render_depth: batch_mpi_rgbas is then the alpha tensor / the depth image [B,1,1,Ht,Wt]
+        shading = ext.pop("_shading", None)   # render_shaded: the shading image [B,1,Ht,Wt] of the shaded render
         chunks = ext.pop("_chunks", None)   # render_chunks: the stack's chunks (batch_mpi_rgbas is then the first of them, looked at for its shape alone)
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
@@ -438,7 +439,7 @@ class MPIRenderer:
             #  backward, and the next render() of this shape would overwrite them through a raw pointer -- no version counter sees that)
             # (nor when the status check lags: the pending entry of this call keeps its camera tensors for the diagnostics of a tripped
             #  assertion -- "pos / dir / min val" of THIS call, printed one or more calls later -- so a later call must not overwrite them)
-            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad)
+            recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (shading is not None and shading.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad)
                                                      or (isinstance(chunks, (list, tuple)) and any(c.requires_grad for c in chunks)))
             ray_t, eye_t, zd_t = self._generate_rays_hip(c2w, reuse=not recording and defer != "lag")
         else:
@@ -463,6 +464,11 @@ class MPIRenderer:
             res = self.mpi.render_views_chunks(
                 chunks, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi, check_last_plane=assert_not_out_of_last_plane, out_pm1=True,
                 want_transmittance=want_T, c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer)
+        elif shading is not None:
+            res = self.mpi.render_views_shaded(
+                batch_mpi_rgbas, shading, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
+                check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
+                c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique)
         else:
             res = self.mpi.render_views(
                 batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
@@ -497,6 +503,17 @@ class MPIRenderer:
             yield from it
         shape_only = first.new_empty((first.shape[0], 0))   # (render reads the number of MPIs off it; no view of the chunk: that would keep its storage)
         return self.render(shape_only, render_h, render_w, _chunks=rest(), **kwargs)
+
+    def render_shaded(self, batch_mpi_rgbas, shading, render_h, render_w, **kwargs):
+        """`render` of the volume `apply_shading(batch_mpi_rgbas, shading)` without building it (`MPI.render_views_shaded`): batch_mpi_rgbas
+        [B,D,4,Ht,Wt], shading [B,1,Ht,Wt] -- `LightRenderer.shading_image(batch_mpi_rgbas, ...)` for the reference's augmentation, whose two
+        lines `mpi = light_renderer.render(mpi, ...); mpi_renderer.render(mpi, ...)` become `s = light_renderer.shading_image(mpi, ...);
+        mpi_renderer.render_shaded(mpi, s, ...)`.  Keyword arguments, return tuple, pose sampling, camera hints and the consumption of the torch RNG
+        are `render`'s: a seeded call returns the c2w and angles `render` returns for the shaded volume.  Under autograd the gradient reaches both
+        tensors; nothing volume-sized is allocated but the one fp32 gradient of the volume."""
+        if shading is None:
+            raise ValueError("render_shaded needs a shading image [B,1,Ht,Wt]")
+        return self.render(batch_mpi_rgbas, render_h, render_w, _shading=shading, **kwargs)
 
     def render_shared(self, batch_mpi_rgb, batch_mpi_alpha, render_h, render_w, *, background_rgb=None, variant=None, **kwargs):
         """`render` of the volume `expand_shared_color(batch_mpi_rgb, batch_mpi_alpha, background_rgb)` without building it (the layout GMPI's
