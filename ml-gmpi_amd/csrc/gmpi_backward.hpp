@@ -8,8 +8,9 @@
 //                                   plane-chunked stack, the sweep CONTINUED from T_in / S_in; bwd_store_suffix hands S to the chunk in front
 //   BwdPixel::plane / plane_recip   one plane of the sweep (division form / the same quotients through a rounded reciprocal)
 //   PairTaps / pair_tap_coord / fetch_pair_taps / pair_samples     the pair-load tap fetch and its bilinear sample
-//   NoShade / ShadeK / shade_texel / shaded_gather_sample / shade_pair_taps     the Shade policy of the shaded render (render_shaded.hip; the *_shaded_kernel
-//                                   twins of render_backward.hip): colour taps multiplied by the shading texel of their position and clipped, alpha raw
+//   shade_pair_taps                 the pair-load form of the Shade policy of the shaded render (the *_shaded_kernel twins of render_backward.hip): colour
+//                                   taps multiplied by the shading texel of their position and clipped, alpha raw.  The policy itself -- NoShade / ShadeK /
+//                                   shade_texel / shaded_gather_sample -- lives in gmpi_device.hpp: the forwards of render_shaded.hip sample with it too
 //   cvt_rpi_i32, fix_split, to_fix, abs_bits, lds_barrier, wave_max_u32, wave_max_bits     the fixed-point and wave primitives of the staged scatters
 //   the cross-plane tile frame      what shared_tile and depth_tile stage their cross-plane sums with: the tile constants (kTileW .. kTilePlanes, kCW, kCH),
 //                                   TileFrame / tile_frame / tile_frame_box / tile_grid, FixScale / fix_scale, lds_add_taps, MovingWindow and its flush
@@ -236,54 +237,9 @@ __device__ __forceinline__ void fetch_pair_taps(PairTaps& q, const TexT* __restr
         load_pair<TexT>(pl, ob + c4 * s_chan_b, q.v[4 * c4 + 2], q.v[4 * c4 + 3]);
     }
 }
-// ---- the Shade policy: the shaded render of an RGBA volume (GmpiShading, include/gmpi_render.h; render_shaded.hip) --------------------------------
-// The kernels that take it sample the volume clip(rgb * shading, 0, 1) | alpha without anybody building it: every colour tap is shaded where it is
-// fetched, with the shading texel of the SAME position (one image per MPI), the alpha tap is raw.  NoShade -- the default of every body below -- is a
-// compile-time nothing: the kernels of old.  shade_texel is light_apply_kernel's arithmetic (one rounding for the product; fmaxf drops a NaN: a NaN
-// colour texel is shaded to 0).
-struct NoShade {};
-struct ShadeK {
-    const float* s;          // [M,1,Ht,Wt]
-    int64_t s_mpi, s_row;
-};
-__device__ __forceinline__ float shade_texel(float t, float s) { return fminf(fmaxf(t * s, 0.0f), 1.0f); }
-
-// gather_sample (gmpi_device.hpp) of the shaded volume: the same footprint, addresses, zeroed weights and bilerp, the 12 colour taps shaded with the four
-// shading taps of the footprint.  check_range tests the alpha taps only: a shaded colour is in [0, 1] by construction.  sh: the MPI's shading image.
-template <typename TexT, bool STRICT>
-__device__ __forceinline__ void shaded_gather_sample(const TexT* __restrict__ pl, int64_t s_chan, int64_t s_row, const float* __restrict__ sh, int64_t sh_row,
-                                                     int Ht, int Wt, float ix, float iy, bool check_range, uint32_t& bad, float (&smp)[4]) {
-    Footprint f = footprint(ix, iy, Ht, Wt);
-    const bool x0in = f.x0 >= 0 && f.x0 <= Wt - 1, x1in = f.x0 >= -1 && f.x0 <= Wt - 2;
-    const bool y0in = f.y0 >= 0 && f.y0 <= Ht - 1, y1in = f.y0 >= -1 && f.y0 <= Ht - 2;
-    if (!(x0in && y0in)) f.nw = 0.0f;
-    if (!(x1in && y0in)) f.ne = 0.0f;
-    if (!(x0in && y1in)) f.sw = 0.0f;
-    if (!(x1in && y1in)) f.se = 0.0f;
-    const int xa = min(max(f.x0, 0), Wt - 1), xb = min(max(f.x0 + 1, 0), Wt - 1);
-    const int ya = min(max(f.y0, 0), Ht - 1), yb = min(max(f.y0 + 1, 0), Ht - 1);
-    const int64_t oa = static_cast<int64_t>(ya) * s_row, ob = static_cast<int64_t>(yb) * s_row;
-    const int64_t ha = static_cast<int64_t>(ya) * sh_row, hb = static_cast<int64_t>(yb) * sh_row;
-    const float s_nw = sh[ha + xa], s_ne = sh[ha + xb], s_sw = sh[hb + xa], s_se = sh[hb + xb];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const TexT* __restrict__ ch = pl + c * s_chan;
-        float t_nw = to_f32(ch[oa + xa]);
-        float t_ne = to_f32(ch[oa + xb]);
-        float t_sw = to_f32(ch[ob + xa]);
-        float t_se = to_f32(ch[ob + xb]);
-        if (c < 3) {
-            t_nw = shade_texel(t_nw, s_nw), t_ne = shade_texel(t_ne, s_ne), t_sw = shade_texel(t_sw, s_sw), t_se = shade_texel(t_se, s_se);
-        } else if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) {
-            bad |= GMPI_STATUS_RGBA_RANGE;
-        }
-        smp[c] = bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, f);
-    }
-}
-
-// The pair-load form, next to fetch_pair_taps: the two pair loads of the shading image at the footprint's rows and columns (fetch_pair_taps' addresses),
-// then the multiply and clip of q.v[0..11].  sh: the MPI's shading image, row stride in bytes (the launcher checks that its offsets fit 32 bits, as
-// for a plane of the volume, and Wt >= 2).
+// The Shade policy's pair-load form (NoShade / ShadeK / shade_texel: gmpi_device.hpp), next to fetch_pair_taps: the two pair loads of the shading image
+// at the footprint's rows and columns (fetch_pair_taps' addresses), then the multiply and clip of q.v[0..11].  sh: the MPI's shading image, row stride
+// in bytes (the launcher checks that its offsets fit 32 bits, as for a plane of the volume, and Wt >= 2).
 __device__ __forceinline__ void shade_pair_taps(PairTaps& q, const float* __restrict__ sh, uint32_t sh_row_b, int Ht, int Wt) {
     const int xa = min(max(q.x0, 0), Wt - 2);
     const int ya = min(max(q.y0, 0), Ht - 1), yb = min(max(q.y0 + 1, 0), Ht - 1);

@@ -392,6 +392,51 @@ __device__ __forceinline__ void gather_sample(const TexT* __restrict__ pl, int64
     }
 }
 
+// ---- the Shade policy: the shaded render of an RGBA volume (GmpiShading, include/gmpi_render.h; render_shaded.hip) --------------------------------
+// The kernels that take it sample the volume clip(rgb * shading, 0, 1) | alpha without anybody building it: every colour tap is shaded where it is
+// fetched, with the shading texel of the SAME position (one image per MPI), the alpha tap is raw.  NoShade -- the default of every body that takes the
+// policy (render_backward.hip) -- is a compile-time nothing: the kernels of old.  shade_texel is light_apply_kernel's arithmetic (one
+// rounding for the product; fmaxf drops a NaN: a NaN colour texel is shaded to 0).
+struct NoShade {};
+struct ShadeK {
+    const float* s;          // [M,1,Ht,Wt]
+    int64_t s_mpi, s_row;
+};
+__device__ __forceinline__ float shade_texel(float t, float s) { return fminf(fmaxf(t * s, 0.0f), 1.0f); }
+
+// gather_sample of the shaded volume: the same footprint, addresses, zeroed weights and bilerp, the 12 colour taps shaded with the four shading taps of
+// the footprint.  check_range tests the alpha taps only: a shaded colour is in [0, 1] by construction.  sh: the MPI's shading image.
+template <typename TexT, bool STRICT>
+__device__ __forceinline__ void shaded_gather_sample(const TexT* __restrict__ pl, int64_t s_chan, int64_t s_row, const float* __restrict__ sh, int64_t sh_row,
+                                                     int Ht, int Wt, float ix, float iy, bool check_range, uint32_t& bad, float (&smp)[4]) {
+    Footprint f = footprint(ix, iy, Ht, Wt);
+    const bool x0in = f.x0 >= 0 && f.x0 <= Wt - 1, x1in = f.x0 >= -1 && f.x0 <= Wt - 2;
+    const bool y0in = f.y0 >= 0 && f.y0 <= Ht - 1, y1in = f.y0 >= -1 && f.y0 <= Ht - 2;
+    if (!(x0in && y0in)) f.nw = 0.0f;
+    if (!(x1in && y0in)) f.ne = 0.0f;
+    if (!(x0in && y1in)) f.sw = 0.0f;
+    if (!(x1in && y1in)) f.se = 0.0f;
+    const int xa = min(max(f.x0, 0), Wt - 1), xb = min(max(f.x0 + 1, 0), Wt - 1);
+    const int ya = min(max(f.y0, 0), Ht - 1), yb = min(max(f.y0 + 1, 0), Ht - 1);
+    const int64_t oa = static_cast<int64_t>(ya) * s_row, ob = static_cast<int64_t>(yb) * s_row;
+    const int64_t ha = static_cast<int64_t>(ya) * sh_row, hb = static_cast<int64_t>(yb) * sh_row;
+    const float s_nw = sh[ha + xa], s_ne = sh[ha + xb], s_sw = sh[hb + xa], s_se = sh[hb + xb];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const TexT* __restrict__ ch = pl + c * s_chan;
+        float t_nw = to_f32(ch[oa + xa]);
+        float t_ne = to_f32(ch[oa + xb]);
+        float t_sw = to_f32(ch[ob + xa]);
+        float t_se = to_f32(ch[ob + xb]);
+        if (c < 3) {
+            t_nw = shade_texel(t_nw, s_nw), t_ne = shade_texel(t_ne, s_ne), t_sw = shade_texel(t_sw, s_sw), t_se = shade_texel(t_se, s_se);
+        } else if (check_range && !(in_unit(t_nw) && in_unit(t_ne) && in_unit(t_sw) && in_unit(t_se))) {
+            bad |= GMPI_STATUS_RGBA_RANGE;
+        }
+        smp[c] = bilerp<STRICT>(t_nw, t_ne, t_sw, t_se, f);
+    }
+}
+
 // ---- the forward's frame: what every render kernel does around its plane loop.  A change here reaches all of them, and
 //      the backward sweeps (gmpi_backward.hpp), which read the same view constants and the same dot product.  View / view_setup, check_camera_behind,
 //      ray_dot, last_plane / leaves_last_plane, gather_plane, store_pixel; then the tile frame of the staged tile kernels: view_group_items, fwd_tile_id /

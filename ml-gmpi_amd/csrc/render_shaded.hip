@@ -2,7 +2,7 @@
 // training configuration shades the generator's volume before it renders it (light_renderer.py:189-197: new_rgb = clip(rgb * shading[B,1,1,H,W], 0, 1),
 // alpha passed through; train.py:535-541, 703-709).  The shading is ONE factor per texel, the same for every plane and channel, so the shaded volume
 // need not exist: by definition the result is the render of light_apply_kernel's output (light_kernels.hip), and the multiply and the clip happen on the
-// taps -- shade_texel, gmpi_backward.hpp: that kernel's arithmetic, so the strict-order forward is bit-identical to render_gather.hip on the shaded volume.
+// taps -- shade_texel, gmpi_device.hpp: that kernel's arithmetic, so the strict-order forward is bit-identical to render_gather.hip on the shaded volume.
 //
 //   render_shaded_kernel                 forward, one pixel per lane, any shape / stride / dtype / ray field, every flag (render_gather_kernel's shape)
 //   render_shaded_forward_kernel         forward, staged: the tile frame of render_shared_forward.hip (see the kernel)
@@ -10,10 +10,7 @@
 //                                        (light_apply_backward_kernel without its aliasing promise, any gradient strides) + the shading's gradient
 //
 // The backward kernels are the shaded twins of render_backward.hip (its Shade policy).
-#include "gmpi_backward.hpp"
-#include "gmpi_shared.hpp"
-
-#include <algorithm>
+#include "gmpi_staged_forward.hpp"
 
 namespace gmpi {
 
@@ -58,13 +55,7 @@ __global__ __launch_bounds__(256) void render_shaded_kernel(const KParams p, con
 // the zeros padding); the texels of a ragged last item (Wt % 4 != 0) are zeroed after the shading, as there.  A (tile, plane) whose box does not fit, and
 // a pixel whose footprint lies outside its tile's box, take shaded_gather_sample -- render_shaded_kernel's sampling: a pixel's bits do not depend on the
 // path.  GMPI_FLAG_CHECK_RANGE tests the staged alpha texels raw (and the alpha taps of the direct path); a shaded colour is in [0, 1] by construction.
-constexpr int kSFW = 32, kSFH = 16, kSFThreads = kSFW * kSFH;   // pixel tile, one pixel per thread
-constexpr int kSFPitch = 56, kSFRows = 27;                      // staging buffer: texels per (row, channel) line, texel rows
-constexpr int kSFTPI = 4, kSFCols = kSFPitch / kSFTPI;          // texels per loader item, items per line
-constexpr int kSFBufFloats = kSFRows * 4 * kSFPitch;            // 6048 floats = 24 192 bytes
-constexpr int kSFChunk = 64;                                    // planes per box-table refill
-static_assert(kSFRows * kSFCols <= kSFThreads, "one loader item per thread and channel");
-static_assert(2 * kSFBufFloats * 4 + kSFChunk * (16 + 32 + 8) <= 53 * 1024, "3 workgroups per CU");
+static_assert(staged_forward_fits_lds(16 + 32 + 8), "3 workgroups per CU");   // table bytes per plane: box, org, orgs
 
 template <typename TexT, bool AC, bool STRICT>
 __global__ __launch_bounds__(kSFThreads, 6) void render_shaded_forward_kernel(const KParams p, const ShadeK shade, const int tiles_x, const int tiles_y,
@@ -295,10 +286,8 @@ hipError_t launch_shaded(const KParams& p, int dtype, const ShadeK& sh, hipStrea
 // offsets are kept in 32 bits (shared_forward_supports' rules, extended to the shading image).
 bool shaded_forward_supports(const KParams& p, int dtype, const ShadeK& sh) {
     const int64_t es = dtype == GMPI_DTYPE_F32 ? 4 : 2;
-    auto mult = [](int64_t v) { return v % kSFTPI == 0; };
-    if (reinterpret_cast<uintptr_t>(p.rgba) % static_cast<uintptr_t>(kSFTPI * es) != 0 || !mult(p.s_mpi) || !mult(p.s_plane) || !mult(p.s_chan) || !mult(p.s_row)) return false;
-    if (reinterpret_cast<uintptr_t>(sh.s) % 16 != 0 || !mult(sh.s_mpi) || !mult(sh.s_row)) return false;
-    return (kSFRows + 1) * p.s_row + 128 < (int64_t(1) << 31) / es && (kSFRows + 1) * sh.s_row + 128 < (int64_t(1) << 31) / 4;
+    if (!staged_item_aligned(p.rgba, es, p.s_mpi, p.s_plane, p.s_chan, p.s_row) || !staged_item_aligned(sh.s, 4, sh.s_mpi, sh.s_row)) return false;
+    return staged_offsets_fit(p.s_row, es) && staged_offsets_fit(sh.s_row, 4);
 }
 
 template <typename TexT>

@@ -20,25 +20,15 @@
 // result does not depend on the path, and strict-order mode is bit-identical to render_shared_kernel.
 //
 // GMPI_FLAG_CHECK_RANGE tests every staged texel (the sampled taps plus the items and box rows around them) and every tap of the direct gather.
-#include "gmpi_device.hpp"
-#include "gmpi_shared.hpp"
-
-#include <algorithm>
+#include "gmpi_staged_forward.hpp"
 
 namespace gmpi {
 
-constexpr int kFW = 32, kFH = 16, kFThreads = kFW * kFH;   // pixel tile, one pixel per thread
-constexpr int kFPitch = 56, kFRows = 27;                   // staging buffer: texels per (row, channel) line, texel rows
-constexpr int kFTPI = 4, kFCols = kFPitch / kFTPI;         // texels per loader item, items per line
-constexpr int kFBufFloats = kFRows * 4 * kFPitch;          // 6048 floats = 24 192 bytes
-constexpr int kFChunk = 64;                                // planes per box-table refill
-static_assert(kFRows * kFCols <= kFThreads, "one loader item per thread and channel");
-static_assert(2 * kFBufFloats * 4 + kFChunk * 16 <= 53 * 1024, "3 workgroups per CU");
-
+static_assert(staged_forward_fits_lds(16 + 32), "3 workgroups per CU");   // table bytes per plane: box, org
 // (Item4 -- one loader item, 4 texels of storage -> fp32 -- and f_out_of_unit live in gmpi_shared.hpp: render_depth_window.hip loads with them too)
 
 template <typename TexT, bool AC, bool STRICT>
-__global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(const KParams p, const SharedK sh, const int tiles_x, const int tiles_y,
+__global__ __launch_bounds__(kSFThreads, 6) void render_shared_forward_kernel(const KParams p, const SharedK sh, const int tiles_x, const int tiles_y,
                                                                             const int n_tiles) {
     using I4 = Item4<TexT>;
     using Raw = typename I4::Raw;
@@ -47,9 +37,9 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
     //   box: qx0 (a multiple of 4), by0, items per row (0: not staged), rows
     //   org: byte address of the box origin (texel row by0, column qx0) in the channel images 0, 1 | 2, 3 = words 0, 1 of the four buffer descriptors.
     //        The origin may lie before its image: only lanes inside the texture pass the range test.
-    __shared__ int4 box[kFChunk];
-    __shared__ int4 org[kFChunk][2];
-    __shared__ __attribute__((aligned(16))) float stage[2][kFBufFloats];
+    __shared__ int4 box[kSFChunk];
+    __shared__ int4 org[kSFChunk][2];
+    __shared__ __attribute__((aligned(16))) float stage[2][kSFBufFloats];
 
     // ---- blockIdx -> tile, this lane's pixel, the tile's corner pixels: the tile frame of gmpi_device.hpp -----------------------------------------
     const int tid = threadIdx.x;
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
     auto pixel_of = [&]() {
         int lane = tid;
         asm volatile("" : "+v"(lane));   // (opaque: or the two evaluations are merged and the first one's results kept)
-        return tile_lane<kFW, kFH>(ft.txi, ft.tyi, lane, W, H);
+        return tile_lane<kSFW, kSFH>(ft.txi, ft.tyi, lane, W, H);
     };
     float rx, ry, rz;
     {
@@ -82,23 +72,23 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
     }
     const float dot = ray_dot(vw, rx, ry, rz);
     Accum A;
-    const TileCorners tc = tile_corners<kFW, kFH>(ft.txi, ft.tyi, W, H);
+    const TileCorners tc = tile_corners<kSFW, kSFH>(ft.txi, ft.tyi, W, H);
 
     // ---- loader role: item column lcol of box row lrow, the same for the four channels; byte offsets from the box origin per row stride ---------
-    const int lrow = tid / kFCols, lcol = tid - lrow * kFCols;
-    const bool loader = lrow < kFRows;
-    const uint32_t off_a = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kFTPI * lcol) * kEs;
-    const uint32_t off_c = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(sh.rs_row) + kFTPI * lcol) * kEs;   // (the background's: formed on its one plane)
-    const bool ragged = (Wt % kFTPI) != 0;   // the last item of a texture row holds texels past its end (read from the row's padding, zeroed below)
+    const int lrow = tid / kSFCols, lcol = tid - lrow * kSFCols;
+    const bool loader = lrow < kSFRows;
+    const uint32_t off_a = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kSFTPI * lcol) * kEs;
+    const uint32_t off_c = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(sh.rs_row) + kSFTPI * lcol) * kEs;   // (the background's: formed on its one plane)
+    const bool ragged = (Wt % kSFTPI) != 0;   // the last item of a texture row holds texels past its end (read from the row's padding, zeroed below)
 
-    for (int kc = 0; kc < D; kc += kFChunk) {
-        const int kn = min(kFChunk, D - kc);
+    for (int kc = 0; kc < D; kc += kSFChunk) {
+        const int kn = min(kSFChunk, D - kc);
         __syncthreads();   // the previous chunk's table and buffers are no longer read
-        for (int t = tid; t < kn; t += kFThreads) {
+        for (int t = tid; t < kn; t += kSFThreads) {
             const int k = kc + t;
             const float zdiff = vw.dhw[3 * k] - vw.ez, ph = vw.dhw[3 * k + 1], pw = vw.dhw[3 * k + 2];
             bool fits;
-            int4 bb = item_box<kFTPI>(corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, tc.cx0, tc.cx1, tc.cy0, tc.cy1), kFCols, kFRows, fits);
+            int4 bb = item_box<kSFTPI>(corner_extent<AC>(vw, rdv, W, zdiff, ph, pw, tc.cx0, tc.cx1, tc.cy0, tc.cy1), kSFCols, kSFRows, fits);
             if (!fits) bb.z = 0;
             box[t] = bb;
             const bool last_bg = bgi != nullptr && k == D - 1;
@@ -123,11 +113,11 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             const bool last_bg = bgi != nullptr && kc + t == D - 1;   // uniform
             const int4 o01 = org[min(t, kn - 1)][0], o23 = org[min(t, kn - 1)][1];
             const int ow[8] = {o01.x, o01.y, o01.z, o01.w, o23.x, o23.y, o23.z, o23.w};
-            const int gx = qx0 + kFTPI * lcol, gy = by0 + lrow;
+            const int gx = qx0 + kSFTPI * lcol, gy = by0 + lrow;
             // (bitwise on purpose: `&&` would be lowered to exec-mask control flow)
             const bool ok = (lcol < nq) & (lrow < nrows) & (gx >= 0) & (gx < Wt) & (gy >= 0) & (gy < Ht);
             uint32_t off_col = off_c;
-            if (last_bg) off_col = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(sh.bs_row) + kFTPI * lcol) * kEs;
+            if (last_bg) off_col = (static_cast<uint32_t>(lrow) * static_cast<uint32_t>(sh.bs_row) + kSFTPI * lcol) * kEs;
             const uint32_t oc = ok ? off_col : 0x80000000u, oa = ok ? off_a : 0x80000000u;   // == num_records: rejected
 #pragma unroll
             for (int c = 0; c < 4; ++c) L[c] = I4::load(origin_rsrc(ow[2 * c], ow[2 * c + 1]), c < 3 ? oc : oa);
@@ -137,8 +127,8 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             const int4 bb = box[t];
             const int qx0 = __builtin_amdgcn_readfirstlane(bb.x), nq = __builtin_amdgcn_readfirstlane(bb.z), nrows = __builtin_amdgcn_readfirstlane(bb.w);
             const bool in_box = loader & (lcol < nq) & (lrow < nrows);
-            const int dst0 = lrow * (4 * kFPitch) + kFTPI * lcol;   // floats: line (lrow, channel 0)
-            const int left = Wt - (qx0 + kFTPI * lcol);   // texels of this item that lie inside the texture row (ragged textures)
+            const int dst0 = lrow * (4 * kSFPitch) + kSFTPI * lcol;   // floats: line (lrow, channel 0)
+            const int left = Wt - (qx0 + kSFTPI * lcol);   // texels of this item that lie inside the texture row (ragged textures)
             float4 q[4];
             uint32_t mx = 0;   // max of the fp32 bit patterns this lane staged (rejected items hold zeros)
 #pragma unroll
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
                     if (left < 3) q[c].z = 0.0f;
                     if (left < 4) q[c].w = 0.0f;
                 }
-                if (in_box) *reinterpret_cast<float4*>(buf + dst0 + c * kFPitch) = q[c];
+                if (in_box) *reinterpret_cast<float4*>(buf + dst0 + c * kSFPitch) = q[c];
                 mx = max(max(mx, __float_as_uint(q[c].x)), max(max(__float_as_uint(q[c].y), __float_as_uint(q[c].z)), __float_as_uint(q[c].w)));
             }
             if (check_range && __builtin_expect(mx > 0x3f800000u, 0)) {   // (cold: the exact test, -0.0 is legal)
@@ -172,20 +162,20 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
             bool direct = true;
             if (nq > 0) {   // uniform: the plane is staged
                 const int lx = tp.f.x0 - qx0, ly = tp.f.y0 - by0;
-                const bool inb = (lx >= 0) & (ly >= 0) & (lx + 1 < kFTPI * nq) & (ly + 1 < nrows);
+                const bool inb = (lx >= 0) & (ly >= 0) & (lx + 1 < kSFTPI * nq) & (ly + 1 < nrows);
                 const bool any_w = (tp.f.nw != 0.0f) | (tp.f.ne != 0.0f) | (tp.f.sw != 0.0f) | (tp.f.se != 0.0f);
                 // a footprint outside the box with every weight zero (the sentinel corner of NaN / far-off coordinates) reads texel (0, 0) of the box
-                const uint32_t idx = inb ? static_cast<uint32_t>(ly * (4 * kFPitch) + lx) : 0u;
+                const uint32_t idx = inb ? static_cast<uint32_t>(ly * (4 * kSFPitch) + lx) : 0u;
                 // LDS byte addresses of the two texel rows, opaque to the optimiser so that the 8 tap-pair reads keep immediate offsets (render_lds.hip)
                 typedef const float __attribute__((address_space(3))) lds_cfloat;
                 uint32_t buf_addr = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_cfloat*)buf));
                 asm volatile("" : "+s"(buf_addr));
-                uint32_t a_top = buf_addr + 4u * idx, a_bot = a_top + 16u * kFPitch;
+                uint32_t a_top = buf_addr + 4u * idx, a_bot = a_top + 16u * kSFPitch;
                 asm volatile("" : "+v"(a_top), "+v"(a_bot));
                 lds_cfloat* __restrict__ top = reinterpret_cast<lds_cfloat*>(static_cast<uintptr_t>(a_top));
                 lds_cfloat* __restrict__ bot = reinterpret_cast<lds_cfloat*>(static_cast<uintptr_t>(a_bot));
 #pragma unroll
-                for (int c = 0; c < 4; ++c) smp[c] = bilerp<STRICT>(top[c * kFPitch], top[c * kFPitch + 1], bot[c * kFPitch], bot[c * kFPitch + 1], tp.f);
+                for (int c = 0; c < 4; ++c) smp[c] = bilerp<STRICT>(top[c * kSFPitch], top[c * kSFPitch + 1], bot[c * kSFPitch], bot[c * kSFPitch + 1], tp.f);
                 direct = (!inb) & any_w;   // per lane: a pixel whose taps the box does not hold (no pinhole ray field)
             }
             if (__builtin_expect(direct, 0))
@@ -213,30 +203,25 @@ __global__ __launch_bounds__(kFThreads, 6) void render_shared_forward_kernel(con
 // Loader items are 4 texels: every channel row of the three tensors must start on an item boundary, and the in-box byte offsets are kept in 32 bits.
 bool shared_forward_supports(const KParams& p, int dtype, const SharedK& sh) {
     const int64_t es = dtype == GMPI_DTYPE_F32 ? 4 : 2;
-    const uintptr_t item = static_cast<uintptr_t>(kFTPI * es);
-    auto aligned = [&](const void* base, int64_t s0, int64_t s1, int64_t s2) {
-        return reinterpret_cast<uintptr_t>(base) % item == 0 && s0 % kFTPI == 0 && s1 % kFTPI == 0 && s2 % kFTPI == 0;
-    };
-    if (!aligned(p.rgba, p.s_mpi, p.s_plane, p.s_row) || !aligned(sh.rgb, sh.rs_mpi, sh.rs_chan, sh.rs_row)) return false;
-    if (sh.bg != nullptr && !aligned(sh.bg, sh.bs_mpi, sh.bs_chan, sh.bs_row)) return false;
-    const int64_t row = std::max(p.s_row, std::max(sh.rs_row, sh.bg != nullptr ? sh.bs_row : int64_t(0)));
-    return (kFRows + 1) * row + 128 < (int64_t(1) << 31) / es;
+    if (!staged_item_aligned(p.rgba, es, p.s_mpi, p.s_plane, p.s_row) || !staged_item_aligned(sh.rgb, es, sh.rs_mpi, sh.rs_chan, sh.rs_row)) return false;
+    if (sh.bg != nullptr && !(staged_item_aligned(sh.bg, es, sh.bs_mpi, sh.bs_chan, sh.bs_row) && staged_offsets_fit(sh.bs_row, es))) return false;
+    return staged_offsets_fit(p.s_row, es) && staged_offsets_fit(sh.rs_row, es);
 }
 
 int shared_forward_query(int what) {
     switch (what) {
-        case 12: return kFW;
-        case 13: return kFPitch;
-        case 14: return kFRows;
+        case 12: return kSFW;
+        case 13: return kSFPitch;
+        case 14: return kSFRows;
         default: return -1;
     }
 }
 
 template <typename TexT>
 static hipError_t launch_shared_forward_t(const KParams& p, const SharedK& sh, hipStream_t stream) {
-    const FwdTileGrid tg = fwd_tile_grid<kFW, kFH>(p);
+    const FwdTileGrid tg = fwd_tile_grid<kSFW, kSFH>(p);
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
-        hipLaunchKernelGGL((render_shared_forward_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), tg.grid, dim3(kFThreads), 0, stream, p, sh, tg.tiles_x,
+        hipLaunchKernelGGL((render_shared_forward_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), tg.grid, dim3(kSFThreads), 0, stream, p, sh, tg.tiles_x,
                            tg.tiles_y, tg.n_tiles);
     });
     return hipGetLastError();

@@ -114,7 +114,7 @@ def test_explicit_staged_variants_refuse_strides_they_cannot_address(env, dtype)
 
 def test_shared_forward_supports_answers_zero_for_a_row_stride_over_its_bound(env):
     L, lib, fake, _ = env
-    rows = lib.gmpi_query(14)   # kFRows: box rows of the staged shared-colour forward
+    rows = lib.gmpi_query(14)   # kSFRows: box rows of the staged shared-colour forward
     assert rows > 0
 
     def ask(dtype, s_row, rgb_row=big.PITCH, bg_row=big.PITCH):
@@ -130,7 +130,7 @@ def test_shared_forward_supports_answers_zero_for_a_row_stride_over_its_bound(en
     for dtype, (_, es) in DTYPES.items():
         assert ask(dtype, big.PITCH) == 1
         assert ask(dtype, big.row_stride("rowC", es)) == 0
-        # the bound: (kFRows + 1) row + 128 < 2^31 / es, on whichever of the three tensors has the longest rows (multiples of the 4-texel item)
+        # the bound: (kSFRows + 1) row + 128 < 2^31 / es, on whichever of the three tensors has the longest rows (multiples of the 4-texel item)
         first_bad = -(-(2 ** 31 // es - 128) // (rows + 1))
         first_bad = -(-first_bad // 4) * 4
         last_good = first_bad - 4

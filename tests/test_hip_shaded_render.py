@@ -207,6 +207,76 @@ def test_texture_four_times_finer_than_the_image_gathers_in_the_kernel(abi):
     check_forward(abi, c, variants=("gather", "lds"))
 
 
+# ---- 2b. the paths the staged kernel shares with the shared-colour one (its namesakes: tests/test_hip_shared_forward_staged.py, the same shapes) -----------
+def _strict_pair(abi, vol, s, dhw, ray, eye, zd):
+    """(staged kernel, one-pixel kernel) in strict order; the staged kernel was reached."""
+    from ml_gmpi_amd import _lib as L
+    abi["launched"].clear(), abi["supports"].clear()
+    a = shaded_render(vol, s, dhw, ray, eye, zd, variant="lds", strict=True, check_last=False)
+    assert abi["supports"] == [1] and abi["launched"] == [L.VARIANT_LDS], abi
+    b = shaded_render(vol, s, dhw, ray, eye, zd, variant="gather", strict=True, check_last=False)
+    return a, b
+
+
+def test_nan_ray_component_gives_the_one_pixel_kernels_pixels(abi):
+    """The per-lane direct path of the staged kernel (shaded_gather_sample) and a tile none of whose boxes fits."""
+    vol, s, dhw, ray, eye, zd, _ = case("fwd", torch.float32, True, seed=1, B=2, D=8, S=96)
+    ray = torch.as_tensor(ray).clone()
+    ray[0, 0, 50, 41] = float("nan")      # inside a tile: that pixel alone
+    ray[1, 2, 0, 0] = float("nan")        # a tile corner: the tile's boxes do not fit
+    a, b = _strict_pair(abi, vol, s, dhw, ray, eye, zd)
+    for k in ("color", "depth", "T"):
+        assert np.array_equal(np.isnan(a[k]), np.isnan(b[k])), k
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    assert np.isnan(a["depth"][0, 0, 50, 41]) and int(np.isnan(a["depth"]).sum()) == 2
+    assert int(a["status"][0]) == 0 and int(b["status"][0]) == 0
+
+
+def test_staged_and_gathered_planes_in_one_launch(abi):
+    from test_hip_shared_forward_staged import _boxes, _fit_counts
+    vol, s, dhw, ray, eye, zd, _ = case("mixed", seed=2, B=2, D=12, S=112, T=128, extreme=True)
+    spare, never, n = _fit_counts(_boxes(dhw, ray, eye, 128, 128, True))
+    print("mixed case: boxes that fit with spare", spare, "never", never, "of", n)
+    assert spare > 0 and never > 0, (spare, never, n)
+    a, b = _strict_pair(abi, vol, s, dhw, ray, eye, zd)
+    for k in ("color", "depth", "T"):
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+
+
+def _lds_status(vol, s, dhw, ray, eye, zd):
+    from ml_gmpi_amd import MPI
+    dev = torch.device(DEV)
+    t = lambda a: torch.as_tensor(a).to(dev)
+    mpi = MPI(variant="lds", on_out_of_plane="raise")
+    with torch.no_grad():
+        out = mpi.render_views_shaded(t(vol), t(s), t(dhw), t(ray), t(eye), t(zd), defer_status=True)
+    word = int(out["status"][0].item())
+    out["status"].zero_()
+    return word
+
+
+@pytest.mark.parametrize("path", ["staged", "in-kernel gather"])
+def test_alpha_above_one_sets_the_range_bit_and_a_colour_above_one_before_the_clip_does_not(abi, path):
+    """staged: every box fits, the poked texel is the image centre, which every frontal view samples.  in-kernel gather: no box fits (256^2 texels under
+    32^2 pixels), pixels are 8 texels apart, so a block of 17 x 17 texels around the centre is poked: some footprint lies in it."""
+    from ml_gmpi_amd import _lib as L
+    from test_hip_shared_forward_staged import _boxes, _fit_counts
+    if path == "staged":
+        vol, s, dhw, ray, eye, zd, _ = case("range", seed=3, B=1, D=5, S=64)
+        T, poke = 64, (slice(32, 33), slice(32, 33))
+    else:
+        vol, s, dhw, ray, eye, zd, _ = case("range-fine", seed=32, B=2, D=5, S=32, T=256)
+        T, poke = 256, (slice(120, 137), slice(120, 137))
+        spare, never, n = _fit_counts(_boxes(dhw, ray, eye, T, T, True))
+        assert never == n, (spare, never, n)
+    assert float((vol[:, :, :3] * s[:, None] > 1).float().mean()) >= 0.10   # colours above one before the clip, all over the volume
+    assert _lds_status(vol, s, dhw, ray, eye, zd) == 0
+    bad = vol.clone()
+    bad[0, 0, 3, poke[0], poke[1]] = 1.5
+    assert _lds_status(bad, s, dhw, ray, eye, zd) == 2, path
+    assert abi["launched"] == [L.VARIANT_LDS] * 2 and abi["supports"] == [1, 1], abi
+
+
 # ---- 3. equal to the two-step path on the device -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_strict_bits_equal_the_render_of_apply_shading_on_the_device(dtype):
