@@ -1,6 +1,9 @@
 """The inputs of the deep-plane tests, in one place: tests/test_visible_stacks_cpu.py checks on the CPU that every plane of them is visible
 and that the fp32 reference chain is close enough to float64 for the per-slab gradient bar to mean something; tests/test_hip_deep_planes.py and
-tests/test_hip_deep_gradients.py run the kernels on exactly these inputs.  CPU only (numpy / torch), never imported by the product."""
+tests/test_hip_deep_gradients.py run the kernels on exactly these inputs; tests/test_hip_chunk_gradients.py and tests/test_hip_shaded_gradients.py
+run the chunked and the shaded twins of the volume backward on the `twin_case` inputs at the end.  CPU only (numpy / torch), never imported by the product."""
+import functools
+
 import numpy as np
 import torch
 
@@ -76,14 +79,91 @@ def grad_case(name):
     return dict(rgba=rgba, dhw=dhw, ray=ray, eye=eye, zd=zd, v2m=v2m, gc=gc, gd=gd, gT=gT, dtype=dtype, D=D, N=N, M=M)
 
 
-def volume_grad_ref(case, dtype):
+def volume_grad_ref(case, dtype, align_corners=True, shading=None, out_pm1=False):
     """d(sum gC colour + sum gZ depth + sum gT T) / d rgba of tests/_transmittance_ref.render in `dtype` (float64: the reference; float32: the same
-    chain at the kernels' precision, for e_ref) -> float64 numpy array."""
+    chain at the kernels' precision, for e_ref) -> float64 numpy array.  With a shading ([M,1,Ht,Wt], or ONE image [1,1,Ht,Wt] expanded over the
+    MPIs) the render is that of `shaded_volume(rgba, shading)` in `dtype` (tests/test_hip_shaded_render.py) and the result is the pair (gradient
+    w.r.t. rgba, gradient w.r.t. the shading as it was passed: for one expanded image the sum over the MPIs).  out_pm1: the colour is 2 C - 1."""
     c = lambda a: torch.as_tensor(a).to(dtype)
     vol = c(case["rgba"]).clone().requires_grad_(True)
-    color, depth, T = _transmittance_ref.render(vol, c(case["dhw"]), c(case["ray"]), c(case["eye"]), c(case["zd"]), case["v2m"])
+    s = None
+    if shading is not None:
+        from test_hip_shaded_render import shaded_volume
+        s = c(shading).clone().requires_grad_(True)
+        rendered = shaded_volume(vol, s.expand(vol.shape[0], -1, -1, -1), dtype)
+    else:
+        rendered = vol
+    color, depth, T = _transmittance_ref.render(rendered, c(case["dhw"]), c(case["ray"]), c(case["eye"]), c(case["zd"]), case["v2m"],
+                                                align_corners=align_corners)
+    if out_pm1:
+        color = 2 * color - 1
     ((color * c(case["gc"])).sum() + (depth * c(case["gd"])).sum() + (T * c(case["gT"])).sum()).backward()
-    return vol.grad.double().numpy()
+    if s is None:
+        return vol.grad.double().numpy()
+    return vol.grad.double().numpy(), s.grad.double().numpy()
+
+
+# ---- the twins of the volume backward: one chunk of a plane-chunked stack (CHUNK = true) and the shaded render (Shade = ShadeK) ---------------------
+# 20 x 150 pixels: three columns of 64-pixel tiles, the last 22 wide, and three rows of 8, the last 4 high (five columns of 32 and two rows of 16 for
+# the kernel a one-column texture takes); texture 36 x 52 unless the case says otherwise.  chunk / shaded: which of the two twins runs the case.
+TWIN_H, TWIN_W, TWIN_HT, TWIN_WT = 20, 150, 36, 52
+TWIN_CASES = {
+    "t97-thin": dict(D=97, alpha="thin", ac=True, chunk=True, shaded=True),
+    "t129-surface-ac0": dict(D=129, alpha="surface", ac=False, chunk=True, shaded=True),
+    "t200-thin": dict(D=200, alpha="thin", ac=True, chunk=True, shaded=False),
+    "t97-thin-bf16": dict(D=97, alpha="thin", ac=True, dtype="bf16", chunk=True, shaded=True),
+    "t97-surface-f16-ac0": dict(D=97, alpha="surface", ac=False, dtype="f16", chunk=False, shaded=True),
+    "t12-ragged": dict(D=12, alpha="thin", ac=True, tex=(36, 50), chunk=False, shaded=True),          # Wt % 4 != 0
+    "t12-ragged-ac0": dict(D=12, alpha="thin", ac=False, tex=(36, 50), chunk=False, shaded=True),
+    "t12-column": dict(D=12, alpha="thin", ac=True, tex=(36, 1), chunk=True, shaded=True),            # Wt < 2
+    "t12-column-ac0": dict(D=12, alpha="thin", ac=False, tex=(36, 1), chunk=True, shaded=True),
+    "t6-minified": dict(D=6, alpha="thin", ac=True, tex=(250, 190), img=(24, 40), chunk=False, shaded=True),   # no tile box fits
+    "t12-views-v2m": dict(D=12, alpha="thin", ac=False, N=3, v2m=[0, 1, 1], chunk=True, shaded=True),
+    "t12-views-vpm": dict(D=12, alpha="thin", ac=False, N=4, v2m=[0, 0, 1, 1], vpm=2, chunk=True, shaded=True),
+}
+
+
+def twin_keys(which):
+    """(name, shaded) of every case the `which` twin runs ("chunk": unshaded inputs; "shaded": the colours moved and a shading image)."""
+    return [(n, which == "shaded") for n, cfg in TWIN_CASES.items() if cfg[which]]
+
+
+@functools.lru_cache(maxsize=None)
+def twin_case(name, shaded=False):
+    """`grad_case`'s dict on the small frame, plus ac, H, W, vpm (uniform views per MPI, or None) and, for a shaded case, shading [M,1,Ht,Wt] fp32:
+    the colours are moved to 1.3 rgb - 0.15 before the storage rounding, so that with a shading in [0.4, 1.6] both branches of the clip are taken
+    (products above 1 and below 0); the kernels are then run with range_check="off".  Computed once and left unchanged."""
+    cfg = TWIN_CASES[name]
+    D, N, M = cfg["D"], cfg.get("N", 2), 2
+    (Ht, Wt), (Hh, Ww) = cfg.get("tex", (TWIN_HT, TWIN_WT)), cfg.get("img", (TWIN_H, TWIN_W))
+    dtype = DTYPES[cfg.get("dtype", "f32")]
+    rgba = oracle.synth_rgba(41, (M, D, 4, Ht, Wt))
+    if shaded:
+        rgba[:, :, :3] = 1.3 * rgba[:, :, :3] - 0.15
+    rgba = make_alpha(rgba, cfg["alpha"], dtype=None if dtype is torch.float32 else dtype)
+    ray, eye, zd = _cam(N, Hh, Ww, seed=42, tilt=0.3)
+    g = np.random.default_rng(5)
+    gc = g.standard_normal((N, 3, Hh, Ww)).astype(np.float32)
+    gd = g.standard_normal((N, 1, Hh, Ww)).astype(np.float32)
+    gT = g.standard_normal((N, 1, Hh, Ww)).astype(np.float32)
+    v2m = np.asarray(cfg.get("v2m", np.arange(N) % M), dtype=np.int32)
+    case = dict(rgba=rgba, dhw=_dhw(M, D), ray=ray, eye=eye, zd=zd, v2m=v2m, gc=gc, gd=gd, gT=gT, dtype=dtype, D=D, N=N, M=M, ac=cfg["ac"],
+                H=Hh, W=Ww, vpm=cfg.get("vpm"))
+    if shaded:
+        from test_hip_shaded_render import make_shading
+        case["shading"] = make_shading(5, torch.from_numpy(rgba)).numpy()
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def twin_refs(name, shaded=False, out_pm1=False, one_shading=False):
+    """(float64, fp32) references of a twin case, computed once: each the volume gradient, or -- shaded -- the pair (volume, shading).
+    one_shading: MPI 0's shading image expanded over all MPIs (its gradient is the sum over them)."""
+    case = twin_case(name, shaded)
+    s = case.get("shading")
+    if one_shading:
+        s = s[:1]
+    return tuple(volume_grad_ref(case, dt, align_corners=case["ac"], shading=s, out_pm1=out_pm1) for dt in (torch.float64, torch.float32))
 
 
 # ---- shared-colour backward: alpha gradient per plane, D = 32 and one plane more than the tile backward's tables hold ------------------------------

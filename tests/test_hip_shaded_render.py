@@ -369,11 +369,11 @@ def test_nan_colour_texel_and_alpha_above_one_give_the_two_step_paths_outputs_an
 
 
 # ---- 4. gradients ---------------------------------------------------------------------------------------------------------------------------------
-def _reference_grads(vol, s, dhw, ray, eye, zd, v2m, gc, gd, gT, out_pm1, dtype):
+def _reference_grads(vol, s, dhw, ray, eye, zd, v2m, gc, gd, gT, out_pm1, dtype, align_corners=True):
     """d(sum gC colour + sum gZ depth + sum gT T) / d(vol, s) of tests/_transmittance_ref.render(apply_shading(vol, s)) in `dtype` on the CPU."""
     ins = [vol.to(dtype).clone().requires_grad_(True), s.to(dtype).clone().requires_grad_(True)]
     c = lambda a: torch.as_tensor(a).to(dtype)
-    color, depth, T = _transmittance_ref.render(shaded_volume(ins[0], ins[1], dtype), c(dhw), c(ray), c(eye), c(zd), v2m)
+    color, depth, T = _transmittance_ref.render(shaded_volume(ins[0], ins[1], dtype), c(dhw), c(ray), c(eye), c(zd), v2m, align_corners=align_corners)
     if out_pm1:
         color = 2 * color - 1
     loss = torch.zeros((), dtype=dtype)
@@ -384,14 +384,18 @@ def _reference_grads(vol, s, dhw, ray, eye, zd, v2m, gc, gd, gT, out_pm1, dtype)
     return [(i.grad if i.grad is not None else torch.zeros_like(i)).double().numpy() for i in ins]
 
 
-def _hip_grads(vol, s, dhw, ray, eye, zd, v2m, gc, gd, gT, out_pm1, variant, dtype, needs=(True, True), backward="atomic"):
+def _hip_grads(vol, s, dhw, ray, eye, zd, v2m, gc, gd, gT, out_pm1, variant, dtype, needs=(True, True), backward="atomic", align_corners=True,
+               range_check=None, views_per_mpi=None, prep=None):
+    """-> (the two leaves, the module).  views_per_mpi: uniform views instead of the index v2m.  prep(vol_t, s_t) -> (vol_t, s_t): the tensors the
+    render is given, as views (or functions) of the leaves; ins stays the leaves."""
     from ml_gmpi_amd import MPI
     dev = torch.device(DEV)
     t = lambda a: torch.as_tensor(a).to(dev)
     ins = [t(vol).to(dtype).requires_grad_(needs[0]), t(s).clone().requires_grad_(needs[1])]
-    mpi = MPI(variant=variant, on_out_of_plane="raise", backward=backward)
-    out = mpi.render_views_shaded(ins[0], ins[1], t(dhw), t(ray), t(eye), t(zd), view_to_mpi=t(np.asarray(v2m, dtype=np.int32)), check_last_plane=False,
-                                  out_pm1=out_pm1, want_transmittance=True)
+    mpi = MPI(align_corners=align_corners, variant=variant, on_out_of_plane="raise", backward=backward, range_check=range_check)
+    views = dict(view_to_mpi=t(np.asarray(v2m, dtype=np.int32))) if views_per_mpi is None else dict(views_per_mpi=views_per_mpi)
+    vol_t, s_t = (ins[0], ins[1]) if prep is None else prep(ins[0], ins[1])
+    out = mpi.render_views_shaded(vol_t, s_t, t(dhw), t(ray), t(eye), t(zd), check_last_plane=False, out_pm1=out_pm1, want_transmittance=True, **views)
     loss = 0
     for key, g in (("color", gc), ("depth", gd), ("T", gT)):
         if g is not None:

@@ -7,7 +7,10 @@ restatements only:
   * the blind spot these inputs exist for: on a white-noise stack the same measure is below the bar from plane 32 on;
   * the per-slab gradient bar of `slab_compare` is max(5e-5, 4 e_ref): e_ref <= 1e-4 in every slab of every committed backward case, and
     every slab's scale is >= 1e-3 of the tensor's maximum, so the bar calibrates itself within a factor 8 of the project's 5e-5 and no slab
-    is an afterthought."""
+    is an afterthought;
+  * the same two conditions for the inputs of the chunked and shaded twins of the volume backward (`twin_case`), for the shading gradient per
+    MPI image too; both ends of the clip are taken by at least 5 % of the colour products, fp32 and float64 agree on both gates, and the tile
+    boxes of the 64 x 8 tile backward fit (or, for the minified case, do not fit) as the cases say."""
 import numpy as np
 import pytest
 import torch
@@ -107,6 +110,80 @@ def test_gradient_cases_keep_the_slab_bar_honest(name):
     print(f"{name}: slab scale min {scale.min():.2e} max {scale.max():.2e}; e_ref max {e_ref.max():.2e} median {np.median(e_ref):.2e}")
     assert e_ref.max() <= E_REF_CAP, e_ref.max()
     assert scale.min() >= 1e-3 * scale.max(), (scale.min(), scale.max(), np.unravel_index(scale.argmin(), scale.shape))
+
+
+TWIN_KEYS = C.twin_keys("chunk") + C.twin_keys("shaded")
+
+
+def _assert_honest(label, refs, shaded):
+    """refs = (float64, fp32) of tests/_deep_cases.py `twin_refs`: e_ref and the slab scales of the volume gradient and, shaded, of the shading's."""
+    ref64, ref32 = refs
+    pairs = [("volume", ref64[0], ref32[0]), ("shading", ref64[1], ref32[1])] if shaded else [("volume", ref64, ref32)]
+    for what, r64, r32 in pairs:
+        scale, e_ref = slab_stats(r64, r32)
+        print(f"{label} {what}: slab scale min {scale.min():.2e} max {scale.max():.2e} (min / max {scale.min() / scale.max():.2e}); "
+              f"e_ref max {e_ref.max():.2e} median {np.median(e_ref):.2e}")
+        assert e_ref.max() <= E_REF_CAP, (what, e_ref.max())
+        assert scale.min() >= 1e-3 * scale.max(), (what, scale.min(), scale.max(), np.unravel_index(scale.argmin(), scale.shape))
+
+
+def test_the_further_references_of_the_shaded_twin_keep_the_slab_bar_honest():
+    """The two references tests/test_hip_shaded_gradients.py uses beside the cases' own: colour written as 2 C - 1, and ONE shading image expanded
+    over both MPIs (its gradient is the sum over them)."""
+    _assert_honest("t12-ragged out_pm1", C.twin_refs("t12-ragged", True, out_pm1=True), True)
+    _assert_honest("t12-views-vpm one shading image", C.twin_refs("t12-views-vpm", True, one_shading=True), True)
+
+
+@pytest.mark.parametrize("name,shaded", TWIN_KEYS, ids=[n + ("-shaded" if s else "") for n, s in TWIN_KEYS])
+def test_twin_gradient_cases_keep_the_slab_bar_honest(name, shaded):
+    """The inputs of tests/test_hip_chunk_gradients.py and tests/test_hip_shaded_gradients.py: the two conditions above for the volume gradient and,
+    per MPI image, for the shading gradient; both branches of the clip are taken by at least 5 % of the colour products, and fp32 and float64 agree
+    on both gates for every texel (a texel they disagreed on would carry an O(1) difference no bar could absorb)."""
+    case = C.twin_case(name, shaded)
+    _assert_honest(name, C.twin_refs(name, shaded), shaded)
+    if shaded:
+        rgb, s = torch.from_numpy(case["rgba"][:, :, :3]), torch.from_numpy(case["shading"])
+        p32, p64 = rgb * s[:, None], rgb.double() * s.double()[:, None]
+        above, below = float((p64 > 1).double().mean()), float((p64 < 0).double().mean())
+        print(f"{name}: products above 1 {above:.3f}, below 0 {below:.3f}")
+        assert above >= 0.05 and below >= 0.05, (above, below)
+        assert bool(((p32 > 1) == (p64 > 1)).all()) and bool(((p32 < 0) == (p64 < 0)).all())
+
+
+def _tile_boxes(case, tw, th):
+    """(columns, rows) of the texel box of every (view, tw x th pixel tile, plane): `item_box<1>` of gmpi_device.hpp over the images of the tile's four
+    corner pixels, restated in float64 without its 1/64 texel of slack (the callers leave a texel of margin either way)."""
+    dhw, ray, eye = (np.asarray(case[k], dtype=np.float64) for k in ("dhw", "ray", "eye"))
+    Ht, Wt = case["rgba"].shape[-2:]
+    out = []
+    for n in range(case["N"]):
+        for y0 in range(0, case["H"], th):
+            for x0 in range(0, case["W"], tw):
+                ys, xs = [y0, min(y0 + th - 1, case["H"] - 1)], [x0, min(x0 + tw - 1, case["W"] - 1)]
+                r = ray[n][:, ys][:, :, xs].reshape(3, 4)
+                for d, ph, pw in dhw[case["v2m"][n]]:
+                    s = (d - eye[n, 2]) / r[2]
+                    u, v = 2 * (eye[n, 0] + r[0] * s) / pw, 2 * (eye[n, 1] + r[1] * s) / ph
+                    if case["ac"]:
+                        ix, iy = (u + 1) * (Wt - 1) / 2, (v + 1) * (Ht - 1) / 2
+                    else:
+                        u, v = np.where(np.abs(u) <= 1, u * 0.95, u), np.where(np.abs(v) <= 1, v * 0.95, v)
+                        ix, iy = ((u + 1) * Wt - 1) / 2, ((v + 1) * Ht - 1) / 2
+                    out.append((np.floor(ix.max()) + 1 - np.floor(ix.min()) + 1, np.floor(iy.max()) + 1 - np.floor(iy.min()) + 1))
+    return np.array(out)
+
+
+def test_twin_frames_stage_or_scatter_as_their_cases_say():
+    """The 64 x 8 tile backward stages a plane's scatter when the tile's texel box fits 80 columns x 19 rows (B2Wide, render_backward.hip).  On the
+    20 x 150 frame over 36 x 52 (and 36 x 50) texels every box fits with a texel to spare: the staged path, the flush waves and the fixed-point sums
+    run on every plane.  On t6-minified (250 x 190 texels under 24 x 40 pixels) no box fits by more than a texel: every plane scatters straight to
+    global memory."""
+    for name in ("t97-thin", "t129-surface-ac0", "t12-ragged", "t12-ragged-ac0", "t12-views-v2m", "t12-views-vpm"):
+        b = _tile_boxes(C.twin_case(name), 64, 8)
+        assert (b[:, 0] + 1 <= 80).all() and (b[:, 1] + 1 <= 19).all(), (name, b.max(0))
+    b = _tile_boxes(C.twin_case("t6-minified"), 64, 8)
+    print("t6-minified: smallest box", b.min(0))
+    assert ((b[:, 0] - 1 > 80) | (b[:, 1] - 1 > 19)).all(), b.min(0)
 
 
 @pytest.mark.parametrize("with_bg", [False, True])
