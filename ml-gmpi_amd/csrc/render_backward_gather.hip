@@ -218,7 +218,7 @@ struct Cell {
 // The texel pass of one workgroup: candidate discovery, staging and the fixed-order sums are the same for every layout; what happens to a plane's four
 // sums is the SINK's business (a policy):
 //   Sink::Rec, Sink::load_rec(r, q) the homography record as a chunk descriptor carries it
-//   Sink::add(w, d, acc)            one candidate's term (the volume: an unconditional FMA; the image layouts: gated on w != 0)
+//   Sink::add(w, d, acc)            one candidate's term (four FMAs, gated on w != 0 in every sink: a branch for the volume, selects for the image layouts)
 //   sink.begin(cell)                before the first plane
 //   sink.store_plane(cell, k, acc0, acc1)   plane k is complete, called once per plane of the run in rising order: stores and resets what restarts per plane
 //   sink.finish(cell)               after the last plane
@@ -403,9 +403,15 @@ struct VolumeSink {
     int Ht, Wt;
     using Rec = HRec;
     static __device__ __forceinline__ void load_rec(HRec& r, const HRec& q) { r = q; }
+    // A term is added only where its weight is not zero (as LayoutSink::add below and the atomic kernels' scatter gate theirs): 0 * inf is NaN, and
+    // every candidate of a texel's window -- the stand-in index 0 of a candidate outside the chunk included -- would carry one pixel's non-finite
+    // d_s into cells its footprints never touch.  Written as a branch: hipcc keeps it one (exec mask around the four FMAs); as four selects the
+    // pair's backward was 6.5 % slower at 1024^2 x 32 x 4 (3.75 against 3.51 ms), as a branch 3.54 (profiles/upstream_gradients.txt).
     static __device__ __forceinline__ void add(float w, const float4& d, float (&acc)[4]) {
-        acc[0] = __builtin_fmaf(w, d.x, acc[0]), acc[1] = __builtin_fmaf(w, d.y, acc[1]);
-        acc[2] = __builtin_fmaf(w, d.z, acc[2]), acc[3] = __builtin_fmaf(w, d.w, acc[3]);
+        if (w != 0.0f) {
+            acc[0] = __builtin_fmaf(w, d.x, acc[0]), acc[1] = __builtin_fmaf(w, d.y, acc[1]);
+            acc[2] = __builtin_fmaf(w, d.z, acc[2]), acc[3] = __builtin_fmaf(w, d.w, acc[3]);
+        }
     }
     __device__ __forceinline__ void begin(const Cell&) {}
     __device__ __forceinline__ void finish(const Cell&) {}
