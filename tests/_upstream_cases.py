@@ -90,10 +90,11 @@ def nonzero_pixels(name, N):
 
 
 @functools.lru_cache(maxsize=None)
-def scene(tex, vpm=None, dtype="f32", shaded=False):
+def scene(tex, vpm=None, dtype="f32", shaded=False, field=None):
     """The volume-path inputs on texture `tex`: `_deep_cases.grad_case`'s dict (rgba holding the STORED values) plus ac, H, W, vpm, Ht, Wt and,
     shaded, the shading image (the colours moved to 1.3 rgb - 0.15 first, as `_deep_cases.twin_case` does).  vpm = 2: four views, two per MPI.
-    No upstream gradients: `with_upstream` adds a family's.  Computed once and left unchanged."""
+    No upstream gradients: `with_upstream` adds a family's.  Computed once and left unchanged.  field: a ray field of tests/_ray_field_cases.py
+    by name in place of the pinhole camera's rays (None: the camera's own); the references below read the same tensor."""
     Ht, Wt = TEXTURES[tex]
     N = M * (vpm or 1)
     rgba = oracle.synth_rgba(41, (M, D, 4, Ht, Wt))
@@ -103,6 +104,9 @@ def scene(tex, vpm=None, dtype="f32", shaded=False):
     tdt = {"f32": torch.float32, "bf16": torch.bfloat16}[dtype]
     rgba = torch.from_numpy(rgba).to(tdt).float().numpy()
     ray, eye, zd = _cam(N, H, W, seed=42, tilt=0.3)
+    if field is not None:
+        import _ray_field_cases
+        ray = _ray_field_cases.apply(field, ray)
     v2m = np.asarray([n // (vpm or 1) for n in range(N)], dtype=np.int32)
     case = dict(rgba=rgba, dhw=_dhw(M, D, last=LAST_EXTENT.get(tex, 0.5)), ray=ray, eye=eye, zd=zd, v2m=v2m, dtype=tdt, D=D, N=N, M=M, ac=True, H=H, W=W, vpm=vpm, Ht=Ht, Wt=Wt)
     if shaded:
@@ -117,10 +121,10 @@ def with_upstream(case, family, seed=5):
 
 
 @functools.lru_cache(maxsize=None)
-def volume_refs(tex, family, vpm=None, dtype="f32", shaded=False):
+def volume_refs(tex, family, vpm=None, dtype="f32", shaded=False, field=None):
     """(float64, fp32) references of the volume gradient (shaded: each the pair (volume, shading)), computed once."""
     import _deep_cases
-    case = with_upstream(scene(tex, vpm, dtype, shaded), family)
+    case = with_upstream(scene(tex, vpm, dtype, shaded, field), family)
     return tuple(_deep_cases.volume_grad_ref(case, dt, align_corners=True, shading=case.get("shading")) for dt in (torch.float64, torch.float32))
 
 
@@ -140,9 +144,9 @@ def layout_parts(kind, tex):
 
 
 @functools.lru_cache(maxsize=None)
-def layout_refs(kind, tex, family, vpm=None):
+def layout_refs(kind, tex, family, vpm=None, field=None):
     """(float64, fp32) autograd gradients [rgb, alpha | depth, background] through `expand_shared_color` / `expand_depth_alpha`, computed once."""
-    case = with_upstream(scene(tex, vpm), family)
+    case = with_upstream(scene(tex, vpm, field=field), family)
     parts, extra = layout_parts(kind, tex)
     v2m = [int(m) for m in case["v2m"]]
     out = []

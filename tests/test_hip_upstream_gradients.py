@@ -73,11 +73,12 @@ def _dot(out, gc, gd, gT):
     ((out["color"] * gc).sum() + (out["depth"] * gd).sum() + (out["T"] * gT).sum()).backward()
 
 
-def run(path, tex, ups, backward=_dot):
+def run(path, tex, ups, backward=_dot, field=None):
     """Forward + backward of `path` on the scene of `tex` under the upstream gradients `ups` = (gc, gd, gT) -> the gradients as CPU tensors in
-    the order of the path's references.  backward(out, gc, gd, gT) back-propagates (default: through the sum of the three products)."""
+    the order of the path's references.  backward(out, gc, gd, gT) back-propagates (default: through the sum of the three products).  field: a
+    ray field of tests/_ray_field_cases.py in place of the camera's rays (tests/test_hip_ray_fields.py)."""
     from ml_gmpi_amd import MPI
-    case = U.scene(tex, path.vpm, path.dtype, path.kind == "shaded")
+    case = U.scene(tex, path.vpm, path.dtype, path.kind == "shaded", field)
     geo = tuple(_t(case[k]) for k in ("dhw", "ray", "eye", "zd"))
     kw = dict(views_per_mpi=path.vpm or 1, check_last_plane=False, want_transmittance=True)
     if path.kind in ("volume", "chunks", "shaded"):
