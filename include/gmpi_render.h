@@ -400,7 +400,8 @@ typedef struct GmpiDepthAlpha {
  * GMPI_E_STRIDE; NULL params, shared, depth_alpha, plane_z, rgb or depth image: GMPI_E_NULL.  No workspace.  Stream-ordered, allocates nothing,
  * never synchronises.  A window forward has an entry of its own (gmpi_mpi_render_depth_window_launch, below: this entry keeps its one kernel and
  * still refuses GMPI_VARIANT_LDS).  Gradients w.r.t. the geometry: gmpi_mpi_render_depth_geometry_backward_launch (gmpi_query(30)).  The expected depth of the un-warped stack, for the
- * shading augmentation (LightRenderer): gmpi_ramp_depth_launch (gmpi_query(32)).  Not built: 8-bit storage, gradients w.r.t. plane_z and the ramp's bounds (gmpi_query(22) says whether the layout itself is built in).
+ * shading augmentation (LightRenderer): gmpi_ramp_depth_launch (gmpi_query(32)).  W.r.t. plane_z:
+ * gmpi_mpi_render_depth_geometry_backward_pz_launch (gmpi_query(40)).  Not built: 8-bit storage, gradients w.r.t. the ramp's bounds (gmpi_query(22) says whether the layout itself is built in).
  */
 int gmpi_mpi_render_depth_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha, void *stream);
 
@@ -524,8 +525,8 @@ void gmpi_render_layout_backward_gather_set_runs(int32_t runs);
  *                  re-walk over the ramp samples (the common path of this layout).  A plane whose four ramp taps are all exactly 0 is skipped for that
  *                  pixel, colour taps included (a NaN colour texel under such a region reaches no gradient); a zero alpha SAMPLE alone does not skip.
  * plane_z as [D] or [M,D], any view_to_mpi / views_per_mpi, GMPI_FLAG_OUT_PM1, GMPI_FLAG_STRICT_ORDER (the forward's chain for the flags), fp32 / bf16 /
- * fp16 storage.  No atomics: every output is bit-reproducible.  No status bit is set.  No gradient w.r.t. plane_z or the ramp's bounds.
- * gmpi_query(30) == 1 says that both entries are built in.
+ * fp16 storage.  No atomics: every output is bit-reproducible.  No status bit is set.  The gradient w.r.t. plane_z has an entry of its own
+ * (gmpi_mpi_render_depth_geometry_backward_pz_launch, below); none w.r.t. the ramp's bounds.  gmpi_query(30) == 1 says that both entries are built in.
  */
 int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const float *grad_rgb,
                                                     const float *grad_depth, const float *grad_transmittance, float *grad_ray_dir,
@@ -533,6 +534,29 @@ int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams *para
 int gmpi_mpi_render_depth_geometry_backward_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
                                                    const float *grad_rgb, const float *grad_depth, const float *grad_transmittance,
                                                    float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw, void *stream);
+
+/*
+ * gmpi_mpi_render_depth_geometry_backward_launch with the gradient w.r.t. plane_z: same arguments, same checks, same error codes, and grad_plane_z
+ * before `stream` -- fp32, contiguous, [M, D] when depth_alpha->plane_z_stride != 0, [D] when it is 0 (ONE table for all MPIs: summed over all
+ * views in view order); OVERWRITTEN; NULL = not wanted: the entry above, its kernels and its bits.  The alpha of plane k is a ramp of plane_z[m,k] -
+ * depth, so a plane depth acts twice: through dhw[..., 0], where the ray meets the plane (grad_dhw), and through plane_z, how opaque the plane is
+ * there (this gradient).  By definition torch autograd's through expand_depth_alpha -- for view n of MPI m, pixel p, plane k, taps i = nw, ne, sw, se:
+ *     grad_plane_z[m,k] = (1 / z_den) sum_{n: mpi(n) = m} sum_p  dL/d(alpha sample)(n,p,k)  sum_i w_i in_i tex_i
+ * w_i the bilinear weights, in_i: z_lo <= f32(plane_z - d_i) <= z_hi (bounds included, as torch.clamp passes the gradient), tex_i: tap i lies inside
+ * the texture; term by term minus plane k's share of the depth image's gradient.  With grad_plane_z a plane is skipped for a pixel only when its
+ * four ramp taps are exactly 0 AND none of them lies on the ramp (a tap exactly on the lower bound has alpha 0 and a plane_z term).  The sums go
+ * through the workspace like grad_dhw's, one more slab component per plane: gmpi_render_depth_geometry_backward_workspace_bytes(params, grad_dhw !=
+ * NULL, grad_plane_z != NULL) bytes, 256-byte aligned, else GMPI_E_WORKSPACE.  No atomics: bit-reproducible.  The other outputs are, bit for bit,
+ * those of a launch without grad_plane_z.  gmpi_query(40) == 1 says that the entry is built in.
+ */
+int gmpi_mpi_render_depth_geometry_backward_pz_launch(const GmpiRenderParams *params, const GmpiSharedColor *shared, const GmpiDepthAlpha *depth_alpha,
+                                                      const float *grad_rgb, const float *grad_depth, const float *grad_transmittance,
+                                                      float *grad_ray_dir, float *grad_eye_pos, float *grad_z_dir, float *grad_dhw, float *grad_plane_z,
+                                                      void *stream);
+
+/* Bytes of workspace gmpi_mpi_render_depth_geometry_backward_pz_launch needs: 6 + 3 D [want_dhw] + D [want_plane_z] floats per 64 x 4 pixel tile and
+ * view.  want_plane_z == 0: gmpi_render_geometry_backward_workspace_bytes(params, want_dhw). */
+uint64_t gmpi_render_depth_geometry_backward_workspace_bytes(const GmpiRenderParams *params, int want_dhw, int want_plane_z);
 
 /*
  * ---- the shaded render of an RGBA volume ---------------------------------------------------------------------------------------------------------
@@ -733,7 +757,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * (gmpi_ramp_depth_launch, gmpi_ramp_depth_backward_launch) is built in; 33 is unused (-1); 34 whether the atomics-free backward of the shared-colour
  * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in; 35 is unused (-1); 36 whether the plane-chunked render (gmpi_mpi_render_chunk_launch,
  * gmpi_mpi_render_chunk_backward_launch) is built in; 37 is unused (-1); 38 whether the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch,
- * gmpi_mpi_render_shaded_backward_launch) is built in.  Unknown -> -1.  */
+ * gmpi_mpi_render_shaded_backward_launch) is built in; 39 is unused (-1); 40 whether the gradient w.r.t. plane_z of the depth-alpha layout
+ * (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -52,6 +52,8 @@ EXPORTS = (
     "gmpi_mpi_render_depth_backward_gather_launch",
     "gmpi_mpi_render_shared_geometry_backward_launch",
     "gmpi_mpi_render_depth_geometry_backward_launch",
+    "gmpi_mpi_render_depth_geometry_backward_pz_launch",
+    "gmpi_render_depth_geometry_backward_workspace_bytes",
     "gmpi_last_plane_uv_minmax_launch",
     "gmpi_rgba_range_check_launch",
     "gmpi_frames_to_uint8_launch",
@@ -279,6 +281,10 @@ def load_library():
     lib.gmpi_mpi_render_depth_geometry_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_depth_geometry_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), ctypes.POINTER(GmpiDepthAlpha),
                                                                    vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gmpi_mpi_render_depth_geometry_backward_pz_launch.restype = ctypes.c_int   # (grad_plane_z before the stream)
+    lib.gmpi_mpi_render_depth_geometry_backward_pz_launch.argtypes = list(lib.gmpi_mpi_render_depth_geometry_backward_launch.argtypes) + [vp]
+    lib.gmpi_render_depth_geometry_backward_workspace_bytes.restype = ctypes.c_uint64
+    lib.gmpi_render_depth_geometry_backward_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.c_int, ctypes.c_int]
     lib.gmpi_last_plane_uv_minmax_launch.restype = ctypes.c_int
     lib.gmpi_last_plane_uv_minmax_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
     lib.gmpi_rgba_range_check_launch.restype = ctypes.c_int

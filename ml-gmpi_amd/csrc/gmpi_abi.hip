@@ -29,7 +29,7 @@ uint64_t band_workspace_bytes(const KParams& p, int dtype);                 // r
 uint32_t* band_gate_words(const KParams& p, int dtype);                     // render_band.hip
 int band_pixels_wide(int dtype);                                            // render_band.hip
 uint64_t backward_gather_workspace_bytes(const KParams& p, int dtype);      // render_backward_gather.hip
-uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw);   // render_backward_geometry.hip
+uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw, bool want_plane_z = false);   // render_backward_geometry.hip
 uint64_t layout_gather_workspace_bytes(const KParams& p, bool depth);       // render_backward_gather.hip
 int layout_gather_runs(const KParams& p);                                   // render_backward_gather.hip
 void layout_gather_force_runs(int runs);                                    // render_backward_gather.hip
@@ -64,7 +64,7 @@ int u8_variant_query(int what);                                             // r
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
-                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
+                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, float* g_pz, hipStream_t stream);   // render_backward_geometry.hip
 
 // ---- min/max of the normalised grid on the last plane (mpi.py:103-109 diagnostics) --------------
 template <bool AC>
@@ -552,15 +552,16 @@ int gmpi_mpi_render_geometry_backward_launch(const GmpiRenderParams* params, con
                                                        stream);
 }
 
-// What the three geometry backward entries check once their structs are read: GMPI_OK with *launch = false when there is nothing to do.
+// What the geometry backward entries check once their structs are read: GMPI_OK with *launch = false when there is nothing to do.  grad_plane_z: the
+// depth-alpha layout's _pz entry alone.
 static int geometry_backward_args(const KParams& p, const float* grad_rgb, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir, float* grad_dhw,
-                                  bool* launch) {
+                                  bool* launch, float* grad_plane_z = nullptr) {
     *launch = false;
     if (grad_rgb == nullptr) return GMPI_E_NULL;
     if (p.N > 65535 || p.M > 65535 || 6 + 3 * static_cast<int64_t>(p.D) > (int64_t(1) << 31) - 1) return GMPI_E_SHAPE;   // grid.y: views / MPIs, grid.x: components
-    if (grad_ray_dir == nullptr && grad_eye_pos == nullptr && grad_z_dir == nullptr && grad_dhw == nullptr) return GMPI_OK;
-    if (grad_eye_pos != nullptr || grad_z_dir != nullptr || grad_dhw != nullptr) {   // the slabs of the per-view / per-plane sums
-        const uint64_t need = geometry_backward_workspace_bytes(p, grad_dhw != nullptr);
+    if (grad_ray_dir == nullptr && grad_eye_pos == nullptr && grad_z_dir == nullptr && grad_dhw == nullptr && grad_plane_z == nullptr) return GMPI_OK;
+    if (grad_eye_pos != nullptr || grad_z_dir != nullptr || grad_dhw != nullptr || grad_plane_z != nullptr) {   // the slabs of the per-view / per-plane sums
+        const uint64_t need = geometry_backward_workspace_bytes(p, grad_dhw != nullptr, grad_plane_z != nullptr);
         if (p.ws == nullptr || p.ws_bytes < need || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return GMPI_E_WORKSPACE;
     }
     *launch = true;
@@ -921,22 +922,36 @@ int gmpi_mpi_render_shared_geometry_backward_launch(const GmpiRenderParams* para
     rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
     if (!launch) return rc;
     return hip_rc(launch_backward_geometry_layout(p, params->rgba_dtype, sh, nullptr, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos,
-                                                  grad_z_dir, grad_dhw, static_cast<hipStream_t>(stream)));
+                                                  grad_z_dir, grad_dhw, nullptr, static_cast<hipStream_t>(stream)));
 }
 
 int gmpi_mpi_render_depth_geometry_backward_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
                                                    const float* grad_rgb, const float* grad_depth, const float* grad_transmittance, float* grad_ray_dir,
                                                    float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, void* stream) {
+    return gmpi_mpi_render_depth_geometry_backward_pz_launch(params, shared, depth_alpha, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos,
+                                                             grad_z_dir, grad_dhw, nullptr, stream);
+}
+
+// ... and w.r.t. plane_z (grad_plane_z NULL: the entry above, its kernels and its bits)
+int gmpi_mpi_render_depth_geometry_backward_pz_launch(const GmpiRenderParams* params, const GmpiSharedColor* shared, const GmpiDepthAlpha* depth_alpha,
+                                                      const float* grad_rgb, const float* grad_depth, const float* grad_transmittance, float* grad_ray_dir,
+                                                      float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, float* grad_plane_z, void* stream) {
     KParams p;
     SharedK sh;
     DepthK dk;
     int rc = to_depth(params, shared, depth_alpha, false, p, sh, dk);
     if (rc != GMPI_OK || p.N == 0) return rc;
     bool launch;
-    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch, grad_plane_z);
     if (!launch) return rc;
     return hip_rc(launch_backward_geometry_layout(p, params->rgba_dtype, sh, &dk, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos,
-                                                  grad_z_dir, grad_dhw, static_cast<hipStream_t>(stream)));
+                                                  grad_z_dir, grad_dhw, grad_plane_z, static_cast<hipStream_t>(stream)));
+}
+
+uint64_t gmpi_render_depth_geometry_backward_workspace_bytes(const GmpiRenderParams* params, int want_dhw, int want_plane_z) {
+    KParams p;
+    if (to_kparams(params, p, false, true) != GMPI_OK || p.N == 0) return 0;
+    return geometry_backward_workspace_bytes(p, want_dhw != 0, want_plane_z != 0);
 }
 
 int gmpi_last_plane_uv_minmax_launch(const GmpiRenderParams* params, float* uv_minmax, void* stream) {
@@ -1065,6 +1080,7 @@ int gmpi_query(int32_t what) {
         case 32: return 1;  // compute_depth of the depth-alpha layout (gmpi_ramp_depth_launch, light_kernels.hip) is built in  (31: unused)
         case 34: return 1;  // the atomics-free backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_*_backward_gather_launch) is built in  (33: unused)
         case 38: return 1;  // the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch, gmpi_mpi_render_shaded_backward_launch) is built in  (37: unused)
+        case 40: return 1;  // the gradient w.r.t. plane_z of the depth-alpha layout (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in  (39: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -111,6 +111,7 @@ __device__ __forceinline__ void gather_taps(const TexT* __restrict__ pl, int64_t
 template <typename TexT>
 struct VolumeSource {
     static constexpr bool kSkips = false;          // taps() never returns false
+    static constexpr bool kPlaneZ = false;         // (the depth-alpha layout alone has a plane_z)
     static constexpr bool kForwardAlpha = false;   // the alpha sample is the frame's fma chain in both modes
     const TexT* __restrict__ vol;
     __device__ __forceinline__ VolumeSource(const KParams& p, const BwdView& vw)
@@ -148,6 +149,7 @@ struct ColourImages {
 template <typename TexT>
 struct SharedSource {
     static constexpr bool kSkips = false;
+    static constexpr bool kPlaneZ = false;
     static constexpr bool kForwardAlpha = false;   // (the volume path's sweep exactly)
     const TexT* __restrict__ alpha;   // KParams' volume fields: the alpha planes, s_chan = 0
     ColourImages<TexT> col;
@@ -166,15 +168,19 @@ struct SharedSource {
     }
 };
 
-template <typename TexT>
+// The tag that selects the PZ instances of the frame (the last of Extra; the depth-alpha layout only): the plane's share of dL/d plane_z too.
+struct PlaneZGrad {};
+
+template <typename TexT, bool PZ = false>
 struct DepthSource {
     static constexpr bool kSkips = true;
     static constexpr bool kForwardAlpha = true;    // strict-order mode: bilerp<true> of the ramp taps, as render_depth_kernel
+    static constexpr bool kPlaneZ = PZ;
     const TexT* __restrict__ depth;   // KParams' volume fields: the depth image (s_plane, s_chan unused)
     const float* __restrict__ pz;
     DepthK dk;
     ColourImages<TexT> col;
-    __device__ __forceinline__ DepthSource(const KParams& p, const BwdView& vw, const SharedK& sh, const DepthK& d)
+    __device__ __forceinline__ DepthSource(const KParams& p, const BwdView& vw, const SharedK& sh, const DepthK& d, PlaneZGrad = {})
         : depth(static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi),
           pz(d.plane_z + static_cast<int64_t>(vw.m) * d.pz_stride), dk(d), col(sh, vw.m) {}
     template <bool AC, bool STRICT>
@@ -197,25 +203,48 @@ struct DepthSource {
         col.taps(k, p.D, tp, q);
         return true;
     }
+    // The PZ instances' form: on[i] says whether tap i lies inside the texture AND on the ramp (depth_ramp's `inside`, bounds included: where
+    // torch.clamp passes the gradient, d a_i / d plane_z = 1 / den).  A tap exactly on the lower bound has alpha 0 and is on the ramp: the
+    // plane is skipped only when, besides four zero ramp taps, no tap is on the ramp (the image backward's rule, render_depth.hip).
+    template <bool STRICT>
+    __device__ __forceinline__ bool taps(const KParams& p, int k, int Ht, int Wt, float ix, float iy, Taps& q, bool (&on)[4]) const {
+        const TapPos tp = tap_pos(Ht, Wt, ix, iy, q);
+        float d[4], a[4];
+        load_taps<TexT>(depth, p.s_row, tp, d);
+        const float z = pz[k];
+        bool in[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = depth_ramp<STRICT>(z, d[i], dk, in[i]);
+        pad_taps(tp, a, q.t[3]);
+        on[0] = tp.nw && in[0], on[1] = tp.ne && in[1], on[2] = tp.sw && in[2], on[3] = tp.se && in[3];
+        if (q.t[3][0] == 0.0f && q.t[3][1] == 0.0f && q.t[3][2] == 0.0f && q.t[3][3] == 0.0f && !(on[0] || on[1] || on[2] || on[3])) return false;
+        col.taps(k, p.D, tp, q);
+        return true;
+    }
 };
 
 template <typename TexT, typename... Extra> struct SourceOf;
 template <typename TexT> struct SourceOf<TexT> { using type = VolumeSource<TexT>; };
 template <typename TexT> struct SourceOf<TexT, SharedK> { using type = SharedSource<TexT>; };
 template <typename TexT> struct SourceOf<TexT, SharedK, DepthK> { using type = DepthSource<TexT>; };
+template <typename TexT> struct SourceOf<TexT, SharedK, DepthK, PlaneZGrad> { using type = DepthSource<TexT, true>; };
 
 // Slab layout (floats): component j of tile t of view n at ws[(j * N + n) * T + t];  j = 0..2 eye, 3..5 z_dir, 6 + 3k + (0, 1, 2) = plane k's
-// (d, h, w).  Every slot is written by exactly one workgroup.
+// (d, h, w); the PZ instances add one component per plane BEHIND those, 6 + (3D with dhw, else 0) + k = plane k's plane_z sum (times den), so that
+// the layout without plane_z is what it was.  Every slot is written by exactly one workgroup.
 //
-// The frame.  Extra: the layout's structs -- none: the RGBA volume; SharedK: the shared-colour layout; SharedK, DepthK: the depth-alpha layout -- which
-// select the tap source (SourceOf).
+// The frame.  Extra: the layout's structs -- none: the RGBA volume; SharedK: the shared-colour layout; SharedK, DepthK: the depth-alpha layout;
+// SharedK, DepthK, PlaneZGrad: the depth-alpha layout with the gradient w.r.t. plane_z (the PZ instances: one more wave sum and slab component per
+// plane, and the wider skip rule of DepthSource's second taps()) -- which select the tap source (SourceOf).
 template <typename TexT, bool AC, bool STRICT, bool DHW, typename... Extra>
 __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, const BwdParams b, float* __restrict__ g_ray, float* __restrict__ slab,
                                                              const int tiles_x, const int n_tiles, const Extra... extra) {
     using Src = typename SourceOf<TexT, Extra...>::type;
+    constexpr bool PZ = Src::kPlaneZ;                  // the plane_z term too (the instances with the PlaneZGrad tag)
+    constexpr int kSums = (DHW ? 3 : 0) + (PZ ? 1 : 0);   // wave sums per plane: (d, h, w), then plane_z
     __shared__ float4 pcA[kGChunk];                    // zdiff, w, h, RN(2/w)
     __shared__ float pcB[kGChunk];                     // RN(2/h)
-    __shared__ float red[DHW ? kGWaves * kGChunk * 3 : 1];   // per wave and plane: (d, h, w) partial sums
+    __shared__ float red[kSums ? kGWaves * kGChunk * kSums : 1];   // per wave and plane: (d, h, w) and plane_z partial sums
     __shared__ float red6[kGWaves * 6];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = blockIdx.y;
@@ -261,7 +290,11 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
             }
             Taps q;
             float vd = 0.0f, vh = 0.0f, vw_ = 0.0f;   // this pixel's share of the plane's (d, h, w) sums
-            const bool live = src.template taps<STRICT>(p, kc + t, Ht, Wt, ix, iy, q);
+            float vz = 0.0f;                          // ... and of its plane_z sum (times den)
+            bool on[4];                               // PZ: the taps inside the texture and on the ramp
+            bool live;
+            if constexpr (PZ) live = src.template taps<STRICT>(p, kc + t, Ht, Wt, ix, iy, q, on);
+            else live = src.template taps<STRICT>(p, kc + t, Ht, Wt, ix, iy, q);
             if (!Src::kSkips || live) {   // (false: the plane is the identity of this pixel's sweep)
                 const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
                 float smp[4], dix[4], diy[4];
@@ -300,23 +333,33 @@ __global__ __launch_bounds__(kGT) void geometry_pixel_kernel(const KParams p, co
                     vd = g_s * rrz, vh = -0.5f * g_y * y * rh, vw_ = -0.5f * g_x * x * rw;   // d(2x/w)/dw = -(2/w)(x/w)
                     vd = active ? vd : 0.0f, vh = active ? vh : 0.0f, vw_ = active ? vw_ : 0.0f;
                 }
+                if constexpr (PZ) {   // d a_i / d plane_z = 1 / den on the ramp: d_s[3] sum_i w_i on_i (the reducer divides by den, once)
+                    const float wz = (((on[0] ? w00 : 0.0f) + (on[1] ? w01 : 0.0f)) + (on[2] ? w10 : 0.0f)) + (on[3] ? w11 : 0.0f);
+                    vz = active ? d3 * wz : 0.0f;
+                }
             }
             if (DHW) {   // (every lane of the wave, skipped planes included: the wave sums are cross-lane)
                 vd = wave_sum(vd), vh = wave_sum(vh), vw_ = wave_sum(vw_);
                 if (lane == 0) {
-                    float* o = red + (wave * kGChunk + t) * 3;
+                    float* o = red + (wave * kGChunk + t) * kSums;
                     o[0] = vd, o[1] = vh, o[2] = vw_;
                 }
             }
+            if constexpr (PZ) {
+                vz = wave_sum(vz);
+                if (lane == 0) red[(wave * kGChunk + t) * kSums + (kSums - 1)] = vz;
+            }
         }
-        if (DHW && slab != nullptr) {   // this chunk's plane sums: the waves in order, one slot per (component, plane)
+        if constexpr (kSums != 0) if (slab != nullptr) {   // this chunk's plane sums: the waves in order, one slot per (component, plane)
             __syncthreads();
-            for (int i = tid; i < 3 * kn; i += kGT) {
-                const int t = i / 3, j = i - 3 * t;
-                float v = red[t * 3 + j];
+            for (int i = tid; i < kSums * kn; i += kGT) {
+                const int t = i / kSums, j = i - kSums * t;
+                float v = red[t * kSums + j];
 #pragma unroll
-                for (int wv = 1; wv < kGWaves; ++wv) v += red[(wv * kGChunk + t) * 3 + j];
-                slab[(6 + 3 * static_cast<int64_t>(kc + t) + j) * ncomp_stride + static_cast<int64_t>(n) * n_tiles + tile] = v;
+                for (int wv = 1; wv < kGWaves; ++wv) v += red[(wv * kGChunk + t) * kSums + j];
+                int64_t comp = 6 + 3 * static_cast<int64_t>(kc + t) + j;
+                if (PZ && j == kSums - 1) comp = 6 + (DHW ? 3 * static_cast<int64_t>(p.D) : 0) + (kc + t);   // behind the (d, h, w) components
+                slab[comp * ncomp_stride + static_cast<int64_t>(n) * n_tiles + tile] = v;
             }
         }
     }
@@ -378,27 +421,53 @@ __global__ __launch_bounds__(kGRed) void geometry_reduce_kernel(const KParams p,
     }
 }
 
+// The plane_z sums (the PZ instances' components; comp0 = the first of them).  Block (k, i): plane k of MPI i, summed over every view of the MPI in
+// view order, or (per_mpi false: ONE table for all MPIs) over all views in view order; the same strided sums and LDS tree, then 1 / den, once.
+__global__ __launch_bounds__(kGRed) void plane_z_reduce_kernel(const KParams p, const float* __restrict__ comp0, const int n_tiles, const bool per_mpi,
+                                                               const float den, float* __restrict__ g_pz) {
+    __shared__ float part[kGRed];
+    const int k = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+    const float* __restrict__ comp = comp0 + static_cast<int64_t>(k) * p.N * n_tiles;
+    float acc = 0.0f;
+    for (int n = 0; n < p.N; ++n) {
+        uint32_t bad = 0;
+        if (per_mpi && view_mpi(p, n, bad) != i) continue;
+        for (int t = tid; t < n_tiles; t += kGRed) acc += comp[static_cast<int64_t>(n) * n_tiles + t];
+    }
+    part[tid] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int w = kGRed / 2; w > 0; w >>= 1) {
+        if (tid < w) part[tid] += part[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) g_pz[static_cast<int64_t>(i) * p.D + k] = part[0] / den;
+}
+
 static int tiles_x_of(const KParams& p) { return (p.W + kGTW - 1) / kGTW; }
 static int tiles_of(const KParams& p) { return tiles_x_of(p) * ((p.H + kGTH - 1) / kGTH); }
 
 }  // namespace bwgeo
 
-uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw) {
+uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw, bool want_plane_z) {
     const uint64_t comps = 6u + (want_dhw ? 3u * static_cast<uint64_t>(p.D) : 0u);
-    return (comps * p.N * static_cast<uint64_t>(bwgeo::tiles_of(p)) * sizeof(float) + 255) / 256 * 256;
+    const uint64_t slots = p.N * static_cast<uint64_t>(bwgeo::tiles_of(p)) * sizeof(float);   // bytes per component
+    // (the plane_z components lie directly behind the others; their bytes are rounded up on their own, so that asking for them always asks for more)
+    return (comps * slots + 255) / 256 * 256 + (want_plane_z ? (p.D * slots + 255) / 256 * 256 : 0u);
 }
 
 // g_ray [N,3,H,W], g_eye / g_z [N,3], g_dhw [M,D,3]: overwritten; nullptr = not wanted.  p.ws must hold geometry_backward_workspace_bytes(p,
-// g_dhw != nullptr) bytes when any of g_eye, g_z, g_dhw is wanted (checked by the caller).  pixel(type, AC, STRICT, DHW, grid, b, slab, tiles_x,
-// n_tiles) launches the layout's pixel kernel; the slab reducer is the same for all.
+// g_dhw != nullptr, pz != nullptr) bytes when any of g_eye, g_z, g_dhw, the plane_z gradient is wanted (checked by the caller).  pixel(type, AC,
+// STRICT, DHW, grid, b, slab, tiles_x, n_tiles) launches the layout's pixel kernel; the slab reducer is the same for all.  pz: the depth-alpha
+// layout's DepthK when the gradient w.r.t. plane_z is wanted (g_pz [M,D], or [D] for one table: overwritten; `pixel` launches a PZ instance).
 template <typename Pixel>
 static hipError_t launch_geometry_passes(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_eye, float* g_z,
-                                         float* g_dhw, hipStream_t stream, Pixel&& pixel) {
+                                         float* g_dhw, hipStream_t stream, Pixel&& pixel, const DepthK* pz = nullptr, float* g_pz = nullptr) {
     using namespace bwgeo;
     BwdParams b{};
     b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T;
     const bool want_dhw = g_dhw != nullptr;
-    float* slab = (g_eye || g_z || g_dhw) ? static_cast<float*>(p.ws) : nullptr;
+    float* slab = (g_eye || g_z || g_dhw || g_pz) ? static_cast<float*>(p.ws) : nullptr;
     const int tx = tiles_x_of(p), nt = tiles_of(p);
     const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
     dispatch_dtype(dtype, [&](auto t) {
@@ -408,9 +477,14 @@ static hipError_t launch_geometry_passes(const KParams& p, int dtype, const floa
             });
         });
     });
-    if (slab != nullptr) {
+    if (g_eye || g_z || g_dhw) {
         const dim3 rgrid(6 + (want_dhw ? 3 * p.D : 0), std::max(p.N, p.M));
         hipLaunchKernelGGL(geometry_reduce_kernel, rgrid, dim3(kGRed), 0, stream, p, slab, nt, g_eye, g_z, g_dhw);
+    }
+    if (g_pz != nullptr) {
+        const bool per_mpi = pz->pz_stride != 0;
+        const float* comp0 = slab + (6 + (want_dhw ? 3 * static_cast<int64_t>(p.D) : 0)) * p.N * nt;
+        hipLaunchKernelGGL(plane_z_reduce_kernel, dim3(p.D, per_mpi ? p.M : 1), dim3(kGRed), 0, stream, p, comp0, nt, per_mpi, pz->den, g_pz);
     }
     return hipGetLastError();
 }
@@ -425,17 +499,21 @@ hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_
 }
 
 // The same passes over the shared-colour layout (dk == nullptr; p carries the alpha planes, s_chan = 0) and the depth-alpha layout (p carries the
-// depth image).
+// depth image; g_pz: its gradient w.r.t. plane_z, [M,D] or, with one table for all MPIs, [D]; nullptr = not wanted: today's instances).
 hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
-                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, hipStream_t stream) {
+                                           const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, float* g_pz, hipStream_t stream) {
+    if (dk == nullptr) g_pz = nullptr;
     return launch_geometry_passes(p, dtype, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream,
                                   [&](auto t, auto AC, auto STRICT, auto DHW, dim3 grid, const BwdParams& b, float* slab, int tx, int nt) {
-        if (dk != nullptr) {
+        if (g_pz != nullptr) {
+            hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel, SharedK, DepthK, bwgeo::PlaneZGrad)), grid, dim3(bwgeo::kGT), 0, stream, p, b,
+                               g_ray, slab, tx, nt, sh, *dk, bwgeo::PlaneZGrad{});
+        } else if (dk != nullptr) {
             hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel, SharedK, DepthK)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt, sh, *dk);
         } else {
             hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel, SharedK)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt, sh);
         }
-    });
+    }, dk, g_pz);
 }
 #undef GMPI_GEOMETRY_INSTANCE
 

@@ -386,6 +386,8 @@ def _depth_alpha(plane_z: torch.Tensor, z_lo: float, z_hi: float) -> _lib.GmpiDe
 _Kind = collections.namedtuple("_Kind", "name expand first geometry_entry")
 _SHARED_COLOUR = _Kind("shared-colour", "expand_shared_color", "alpha", "gmpi_mpi_render_shared_geometry_backward_launch")
 _DEPTH_ALPHA = _Kind("depth-alpha", "expand_depth_alpha", "depth", "gmpi_mpi_render_depth_geometry_backward_launch")
+# ... of the depth-alpha geometry backward when plane_z needs a gradient (grad_plane_z before the stream), and its workspace query
+_DEPTH_PZ_ENTRY, _DEPTH_PZ_QUERY = "gmpi_mpi_render_depth_geometry_backward_pz_launch", "gmpi_render_depth_geometry_backward_workspace_bytes"
 # render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
 _DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch",
                            "gather": "gmpi_mpi_render_depth_backward_launch"}
@@ -401,11 +403,13 @@ class _Layout:
     caller's tensors; variant: the kernel asked for by name, or None = the module's own; backward_entry: the C entry of the image backward;
     gather: the backward was asked for as "gather" -- the atomics-free pair (`_GATHER_ENTRIES`) where the library can take the launch, backward_entry
     otherwise; gather_runs: a test-only override of the pair's plane runs per texel tile (None: the library's rule);
-    depth-alpha only: plane_z (detached fp32 on the device, [D] or [M,D]), ramp = (z_lo, z_hi), depth_forward ("pixel", "window" or None)."""
+    depth-alpha only: plane_z (detached fp32 on the device, [D] or [M,D]: what the kernels read), plane_z_arg (the caller's tensor as it came: the
+    input of the autograd node when it needs a gradient), ramp = (z_lo, z_hi), depth_forward ("pixel", "window" or None)."""
 
-    def __init__(self, kind, rgb, background, variant, backward_entry, plane_z=None, ramp=None, depth_forward=None, gather=False, gather_runs=None):
+    def __init__(self, kind, rgb, background, variant, backward_entry, plane_z=None, ramp=None, depth_forward=None, gather=False, gather_runs=None,
+                 plane_z_arg=None):
         self.kind, self.rgb, self.background, self.variant, self.backward_entry = kind, rgb, background, variant, backward_entry
-        self.plane_z, self.ramp, self.depth_forward = plane_z, ramp, depth_forward
+        self.plane_z, self.plane_z_arg, self.ramp, self.depth_forward = plane_z, plane_z_arg, ramp, depth_forward
         self.gather, self.gather_runs = gather, gather_runs
 
     @property
@@ -473,7 +477,8 @@ def _shared_layout(rgb, alpha, background, variant, shared_backward="tile", gath
 
 def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, variant, depth_backward, depth_forward, gather_runs=None):
     """`MPI.render_views_depth` / `MPIRenderer.render_depth`: (the depth image as the view [M,1,1,Ht,Wt], `render_views`' `_layout`); the option
-    names and the checks that need no launch.  depth_forward None reads as "pixel"."""
+    names and the checks that need no launch.  depth_forward None reads as "pixel".  The caller's plane_z is kept as it is next to the detached fp32
+    copy the kernels read: a module with geometry_grad="all" differentiates w.r.t. it, any other detaches it (no gradient, nothing launched)."""
     if variant not in (None, "auto", "gather"):
         raise ValueError(f'the depth-alpha render has one kernel (variant "auto" or "gather"); "{variant}" is not built for this layout')
     if not isinstance(depth_backward, str) or depth_backward not in _DEPTH_BACKWARD_ENTRIES:
@@ -488,7 +493,7 @@ def _depth_layout(rgb, depth, plane_z, z_bounds, background, n_planes: int, vari
     assert z_lo < z_hi, (z_lo, z_hi)
     return depth.unsqueeze(1), _Layout(_DEPTH_ALPHA, rgb, background, variant, _DEPTH_BACKWARD_ENTRIES[depth_backward],
                                        _f32_on(plane_z.detach(), depth.device), (z_lo, z_hi), depth_forward, gather=depth_backward == "gather",
-                                       gather_runs=gather_runs)
+                                       gather_runs=gather_runs, plane_z_arg=plane_z)
 
 
 def _lend(p: _lib.GmpiRenderParams, ws: torch.Tensor) -> None:
@@ -913,8 +918,10 @@ class MPI(nn.Module):
             raise NotImplementedError(f"the {layout.kind.name} render has no gradient w.r.t. the plane geometry or the camera tensors under "
                                       f'geometry_grad=True: build the module with geometry_grad="all" for that (or render the expanded '
                                       f"volume, {layout.kind.expand}, with render_views)")
-        if geometry or rgba.requires_grad or layout.requires_grad:
-            return _LayoutRenderFunction, (layout.rgb, rgba, layout.background)
+        # (depth-alpha, geometry_grad="all": a plane_z that requires grad is an input of the node; any other module detaches it, as ever)
+        plane_z = layout.plane_z_arg if self.geometry_grad_layouts and layout.plane_z_arg is not None and layout.plane_z_arg.requires_grad else None
+        if geometry or rgba.requires_grad or layout.requires_grad or plane_z is not None:
+            return _LayoutRenderFunction, (layout.rgb, rgba, layout.background, plane_z)
         return None
 
     def _shaded_bridge(self, rgba, shading, dhw, ray_dir, eye_pos, z_dir):
@@ -1008,7 +1015,10 @@ class MPI(nn.Module):
         reaches rgb, depth and background in their own dtypes (gmpi_mpi_render_depth_backward_launch: the gradient of all D alpha planes lands in
         the one depth image); w.r.t. dhw and the camera tensors with geometry_grad="all" (one extra launch after the image backward, which is
         skipped when no image needs a gradient; geometry_grad=True and a camera / dhw tensor that requires grad raise NotImplementedError);
-        never w.r.t. plane_z or the ramp's bounds.  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
+        w.r.t. plane_z with geometry_grad="all" too (the same extra launch, through gmpi_mpi_render_depth_geometry_backward_pz_launch: how opaque each
+        plane is where the ray meets it -- the other half of a plane depth's gradient, next to dhw[..., 0]'s; `plane_z.grad` in plane_z's shape, a [D]
+        table summed over the MPIs; bit-reproducible); with geometry_grad False or True a plane_z that requires grad is detached, as ever: no gradient,
+        nothing new is launched; never w.r.t. the ramp's bounds.  The three images must have ONE dtype (TypeError otherwise; uint8: TypeError).  range_check="full" passes over rgb and
         background (a depth image is no [0, 1] tensor); "touched" also sets the range bit for a NaN depth some pixel samples.
         `depth_backward`: "pixel" (the default) back-propagates with the one-pixel-per-lane kernel; "tile" with
         gmpi_mpi_render_depth_backward_tile_launch -- one workgroup per 32 x 16 pixel tile, the gradients of rgb and depth summed in LDS across
@@ -1145,15 +1155,24 @@ def _upstream(ctx, dev, g_color, g_depth, g_T):
     return g_color, g_depth, g_T
 
 
-def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream):
+def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream, plane_z=None):
     """The gradient w.r.t. the sample positions (render_backward_geometry.hip) for the inputs (dhw, ray_dir, eye_pos, z_dir) flagged in `want`, in
     each input's own dtype and device (ctx.geo_meta): every output overwritten, NULL = not wanted; the per-view and per-plane sums go through
     slabs in a workspace lent for this call (no atomics: bit-reproducible).  entry: the C entry; structs: what it takes between the parameter
-    struct and the upstream gradients (the layout's structs)."""
+    struct and the upstream gradients (the layout's structs).  plane_z (depth-alpha: the table the kernels read, when ITS gradient is wanted): the
+    pass is then the _pz entry behind its own workspace query, once, whatever else is wanted, and a fifth gradient -- fp32, plane_z's shape -- is
+    returned behind the four."""
     p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved tensors
     shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
     out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
     ws = None   # (held until this call returns: the launch that uses it is on the stream by then)
+    if plane_z is not None:
+        g_pz = torch.empty(tuple(plane_z.shape), dtype=torch.float32, device=dev)
+        need = int(getattr(_lib.load_library(), _DEPTH_PZ_QUERY)(ctypes.byref(p), int(want[0]), 1))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _lend(p, ws)
+        _call(_DEPTH_PZ_ENTRY, dev, ctypes.byref(p), *structs, *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), _ptr(g_pz), stream=stream)
+        return [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)] + [g_pz]
     if want[0] or want[2] or want[3]:
         need = int(_lib.load_library().gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
@@ -1459,10 +1478,13 @@ class _LayoutRenderFunction(torch.autograd.Function):
     overwrites, where the library can take the launch) into zero-filled fp32 gradients of rgb, the alpha tensor / depth image and
     the background -- those that need one: the others are passed as NULL and skipped by the kernel, and the launch is skipped when none does.
     Saved tensors (plane_z among them), private T buffer, unused outputs as None: as there.  For a module with geometry_grad="all" the node is
-    also recorded when only dhw or a camera tensor requires grad, and its backward ends with the layout's geometry entry: one extra launch."""
+    also recorded when only dhw or a camera tensor requires grad, and its backward ends with the layout's geometry entry: one extra launch.
+    plane_z_in: the caller's plane_z when such a module has to differentiate w.r.t. it (depth-alpha; the node is then recorded for it alone too),
+    else None.  With it the geometry pass is gmpi_mpi_render_depth_geometry_backward_pz_launch behind its own workspace query, once, whatever else
+    is wanted, and the gradient goes back in plane_z's own shape, dtype and device; without it the old query and the old entry with the old arguments."""
 
     @staticmethod
-    def forward(ctx, rgb, mid, background, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
+    def forward(ctx, rgb, mid, background, plane_z_in, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
         layout = kwargs["_layout"]
         res, keep, (rgb_k, bg_k) = _bridge_forward(ctx, mpi, mid, (dhw, ray_dir, eye_pos, z_dir), kwargs)
         ctx.save_for_backward(keep.rgba, rgb_k, *keep[1:5], res["T"], bg_k, keep.view_to_mpi, layout.plane_z)   # (None where there is none)
@@ -1470,6 +1492,7 @@ class _LayoutRenderFunction(torch.autograd.Function):
         ctx.gather, ctx.gather_runs, ctx.kind, ctx.mpi = layout.gather, layout.gather_runs, layout.kind, mpi
         ctx.meta = [(t.dtype, tuple(t.shape)) if t is not None else None for t in (rgb, mid, background)]
         ctx.geometry = mpi.geometry_grad_layouts
+        ctx.pz_meta = None if plane_z_in is None else (plane_z_in.dtype, plane_z_in.device, tuple(plane_z_in.shape))
         ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
         return res["color"], res["depth"], res["T"], res["status"]
 
@@ -1478,9 +1501,10 @@ class _LayoutRenderFunction(torch.autograd.Function):
         mid, rgb, dhw, ray_dir, eye_pos, z_dir, T, bg, view_to_mpi, plane_z = ctx.saved_tensors
         keep, dev = _Keep(mid, dhw, ray_dir, eye_pos, z_dir, view_to_mpi), mid.device
         want = [ctx.needs_input_grad[i] and ctx.meta[i] is not None for i in (0, 1, 2)]
-        geo_want = [ctx.geometry and ctx.needs_input_grad[i] for i in (4, 5, 6, 7)]   # dhw, ray_dir, eye_pos, z_dir
-        if not (any(want) or any(geo_want)) or (g_color is None and g_depth is None and g_T is None):
-            return (None,) * 9
+        geo_want = [ctx.geometry and ctx.needs_input_grad[i] for i in (5, 6, 7, 8)]   # dhw, ray_dir, eye_pos, z_dir
+        pz_want = ctx.geometry and ctx.pz_meta is not None and ctx.needs_input_grad[3]
+        if not (any(want) or any(geo_want) or pz_want) or (g_color is None and g_depth is None and g_T is None):
+            return (None,) * 10
         g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)   # (g_T None: the launch stays on the path without a transmittance gradient)
         upstream = (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T))
         sc = _shared_color(rgb, bg)   # the forward's structs, rebuilt from the saved tensors
@@ -1520,11 +1544,13 @@ class _LayoutRenderFunction(torch.autograd.Function):
                 if forced:
                     lib.gmpi_render_layout_backward_gather_set_runs(0)
             out = [g.to(ctx.meta[i][0]).reshape(ctx.meta[i][1]) if g is not None else None for i, g in enumerate(grads)]
-        geo = [None] * 4
-        if any(geo_want):   # a module with geometry_grad="all": the geometry pass with the layout's structs
+        geo = [None] * 5
+        if any(geo_want) or pz_want:   # a module with geometry_grad="all": the geometry pass with the layout's structs
             stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-            geo = _geometry_pass(ctx, keep, T, dev, stream, geo_want, ctx.geometry_entry, structs, upstream)
-        return out[0], out[1], out[2], None, geo[0], geo[1], geo[2], geo[3], None
+            geo = _geometry_pass(ctx, keep, T, dev, stream, geo_want, ctx.geometry_entry, structs, upstream, plane_z if pz_want else None) + [None]
+            if pz_want:
+                geo[4] = geo[4].to(device=ctx.pz_meta[1], dtype=ctx.pz_meta[0]).reshape(ctx.pz_meta[2])
+        return out[0], out[1], out[2], geo[4], None, geo[0], geo[1], geo[2], geo[3], None
 
 
 HipMPI = MPI

@@ -158,15 +158,22 @@ class MPIRenderer:
     def get_xyz_single_res(self, tex_h, tex_w, only_z=False):
         if only_z:
             z = self.dynamic_mpi_plane_dhws[:, 0].reshape((-1, 1, 1, 1))
-            normalized_z = (z - self.plane_min_d) / (self.plane_max_d - self.plane_min_d)
-            if self.normalized_xyz_range == "-11":
-                normalized_z = 2 * normalized_z - 1
-            return z.to(self.device), normalized_z.to(self.device)
+            return z.to(self.device), self.normalized_plane_z(z).to(self.device)
         if self.mpi_tex_h is None or self.mpi_tex_h != tex_h:
             self.comput_tex_pixels_3d_coords(tex_h, tex_w)
             self.comput_tex_pixels_3d_normalized_coords_mpi(self.mpi_tex_pix_3d_coords)
         normalized = self.mpi_tex_pix_3d_normalized_coords if self.use_normalized_xyz else None
         return self.mpi_tex_pix_3d_coords[..., :3], normalized
+
+    def normalized_plane_z(self, plane_ds: torch.Tensor) -> torch.Tensor:
+        """The normalised depths of planes at distances plane_ds (any shape): `get_xyz_single_res(only_z=True)`'s formula on a tensor argument, so
+        it is differentiable -- for `dynamic_mpi_plane_dhws[:, 0]` the bits of `get_xyz_single_res(...)[1].reshape(-1)`, what `render_depth` compares
+        the depth image with by default.  With it ONE learnable plane_ds reaches the loss through both `dhw[..., 0]` (where the ray meets the plane)
+        and `render_depth(plane_z=...)` (how opaque the plane is there) of a renderer built with geometry_grad="all"."""
+        normalized_z = (plane_ds - self.plane_min_d) / (self.plane_max_d - self.plane_min_d)
+        if self.normalized_xyz_range == "-11":
+            normalized_z = 2 * normalized_z - 1
+        return normalized_z
 
     def get_xyz_interpolate_ws(self, n_src_planes, n_tgt_planes):
         """[#tgt, #src+2] linear interpolation weights of target plane depths between source plane depths."""
@@ -440,6 +447,7 @@ class MPIRenderer:
             # (nor when the status check lags: the pending entry of this call keeps its camera tensors for the diagnostics of a tripped
             #  assertion -- "pos / dir / min val" of THIS call, printed one or more calls later -- so a later call must not overwrite them)
             recording = torch.is_grad_enabled() and (batch_mpi_rgbas.requires_grad or (layout is not None and layout.requires_grad) or (shading is not None and shading.requires_grad) or (self.mpi.geometry_grad and self._dhw_for(n_mpis).requires_grad)
+                                                     or (layout is not None and self.mpi.geometry_grad_layouts and layout.plane_z_arg is not None and layout.plane_z_arg.requires_grad)
                                                      or (isinstance(chunks, (list, tuple)) and any(c.requires_grad for c in chunks)))
             ray_t, eye_t, zd_t = self._generate_rays_hip(c2w, reuse=not recording and defer != "lag")
         else:
@@ -532,7 +540,9 @@ class MPIRenderer:
         """`render` of the volume `expand_depth_alpha(batch_rgb, batch_depth, plane_z, *depth_alpha_bounds(z_range, n_z_bins), background_rgb)`
         without building it (the output of GMPI's "depth2alpha" generator): batch_rgb [B,3,Ht,Wt], batch_depth [B,1,Ht,Wt], background_rgb
         [B,3,Ht,Wt] or None = the last plane's own colour.  plane_z [D] or [B,D]: None takes this renderer's normalised plane depths,
-        `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with.  Keyword arguments, return tuple, pose
+        `get_xyz_single_res(Ht, Wt, only_z=True)[1]`, what the generator compares the depth with; the tensor is passed through as it is: a
+        renderer built with geometry_grad="all" differentiates w.r.t. a plane_z that requires grad (`normalized_plane_z` makes one of learnable
+        plane distances), any other detaches it, as ever (no gradient, nothing new is launched).  Keyword arguments, return tuple, pose
         sampling and the consumption of the torch RNG are `render`'s.  `depth_backward`: "pixel" (default), "tile" or "gather", as in
         `MPI.render_views_depth` -- the tile backward assumes a pinhole ray field (this renderer's rays are one) and takes D <= 128, else the
         one-pixel-per-lane kernel runs; "gather" back-propagates without atomics (bit-reproducible gradients); any other name is a ValueError
