@@ -192,6 +192,38 @@ uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams *params);
 int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
 
 /*
+ * gmpi_mpi_render_launch over channels-last FLOAT layers: rgba is [M, D, Ht, Wt, 4] in memory (what image files, numpy and channels-last networks
+ * hold), described in the struct as the volume [M, D, 4, Ht, Wt] it is a view of -- rgba_dtype F32 / BF16 / F16 and rgba_stride, in elements as ever,
+ * [s_M, s_D, 1, s_row, 4]: channel stride 1, texel stride 4, s_row >= 4 Wt (padded rows are fine), s_M and s_D >= 0 (0 on s_M: one MPI for every
+ * view group).  Any other stride combination is GMPI_E_STRIDE: planar strides, a channel stride other than 1, a texel stride other than 4, rows
+ * that overlap, a negative stride.  Every other field means what it means for gmpi_mpi_render_launch; the camera hints are accepted and ignored; no
+ * workspace is used.  The layers are read in place by instances of their own over whole texels (16 bytes of fp32, 8 bytes of 16-bit storage):
+ *   GMPI_VARIANT_GATHER  the one-pixel-per-lane kernel, one load per tap of the whole texel at the element's alignment: any Wt, any such strides.
+ *                        The planar gather kernel's arithmetic behind the load: its bits, in both modes.
+ *   GMPI_VARIANT_LDS     render_layers.hip: 32 x 16 pixel tiles, per plane a box of up to 64 x 32 raw texels in LDS, loaded 16 bytes at a time.
+ *                        It takes the tensors gmpi_render_layers_supports() answers 1 for, else GMPI_E_VARIANT.  Bit-identical to GATHER (and to the
+ *                        render of the planar copy of the same values) with GMPI_FLAG_STRICT_ORDER, within 1e-5 of it without.
+ *                        GMPI_FLAG_CHECK_RANGE tests every staged texel (a superset of the sampled ones).  A (tile, plane) whose box exceeds the
+ *                        buffer, and a pixel whose footprint leaves its tile's box (no pinhole ray field), are gathered from global memory.
+ *   GMPI_VARIANT_AUTO    LDS where gmpi_render_layers_supports() says 1, else GATHER.
+ *   WAVE, BAND, DMA and unknown values: GMPI_E_VARIANT.
+ * GMPI_DTYPE_U8 with these strides is forwarded to gmpi_mpi_render_launch (the interleaved uint8 layout above: same kernels, same bits).
+ * gmpi_mpi_render_launch and every other entry keep refusing the layout for the float types (GMPI_E_STRIDE).  Not built for the layout: backward,
+ * chunked, shaded, shared-colour and depth-alpha forms, the strip and band kernels, texel strides other than 4.  gmpi_query(42) == 1 says the two
+ * entries are built in.
+ */
+int gmpi_mpi_render_layers_launch(const GmpiRenderParams *params, void *stream);
+
+/* 1: GMPI_VARIANT_LDS of gmpi_mpi_render_layers_launch can stage these layers, 0: it cannot (AUTO runs GATHER, an explicit LDS is GMPI_E_VARIANT),
+ * < 0: the error the launch would return for the struct.  The rule: every 16-byte loader item is a run of naturally aligned dwords that does not
+ * straddle the texture's border --
+ *   fp32    one texel per item: any Wt; the element's alignment is dword alignment, nothing more is asked;
+ *   16-bit  two texels per item: Wt even, and the base pointer and the row, plane and MPI strides multiples of 4 bytes (2 elements);
+ * and the byte offsets inside one staged box stay below 2^31: 33 rows of s_row bytes + 1152.  GMPI_DTYPE_U8: the rule of the interleaved uint8
+ * layout (gmpi_mpi_render_launch).  Launches nothing. */
+int gmpi_render_layers_supports(const GmpiRenderParams *params);
+
+/*
  * Gradient of the render w.r.t. the RGBA volume -- what autograd computes when the reference's G-step
  * back-propagates through MPIRenderer.render (gmpi/train.py:740-779; the sampling grid carries no gradient,
  * mpi.py:65).  `params` are the forward's parameters; rgb_out / depth_out may be NULL; transmittance_out, when not
@@ -758,7 +790,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * and depth-alpha layouts (gmpi_mpi_render_shared_backward_gather_launch, gmpi_mpi_render_depth_backward_gather_launch) is built in; 35 is unused (-1); 36 whether the plane-chunked render (gmpi_mpi_render_chunk_launch,
  * gmpi_mpi_render_chunk_backward_launch) is built in; 37 is unused (-1); 38 whether the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch,
  * gmpi_mpi_render_shaded_backward_launch) is built in; 39 is unused (-1); 40 whether the gradient w.r.t. plane_z of the depth-alpha layout
- * (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in.  Unknown -> -1.  */
+ * (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in; 41 is unused (-1); 42 whether channels-last float layers
+ * (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

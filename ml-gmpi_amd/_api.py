@@ -9,6 +9,7 @@ from .shared_color import expand_shared_color, split_shared_color
 from .shaded import apply_shading
 from .depth_alpha import depth_alpha_bounds, depth_alpha_planes, expand_depth_alpha
 from .quantized import quantize_volume, dequantize_volume, layers_as_volume, volume_as_layers
+from .layers import is_float_layers
 
 __all__ = [
     "GmpiError", "build_extension", "library_path", "load_library",
@@ -18,4 +19,5 @@ __all__ = [
     "apply_shading",
     "depth_alpha_bounds", "depth_alpha_planes", "expand_depth_alpha",
     "quantize_volume", "dequantize_volume", "layers_as_volume", "volume_as_layers",
+    "is_float_layers",
 ]

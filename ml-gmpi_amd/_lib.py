@@ -34,6 +34,8 @@ EXPORTS = (
     "gmpi_mpi_render_geometry_backward_ex_launch",
     "gmpi_mpi_render_chunk_launch",
     "gmpi_mpi_render_chunk_backward_launch",
+    "gmpi_mpi_render_layers_launch",
+    "gmpi_render_layers_supports",
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
@@ -77,7 +79,7 @@ _ERRORS = {
     -1: "GMPI_E_NULL (required pointer is NULL)",
     -2: "GMPI_E_SHAPE (non-positive or inconsistent extent, or more than 65535 views for the gather kernel / the backward)",
     -3: "GMPI_E_DTYPE (unknown rgba dtype, or uint8 storage handed to an entry other than the forward render)",
-    -4: "GMPI_E_STRIDE (innermost rgba stride must be 1 -- or 4 with channel stride 1 for interleaved uint8 texels in the forward render --, strides non-negative)",
+    -4: "GMPI_E_STRIDE (innermost rgba stride must be 1 -- or 4 with channel stride 1 for interleaved uint8 texels in the forward render, or for float layers at gmpi_mpi_render_layers_launch --, strides non-negative)",
     -5: "GMPI_E_ABI (GmpiRenderParams size mismatch between binding and library)",
     -6: "GMPI_E_VARIANT (requested kernel variant cannot run this shape)",
     -7: "GMPI_E_FLAGS (undefined bit in GmpiRenderParams.flags)",
@@ -240,6 +242,11 @@ def load_library():
     lib.gmpi_mpi_render_chunk_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_chunk_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp,
                                                           ctypes.POINTER(ctypes.c_int64), vp]
+    # channels-last float layers [M,D,Ht,Wt,4] in place (rgba_stride [s_M, s_D, 1, s_row, 4]; gmpi_query(42)): the launch, and whether its staged kernel takes the tensors
+    lib.gmpi_mpi_render_layers_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_layers_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp]
+    lib.gmpi_render_layers_supports.restype = ctypes.c_int
+    lib.gmpi_render_layers_supports.argtypes = [ctypes.POINTER(GmpiRenderParams)]
     lib.gmpi_mpi_render_shared_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp]
     i64p = ctypes.POINTER(ctypes.c_int64)

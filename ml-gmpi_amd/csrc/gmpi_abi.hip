@@ -61,6 +61,9 @@ int depth_window_query(int what);                                           // r
 hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
 bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
 int u8_variant_query(int what);                                             // render_u8.hip
+hipError_t launch_gather_layers(const KParams& p, int dtype, hipStream_t stream);   // render_gather.hip
+hipError_t launch_layers(const KParams& p, int dtype, hipStream_t stream);  // render_layers.hip
+bool layers_variant_supports(const KParams& p, int dtype);                  // render_layers.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
@@ -363,6 +366,25 @@ static bool auto_takes_band(const KParams& p, int dtype) {
 
 static int hip_rc(hipError_t e) { return e == hipSuccess ? GMPI_OK : GMPI_E_LAUNCH - static_cast<int>(e); }
 
+// Channels-last layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports): rgba_stride = [s_M, s_D, 1, s_row, 4] in elements, s_row >= 4 Wt, s_M and
+// s_D >= 0.  Anything else is GMPI_E_STRIDE, before any other field is looked at.
+static int layers_strides_ok(const GmpiRenderParams* q) {
+    if (q->rgba_stride[2] != 1 || q->rgba_stride[4] != 4) return GMPI_E_STRIDE;
+    if (q->rgba_stride[0] < 0 || q->rgba_stride[1] < 0 || q->rgba_stride[3] < 4 * static_cast<int64_t>(q->Wt)) return GMPI_E_STRIDE;
+    return GMPI_OK;
+}
+// The float layers of *q as the texel instances read them: everything but the strides validated by to_kparams (over a planar stand-in for them), the strides
+// in BYTES, s_chan unused.  GMPI_DTYPE_U8 does not come here: the callers forward it to the entries that have the type.
+static int to_kparams_layers(const GmpiRenderParams* q, KParams& p) {
+    GmpiRenderParams planar = *q;
+    planar.rgba_stride[0] = planar.rgba_stride[1] = planar.rgba_stride[2] = 1, planar.rgba_stride[3] = q->Wt, planar.rgba_stride[4] = 1;
+    const int rc = to_kparams(&planar, p, true);
+    if (rc != GMPI_OK) return rc;
+    const int64_t esize = q->rgba_dtype == GMPI_DTYPE_F32 ? 4 : 2;
+    p.s_mpi = q->rgba_stride[0] * esize, p.s_plane = q->rgba_stride[1] * esize, p.s_row = q->rgba_stride[3] * esize, p.s_chan = 0;
+    return GMPI_OK;
+}
+
 }  // namespace gmpi
 
 using namespace gmpi;
@@ -461,6 +483,44 @@ int gmpi_mpi_render_launch(const GmpiRenderParams* params, void* stream) {
     // (GMPI_VARIANT_DMA -- round 3's LDS-DMA loader inside the 32 x 16 tile decomposition, the A/B that separated the loader from the
     //  decomposition -- was retired in round 4: the band kernel is that loader's home.  The value stays reserved and is refused.)
     return GMPI_E_VARIANT;
+}
+
+int gmpi_render_layers_supports(const GmpiRenderParams* params) {
+    if (params == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    const int rs = layers_strides_ok(params);
+    if (rs != GMPI_OK) return rs;
+    KParams p;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) {   // the existing uint8 path's rule
+        const int rc = to_kparams(params, p, true, false, true);
+        return rc != GMPI_OK ? rc : (u8_variant_supports(p) ? 1 : 0);
+    }
+    const int rc = to_kparams_layers(params, p);
+    return rc != GMPI_OK ? rc : (layers_variant_supports(p, params->rgba_dtype) ? 1 : 0);
+}
+
+int gmpi_mpi_render_layers_launch(const GmpiRenderParams* params, void* stream) {
+    if (params == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    if (params->N == 0) return GMPI_OK;  // no views
+    const int rs = layers_strides_ok(params);
+    if (rs != GMPI_OK) return rs;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) return gmpi_mpi_render_launch(params, stream);   // channels-last codes: the kernels that exist, the same bits
+    KParams p;
+    const int rc = to_kparams_layers(params, p);
+    if (rc != GMPI_OK) return rc;
+    int variant = params->variant;
+    if (variant != GMPI_VARIANT_AUTO && variant != GMPI_VARIANT_GATHER && variant != GMPI_VARIANT_LDS) return GMPI_E_VARIANT;   // WAVE, BAND, DMA: not built for the layout
+    // AUTO is the staged kernel wherever it can take the tensors: no threshold, the camera hints change nothing, no workspace
+    const bool staged = layers_variant_supports(p, params->rgba_dtype);
+    if (variant == GMPI_VARIANT_AUTO) variant = staged ? GMPI_VARIANT_LDS : GMPI_VARIANT_GATHER;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (variant == GMPI_VARIANT_GATHER) {
+        if (p.N > 65535) return GMPI_E_SHAPE;  // the gather kernel puts the view index in grid.z
+        return hip_rc(launch_gather_layers(p, params->rgba_dtype, st));
+    }
+    if (!staged) return GMPI_E_VARIANT;   // LDS by name over tensors its 16-byte items cannot take
+    return hip_rc(launch_layers(p, params->rgba_dtype, st));
 }
 
 uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams* params) {
@@ -1081,6 +1141,7 @@ int gmpi_query(int32_t what) {
         case 34: return 1;  // the atomics-free backward of the shared-colour and depth-alpha layouts (gmpi_mpi_render_*_backward_gather_launch) is built in  (33: unused)
         case 38: return 1;  // the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch, gmpi_mpi_render_shaded_backward_launch) is built in  (37: unused)
         case 40: return 1;  // the gradient w.r.t. plane_z of the depth-alpha layout (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in  (39: unused)
+        case 42: return 1;  // channels-last float layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in  (41: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -35,7 +35,7 @@ struct KParams {
     float* depth_out;
     float* T_out;
     uint32_t* status;
-    int64_t s_mpi, s_plane, s_chan, s_row;  // element strides of rgba [M,D,4,Ht,Wt] (col stride 1; rgba8_t instances: bytes, texel stride 4, s_chan unused)
+    int64_t s_mpi, s_plane, s_chan, s_row;  // element strides of rgba [M,D,4,Ht,Wt] (col stride 1; rgba8_t and float-texel instances: bytes, texel stride 4 elements, s_chan unused)
     int32_t N, M, D, Ht, Wt, H, W, views_per_mpi;
     uint32_t flags;
     void* ws;           // caller's workspace (GmpiRenderParams.workspace): the band kernel's geometry table
@@ -132,8 +132,23 @@ __device__ __forceinline__ float to_f32(u8_t v) { return unorm8_to_f32(static_ca
 // its own, so that no other instance carries a texel stride.  The strides of such a volume count BYTES (tex_offset); alignment 1: a base pointer may
 // sit at any byte.
 struct rgba8_t { uint8_t c[4]; };
+// Channels-last FLOAT layers (gmpi_mpi_render_layers_launch: [M,D,Ht,Wt,4], channel stride 1, texel stride 4 elements): one texel = R, G, B, A of the
+// element type, 16 bytes of fp32 or 8 bytes of 16-bit storage.  Storage types of their own, as rgba8_t: the instances over them learn the layout from
+// the template argument, KParams carries no texel stride and no other instance changes.  Their strides count BYTES (tex_offset; the launcher
+// converts the struct's element strides), s_chan is unused.  Alignment: the element's -- a texel may start at any element (a column slice).
+struct rgba32f_t { float c[4]; };
+struct rgba16h_t { f16_t c[4]; };
+struct rgba16b_t { bf16_t c[4]; };
+template <typename TexT> struct FloatTexel { static constexpr bool value = false; };
+template <> struct FloatTexel<rgba32f_t> { static constexpr bool value = true; using elem = float; };
+template <> struct FloatTexel<rgba16h_t> { static constexpr bool value = true; using elem = f16_t; };
+template <> struct FloatTexel<rgba16b_t> { static constexpr bool value = true; using elem = bf16_t; };
+template <typename TexT> constexpr bool is_float_texel = FloatTexel<TexT>::value;
 template <typename TexT>
-__device__ __forceinline__ const TexT* tex_offset(const TexT* p, int64_t n) { return p + n; }
+__device__ __forceinline__ const TexT* tex_offset(const TexT* p, int64_t n) {
+    if constexpr (is_float_texel<TexT>) return reinterpret_cast<const TexT*>(reinterpret_cast<const uint8_t*>(p) + n);
+    else return p + n;
+}
 __device__ __forceinline__ const rgba8_t* tex_offset(const rgba8_t* p, int64_t n) {
     return reinterpret_cast<const rgba8_t*>(reinterpret_cast<const uint8_t*>(p) + n);
 }
@@ -144,6 +159,15 @@ __device__ __forceinline__ uint32_t load_texel(const rgba8_t* p, int64_t byte_of
     return t;
 }
 __device__ __forceinline__ float texel_code(uint32_t t, int c) { return static_cast<float>((t >> (8 * c)) & 0xffu); }   // v_cvt_f32_ubyte<c>: exact
+
+// One whole texel in a single load (global_load_dwordx4 / dwordx2) at the ELEMENT's alignment: the memcpy from an element pointer says so.
+template <typename TexT, std::enable_if_t<is_float_texel<TexT>, int> = 0>
+__device__ __forceinline__ TexT load_texel(const TexT* p, int64_t byte_off) {
+    using E = typename FloatTexel<TexT>::elem;
+    TexT t;
+    __builtin_memcpy(&t, __builtin_assume_aligned(reinterpret_cast<const uint8_t*>(p) + byte_off, alignof(E)), sizeof(TexT));
+    return t;
+}
 
 // Host side: a run-time dtype (GMPI_DTYPE_F32 / _BF16 / _F16 = 0 / 1 / 2, validated by the C ABI) or flag picks the template instance.
 // f is a generic lambda: it gets TypeTag<float | bf16_t | f16_t>{} (storage type: `typename decltype(t)::type`), resp. std::true_type{} /
@@ -378,6 +402,16 @@ __device__ __forceinline__ void gather_sample(const TexT* __restrict__ pl, int64
         for (int c = 0; c < 4; ++c)   // to_f32(u8_t) per tap, as the planar instance: the same bits
             smp[c] = bilerp<STRICT>(unorm8_to_f32(texel_code(t_nw, c)), unorm8_to_f32(texel_code(t_ne, c)), unorm8_to_f32(texel_code(t_sw, c)),
                                     unorm8_to_f32(texel_code(t_se, c)), f);
+    } else if constexpr (is_float_texel<TexT>) {   // float layers: one load per tap of the whole texel, then the planar instance's arithmetic per channel
+        constexpr int64_t kTexel = sizeof(TexT);
+        const TexT t_nw = load_texel(pl, oa + kTexel * xa), t_ne = load_texel(pl, oa + kTexel * xb);
+        const TexT t_sw = load_texel(pl, ob + kTexel * xa), t_se = load_texel(pl, ob + kTexel * xb);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float c_nw = to_f32(t_nw.c[c]), c_ne = to_f32(t_ne.c[c]), c_sw = to_f32(t_sw.c[c]), c_se = to_f32(t_se.c[c]);
+            if (check_range && !(in_unit(c_nw) && in_unit(c_ne) && in_unit(c_sw) && in_unit(c_se))) bad |= GMPI_STATUS_RGBA_RANGE;
+            smp[c] = bilerp<STRICT>(c_nw, c_ne, c_sw, c_se, f);
+        }
     } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {

@@ -78,4 +78,24 @@ static hipError_t launch_gather_any(const KParams& p, const CarryK* carry, int d
 hipError_t launch_gather(const KParams& p, int dtype, hipStream_t stream) { return launch_gather_any(p, nullptr, dtype, stream); }
 hipError_t launch_gather_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream) { return launch_gather_any(p, &carry, dtype, stream); }
 
+// Channels-last float layers (gmpi_mpi_render_layers_launch): the instances over the texel types of gmpi_device.hpp -- one load per tap, the planar
+// instance's arithmetic behind it, hence its bits in both modes.  p's strides count bytes.  One-shot only: the layout has no chunked form.
+template <typename TexT>
+static hipError_t launch_gather_layers_t(const KParams& p, hipStream_t stream) {
+    const dim3 block(kGatherTileW, kGatherTileH);
+    const dim3 grid((p.W + kGatherTileW - 1) / kGatherTileW, (p.H + kGatherTileH - 1) / kGatherTileH, p.N);
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        hipLaunchKernelGGL((render_gather_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value>), grid, block, 0, stream, p);
+    });
+    return hipGetLastError();
+}
+hipError_t launch_gather_layers(const KParams& p, int dtype, hipStream_t stream) {
+    switch (dtype) {
+        case GMPI_DTYPE_F32: return launch_gather_layers_t<rgba32f_t>(p, stream);
+        case GMPI_DTYPE_F16: return launch_gather_layers_t<rgba16h_t>(p, stream);
+        case GMPI_DTYPE_BF16: return launch_gather_layers_t<rgba16b_t>(p, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace gmpi

@@ -188,6 +188,20 @@ class ViewBatchDriver:
         return self._render_path(launch, mpi_rgbas.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
 
     @torch.no_grad()
+    def render_path_layers(self, layers: torch.Tensor, render_size: int, yaws: Sequence[float], pitches: Sequence[float],
+                           indices: Optional[Sequence[int]] = None, to_uint8: bool = False, depth_range=None, want_transmittance: bool = False,
+                           to_host: bool = False, variant: Optional[str] = None):
+        """`render_path` of ONE MPI held as channels-last float layers [1,D,Ht,Wt,4] (fp32 / bf16 / fp16; `MPI.render_views_layers`), read in place: the
+        same grouping of poses and rays, single status read-back, uint8 epilogue, second-stream copies and returned dict as `render_path` of the
+        planar volume `layers.permute(0, 1, 4, 2, 3)`.  `variant`: "auto", "gather", "lds" or None = the renderer's own."""
+        assert layers.ndim == 5 and layers.shape[4] == 4 and layers.shape[0] == 1, "render_path_layers draws many views of one MPI [1,D,Ht,Wt,4]"
+        r = self.renderer
+
+        def launch(dhw, ray, eye, zd, **kw):
+            r.mpi.render_views_layers(layers, dhw, ray, eye, zd, variant=variant, **kw)
+        return self._render_path(launch, layers.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
+
+    @torch.no_grad()
     def render_path_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, render_size: int, yaws: Sequence[float], pitches: Sequence[float],
                            background: Optional[torch.Tensor] = None, indices: Optional[Sequence[int]] = None, to_uint8: bool = False,
                            depth_range=None, want_transmittance: bool = False, to_host: bool = False, variant: Optional[str] = "lds"):
@@ -298,6 +312,14 @@ class ViewBatchDriver:
         def render(s):
             return self.renderer.render(mpi_rgbas[s:s + self.batch], render_size, render_size, views_per_mpi=views_per_mpi, **render_kwargs)
         return self._render_seeds(render, mpi_rgbas.shape[0], render_kwargs)
+
+    @torch.no_grad()
+    def render_seeds_layers(self, layers: torch.Tensor, render_size: int, views_per_mpi: int = 1, variant: Optional[str] = None, **render_kwargs):
+        """`render_seeds` of a stack of MPIs held as channels-last float layers [B,D,Ht,Wt,4], through `MPIRenderer.render_layers`, `batch` MPIs per
+        launch, read in place: the poses, the returned 4-tuple and the consumption of the torch RNG of `render_seeds` on the planar volume."""
+        def render(s):
+            return self.renderer.render_layers(layers[s:s + self.batch], render_size, render_size, variant=variant, views_per_mpi=views_per_mpi, **render_kwargs)
+        return self._render_seeds(render, layers.shape[0], render_kwargs)
 
     @torch.no_grad()
     def render_seeds_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, render_size: int, background: Optional[torch.Tensor] = None,
