@@ -208,9 +208,9 @@ int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
  *   GMPI_VARIANT_AUTO    LDS where gmpi_render_layers_supports() says 1, else GATHER.
  *   WAVE, BAND, DMA and unknown values: GMPI_E_VARIANT.
  * GMPI_DTYPE_U8 with these strides is forwarded to gmpi_mpi_render_launch (the interleaved uint8 layout above: same kernels, same bits).
- * gmpi_mpi_render_launch and every other entry keep refusing the layout for the float types (GMPI_E_STRIDE).  Not built for the layout: backward,
- * chunked, shaded, shared-colour and depth-alpha forms, the strip and band kernels, texel strides other than 4.  gmpi_query(42) == 1 says the two
- * entries are built in.
+ * gmpi_mpi_render_launch and every other entry but gmpi_mpi_render_layers_backward_launch (below) keep refusing the layout for the float types
+ * (GMPI_E_STRIDE).  Not built for the layout: the atomics-free backward pair, geometry gradients, the chunked, shaded, shared-colour and depth-alpha
+ * forms, the strip and band kernels, texel strides other than 4.  gmpi_query(42) == 1 says the two entries are built in.
  */
 int gmpi_mpi_render_layers_launch(const GmpiRenderParams *params, void *stream);
 
@@ -222,6 +222,34 @@ int gmpi_mpi_render_layers_launch(const GmpiRenderParams *params, void *stream);
  * and the byte offsets inside one staged box stay below 2^31: 33 rows of s_row bytes + 1152.  GMPI_DTYPE_U8: the rule of the interleaved uint8
  * layout (gmpi_mpi_render_launch).  Launches nothing. */
 int gmpi_render_layers_supports(const GmpiRenderParams *params);
+
+/*
+ * Gradient of gmpi_mpi_render_layers_launch w.r.t. the float layers, IN PLACE: the layers are read where they lie and the gradient has their order --
+ * no planar copy of either.  `params` describe the layers exactly as gmpi_mpi_render_layers_launch takes them (rgba_stride [s_M, s_D, 1, s_row, 4],
+ * rgba_dtype F32 / BF16 / F16; planar or any other strides: GMPI_E_STRIDE; GMPI_DTYPE_U8: GMPI_E_DTYPE -- no gradient flows to codes); rgb_out,
+ * depth_out and status may be NULL; transmittance_out, GMPI_FLAG_OUT_PM1, view_to_mpi / views_per_mpi, grad_rgb, grad_depth (or NULL) and
+ * grad_transmittance (or NULL) mean what they mean for gmpi_mpi_render_backward_ex_launch.  grad_layers is fp32 [M, D, Ht, Wt, 4] and is ACCUMULATED
+ * into (the caller zero-fills it); grad_layers_stride, in elements, is [gs_M, gs_D, 1, gs_row, 4] with gs_row >= 4 Wt, gs_D > 0 and gs_M > 0 (0 for
+ * M == 1) -- anything else is GMPI_E_STRIDE.  A NULL grad_rgb, grad_layers or grad_layers_stride is GMPI_E_NULL.  N == 0 returns GMPI_OK; N is not
+ * limited.  No workspace is read: the atomics-free pair has no texel form.  Two kernels, instances of the planar backward's two bodies over whole texels:
+ *   GMPI_VARIANT_GATHER  one pixel per lane: one whole-texel load per tap, the planar one-pixel kernel's arithmetic behind it, 16 fp32 atomics per
+ *                        pixel and plane at 64-bit offsets.  Any Wt, any such strides.
+ *   any other variant    the 64 x 8 tile kernel (the fixed-point scatter staged in LDS, as for the planar layout: for equal inputs the staged sums
+ *                        have the planar kernel's bits) where gmpi_render_layers_backward_supports() answers 1, else the one-pixel kernel -- the launch
+ *                        never fails for that reason.  A tap pair (x, x + 1) of a row is one run of 32 bytes (16 for 16-bit storage) loaded at the
+ *                        element's alignment; the flush walks box ROWS -- in the layers' order the 4 nx gradient dwords of a box row are contiguous
+ *                        -- with one atomic per dword, consecutive lanes on consecutive dwords.
+ * gmpi_query(44) == 1 says the two entries are built in.
+ */
+int gmpi_mpi_render_layers_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                           const float *grad_transmittance /* or NULL */, float *grad_layers,
+                                           const int64_t *grad_layers_stride /* [5], elements: [gs_M, gs_D, 1, gs_row, 4] */, void *stream);
+
+/* 1: gmpi_mpi_render_layers_backward_launch runs its tile kernel on these tensors (unless the variant is GATHER, which this query does not look at),
+ * 0: its one-pixel kernel, < 0: the error the launch would return for the struct and the gradient strides.  The tile kernel's guards: Wt >= 2 (pair
+ * loads); N <= 65535 (the view index in grid.y); the byte offsets inside one plane of the layers fit 31 bits, (Ht s_row + 4 Wt) x the element size
+ * < 2^31; the dword offsets inside one plane of the gradient do, Ht gs_row + 4 Wt < 2^31.  Launches nothing. */
+int gmpi_render_layers_backward_supports(const GmpiRenderParams *params, const int64_t *grad_layers_stride);
 
 /*
  * Gradient of the render w.r.t. the RGBA volume -- what autograd computes when the reference's G-step
@@ -791,7 +819,8 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * gmpi_mpi_render_chunk_backward_launch) is built in; 37 is unused (-1); 38 whether the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch,
  * gmpi_mpi_render_shaded_backward_launch) is built in; 39 is unused (-1); 40 whether the gradient w.r.t. plane_z of the depth-alpha layout
  * (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in; 41 is unused (-1); 42 whether channels-last float layers
- * (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in.  Unknown -> -1.  */
+ * (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in; 43 is unused (-1); 44 whether their in-place backward
+ * (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -36,6 +36,8 @@ EXPORTS = (
     "gmpi_mpi_render_chunk_backward_launch",
     "gmpi_mpi_render_layers_launch",
     "gmpi_render_layers_supports",
+    "gmpi_mpi_render_layers_backward_launch",
+    "gmpi_render_layers_backward_supports",
     "gmpi_mpi_render_shared_launch",
     "gmpi_mpi_render_shared_backward_launch",
     "gmpi_render_shared_supports",
@@ -247,6 +249,11 @@ def load_library():
     lib.gmpi_mpi_render_layers_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp]
     lib.gmpi_render_layers_supports.restype = ctypes.c_int
     lib.gmpi_render_layers_supports.argtypes = [ctypes.POINTER(GmpiRenderParams)]
+    # ... and their in-place backward (gmpi_query(44)): the fp32 gradient in the layers' order, strides [gs_M, gs_D, 1, gs_row, 4]; 1 = its tile kernel takes the tensors
+    lib.gmpi_mpi_render_layers_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_layers_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+    lib.gmpi_render_layers_backward_supports.restype = ctypes.c_int
+    lib.gmpi_render_layers_backward_supports.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(ctypes.c_int64)]
     lib.gmpi_mpi_render_shared_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_shared_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiSharedColor), vp]
     i64p = ctypes.POINTER(ctypes.c_int64)

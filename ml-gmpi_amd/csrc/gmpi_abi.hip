@@ -64,6 +64,9 @@ int u8_variant_query(int what);                                             // r
 hipError_t launch_gather_layers(const KParams& p, int dtype, hipStream_t stream);   // render_gather.hip
 hipError_t launch_layers(const KParams& p, int dtype, hipStream_t stream);  // render_layers.hip
 bool layers_variant_supports(const KParams& p, int dtype);                  // render_layers.hip
+hipError_t launch_backward_layers(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_layers, const int64_t* gstride,
+                                  bool tiles, hipStream_t stream);   // render_backward.hip
+bool backward_layers_tile_supports(const KParams& p, int dtype, const int64_t* gstride);   // render_backward.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
@@ -374,14 +377,31 @@ static int layers_strides_ok(const GmpiRenderParams* q) {
     return GMPI_OK;
 }
 // The float layers of *q as the texel instances read them: everything but the strides validated by to_kparams (over a planar stand-in for them), the strides
-// in BYTES, s_chan unused.  GMPI_DTYPE_U8 does not come here: the callers forward it to the entries that have the type.
-static int to_kparams_layers(const GmpiRenderParams* q, KParams& p) {
+// in BYTES, s_chan unused.  GMPI_DTYPE_U8 does not come here: the callers forward it to the entries that have the type (the backward refuses it).
+// backward: the layers' backward entries -- the volume is needed, the forward's outputs are not.
+static int to_kparams_layers(const GmpiRenderParams* q, KParams& p, bool backward = false) {
     GmpiRenderParams planar = *q;
     planar.rgba_stride[0] = planar.rgba_stride[1] = planar.rgba_stride[2] = 1, planar.rgba_stride[3] = q->Wt, planar.rgba_stride[4] = 1;
-    const int rc = to_kparams(&planar, p, true);
+    const int rc = to_kparams(&planar, p, !backward, backward);
     if (rc != GMPI_OK) return rc;
     const int64_t esize = q->rgba_dtype == GMPI_DTYPE_F32 ? 4 : 2;
     p.s_mpi = q->rgba_stride[0] * esize, p.s_plane = q->rgba_stride[1] * esize, p.s_row = q->rgba_stride[3] * esize, p.s_chan = 0;
+    return GMPI_OK;
+}
+// What gmpi_mpi_render_layers_backward_launch and gmpi_render_layers_backward_supports check alike, in this order: the struct, the layers' strides, the
+// type (float layers only), every other field, then the gradient's strides -- [gs_M, gs_D, 1, gs_row, 4] in elements, gs_row >= 4 Wt, gs_M and gs_D positive
+// (gs_M = 0 for one MPI).  Fills p (strides in bytes) on GMPI_OK.
+static int layers_backward_args(const GmpiRenderParams* q, const int64_t* gst, KParams& p) {
+    if (q == nullptr) return GMPI_E_NULL;
+    if (q->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    const int rs = layers_strides_ok(q);
+    if (rs != GMPI_OK) return rs;
+    if (q->rgba_dtype == GMPI_DTYPE_U8) return GMPI_E_DTYPE;   // no gradient flows to codes
+    const int rc = to_kparams_layers(q, p, true);
+    if (rc != GMPI_OK) return rc;
+    if (gst == nullptr) return GMPI_E_NULL;
+    if (gst[2] != 1 || gst[4] != 4 || gst[3] < 4 * static_cast<int64_t>(q->Wt)) return GMPI_E_STRIDE;
+    if (gst[1] <= 0 || (gst[0] <= 0 && !(gst[0] == 0 && q->M == 1))) return GMPI_E_STRIDE;
     return GMPI_OK;
 }
 
@@ -521,6 +541,24 @@ int gmpi_mpi_render_layers_launch(const GmpiRenderParams* params, void* stream) 
     }
     if (!staged) return GMPI_E_VARIANT;   // LDS by name over tensors its 16-byte items cannot take
     return hip_rc(launch_layers(p, params->rgba_dtype, st));
+}
+
+int gmpi_render_layers_backward_supports(const GmpiRenderParams* params, const int64_t* grad_layers_stride) {
+    KParams p;
+    const int rc = layers_backward_args(params, grad_layers_stride, p);
+    return rc != GMPI_OK ? rc : (backward_layers_tile_supports(p, params->rgba_dtype, grad_layers_stride) ? 1 : 0);
+}
+
+int gmpi_mpi_render_layers_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, const float* grad_transmittance,
+                                           float* grad_layers, const int64_t* grad_layers_stride, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;  // no views
+    KParams p;
+    const int rc = layers_backward_args(params, grad_layers_stride, p);
+    if (rc != GMPI_OK) return rc;
+    if (grad_rgb == nullptr || grad_layers == nullptr) return GMPI_E_NULL;
+    // GATHER: the one-pixel kernel; anything else: the 64 x 8 tile kernel where its guards allow (launch_backward_layers), else the one-pixel kernel
+    return hip_rc(launch_backward_layers(p, params->rgba_dtype, grad_rgb, grad_depth, grad_transmittance, grad_layers, grad_layers_stride,
+                                         params->variant != GMPI_VARIANT_GATHER, static_cast<hipStream_t>(stream)));
 }
 
 uint64_t gmpi_render_workspace_bytes(const GmpiRenderParams* params) {
@@ -1142,6 +1180,7 @@ int gmpi_query(int32_t what) {
         case 38: return 1;  // the shaded render of an RGBA volume (gmpi_mpi_render_shaded_launch, gmpi_mpi_render_shaded_backward_launch) is built in  (37: unused)
         case 40: return 1;  // the gradient w.r.t. plane_z of the depth-alpha layout (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in  (39: unused)
         case 42: return 1;  // channels-last float layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in  (41: unused)
+        case 44: return 1;  // the in-place backward of channels-last float layers (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in  (43: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -67,7 +67,7 @@ __device__ __forceinline__ XT total_transmittance(const KParams& p, const float*
         float ix, iy, s, u, v;
         plane_coord<AC>(dhw[3 * k] - ez, dhw[3 * k + 1], dhw[3 * k + 2], ex, ey, rx, ry, rz, cx, cy, ix, iy, s, u, v);
         float smp[4];
-        gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, false, unused, smp);
+        gather_sample<TexT, false>(tex_offset(vol, static_cast<int64_t>(k) * p.s_plane), p.s_chan, p.s_row, p.Ht, p.Wt, ix, iy, false, unused, smp);
         t.m *= (1.0f - smp[3]) + 1e-10f;
         t.renorm();
     }
@@ -236,6 +236,38 @@ __device__ __forceinline__ void fetch_pair_taps(PairTaps& q, const TexT* __restr
         load_pair<TexT>(pl, oa + c4 * s_chan_b, q.v[4 * c4 + 0], q.v[4 * c4 + 1]);
         load_pair<TexT>(pl, ob + c4 * s_chan_b, q.v[4 * c4 + 2], q.v[4 * c4 + 3]);
     }
+}
+// The same taps of channels-last float layers (rgba32f_t / rgba16h_t / rgba16b_t, gmpi_device.hpp; the texel instances of render_backward.hip): the pair
+// (x, x + 1) of a row is two whole texels side by side -- ONE run of 32 bytes of fp32 (two 16-byte loads) or 16 bytes of 16-bit storage (one), loaded at
+// the ELEMENT's alignment (a column slice may start a texel at any element), 32-bit offsets from a uniform base (the launcher checks Wt >= 2 and
+// layers_offsets_fit_32).  Clamps, and hence the re-assigned border weights of pair_samples, are fetch_pair_taps'; the taps land in q.v in its order.
+// plane: texel (0, 0) of the plane; the row stride in bytes.
+template <typename TexT>
+__device__ __forceinline__ void fetch_texel_pair_taps(PairTaps& q, const TexT* __restrict__ plane, uint32_t s_row_b, int Ht, int Wt) {
+    using E = typename FloatTexel<TexT>::elem;
+    constexpr uint32_t kTexel = sizeof(TexT);
+    struct Pair { TexT t[2]; };
+    const int xa = min(max(q.x0, 0), Wt - 2);
+    const int ya = min(max(q.y0, 0), Ht - 1), yb = min(max(q.y0 + 1, 0), Ht - 1);
+    const unsigned char* __restrict__ pl = reinterpret_cast<const unsigned char*>(plane);
+    const uint32_t oa = static_cast<uint32_t>(ya) * s_row_b + static_cast<uint32_t>(xa) * kTexel;
+    const uint32_t ob = static_cast<uint32_t>(yb) * s_row_b + static_cast<uint32_t>(xa) * kTexel;
+    Pair top, bot;
+    __builtin_memcpy(&top, __builtin_assume_aligned(pl + oa, alignof(E)), sizeof(Pair));
+    __builtin_memcpy(&bot, __builtin_assume_aligned(pl + ob, alignof(E)), sizeof(Pair));
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        q.v[4 * c4 + 0] = to_f32(top.t[0].c[c4]), q.v[4 * c4 + 1] = to_f32(top.t[1].c[c4]);
+        q.v[4 * c4 + 2] = to_f32(bot.t[0].c[c4]), q.v[4 * c4 + 3] = to_f32(bot.t[1].c[c4]);
+    }
+}
+// Host side, the texel twin of plane_offsets_fit_32: do all offsets inside one plane of [.., Ht, Wt, 4] layers -- Ht rows of s_row + Wt texels of 4 items,
+// items of `es` bytes -- fit 31 bits?  (the layers: s_row in ELEMENTS, es = the element size; their fp32 gradient, whose offsets count dwords: es = 1)
+inline bool layers_offsets_fit_32(int64_t s_row, int Ht, int Wt, int es) {
+    if (s_row < 0) return false;
+    const int64_t lim = (int64_t(1) << 31) / es;
+    if (s_row >= lim) return false;
+    return static_cast<int64_t>(Ht) * s_row + 4 * static_cast<int64_t>(Wt) < lim;
 }
 // The Shade policy's pair-load form (NoShade / ShadeK / shade_texel: gmpi_device.hpp), next to fetch_pair_taps: the two pair loads of the shading image
 // at the footprint's rows and columns (fetch_pair_taps' addresses), then the multiply and clip of q.v[0..11].  sh: the MPI's shading image, row stride

@@ -29,16 +29,21 @@ namespace gmpi {
 // A third instance of the one-pixel body and of the 64 x 8 tile body: Shade = ShadeK (gmpi_backward.hpp), the *_shaded_kernel twins of the shaded render
 // (gmpi_mpi_render_shaded_backward_launch) -- the colour taps are shaded as its forward shades them, so what is scattered is the gradient w.r.t. the
 // SHADED texels; the chain rule through the clip follows in place (render_shaded.hip).  NoShade, the default, compiles to the kernels of old.
+// A fourth instance of the one-pixel body and of the 64 x 8 tile body: TexT = rgba32f_t / rgba16b_t / rgba16h_t (gmpi_device.hpp), the *_layers_kernel twins
+// of gmpi_mpi_render_layers_backward_launch -- channels-last float layers read where they lie (whole-texel loads, strides in bytes: tex_offset), the gradient
+// accumulated in the layers' own order (kGX = 4 dwords from a texel to its right neighbour, BwdParams::gs_chan = 1).  The arithmetic behind the loads is the
+// planar instances'.  n0 (these twins only): the first view of the launch -- a batch of more than 65535 views is launched in pieces.
 template <typename TexT, bool AC, bool CHUNK, typename Shade = NoShade>
-__device__ __forceinline__ void render_backward_pixel(const KParams& p, const BwdParams& b, const Shade& shade = Shade{}) {
+__device__ __forceinline__ void render_backward_pixel(const KParams& p, const BwdParams& b, const Shade& shade = Shade{}, const int n0 = 0) {
     constexpr bool SHADED = !std::is_same_v<Shade, NoShade>;
-    const int n = blockIdx.z;
+    constexpr int kGX = is_float_texel<TexT> ? 4 : 1;   // gradient items between horizontal neighbours
+    const int n = blockIdx.z + n0;
     const int px = blockIdx.x * 64 + threadIdx.x;
     const int py = blockIdx.y * 4 + threadIdx.y;
     if (px >= p.W || py >= p.H) return;
     const BwdView vw = bwd_view<AC>(p, n);
     const int Ht = p.Ht, Wt = p.Wt;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
     float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
     BwdPixel bp;
     bwd_pixel_setup<TexT, AC, false>(bp, p, vw, n, px, py, true, b.g_rgb, b.g_depth, b.g_T, vol, CHUNK ? b.T_in : nullptr, CHUNK ? b.S_in : nullptr);
@@ -53,22 +58,22 @@ __device__ __forceinline__ void render_backward_pixel(const KParams& p, const Bw
             shaded_gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, shade.s + static_cast<int64_t>(vw.m) * shade.s_mpi,
                                               shade.s_row, Ht, Wt, ix, iy, false, unused, smp);
         else
-            gather_sample<TexT, false>(vol + static_cast<int64_t>(k) * p.s_plane, p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
+            gather_sample<TexT, false>(tex_offset(vol, static_cast<int64_t>(k) * p.s_plane), p.s_chan, p.s_row, Ht, Wt, ix, iy, false, unused, smp);
         bp.plane(smp, s, d_s);
 
         Footprint f = footprint(ix, iy, Ht, Wt);
         const bool x0in = f.x0 >= 0 && f.x0 <= Wt - 1, x1in = f.x0 >= -1 && f.x0 <= Wt - 2;
         const bool y0in = f.y0 >= 0 && f.y0 <= Ht - 1, y1in = f.y0 >= -1 && f.y0 <= Ht - 2;
         float* __restrict__ gp = gvol + static_cast<int64_t>(k) * b.gs_plane;
-        const int64_t oa = static_cast<int64_t>(f.y0) * b.gs_row + f.x0, ob = oa + b.gs_row;
+        const int64_t oa = static_cast<int64_t>(f.y0) * b.gs_row + static_cast<int64_t>(f.x0) * kGX, ob = oa + b.gs_row;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float* __restrict__ gc = gp + c * b.gs_chan;
             const float d = d_s[c];
             if (x0in && y0in) atomicAdd(gc + oa, d * f.nw);
-            if (x1in && y0in) atomicAdd(gc + oa + 1, d * f.ne);
+            if (x1in && y0in) atomicAdd(gc + oa + kGX, d * f.ne);
             if (x0in && y1in) atomicAdd(gc + ob, d * f.sw);
-            if (x1in && y1in) atomicAdd(gc + ob + 1, d * f.se);
+            if (x1in && y1in) atomicAdd(gc + ob + kGX, d * f.se);
         }
     }
     if constexpr (CHUNK) bwd_store_suffix(b, bp, n, vw.HW, true);
@@ -84,6 +89,11 @@ __global__ __launch_bounds__(256) void render_backward_chunk_kernel(const KParam
 template <typename TexT, bool AC>
 __global__ __launch_bounds__(256) void render_backward_shaded_kernel(const KParams p, const BwdParams b, const ShadeK shade) {
     render_backward_pixel<TexT, AC, false>(p, b, shade);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(256) void render_backward_layers_kernel(const KParams p, const BwdParams b, const int n0) {
+    static_assert(is_float_texel<TexT>, "the texel instances");
+    render_backward_pixel<TexT, AC, false>(p, b, NoShade{}, n0);
 }
 
 // The shaded render's backward when ONLY the shading wants a gradient (gmpi_mpi_render_shaded_backward_launch with grad_rgba == NULL): no volume-sized
@@ -327,7 +337,13 @@ template <int TW_, int TH_, int PITCH_, int ROWS_> struct B2Geo {
 };
 using B2Tall = B2Geo<32, 16, 56, 27>;   // 23.6 KB per box
 using B2Wide = B2Geo<64, 8, 80, 19>;    // 23.8 KB per box
-constexpr int kBwdDefaultGeo = 2;       // 1 = 32 x 16 tiles (round 5) | 2 = 64 x 8 tiles (profiles/r06_backward.txt)
+// The texel instances' 64 x 8 tiles (float layers, the row flush): B2Wide with a box pitch of 88.  The row flush reads channel l & 3 of texel l >> 2: at pitch 80
+// (= 16 mod 32) channels 0 / 2 and 1 / 3 of a 32-lane half meet in the same banks (ds_read_b32: bank (a / 4) mod 32), a 2-way conflict on the kernel's
+// critical path; a pitch of 8 or 24 mod 32 is conflict-free.  88, not 72: it stages every box B2Wide stages (72 would send boxes 73..80 texels wide down
+// the cold scatter), and its 56.75 KB per workgroup cost no occupancy -- a workgroup is 12 waves, so the CU's 32 wave slots (and the 80-VGPR launch
+// bound: 6 waves per SIMD) hold two workgroups whatever the LDS says, and two fit 160 KB at either pitch.  (No SQ_LDS_BANK_CONFLICT count was taken.)
+using B2Texel = B2Geo<64, 8, 88, 19>;   // 26.1 KB per box
+constexpr int kBwdDefaultGeo = 2;      // 1 = 32 x 16 tiles (round 5) | 2 = 64 x 8 tiles (profiles/r06_backward.txt)
 
 template <typename TexT, bool AC, typename G, bool CHUNK, typename Shade = NoShade>
 __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, const BwdParams& b, const int tiles_x, const Shade& shade = Shade{}) {
@@ -342,7 +358,14 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
     __shared__ uint32_t lds_pad[GMPI_B2_PAD / 4];
     lds_pad[threadIdx.x] = 0u;
 #endif
-    constexpr int kES = static_cast<int>(sizeof(TexT));
+    // TEXEL (the *_layers_tile_kernel twins: channels-last float layers, G = B2Texel): p's strides count bytes already, a tap pair is one run of two whole
+    // texels (fetch_texel_pair_taps), the gradient has the layers' order -- kGX dwords between horizontal neighbours, gs_chan = 1 -- and the flush walks box
+    // ROWS (the TEXEL branch of flush below).  Everything else -- the pixel waves' arithmetic, the fixed-point scatter into the [row][channel][x] box, the scale rules, the
+    // wide cells, the barriers -- is the one text of all instances.
+    constexpr bool TEXEL = is_float_texel<TexT>;
+    static_assert(!(TEXEL && (CHUNK || SHADED)), "the texel instances have no chunk and no shaded form");
+    constexpr int kES = TEXEL ? 1 : static_cast<int>(sizeof(TexT));
+    constexpr int kGX = TEXEL ? 4 : 1;
     const int tid = threadIdx.x;
     // the role of a WAVE (kB2Pix is a multiple of 64), as a scalar: the two roles run separate loop nests behind a scalar branch -- as
     // divergent control flow the compiler would serialise both bodies in every wave and order the flush's atomics against the taps' loads
@@ -369,7 +392,7 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
     constexpr bool abl_noglobal = false, abl_nolds = false, abl_notaps = false;
 #endif
     const int Ht = p.Ht, Wt = p.Wt;
-    const TexT* __restrict__ vol = static_cast<const TexT*>(p.rgba) + static_cast<int64_t>(vw.m) * p.s_mpi;
+    const TexT* __restrict__ vol = tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi);
     float* __restrict__ gvol = b.g_rgba + static_cast<int64_t>(vw.m) * b.gs_mpi;
     // (the launcher has checked that a plane's byte offsets fit 32 bits, for the volume and for its gradient)
     const uint32_t s_chan_b = static_cast<uint32_t>(p.s_chan) * kES, s_row_b = static_cast<uint32_t>(p.s_row) * kES;
@@ -390,7 +413,8 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
         float ix, iy;
         pair_tap_coord<AC>(q, bp, vw, pcA[t], pcB[t].x, Ht, Wt, ix, iy);
         if (abl_notaps) return;
-        fetch_pair_taps<TexT>(q, vol + static_cast<int64_t>(k) * p.s_plane, s_chan_b, s_row_b, Ht, Wt);
+        if constexpr (TEXEL) fetch_texel_pair_taps<TexT>(q, tex_offset(vol, static_cast<int64_t>(k) * p.s_plane), s_row_b, Ht, Wt);
+        else fetch_pair_taps<TexT>(q, vol + static_cast<int64_t>(k) * p.s_plane, s_chan_b, s_row_b, Ht, Wt);
     };
     // the taps have landed: bilinear samples, the plane's gradients, the tile maximum
     auto grads = [&](int t, PairTaps& q, Grad& gq) -> uint2 {
@@ -475,15 +499,15 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
         if (__any(active && any_w && !(staged && in_box))) {
             if (active && any_w && !(staged && in_box)) {
                 float* __restrict__ gp = gvol + static_cast<int64_t>(k) * b.gs_plane;
-                const int64_t oa = static_cast<int64_t>(y0) * b.gs_row + x0, ob = oa + b.gs_row;
+                const int64_t oa = static_cast<int64_t>(y0) * b.gs_row + static_cast<int64_t>(x0) * kGX, ob = oa + b.gs_row;
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) {
                     float* __restrict__ gc = gp + c4 * b.gs_chan;
                     const float d = gq.d[c4];
                     if (nw != 0.0f) atomicAdd(gc + oa, d * nw);        // (a weight that is not zero belongs to a tap inside the texture)
-                    if (ne != 0.0f) atomicAdd(gc + oa + 1, d * ne);
+                    if (ne != 0.0f) atomicAdd(gc + oa + kGX, d * ne);
                     if (sw != 0.0f) atomicAdd(gc + ob, d * sw);
-                    if (se != 0.0f) atomicAdd(gc + ob + 1, d * se);
+                    if (se != 0.0f) atomicAdd(gc + ob + kGX, d * se);
                 }
             }
         }
@@ -512,7 +536,54 @@ __device__ __forceinline__ void render_backward_tile2_body(const KParams& p, con
         const float inv = __builtin_amdgcn_ldexpf(1.0f, (fw & 3) == 3 ? -sha : -shc);
         const int nx = __builtin_amdgcn_readfirstlane(bb.z), nlines = __builtin_amdgcn_readfirstlane(bb.w) * 4;
         const int bx = __builtin_amdgcn_readfirstlane(bb.x), by = __builtin_amdgcn_readfirstlane(bb.y);
-        float* __restrict__ gp = gvol + static_cast<int64_t>(k) * b.gs_plane + static_cast<int64_t>(by) * b.gs_row + bx;
+        float* __restrict__ gp = gvol + static_cast<int64_t>(k) * b.gs_plane + static_cast<int64_t>(by) * b.gs_row + static_cast<int64_t>(bx) * kGX;
+        if constexpr (TEXEL) {
+            // Layers' order: the 4 nx gradient dwords of a box row are ONE contiguous run.  A flush wave takes box rows fw, fw + kFW, ...; lane l of a pass
+            // handles dword c0 + l of the run: texel x = (c0 + l) >> 2, channel l & 3 (c0 is a multiple of 4) -- consecutive lanes, consecutive dwords
+            // across the whole row, where the planar flush ends a line, and an atomic segment, per channel.  The box stays [row][channel][x]: the lane
+            // reads acc[(row 4 + c) Pitch + x], and with Pitch = 8 or 24 (mod 32) the four channels of a 32-lane half fall on disjoint banks (B2Texel).
+            // The scale is per LANE (colour | alpha).  Four passes' reads in flight per wave (one group covers a row of up to 64 texels).
+            const float inv_t = __builtin_amdgcn_ldexpf(1.0f, (flane & 3) == 3 ? -sha : -shc);
+            const int ndw = 4 * nx, nrows = __builtin_amdgcn_readfirstlane(bb.w);
+            uint32_t* __restrict__ srcl = bx_acc + (flane & 3) * kB2Pitch + (flane >> 2);
+            float* __restrict__ gl = gp + flane;
+            if (wide) {
+                for (int row = fw; row < nrows; row += kFW) {
+                    for (int c0 = 0; c0 < ndw; c0 += 64) {
+                        const bool on = c0 + flane < ndw;
+                        uint32_t* __restrict__ src = srcl + row * (4 * kB2Pitch) + (c0 >> 2);
+                        const int qh = on ? static_cast<int>(src[0]) : 0, ql = on ? static_cast<int>(src[kB2Cap / 2]) : 0;
+                        if ((qh | ql) != 0) {
+                            src[0] = 0u, src[kB2Cap / 2] = 0u;
+                            const float v = __builtin_fmaf(static_cast<float>(qh), 4096.0f, static_cast<float>(ql)) * inv_t;
+                            if (!abl_noglobal) atomicAdd(gl + (static_cast<uint32_t>(row) * gs_row + static_cast<uint32_t>(c0)), v);
+                        }
+                    }
+                }
+                return;
+            }
+            for (int row = fw; row < nrows; row += kFW) {
+                uint32_t* __restrict__ srow = srcl + row * (4 * kB2Pitch);
+                const uint32_t grow = static_cast<uint32_t>(row) * gs_row;
+                for (int c0 = 0; c0 < ndw; c0 += 4 * 64) {
+                    int q[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int d0 = c0 + u * 64;
+                        q[u] = (d0 + flane < ndw) ? static_cast<int>(srow[d0 >> 2]) : 0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int d0 = c0 + u * 64;
+                        if (q[u] != 0) {
+                            srow[d0 >> 2] = 0u;
+                            if (!abl_noglobal) atomicAdd(gl + (grow + static_cast<uint32_t>(d0)), static_cast<float>(q[u]) * inv_t);
+                        }
+                    }
+                }
+            }
+            return;
+        }
         if (wide) {   // two words per cell (see the tables): value = hi * 2^12 + lo.  (Textures several times coarser than the image: small boxes, atomics only.)
             for (int c0 = 0; c0 < nx; c0 += 64) {
                 const bool on = c0 + flane < nx;
@@ -673,6 +744,54 @@ __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_chunk_ker
 template <typename TexT, bool AC, typename G>
 __global__ __launch_bounds__(kB2Threads, 6) void render_backward_tile2_shaded_kernel(const KParams p, const BwdParams b, const int tiles_x, const ShadeK shade) {
     render_backward_tile2_body<TexT, AC, G, false>(p, b, tiles_x, shade);
+}
+template <typename TexT, bool AC>
+__global__ __launch_bounds__(kB2Threads, 6) void render_backward_layers_tile_kernel(const KParams p, const BwdParams b, const int tiles_x) {
+    static_assert(is_float_texel<TexT>, "the texel instances");
+    render_backward_tile2_body<TexT, AC, B2Texel, false>(p, b, tiles_x);
+}
+
+// ---- channels-last float layers (gmpi_mpi_render_layers_backward_launch): the texel instances ----------------------------------------------------------
+// p: the layers as to_kparams_layers leaves them (strides in BYTES, s_chan unused); gstride: the fp32 gradient's [gs_M, gs_D, 1, gs_row, 4] in elements.
+// The guards of the tile kernel -- two columns for the pair loads, the view index in grid.y, a plane's offsets in 31 bits for the layers (bytes) and for
+// the gradient (dwords); whatever fails them goes to the one-pixel kernel.
+bool backward_layers_tile_supports(const KParams& p, int dtype, const int64_t* gstride) {
+    const int es = dtype == GMPI_DTYPE_F32 ? 4 : 2;
+    return p.Wt >= 2 && p.N <= 65535 && layers_offsets_fit_32(p.s_row / es, p.Ht, p.Wt, es) && layers_offsets_fit_32(gstride[3], p.Ht, p.Wt, 1);
+}
+template <typename TexT>
+static hipError_t launch_backward_layers_t(const KParams& p, const BwdParams& b, bool tiles, hipStream_t stream) {
+    const bool ac = p.flags & GMPI_FLAG_ALIGN_CORNERS;
+    if (tiles) {
+        using G = B2Texel;
+        const int tx = (p.W + G::TW - 1) / G::TW, ty = (p.H + G::TH - 1) / G::TH;
+        const dim3 grid2(xcd_grid_per_group(tx * ty, tx * ty), p.N);
+        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_layers_tile_kernel<TexT, decltype(AC)::value>), grid2, dim3(kB2Threads), 0, stream, p, b, tx); });
+        return hipGetLastError();
+    }
+    // one pixel per lane, the view index in grid.z: a longer batch in pieces of 65535 views
+    for (int n0 = 0; n0 < p.N; n0 += 65535) {
+        const dim3 block(64, 4), grid((p.W + 63) / 64, (p.H + 3) / 4, min(p.N - n0, 65535));
+        dispatch_bool(ac, [&](auto AC) { hipLaunchKernelGGL((render_backward_layers_kernel<TexT, decltype(AC)::value>), grid, block, 0, stream, p, b, n0); });
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+hipError_t launch_backward_layers(const KParams& p0, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_layers, const int64_t* gstride,
+                                  bool tiles, hipStream_t stream) {
+    KParams p = p0;
+    p.ws = nullptr, p.ws_bytes = 0;   // no workspace is read: the atomics-free pair has no texel form
+    BwdParams b;
+    b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T, b.g_rgba = g_layers;
+    b.gs_mpi = gstride[0], b.gs_plane = gstride[1], b.gs_chan = 1, b.gs_row = gstride[3];
+    tiles = tiles && backward_layers_tile_supports(p, dtype, gstride);
+    switch (dtype) {
+        case GMPI_DTYPE_F32: return launch_backward_layers_t<rgba32f_t>(p, b, tiles, stream);
+        case GMPI_DTYPE_F16: return launch_backward_layers_t<rgba16h_t>(p, b, tiles, stream);
+        case GMPI_DTYPE_BF16: return launch_backward_layers_t<rgba16b_t>(p, b, tiles, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <typename TexT, bool CHUNK = false>

@@ -609,6 +609,7 @@ def _warn_gather_fallback(kind: _Kind) -> None:
 
 _LAYERS_COPY_WARNED = False
 _LAYERS_LDS_WARNED = False
+_LAYERS_BACKWARD_WARNED = False
 
 
 def _warn_layers_copy() -> None:
@@ -619,6 +620,16 @@ def _warn_layers_copy() -> None:
         warnings.warn("float layers: these layers are not read in place (the last two strides must be (4, 1), rows must not overlap and no stride may be "
                       "negative); a contiguous copy of the layers is rendered instead (counted in MPI.layers_copies; this warning is given once)",
                       RuntimeWarning, stacklevel=4)
+
+
+def _warn_layers_backward_fallback() -> None:
+    """Once per process: layers_backward="texel" ran the one-pixel-per-lane kernel (every such launch is counted in `MPI.layers_backward_fallbacks`)."""
+    global _LAYERS_BACKWARD_WARNED
+    if not _LAYERS_BACKWARD_WARNED:
+        _LAYERS_BACKWARD_WARNED = True
+        warnings.warn('float layers, layers_backward="texel": the tile kernel cannot take these tensors (it needs Wt >= 2, at most 65535 views, and the '
+                      "offsets inside one plane of the layers (bytes) and of their gradient (dwords) below 2^31); the one-pixel-per-lane kernel runs "
+                      "instead (counted in MPI.layers_backward_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=2)
 
 
 def _warn_layers_lds_fallback() -> None:
@@ -738,6 +749,7 @@ class MPI(nn.Module):
         self.shaded_backward_fallbacks = 0   # shaded backwards of a module built with backward="gather", which ran the default backward instead
         self.layers_copies = 0           # render_views_layers calls whose layers were not read in place: a contiguous copy of the layers was rendered
         self.layers_lds_fallbacks = 0    # float-layer launches that asked for "lds" and ran the one-pixel kernel instead
+        self.layers_backward_fallbacks = 0   # layers_backward="texel" backward launches whose tensors the tile kernel could not take: the one-pixel kernel ran
 
     # -- range_check="full": the exhaustive pass is skipped while the volume that passed it last is provably unchanged ------------------
     # The reference asserts min/max over the WHOLE volume in every call (mpi_renderer.py:447-449, mpi.py:185-187); its video loop
@@ -821,7 +833,8 @@ class MPI(nn.Module):
                      out_pm1: bool = False, want_transmittance: bool = False, c2w_mat=None, sphere_c=None,
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
-                     _layout: Optional[_Layout] = None, _shading: Optional[torch.Tensor] = None, _layers: Optional[str] = None):
+                     _layout: Optional[_Layout] = None, _shading: Optional[torch.Tensor] = None, _layers: Optional[str] = None,
+                     _layers_backward: str = "planar"):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -856,7 +869,7 @@ class MPI(nn.Module):
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint,
                               _layout=_layout, _shading=_shading)
                 if _layers is not None:
-                    kwargs["_layers"] = _layers
+                    kwargs["_layers"], kwargs["_layers_backward"] = _layers, _layers_backward
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
                 return dict(color=color, depth=depth, T=T if want_transmittance else None, status=st)
         # (`records_only`: a stub library that records the parameter structs instead of launching -- the seam test of
@@ -1015,7 +1028,7 @@ class MPI(nn.Module):
                                   "defer_status", "out", "frontal_hint", "tilted_hint", "oblique_hint"))
 
     def render_views_layers(self, layers: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor, z_dir: torch.Tensor,
-                            variant: Optional[str] = None, **kwargs):
+                            variant: Optional[str] = None, layers_backward: str = "planar", **kwargs):
         """`render_views` of the volume `layers.permute(0, 1, 4, 2, 3)` without building it: layers [M,D,Ht,Wt,4], fp32 / bf16 / fp16 -- the order image
         files, numpy and channels-last networks hold -- are read IN PLACE by kernels over whole texels (gmpi_mpi_render_layers_launch: the tensor's
         own pointer, strides [s_M, s_D, 1, s_row, 4]); `render_views` of that permuted view copies the whole volume first.  Slices along M, D, rows
@@ -1030,10 +1043,16 @@ class MPI(nn.Module):
         pointer / strides that are no multiples of 4 bytes) runs the one-pixel kernel: `layers_lds_fallbacks`, one RuntimeWarning per process.
         Strict-order mode is bit-identical to `render_views` of the planar copy with either kernel; in default mode the one-pixel kernel gives the
         planar one-pixel kernel's bits.  range_check="full" passes over the layers' own storage (a strided view is copied for that pass alone).
-        Under autograd, layers that require grad are rendered in place and the node saves the layers themselves; its backward makes the planar
-        copy then (transient, freed with the call), launches the existing backward (the atomic tile kernels, whatever the module's `backward`) and
-        returns the gradient in the layers' shape and dtype -- a backward that reads the texels in place is not built.  geometry_grad with a
-        camera or dhw tensor that requires grad raises NotImplementedError."""
+        Under autograd, layers that require grad are rendered in place and the node saves the layers themselves.  `layers_backward`: "planar" (the
+        default) -- the backward makes the planar copy then (transient, freed with the call), launches the planar backward into a zero-filled planar
+        fp32 gradient and permutes that back: two transposing copies and two fp32 volumes at the peak; "texel" -- the backward reads the saved layers
+        IN PLACE and accumulates into ONE zero-filled fp32 tensor of the layers' shape and order (gmpi_mpi_render_layers_backward_launch: the 64 x 8
+        tile kernel, or the one-pixel kernel for variant "gather"), which IS the gradient of fp32 layers and is cast once for 16-bit ones.  Tensors
+        the tile kernel cannot take (Wt = 1, more than 65535 views, in-plane offsets past 2^31) run the one-pixel kernel: `layers_backward_fallbacks`,
+        one RuntimeWarning per process.  Layers that had to be copied (`layers_copies`) take the same path over the copy.  Anything else is a
+        ValueError.  Either way the atomic kernels run, whatever the module's `backward` (MPI(backward="gather") included: the atomics-free pair has
+        no form for the layout), and the gradient comes back in the layers' shape and dtype.  geometry_grad with a camera or dhw tensor that requires
+        grad raises NotImplementedError.  Measured, not routed: profiles/float_layers_backward.txt."""
         if layers.ndim != 5 or layers.shape[4] != 4:
             raise ValueError(f"render_views_layers takes layers of shape [M, D, Ht, Wt, 4], got {tuple(layers.shape)}")
         unknown = set(kwargs) - self._LAYERS_KEYWORDS
@@ -1044,6 +1063,8 @@ class MPI(nn.Module):
         variant = self.variant if variant is None else variant
         if variant not in ("auto", "gather", "lds"):
             raise ValueError(f'float layers render with variant "auto", "gather" or "lds", not {variant!r}')
+        if layers_backward not in ("planar", "texel"):
+            raise ValueError(f'layers_backward is "planar" or "texel", not {layers_backward!r}')
         if layers.dtype is torch.float64:
             layers = layers.float()
         if layers.dtype not in FLOAT_DTYPES:
@@ -1052,7 +1073,7 @@ class MPI(nn.Module):
             layers = layers.contiguous()
             self.layers_copies += 1
             _warn_layers_copy()
-        return self.render_views(layers, dhw, ray_dir, eye_pos, z_dir, _layers=variant, **kwargs)
+        return self.render_views(layers, dhw, ray_dir, eye_pos, z_dir, _layers=variant, _layers_backward=layers_backward, **kwargs)
 
     # -- shaded RGBA volume ------------------------------------------------------------------------------------------------------------
     def render_views_shaded(self, rgba: torch.Tensor, shading: torch.Tensor, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor,
@@ -1348,9 +1369,10 @@ class _RenderFunction(torch.autograd.Function):
 
 class _LayersRenderFunction(torch.autograd.Function):
     """autograd bridge of `MPI.render_views_layers`: forward = gmpi_mpi_render_layers_launch over the layers in place; the node saves the LAYERS, not a
-    planar copy.  backward = gmpi_mpi_render_backward_launch (its _ex form when the loss reaches T) over the planar copy of the saved layers, made then
-    and freed with the call, into a zero-filled planar fp32 gradient that goes back in the layers' order, shape and dtype.  A backward that reads the
-    texels in place is not built; nor is backward="gather" for the layout (the atomic kernels run)."""
+    planar copy.  backward, layers_backward="planar" (the default) = gmpi_mpi_render_backward_launch (its _ex form when the loss reaches T) over the
+    planar copy of the saved layers, made then and freed with the call, into a zero-filled planar fp32 gradient that goes back in the layers' order,
+    shape and dtype; layers_backward="texel" = gmpi_mpi_render_layers_backward_launch over the saved layers themselves into ONE zero-filled fp32
+    tensor of the layers' shape and order.  backward="gather" is not built for the layout (the atomic kernels run either way)."""
 
     @staticmethod
     def forward(ctx, layers, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
@@ -1358,10 +1380,35 @@ class _LayersRenderFunction(torch.autograd.Function):
         ctx.has_v2m = keep.view_to_mpi is not None
         ctx.save_for_backward(*keep[:5], res["T"], *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.in_dtype = layers.dtype
+        ctx.texel, ctx.mpi = kwargs.get("_layers_backward", "planar") == "texel", mpi
         return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
+    def _backward_texel(ctx, g_color, g_depth, g_T):
+        saved = ctx.saved_tensors
+        layers = saved[0]
+        keep, T = _Keep(layers, *saved[1:5], saved[6] if ctx.has_v2m else None), saved[5]
+        dev = layers.device
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved layers ...
+        p.rgba_stride[:] = layer_strides(layers)     # ... as the volume they are a view of: [s_M, s_D, 1, s_row, 4]
+        grad = torch.zeros(tuple(layers.shape), dtype=torch.float32, device=dev)   # the ONE fp32 tensor: contiguous in the layers' order
+        gst = (ctypes.c_int64 * 5)(grad.stride(0), grad.stride(1), 1, grad.stride(2), 4)
+        if p.variant != _lib.VARIANT_GATHER and dev.type == "cuda":   # (variant "gather": the one-pixel kernel by choice)
+            rc = _lib.load_library().gmpi_render_layers_backward_supports(ctypes.byref(p), gst)
+            if rc < 0:
+                _lib.check(rc, "gmpi_render_layers_backward_supports")
+            if rc == 0:
+                ctx.mpi.layers_backward_fallbacks += 1
+                _warn_layers_backward_fallback()
+        _call("gmpi_mpi_render_layers_backward_launch", dev, ctypes.byref(p), g_color.data_ptr(), _ptr(g_depth), _ptr(g_T), grad.data_ptr(), gst, stream=stream)
+        return grad.to(ctx.in_dtype)   # (fp32 layers: the filled tensor itself)
+
+    @staticmethod
     def backward(ctx, g_color, g_depth, g_T, g_status):
+        if ctx.texel:
+            return _LayersRenderFunction._backward_texel(ctx, g_color, g_depth, g_T), None, None, None, None, None, None
         saved = ctx.saved_tensors
         planar = saved[0].permute(0, 1, 4, 2, 3).contiguous()   # the transient planar copy [M,D,4,Ht,Wt]
         keep, T = _Keep(planar, *saved[1:5], saved[6] if ctx.has_v2m else None), saved[5]

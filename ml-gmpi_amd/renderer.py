@@ -427,7 +427,7 @@ class MPIRenderer:
         want_T = bool(ext.pop("want_transmittance", False))
         layout = ext.pop("_layout", None)   # render_shared / render_depth: batch_mpi_rgbas is then the alpha tensor / the depth image [B,1,1,Ht,Wt]
         shading = ext.pop("_shading", None)   # render_shaded: the shading image [B,1,Ht,Wt] of the shaded render
-        layers_variant = ext.pop("_layers", None)   # render_layers: batch_mpi_rgbas is then the stack of layers [B,D,Ht,Wt,4]; (variant,)
+        layers_variant = ext.pop("_layers", None)   # render_layers: batch_mpi_rgbas is then the stack of layers [B,D,Ht,Wt,4]; (variant, layers_backward)
         chunks = ext.pop("_chunks", None)   # render_chunks: the stack's chunks (batch_mpi_rgbas is then the first of them, looked at for its shape alone)
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
@@ -475,7 +475,7 @@ class MPIRenderer:
                 want_transmittance=want_T, c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer)
         elif layers_variant is not None:   # (the camera hints are accepted and ignored by the layout's entry: not passed)
             res = self.mpi.render_views_layers(
-                batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, variant=layers_variant[0], views_per_mpi=views_per_mpi,
+                batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, variant=layers_variant[0], layers_backward=layers_variant[1], views_per_mpi=views_per_mpi,
                 check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
                 c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer)
         elif shading is not None:
@@ -518,14 +518,18 @@ class MPIRenderer:
         shape_only = first.new_empty((first.shape[0], 0))   # (render reads the number of MPIs off it; no view of the chunk: that would keep its storage)
         return self.render(shape_only, render_h, render_w, _chunks=rest(), **kwargs)
 
-    def render_layers(self, layers, render_h, render_w, *, variant=None, **kwargs):
+    def render_layers(self, layers, render_h, render_w, *, variant=None, layers_backward="planar", **kwargs):
         """`render` of the volume `layers.permute(0, 1, 4, 2, 3)` without building it (`MPI.render_views_layers`): layers [B,D,Ht,Wt,4], fp32 / bf16 /
         fp16 channels-last (uint8 layers take the existing uint8 path), read in place.  Keyword arguments, return tuple, pose sampling and the
         consumption of the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the planar volume.  `variant`:
-        "auto", "gather", "lds" or None = the renderer's own, as in `MPI.render_views_layers`."""
+        "auto", "gather", "lds" or None = the renderer's own, as in `MPI.render_views_layers`.  `layers_backward`: "planar" (the default: the backward
+        over a transient planar copy) or "texel" (the backward that reads the saved layers and writes their gradient in place), as in
+        `MPI.render_views_layers`; anything else is a ValueError."""
         if layers.ndim != 5 or layers.shape[4] != 4:
             raise ValueError(f"render_layers takes layers of shape [B, D, Ht, Wt, 4], got {tuple(layers.shape)}")
-        return self.render(layers, render_h, render_w, _layers=(variant,), **kwargs)
+        if layers_backward not in ("planar", "texel"):
+            raise ValueError(f'layers_backward is "planar" or "texel", not {layers_backward!r}')
+        return self.render(layers, render_h, render_w, _layers=(variant, layers_backward), **kwargs)
 
     def render_shaded(self, batch_mpi_rgbas, shading, render_h, render_w, **kwargs):
         """`render` of the volume `apply_shading(batch_mpi_rgbas, shading)` without building it (`MPI.render_views_shaded`): batch_mpi_rgbas
