@@ -758,6 +758,42 @@ int gmpi_alpha_depth_backward_ex_launch(const void *alpha, int32_t alpha_dtype, 
                                         int32_t H, int32_t W, void *stream);
 
 /*
+ * Backward of the image-sized middle of the augmentation (gmpi_light_blur_launch, gmpi_light_shading_launch), and the image-sized ends of the
+ * shared-colour and depth-alpha layouts: what LightRenderer(middle="hip") of the Python package runs instead of torch autograd over a torch
+ * restatement.  All four are gathers: one thread owns one cell of each gradient and writes it once.  No atomics: two runs give the same bits.
+ * Stream-ordered, allocate nothing, never synchronise.  gmpi_query(46) == 1 says that they are built in.
+ *  - gmpi_light_shading_backward_launch: grad_shading [B,H,W] -> grad_blurred [B,H,W] (both fp32 contiguous), the adjoint of
+ *    gmpi_light_shading_launch w.r.t. depth_blurred (none w.r.t. xyz_last or light_dir; ka does not enter).  The upstream gradient of an interior
+ *    cell is the sum of grad_shading over the pixels that take its normal (replicate padding: 1, 2 or 4 pixels; a whole row, column or image
+ *    where H == 3 or W == 3); the clamp passes it where -n.l >= 0, zero included, as torch.clamp does; the normal is the forward's, bit for bit.
+ *    Where the un-normalised normal is exactly 0 (a zero depth image, say) the cell contributes 0: torch autograd over the same formula yields NaN
+ *    there (pow(0.5) at 0).  H, W >= 3 as in the forward.
+ *  - gmpi_light_blur_backward_launch: grad_blurred [B,H,W] -> grad_depth [B,H,W], the adjoint (transpose) of gmpi_light_blur_launch's
+ *    reflect-padded separable blur; the same limits: ksize odd, ksize/2 < H, W.
+ *  - gmpi_light_shade_images_launch: rgb_out = clip(rgb * shading, 0, 1) and, with a background, background_out likewise.  rgb and background are
+ *    [B,3,H,W] in fp32 / bf16 / fp16 (each its own dtype) with element strides {MPI, channel, row} (innermost 1; MPI >= 0, channel > 0, row >= W);
+ *    background may be NULL (background_dtype / background_stride / background_out are then ignored); shading [B,H,W] and the outputs [B,3,H,W]
+ *    are fp32 contiguous.  A NaN colour shades to 0, as in gmpi_light_apply_launch.
+ *  - gmpi_light_shade_images_backward_launch: grad_rgb = grad_rgb_out * shading * mask, grad_background likewise, and
+ *    grad_shading[b,y,x] = sum over the channels of BOTH images of grad_*_out * colour * mask, in one launch; mask = [0 <= colour * shading <= 1],
+ *    bounds included (gmpi_light_apply_backward_launch's).  A NULL grad_rgb_out / grad_background_out counts as zero; each of the three outputs
+ *    may be NULL and is then not written (all three NULL: GMPI_E_NULL; grad_background_out or grad_background without a background: GMPI_E_NULL).
+ * Errors, all before any launch: B < 0, H or W <= 0 (< 3 for the shading backward), B or H > 65535, the ksize limits: GMPI_E_SHAPE; B == 0:
+ * GMPI_OK; a required pointer NULL: GMPI_E_NULL; a dtype outside fp32 / bf16 / fp16: GMPI_E_DTYPE; a stride outside the above: GMPI_E_STRIDE.
+ */
+int gmpi_light_shading_backward_launch(const float *depth_blurred, const float *xyz_last, const float *light_dir, float kd,
+                                       const float *grad_shading, int32_t B, int32_t H, int32_t W, float *grad_blurred, void *stream);
+int gmpi_light_blur_backward_launch(const float *grad_blurred, float *grad_depth, int32_t B, int32_t H, int32_t W,
+                                    const float *kernel1d, int32_t ksize, void *stream);
+int gmpi_light_shade_images_launch(const void *rgb, int32_t rgb_dtype, const int64_t *rgb_stride, const void *background,
+                                   int32_t background_dtype, const int64_t *background_stride, const float *shading, float *rgb_out,
+                                   float *background_out, int32_t B, int32_t H, int32_t W, void *stream);
+int gmpi_light_shade_images_backward_launch(const void *rgb, int32_t rgb_dtype, const int64_t *rgb_stride, const void *background,
+                                            int32_t background_dtype, const int64_t *background_stride, const float *shading,
+                                            const float *grad_rgb_out, const float *grad_background_out, float *grad_rgb,
+                                            float *grad_background, float *grad_shading, int32_t B, int32_t H, int32_t W, void *stream);
+
+/*
  * gmpi_alpha_depth_launch and gmpi_alpha_depth_backward_ex_launch for a depth-alpha MPI, WITHOUT the alpha planes (what the shading augmentation
  * needs of this layout: LightRenderer.render_depth in the Python package).  By definition gmpi_ramp_depth_launch equals gmpi_alpha_depth_launch on
  *     a_k = (min(max(plane_z[k] - depth, z_lo), z_hi) - z_lo) / z_den       (GmpiDepthAlpha above: fp32, one rounding per step, the IEEE quotient),
@@ -820,7 +856,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * gmpi_mpi_render_shaded_backward_launch) is built in; 39 is unused (-1); 40 whether the gradient w.r.t. plane_z of the depth-alpha layout
  * (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in; 41 is unused (-1); 42 whether channels-last float layers
  * (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in; 43 is unused (-1); 44 whether their in-place backward
- * (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in.  Unknown -> -1.  */
+ * (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in; 45 is unused (-1); 46 whether the backward of the shading augmentation's image-sized middle and
+ * the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch,
+ * gmpi_light_shade_images_backward_launch) are built in.  Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -67,6 +67,10 @@ EXPORTS = (
     "gmpi_light_shading_launch",
     "gmpi_light_apply_launch",
     "gmpi_light_apply_backward_launch",
+    "gmpi_light_shading_backward_launch",
+    "gmpi_light_blur_backward_launch",
+    "gmpi_light_shade_images_launch",
+    "gmpi_light_shade_images_backward_launch",
     "gmpi_alpha_depth_backward_launch",
     "gmpi_alpha_depth_backward_ex_launch",
     "gmpi_ramp_depth_launch",
@@ -322,6 +326,18 @@ def load_library():
     lib.gmpi_light_apply_backward_launch.restype = ctypes.c_int
     lib.gmpi_light_apply_backward_launch.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), vp, vp, vp, vp,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
+    # the image-sized middle's backward and the shade-images pair (gmpi_query(46)); image strides are int64[3] = {MPI, channel, row}
+    lib.gmpi_light_shading_backward_launch.restype = ctypes.c_int
+    lib.gmpi_light_shading_backward_launch.argtypes = [vp, vp, vp, ctypes.c_float, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp]
+    lib.gmpi_light_blur_backward_launch.restype = ctypes.c_int
+    lib.gmpi_light_blur_backward_launch.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp]
+    lib.gmpi_light_shade_images_launch.restype = ctypes.c_int
+    lib.gmpi_light_shade_images_launch.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                                   vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
+    lib.gmpi_light_shade_images_backward_launch.restype = ctypes.c_int
+    lib.gmpi_light_shade_images_backward_launch.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), vp, ctypes.c_int32,
+                                                            ctypes.POINTER(ctypes.c_int64), vp, vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
+                                                            ctypes.c_int32, vp]
     lib.gmpi_alpha_depth_backward_launch.restype = ctypes.c_int
     lib.gmpi_alpha_depth_backward_launch.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                                                      vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,

@@ -1181,6 +1181,7 @@ int gmpi_query(int32_t what) {
         case 40: return 1;  // the gradient w.r.t. plane_z of the depth-alpha layout (gmpi_mpi_render_depth_geometry_backward_pz_launch) is built in  (39: unused)
         case 42: return 1;  // channels-last float layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in  (41: unused)
         case 44: return 1;  // the in-place backward of channels-last float layers (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in  (43: unused)
+        case 46: return 1;  // the backward of the shading augmentation's image-sized middle and the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch, gmpi_light_shade_images_backward_launch) are built in  (45: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -109,8 +109,9 @@ static void launch_light_apply(const void* rgba, const int64_t* st, const float*
 }
 
 // ---- backward of the augmentation (the reference applies it inside the G-step, train.py:535-541, 703-709) -------------
-// Only the two volume-sized ops need kernels; the B*H*W middle (blur, point cloud, normals, Lambert) is differentiated by
-// torch autograd in light.py.
+// (1), (2): the two volume-sized ops.  The B*H*W middle (blur, point cloud, normals, Lambert) is differentiated by torch autograd in
+// light.py by default, and by the kernels (3), (4) below with LightRenderer(middle="hip"); (5) are the image-sized ends of the
+// shared-colour and depth-alpha layouts in that mode.
 //
 // (1) out = clip(rgb * s, 0, 1) | alpha:   g_rgb = g_out * s * [0 < rgb*s < 1],  g_alpha = g_out_alpha (more is added by (2)),
 //     g_s[b,y,x] = sum_{k,c} g_out * rgb * [0 < rgb*s < 1].  One pixel column per thread, planes in a loop (coalesced in x).
@@ -207,7 +208,170 @@ __global__ __launch_bounds__(256) void ramp_depth_backward_kernel(const T* __res
     *gi += -acc / dk.den;
 }
 
+// ---- backward of the image-sized middle (LightRenderer(middle="hip"); the default differentiates a torch restatement) ---------------------------------
+// Gather form throughout: one thread owns one texel of the gradient and writes it once; no atomics, the same bits on every run.
+//
+// (3) adjoint of light_shading_kernel.  A pixel takes the normal of its clamped interior cell, and everything after the normal is the same for all
+//     replicas: the upstream gradient of an interior cell is the sum of grad_shading over the pixels that clamp to it -- the cell itself, and the
+//     border row / column / corner next to it (a whole row, column or image where H == 3 or W == 3).
+__device__ __forceinline__ float replica_sum(const float* __restrict__ gs, int cy, int cx, int H, int W) {
+    const int y0 = cy == 1 ? 0 : cy, y1 = cy == H - 2 ? H - 1 : cy;
+    const int x0 = cx == 1 ? 0 : cx, x1 = cx == W - 2 ? W - 1 : cx;
+    float acc = 0.0f;
+    for (int yy = y0; yy <= y1; ++yy)
+        for (int xx = x0; xx <= x1; ++xx) acc += gs[static_cast<int64_t>(yy) * W + xx];
+    return acc;
+}
+
+//     Per cell, with n the forward's normal (the same operations in the same order, so the clamp's mask is the forward's): shading = ka + kd max(-nh.l, 0),
+//     nh = n / (|n| + EPS)  ->  g_nh = -kd G l where -nh.l >= 0 (closed, as torch.clamp passes it), g_n = g_nh / (|n| + EPS) - nh (g_nh . nh) / |n|,
+//     and 0 where |n| == 0 (torch's pow(0.5) yields NaN there).  The four cross products add up to n = (up - down) x (left - right): the centre
+//     cancels, so a point p receives a gradient only from the (at most four) interior cells that have it as a neighbour:
+//         as up: (left - right) x g_n,  as down: the negative;  as right: (up - down) x g_n,  as left: the negative
+//     with the points of THAT cell.  Finally p = xyz d / (xyz_z + EPS): grad_blurred = g_p . xyz / (xyz_z + EPS).  13-point diamond read of the depth.
+__global__ __launch_bounds__(256) void light_shading_backward_kernel(const float* __restrict__ depth, const float* __restrict__ xyz_last,
+                                                                     const float* __restrict__ light_dir, float kd,
+                                                                     const float* __restrict__ grad_shading, int H, int W,
+                                                                     float* __restrict__ grad_blurred) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= W) return;
+    const float* __restrict__ d = depth + static_cast<int64_t>(b) * H * W;
+    const float* __restrict__ gs = grad_shading + static_cast<int64_t>(b) * H * W;
+    const float* __restrict__ l = light_dir + 3 * b;
+    auto pcl = [&](int yy, int xx) {
+        const float* __restrict__ p = xyz_last + (static_cast<int64_t>(yy) * W + xx) * 3;
+        const float scale = d[static_cast<int64_t>(yy) * W + xx] / (p[2] + kLightEps);
+        return V3{p[0] * scale, p[1] * scale, p[2] * scale};
+    };
+    // g_n of the interior cell (cy, cx) and its two diagonals; false where the cell does not exist or passes nothing
+    auto cell = [&](int cy, int cx, V3& gn, V3& ud, V3& lr) {
+        if (cy < 1 || cy > H - 2 || cx < 1 || cx > W - 2) return false;
+        const V3 c = pcl(cy, cx), up = pcl(cy - 1, cx), down = pcl(cy + 1, cx), left = pcl(cy, cx - 1), right = pcl(cy, cx + 1);
+        V3 n = cross(up - c, left - c) + cross(left - c, down - c);
+        n = n + cross(down - c, right - c);
+        n = n + cross(right - c, up - c);
+        float len2 = n.x * n.x;
+        len2 = len2 + n.y * n.y;
+        len2 = len2 + n.z * n.z;
+        const float norm = sqrtf(len2), len = norm + kLightEps;
+        const V3 nh = {n.x / len, n.y / len, n.z / len};
+        float dotv = nh.x * l[0];
+        dotv = dotv + nh.y * l[1];
+        dotv = dotv + nh.z * l[2];
+        if (!(-1.0f * dotv >= 0.0f) || !(norm > 0.0f)) return false;
+        const float g_dot = -(kd * replica_sum(gs, cy, cx, H, W));
+        const V3 g_nh = {g_dot * l[0], g_dot * l[1], g_dot * l[2]};
+        const float along = (g_nh.x * nh.x + g_nh.y * nh.y + g_nh.z * nh.z) / norm;
+        gn = {g_nh.x / len - nh.x * along, g_nh.y / len - nh.y * along, g_nh.z / len - nh.z * along};
+        ud = up - down, lr = left - right;
+        return true;
+    };
+    V3 g = {0.0f, 0.0f, 0.0f}, gn, ud, lr;
+    if (cell(y + 1, x, gn, ud, lr)) g = g + cross(lr, gn);   // this texel is that cell's `up`
+    if (cell(y - 1, x, gn, ud, lr)) g = g - cross(lr, gn);   // ... `down`
+    if (cell(y, x + 1, gn, ud, lr)) g = g - cross(ud, gn);   // ... `left`
+    if (cell(y, x - 1, gn, ud, lr)) g = g + cross(ud, gn);   // ... `right`
+    const float* __restrict__ p = xyz_last + (static_cast<int64_t>(y) * W + x) * 3;
+    grad_blurred[(static_cast<int64_t>(b) * H + y) * W + x] = (g.x * p[0] + g.y * p[1] + g.z * p[2]) / (p[2] + kLightEps);
+}
+
+// (4) adjoint of gaussian_blur_kernel.  Along one axis of length n, input i is read by output j through tap t wherever refl(j + t - r) == i.  The
+//     unpadded sources with that image are s = i, s = -i (i != 0) and s = 2(n-1) - i (i != n-1), and j = s - t + r must lie in [0, n): taps
+//     max(0, s + r - (n-1)) .. min(ksize-1, s + r), an empty range for a reflected source away from its border (both can be live when n is as small as
+//     r + 1).  A row is summed first, then weighted: n_x + n_y roundings per texel instead of n_x n_y.
+__device__ __forceinline__ bool blur_source(int a, int i, int n, int& s) {
+    s = a == 0 ? i : a == 1 ? -i : 2 * (n - 1) - i;
+    return a == 0 || (a == 1 ? i != 0 : i != n - 1);
+}
+
+__global__ __launch_bounds__(256) void gaussian_blur_backward_kernel(const float* __restrict__ grad_blurred, float* __restrict__ grad_depth, int H,
+                                                                     int W, const float* __restrict__ k1d, int ksize) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const float* __restrict__ img = grad_blurred + static_cast<int64_t>(blockIdx.z) * H * W;
+    const int r = ksize / 2;
+    float acc = 0.0f;
+    for (int ay = 0; ay < 3; ++ay) {
+        int sy;
+        if (!blur_source(ay, y, H, sy)) continue;
+        for (int ty = max(0, sy + r - (H - 1)); ty <= min(ksize - 1, sy + r); ++ty) {
+            const float* __restrict__ row = img + static_cast<int64_t>(sy - ty + r) * W;
+            float racc = 0.0f;
+            for (int ax = 0; ax < 3; ++ax) {
+                int sx;
+                if (!blur_source(ax, x, W, sx)) continue;
+                for (int tx = max(0, sx + r - (W - 1)); tx <= min(ksize - 1, sx + r); ++tx) racc += k1d[tx] * row[sx - tx + r];
+            }
+            acc += k1d[ty] * racc;
+        }
+    }
+    grad_depth[(static_cast<int64_t>(blockIdx.z) * H + y) * W + x] = acc;
+}
+
+// (5) the image-sized ends of the shared-colour and depth-alpha layouts: clip(c * shading, 0, 1) on the colour image and, where there is one, the
+//     background image, and its backward.  The two images may differ in storage type and strides: the type is a wave-uniform switch, not an instance.
+struct LightImage {
+    const void* p;   // [B,3,H,W], innermost stride 1; nullptr: no such image
+    int32_t dtype;
+    int64_t sb, sc, sr;
+};
+__device__ __forceinline__ float load_image(const LightImage& im, int64_t off) {
+    switch (im.dtype) {
+        case GMPI_DTYPE_BF16: return to_f32(static_cast<const bf16_t*>(im.p)[off]);
+        case GMPI_DTYPE_F16: return to_f32(static_cast<const f16_t*>(im.p)[off]);
+        default: return static_cast<const float*>(im.p)[off];
+    }
+}
+
+__global__ __launch_bounds__(256) void light_shade_images_kernel(LightImage rgb, LightImage bg, const float* __restrict__ shading,
+                                                                 float* __restrict__ rgb_out, float* __restrict__ bg_out, int H, int W) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= W) return;
+    const int64_t plane = static_cast<int64_t>(H) * W, pix = static_cast<int64_t>(y) * W + x;
+    const float s = shading[b * plane + pix];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {   // (a NaN colour shades to 0, as in light_apply_kernel)
+        rgb_out[(static_cast<int64_t>(b) * 3 + c) * plane + pix] = fminf(fmaxf(load_image(rgb, b * rgb.sb + c * rgb.sc + y * rgb.sr + x) * s, 0.0f), 1.0f);
+        if (bg.p) bg_out[(static_cast<int64_t>(b) * 3 + c) * plane + pix] = fminf(fmaxf(load_image(bg, b * bg.sb + c * bg.sc + y * bg.sr + x) * s, 0.0f), 1.0f);
+    }
+}
+
+//     g_c = g * s * mask and g_shading = sum over the channels of both images of g * c * mask, mask = [0 <= c * s <= 1] (closed: light_apply_backward_kernel's).
+//     An upstream gradient that is nullptr counts as zero; an output that is nullptr is not written.
+__global__ __launch_bounds__(256) void light_shade_images_backward_kernel(LightImage rgb, LightImage bg, const float* __restrict__ shading,
+                                                                          const float* __restrict__ g_rgb_out, const float* __restrict__ g_bg_out,
+                                                                          float* __restrict__ g_rgb, float* __restrict__ g_bg,
+                                                                          float* __restrict__ g_shading, int H, int W) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= W) return;
+    const int64_t plane = static_cast<int64_t>(H) * W, pix = static_cast<int64_t>(y) * W + x;
+    const float s = shading[b * plane + pix];
+    float gs = 0.0f;
+    auto image = [&](const LightImage& im, const float* __restrict__ g_out, float* __restrict__ g_in) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int64_t o = (static_cast<int64_t>(b) * 3 + c) * plane + pix;
+            const float v = load_image(im, b * im.sb + c * im.sc + y * im.sr + x), t = v * s, g = g_out ? g_out[o] : 0.0f;
+            const bool pass = t >= 0.0f && t <= 1.0f;
+            if (g_in) g_in[o] = pass ? g * s : 0.0f;
+            gs += pass ? g * v : 0.0f;
+        }
+    };
+    image(rgb, g_rgb_out, g_rgb);
+    if (bg.p) image(bg, g_bg_out, g_bg);
+    if (g_shading) g_shading[b * plane + pix] = gs;
+}
+
 static int rc_of(hipError_t e) { return e == hipSuccess ? GMPI_OK : GMPI_E_LAUNCH - static_cast<int>(e); }
+
+// The checks of one image operand of the two shade-images entries.
+static int to_light_image(const void* p, int32_t dtype, const int64_t* stride, int32_t W, LightImage& im) {
+    if (!stride) return GMPI_E_NULL;
+    if (dtype < GMPI_DTYPE_F32 || dtype > GMPI_DTYPE_F16) return GMPI_E_DTYPE;
+    if (stride[0] < 0 || stride[1] <= 0 || stride[2] < W) return GMPI_E_STRIDE;
+    im = {p, dtype, stride[0], stride[1], stride[2]};
+    return GMPI_OK;
+}
 
 }  // namespace gmpi
 
@@ -353,6 +517,59 @@ int gmpi_ramp_depth_backward_launch(const void* depth_image, int32_t depth_dtype
         hipLaunchKernelGGL(ramp_depth_backward_kernel<T>, grid, block, 0, st, static_cast<const T*>(depth_image), stride_b, stride_row, dk, plane_ds, transmittance,
                            grad_depth, grad_transmittance, grad_depth_image, gstride_b, gstride_row, D, H, W);
     });
+    return rc_of(hipGetLastError());
+}
+
+int gmpi_light_shading_backward_launch(const float* depth_blurred, const float* xyz_last, const float* light_dir, float kd, const float* grad_shading,
+                                       int32_t B, int32_t H, int32_t W, float* grad_blurred, void* stream) {
+    if (B < 0 || H < 3 || W < 3 || B > 65535 || H > 65535) return GMPI_E_SHAPE;   // (rows and images are grid.y and grid.z)
+    if (B == 0) return GMPI_OK;
+    if (!depth_blurred || !xyz_last || !light_dir || !grad_shading || !grad_blurred) return GMPI_E_NULL;
+    hipLaunchKernelGGL(light_shading_backward_kernel, dim3((W + 255) / 256, H, B), dim3(256), 0, static_cast<hipStream_t>(stream), depth_blurred,
+                       xyz_last, light_dir, kd, grad_shading, H, W, grad_blurred);
+    return rc_of(hipGetLastError());
+}
+
+int gmpi_light_blur_backward_launch(const float* grad_blurred, float* grad_depth, int32_t B, int32_t H, int32_t W, const float* kernel1d,
+                                    int32_t ksize, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || B > 65535 || H > 65535 || ksize <= 0 || (ksize & 1) == 0) return GMPI_E_SHAPE;
+    if (ksize / 2 >= H || ksize / 2 >= W) return GMPI_E_SHAPE;  // the forward's limit: reflect padding needs pad < size
+    if (B == 0) return GMPI_OK;
+    if (!grad_blurred || !grad_depth || !kernel1d) return GMPI_E_NULL;
+    hipLaunchKernelGGL(gaussian_blur_backward_kernel, dim3((W + 255) / 256, H, B), dim3(256), 0, static_cast<hipStream_t>(stream), grad_blurred,
+                       grad_depth, H, W, kernel1d, ksize);
+    return rc_of(hipGetLastError());
+}
+
+int gmpi_light_shade_images_launch(const void* rgb, int32_t rgb_dtype, const int64_t* rgb_stride, const void* background, int32_t background_dtype,
+                                   const int64_t* background_stride, const float* shading, float* rgb_out, float* background_out, int32_t B,
+                                   int32_t H, int32_t W, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || B > 65535 || H > 65535) return GMPI_E_SHAPE;
+    if (B == 0) return GMPI_OK;
+    if (!rgb || !shading || !rgb_out || (background && !background_out)) return GMPI_E_NULL;
+    LightImage c{}, bg{};
+    int rc = to_light_image(rgb, rgb_dtype, rgb_stride, W, c);
+    if (rc == GMPI_OK && background) rc = to_light_image(background, background_dtype, background_stride, W, bg);
+    if (rc != GMPI_OK) return rc;
+    hipLaunchKernelGGL(light_shade_images_kernel, dim3((W + 255) / 256, H, B), dim3(256), 0, static_cast<hipStream_t>(stream), c, bg, shading, rgb_out,
+                       background_out, H, W);
+    return rc_of(hipGetLastError());
+}
+
+int gmpi_light_shade_images_backward_launch(const void* rgb, int32_t rgb_dtype, const int64_t* rgb_stride, const void* background,
+                                            int32_t background_dtype, const int64_t* background_stride, const float* shading,
+                                            const float* grad_rgb_out, const float* grad_background_out, float* grad_rgb, float* grad_background,
+                                            float* grad_shading, int32_t B, int32_t H, int32_t W, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || B > 65535 || H > 65535) return GMPI_E_SHAPE;
+    if (B == 0) return GMPI_OK;
+    if (!rgb || !shading || (!grad_rgb && !grad_background && !grad_shading)) return GMPI_E_NULL;
+    if (!background && (grad_background_out || grad_background)) return GMPI_E_NULL;
+    LightImage c{}, bg{};
+    int rc = to_light_image(rgb, rgb_dtype, rgb_stride, W, c);
+    if (rc == GMPI_OK && background) rc = to_light_image(background, background_dtype, background_stride, W, bg);
+    if (rc != GMPI_OK) return rc;
+    hipLaunchKernelGGL(light_shade_images_backward_kernel, dim3((W + 255) / 256, H, B), dim3(256), 0, static_cast<hipStream_t>(stream), c, bg, shading,
+                       grad_rgb_out, grad_background_out, grad_rgb, grad_background, grad_shading, H, W);
     return rc_of(hipGetLastError());
 }
 

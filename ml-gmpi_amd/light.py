@@ -8,7 +8,8 @@ point cloud -> normals -> Lambert shading per texel, and `clip(rgb * shading, 0,
 
 The reference applies the augmentation inside the G-step (train.py:535-541): when the volume requires grad the same
 kernels run under a `torch.autograd.Function` whose backward uses two more streaming kernels for the volume-sized ops
-(clip(rgb*shading) and the alpha compositing of the depth) and torch autograd for the B*H*W middle (blur, normals, Lambert).
+(clip(rgb*shading) and the alpha compositing of the depth) and, for the B*H*W middle (blur, normals, Lambert), torch autograd
+over a torch restatement (`LightRenderer(middle="torch")`, the default) or two adjoint kernels (`middle="hip"`).
 
 `render_shared` and `render_depth` are the augmentation for the shared-colour and the depth-alpha layout: there the shaded MPI is an MPI of
 the same layout, and only the expected depth needs a kernel (`compute_depth`; `compute_depth_ramp`, which reads one depth image and no planes).
@@ -234,9 +235,38 @@ def _shading_torch(depth_blurred: torch.Tensor, xyz_last: torch.Tensor, light_di
     return ka + diffuse * kd
 
 
-def _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading):
-    """dL/d depth [B,1,H,W] from dL/d shading [B,H,W] through the image-sized middle (blur, point cloud, normals, Lambert): torch autograd over
-    the torch restatement of the two kernels.  The ONE backward of the middle: `_LightFunction` and `_ShadingFunction` both call it."""
+MIDDLES = ("torch", "hip")
+
+
+def _middle_saved(renderer, depth, blurred):
+    """What a node saves in its forward for `_middle_backward`, all on the device already.  "torch": the expected depth and the two `_blur_matrix`
+    operands; "hip": the forward's blurred depth and the 1-D kernel (the matrices are never built)."""
+    dev = depth.device
+    H, W = depth.shape[-2:]
+    if renderer.middle == "hip":
+        return blurred, renderer._k1d.to(dev, torch.float32)
+    return depth, _blur_matrix(H, renderer._k1d, dev), _blur_matrix(W, renderer._k1d, dev)
+
+
+def _middle_backward(mode, saved, xyz_last, light_dir, ka, kd, g_shading):
+    """dL/d depth [B,1,H,W] from dL/d shading [B,H,W] through the image-sized middle (blur, point cloud, normals, Lambert); `saved` is what
+    `_middle_saved` returned for `mode`.  The ONE backward of the middle: `_LightFunction`, `_ShadingFunction` and `_ShadeImagesFunction` call it.
+
+    "torch": torch autograd over the torch restatement of the two kernels.
+    "hip": gmpi_light_shading_backward_launch on the forward's blurred depth, then gmpi_light_blur_backward_launch: two gathers, no atomics, the
+    same bits on every run.  Where a cell's un-normalised normal is exactly 0 it contributes 0; the restatement yields NaN there (pow(0.5) at 0)."""
+    if mode == "hip":
+        blurred, k1d = saved
+        B, _, H, W = blurred.shape
+        dev = blurred.device
+        g_shading = g_shading.to(torch.float32).contiguous()
+        g_blurred = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        g_depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        _call("gmpi_light_shading_backward_launch", dev, blurred.data_ptr(), xyz_last.data_ptr(), light_dir.data_ptr(), float(kd), g_shading.data_ptr(),
+              B, H, W, g_blurred.data_ptr())
+        _call("gmpi_light_blur_backward_launch", dev, g_blurred.data_ptr(), g_depth.data_ptr(), B, H, W, k1d.data_ptr(), k1d.numel())
+        return g_depth
+    depth, my, mx = saved
     with torch.enable_grad():
         d = depth.detach().requires_grad_(True)
         s = _shading_torch(_blur_torch(d, my, mx), xyz_last, light_dir, ka, kd)
@@ -250,21 +280,19 @@ class _LightFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vol, renderer, plane_ds, xyz_last, light_dir, ka, kd):
-        out, depth, T, shading = renderer._forward_kernels(vol.detach(), plane_ds, xyz_last, light_dir, ka, kd)
+        out, depth, T, shading, blurred = renderer._forward_kernels(vol.detach(), plane_ds, xyz_last, light_dir, ka, kd, want_blurred=True)
         dev = vol.device
-        H, W = vol.shape[-2:]
         # everything the backward needs is put on the device here: CPU tensor ops inside the autograd worker thread start
         # a second OpenMP pool, and the two pools then fight for the cores (milliseconds per tiny host op)
-        ctx.save_for_backward(vol.detach(), depth, T, shading, _blur_matrix(H, renderer._k1d, dev), _blur_matrix(W, renderer._k1d, dev),
-                              xyz_last.to(dev, torch.float32), light_dir.to(dev, torch.float32),
-                              plane_ds.reshape(-1).to(dev, torch.float32).contiguous())
-        ctx.misc = (ka, kd, vol.dtype)
+        ctx.save_for_backward(vol.detach(), T, shading, xyz_last.to(dev, torch.float32).contiguous(), light_dir.to(dev, torch.float32).contiguous(),
+                              plane_ds.reshape(-1).to(dev, torch.float32).contiguous(), *_middle_saved(renderer, depth, blurred))
+        ctx.misc = (ka, kd, vol.dtype, renderer.middle)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        vol, depth, T, shading, my, mx, xyz_last, light_dir, ds = ctx.saved_tensors
-        ka, kd, in_dtype = ctx.misc
+        vol, T, shading, xyz_last, light_dir, ds, *middle = ctx.saved_tensors
+        ka, kd, in_dtype, mode = ctx.misc
         dev = vol.device
         B, D, _, H, W = vol.shape
         g_out = g_out.to(torch.float32).contiguous()
@@ -274,7 +302,7 @@ class _LightFunction(torch.autograd.Function):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _call("gmpi_light_apply_backward_launch", dev, vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(), g_out.data_ptr(),
               g_rgba.data_ptr(), g_shading.data_ptr(), B, D, H, W, stream=stream)
-        g_depth = _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading).contiguous()
+        g_depth = _middle_backward(mode, middle, xyz_last, light_dir, ka, kd, g_shading).contiguous()
         alpha = vol[:, :, 3:]
         plane = H * W
         _call("gmpi_alpha_depth_backward_launch", dev, alpha.data_ptr(), _DTYPES[vol.dtype], alpha.stride(0), alpha.stride(1), alpha.stride(3),
@@ -285,32 +313,104 @@ class _LightFunction(torch.autograd.Function):
 
 class _ShadingFunction(torch.autograd.Function):
     """The image-sized middle of `LightRenderer.shading_image` as one autograd node: forward = the blur and shading kernels `render` runs (the
-    same bits), backward = torch autograd through their torch restatements, as in `_LightFunction.backward`."""
+    same bits), backward = `_middle_backward` in the renderer's mode, as in `_LightFunction.backward`."""
 
     @staticmethod
     def forward(ctx, depth, renderer, xyz_last, light_dir, ka, kd):
         dev = depth.device
-        H, W = depth.shape[-2:]
         d = depth.detach()
-        shading = renderer.shading(renderer.blurrer_func(d), xyz_last, light_dir, ka, kd).unsqueeze(1)
-        ctx.save_for_backward(d, _blur_matrix(H, renderer._k1d, dev), _blur_matrix(W, renderer._k1d, dev), xyz_last.to(dev, torch.float32),
-                              light_dir.to(dev, torch.float32))
-        ctx.misc = (ka, kd)
+        blurred = renderer.blurrer_func(d)
+        shading = renderer.shading(blurred, xyz_last, light_dir, ka, kd).unsqueeze(1)
+        ctx.save_for_backward(xyz_last.to(dev, torch.float32).contiguous(), light_dir.to(dev, torch.float32).contiguous(),
+                              *_middle_saved(renderer, d, blurred))
+        ctx.misc = (ka, kd, renderer.middle)
         return shading
 
     @staticmethod
     def backward(ctx, g_shading):
-        depth, my, mx, xyz_last, light_dir = ctx.saved_tensors
-        ka, kd = ctx.misc
-        return _middle_backward(depth, my, mx, xyz_last, light_dir, ka, kd, g_shading[:, 0].to(torch.float32)), None, None, None, None, None
+        xyz_last, light_dir, *middle = ctx.saved_tensors
+        ka, kd, mode = ctx.misc
+        return _middle_backward(mode, middle, xyz_last, light_dir, ka, kd, g_shading[:, 0].to(torch.float32)), None, None, None, None, None
+
+
+def _image_operand(image: torch.Tensor) -> torch.Tensor:
+    """The colour image the shade-images entries read: a storage dtype they take, innermost stride 1, rows that do not overlap, a channel stride
+    above 0, no negative MPI stride (such views are passed as they are; an expanded batch is one of them)."""
+    if image.dtype not in _DTYPES:
+        image = image.float()
+    if image.stride(3) != 1 or image.stride(0) < 0 or image.stride(1) <= 0 or image.stride(2) < image.shape[3]:
+        image = image.contiguous()
+    return image
+
+
+def _image_args(image):
+    """(pointer, dtype code, strides {MPI, channel, row}) of an image operand, NULLs for None."""
+    if image is None:
+        return None, 0, None
+    return image.data_ptr(), _DTYPES[image.dtype], (ctypes.c_int64 * 3)(image.stride(0), image.stride(1), image.stride(2))
+
+
+class _ShadeImagesFunction(torch.autograd.Function):
+    """`LightRenderer._shade_images` with middle="hip" as one autograd node: expected depth [B,1,H,W] fp32, colour image, background image or None
+    -> (clip(rgb * shading, 0, 1), clip(background * shading, 0, 1) or None), float32.  Forward = the blur and shading kernels `render` runs (the
+    shading has the bits of `shading_image()`), then gmpi_light_shade_images_launch.  Backward = gmpi_light_shade_images_backward_launch (both
+    images and grad_shading in one launch), then `_middle_backward`: the gradient w.r.t. the expected depth goes on to `compute_depth` /
+    `compute_depth_ramp`.  Each gradient comes back in its input's dtype; what requires no grad gets no buffer, and the middle is skipped when the
+    depth requires none.  An output the loss does not use arrives as None and is passed as NULL."""
+
+    @staticmethod
+    def forward(ctx, depth, rgb, background, renderer, xyz_last, light_dir, ka, kd):
+        dev = depth.device
+        d = depth.detach()
+        B, _, H, W = d.shape
+        blurred = renderer.blurrer_func(d)
+        shading = renderer.shading(blurred, xyz_last, light_dir, ka, kd)
+        c, bg = _image_operand(rgb.detach()), (None if background is None else _image_operand(background.detach()))
+        o_rgb = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        o_bg = None if bg is None else torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        _call("gmpi_light_shade_images_launch", dev, *_image_args(c), *_image_args(bg), shading.data_ptr(), o_rgb.data_ptr(), _ptr(o_bg), B, H, W)
+        ctx.save_for_backward(c, shading, xyz_last.to(dev, torch.float32).contiguous(), light_dir.to(dev, torch.float32).contiguous(),
+                              blurred, renderer._k1d.to(dev, torch.float32), *(() if bg is None else (bg,)))
+        ctx.misc = (ka, kd, rgb.dtype, None if background is None else background.dtype)
+        ctx.set_materialize_grads(False)
+        return o_rgb, o_bg
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_bg):
+        c, shading, xyz_last, light_dir, blurred, k1d, *rest = ctx.saved_tensors
+        bg = rest[0] if rest else None
+        ka, kd, rgb_dtype, bg_dtype = ctx.misc
+        need_depth, need_rgb, need_bg = ctx.needs_input_grad[0], ctx.needs_input_grad[1], bg is not None and ctx.needs_input_grad[2]
+        if (g_rgb is None and g_bg is None) or not (need_depth or need_rgb or need_bg):
+            return (None,) * 8
+        dev = c.device
+        B, _, H, W = c.shape
+        g_rgb = None if g_rgb is None else g_rgb.to(torch.float32).contiguous()
+        g_bg = None if g_bg is None or bg is None else g_bg.to(torch.float32).contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        grad_rgb, grad_bg, g_shading = (new(B, 3, H, W) if need_rgb else None, new(B, 3, H, W) if need_bg else None,
+                                        new(B, H, W) if need_depth else None)
+        _call("gmpi_light_shade_images_backward_launch", dev, *_image_args(c), *_image_args(bg), shading.data_ptr(), _ptr(g_rgb), _ptr(g_bg),
+              _ptr(grad_rgb), _ptr(grad_bg), _ptr(g_shading), B, H, W)
+        g_depth = _middle_backward("hip", (blurred, k1d), xyz_last, light_dir, ka, kd, g_shading) if need_depth else None
+        return (g_depth, None if grad_rgb is None else grad_rgb.to(rgb_dtype), None if grad_bg is None else grad_bg.to(bg_dtype),
+                None, None, None, None, None)
 
 
 class LightRenderer:
     """Same constructor, attributes (`step`, `cur_ka`, `cur_kd`, `sphere_center`, ...) and method signatures as the
-    reference class (light_renderer.py:11-199); tensors live on the ROCm device of `batch_mpi`."""
+    reference class (light_renderer.py:11-199); tensors live on the ROCm device of `batch_mpi`.
+
+    One keyword of this package's own: `middle` says how the image-sized middle of the augmentation (blur, point cloud, normals, Lambert) is
+    differentiated, and how `render_shared` / `render_depth` run it.  "torch" (the default): torch autograd over a torch restatement of the two
+    kernels.  "hip": the adjoint kernels of csrc/light_kernels.hip (`_middle_backward`), atomics-free and bit-reproducible, and one autograd node
+    of kernels for the two layouts (`_ShadeImagesFunction`).  The forward of `render` and `shading_image` is the same kernels in both modes."""
 
     def __init__(self, *, sphere_center_z, sphere_r, ka_max=1.0, kd_max=0.0, n_grow_iters=1000, l_h_mean=0.0, l_h_std=0.2,
-                 l_v_mean=0.2, l_v_std=0.05, blur_ksize=9):
+                 l_v_mean=0.2, l_v_std=0.05, blur_ksize=9, middle="torch"):
+        if middle not in MIDDLES:
+            raise ValueError(f"middle must be one of {MIDDLES}, got {middle!r}")
+        self.middle = middle
         self.ka_max, self.kd_max, self.n_grow_iters = ka_max, kd_max, n_grow_iters
         self.cur_ka = self.cur_kd = 0.0
         self.l_h_mean, self.l_h_std, self.l_v_mean, self.l_v_std = l_h_mean, l_h_std, l_v_mean, l_v_std
@@ -348,7 +448,7 @@ class LightRenderer:
 
     # -- light_renderer.py:122-199 ------------------------------------------------------------------------------
     @torch.no_grad()
-    def _forward_kernels(self, vol, plane_ds, xyz_last, light_direction, ka, kd):
+    def _forward_kernels(self, vol, plane_ds, xyz_last, light_direction, ka, kd, want_blurred=False):
         dev = vol.device
         B, D, _, H, W = vol.shape
         depth, T = compute_depth(vol[:, :, 3:], plane_ds, want_transmittance=True)
@@ -357,7 +457,7 @@ class LightRenderer:
         out = torch.empty((B, D, 4, H, W), dtype=torch.float32, device=dev)
         strides = (ctypes.c_int64 * 5)(*vol.stride())
         _call("gmpi_light_apply_launch", dev, vol.data_ptr(), _DTYPES[vol.dtype], strides, shading.data_ptr(), out.data_ptr(), B, D, H, W)
-        return out, depth, T, shading
+        return (out, depth, T, shading, blurred) if want_blurred else (out, depth, T, shading)
 
     def render_shared(self, rgb: torch.Tensor, alpha: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor,
                       background: torch.Tensor = None):
@@ -365,7 +465,9 @@ class LightRenderer:
         texel, the same for every plane, so the shaded MPI is a shared-colour MPI again -- (clip(rgb * shading, 0, 1), alpha, clip(background
         * shading, 0, 1) or None), colours in float32.  Equal to `render(expand_shared_color(rgb, alpha, background))` split again; the step
         counter, cur_ka / cur_kd and the torch RNG advance as in `render`.  The depth comes from the differentiable `compute_depth` kernel (one
-        pass over the alpha planes), the rest is image-sized torch: differentiable w.r.t. rgb, alpha and background."""
+        pass over the alpha planes).  The rest is image-sized torch with middle="torch"; with middle="hip" it is one autograd node of kernels
+        (`_ShadeImagesFunction`: the shading has the bits of `shading_image()`, the colours are within one fp32 rounding of the torch mode's, the
+        backward is bit-reproducible).  Differentiable w.r.t. rgb, alpha and background, each gradient in its tensor's dtype."""
         _refuse_uint8("LightRenderer.render_shared", rgb, alpha, background)
         if not alpha.is_cuda:
             raise _lib.GmpiError("LightRenderer.render_shared needs tensors on a ROCm device (no CPU path)")
@@ -375,8 +477,8 @@ class LightRenderer:
         light_direction = self._next_light(alpha.shape[0])
         plane_ds = mpi_plane_dhws[:, :1].detach().to(dev)
         depth = compute_depth(alpha, plane_ds)                                                      # [B,1,H,W] float32
-        shade = self._shade_images(depth, mpi_tex_pix_xyz, light_direction)
-        return shade(rgb), alpha, (None if background is None else shade(background))
+        o_rgb, o_bg = self._shade_images(depth, mpi_tex_pix_xyz, light_direction, rgb, background)
+        return o_rgb, alpha, o_bg
 
     def render_depth(self, rgb: torch.Tensor, depth: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, *,
                      plane_z: torch.Tensor, z_range: float, n_z_bins: int, background: torch.Tensor = None):
@@ -385,7 +487,8 @@ class LightRenderer:
         depth-alpha MPI again -- (clip(rgb * shading, 0, 1), depth, clip(background * shading, 0, 1) or None), colours in float32, the depth
         image as it was handed in.  Equal to `render(expand_depth_alpha(rgb, depth, plane_z, z_lo, z_hi, background))` read back as such an MPI;
         the step counter, cur_ka / cur_kd and the torch RNG advance as in `render`.  The expected depth comes from the differentiable
-        `compute_depth_ramp` kernel (no alpha planes), the rest is image-sized torch: differentiable w.r.t. rgb, depth and background."""
+        `compute_depth_ramp` kernel (no alpha planes).  The rest is image-sized torch with middle="torch", one autograd node of kernels with
+        middle="hip", as in `render_shared`.  Differentiable w.r.t. rgb, depth and background, each gradient in its tensor's dtype."""
         from .depth_alpha import _check, depth_alpha_bounds
         _refuse_uint8("LightRenderer.render_depth", rgb, depth, background)
         if not depth.is_cuda:
@@ -395,8 +498,8 @@ class LightRenderer:
         light_direction = self._next_light(depth.shape[0])
         plane_ds = mpi_plane_dhws[:, :1].detach().to(depth.device)
         z = compute_depth_ramp(depth, plane_z, z_lo, z_hi, plane_ds)                                # [B,1,H,W] float32
-        shade = self._shade_images(z, mpi_tex_pix_xyz, light_direction)
-        return shade(rgb), depth, (None if background is None else shade(background))
+        o_rgb, o_bg = self._shade_images(z, mpi_tex_pix_xyz, light_direction, rgb, background)
+        return o_rgb, depth, o_bg
 
     def shading_image(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
         """The shading `render` multiplies the colours by, as an image: batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3]
@@ -404,7 +507,8 @@ class LightRenderer:
         `apply_shading(mpi, shading_image(mpi))` bit for bit (the depth, blur and shading kernels are `render`'s).  One step of the schedule: the
         step counter, cur_ka / cur_kd and the torch RNG advance exactly as in `render` -- call one or the other per step.  Nothing volume-sized is
         allocated in the forward.  Differentiable w.r.t. the alpha channel of batch_mpi: the expected depth comes from the differentiable
-        `compute_depth`, the image-sized middle back-propagates through its torch restatement (the one `_shade_images` runs)."""
+        `compute_depth`; the image-sized middle back-propagates through its torch restatement (the one `_shade_images` runs) with
+        middle="torch", through the two adjoint kernels of `_middle_backward` with middle="hip".  The forward is the same in both modes."""
         _refuse_uint8("LightRenderer.shading_image", batch_mpi)
         if not batch_mpi.is_cuda:
             raise _lib.GmpiError("LightRenderer.shading_image needs tensors on a ROCm device (no CPU path)")
@@ -417,15 +521,21 @@ class LightRenderer:
             return _ShadingFunction.apply(depth, self, xyz_last, light_direction, self.cur_ka, self.cur_kd)
         return self.shading(self.blurrer_func(depth), xyz_last, light_direction, self.cur_ka, self.cur_kd).unsqueeze(1)
 
-    def _shade_images(self, depth: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, light_direction: torch.Tensor):
-        """The image-sized middle of the augmentation in torch (blur, point cloud, normals, Lambert), shared by `render_shared` and
-        `render_depth`: expected depth [B,1,H,W] fp32 -> the function colour image -> clip(image * shading, 0, 1) in float32."""
+    def _shade_images(self, depth: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor, light_direction: torch.Tensor, rgb: torch.Tensor,
+                      background: torch.Tensor):
+        """The image-sized middle of the augmentation (blur, point cloud, normals, Lambert) and the shading of the colour images, shared by
+        `render_shared` and `render_depth`: expected depth [B,1,H,W] fp32, rgb, background or None -> (clip(rgb * shading, 0, 1),
+        clip(background * shading, 0, 1) or None) in float32.  middle="torch": torch ops under autograd; middle="hip": `_ShadeImagesFunction`."""
         dev = depth.device
         H, W = depth.shape[-2:]
+        if self.middle == "hip":
+            return _ShadeImagesFunction.apply(depth, rgb, background, self, mpi_tex_pix_xyz[-1, :, :, :3].detach(), light_direction, self.cur_ka,
+                                              self.cur_kd)
         xyz_last = mpi_tex_pix_xyz[-1, :, :, :3].detach().to(dev, torch.float32)
         blurred = _blur_torch(depth, _blur_matrix(H, self._k1d, dev), _blur_matrix(W, self._k1d, dev))
         shading = _shading_torch(blurred, xyz_last, light_direction.to(dev, torch.float32), self.cur_ka, self.cur_kd).unsqueeze(1)   # [B,1,H,W]
-        return lambda c: torch.clip(c.to(torch.float32) * shading, min=0.0, max=1.0)
+        shade = lambda c: torch.clip(c.to(torch.float32) * shading, min=0.0, max=1.0)
+        return shade(rgb), (None if background is None else shade(background))
 
     def _next_light(self, B: int) -> torch.Tensor:
         """One step of the augmentation's schedule: advances `step`, draws the light position on the sphere (consumes the torch RNG exactly as
@@ -445,7 +555,9 @@ class LightRenderer:
 
     def render(self, batch_mpi: torch.Tensor, mpi_plane_dhws: torch.Tensor, mpi_tex_pix_xyz: torch.Tensor) -> torch.Tensor:
         """batch_mpi [B,D,4,H,W], mpi_plane_dhws [D,3], mpi_tex_pix_xyz [D,H,W,>=3] -> shaded MPI [B,D,4,H,W] float32
-        (differentiable w.r.t. batch_mpi)."""
+        (differentiable w.r.t. batch_mpi: two streaming kernels for the volume-sized ends, the image-sized middle by `_middle_backward` in the
+        mode of this renderer -- torch autograd over a restatement, or with middle="hip" two adjoint kernels, where a cell whose un-normalised
+        normal is exactly 0 contributes 0 instead of the restatement's NaN; the forward does not depend on the mode)."""
         _refuse_uint8("LightRenderer.render", batch_mpi)
         if not batch_mpi.is_cuda:
             raise _lib.GmpiError("LightRenderer.render needs tensors on a ROCm device (no CPU path)")
