@@ -26,6 +26,7 @@
 // they cost 5 %), and the records of a plane must share one cache line across the sub-blocks for that to work (a plane-major table: +10 %).
 // Arithmetic: gmpi_device.hpp (bit-identical to the oracle in strict-order mode).
 #include "gmpi_device.hpp"
+#include "gmpi_band_masks.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -105,6 +106,7 @@ template <typename TexT> struct Geo {
     static constexpr int kPassItems = kRPP * kIPR;          // 240 (bf16) / 480 (fp32) active lanes
     static constexpr int kNP = (kMaxRows + kRPP - 1) / kRPP;  // DMA passes per plane at most: 3 as shipped, 5 with half the loader lanes
     static_assert(kNP == 3 || kNP == 5, "passes");
+    using Masks = LoaderMasks<kCols, kIPR, kRPP, kSubLanes, kPassItems, kNP>;  // the passes' exec masks from (items, rows, wave): scalar arithmetic
     static constexpr int kOffBytes = kThreads * 4;          // per-lane loader offsets (kept in LDS: a VGPR through the plane loop is dearer)
     static constexpr int kLdsBytes = kOffBytes + 2 * kBufBytes;
 };
@@ -318,7 +320,8 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
     constexpr int NSB = G::NSB, PPT = G::PPT, WPS = G::WPS, kSubLanes = G::kSubLanes;
     constexpr int kLineBytes = G::kLineBytes, kRowBytes = G::kRowBytes, kSubBytes = G::kSubBytes, kBufBytes = G::kBufBytes;
     constexpr int kRPP = G::kRPP, kPassItems = G::kPassItems;
-    constexpr bool BF = kES == 2;                              // 16-bit texels (bf16 or fp16): the two-pixel geometry, taps by ds_read_u16_d16_hi
+    using Masks = typename G::Masks;
+    constexpr bool BF = kES == 2;                             // 16-bit texels (bf16 or fp16): the two-pixel geometry, taps by ds_read_u16_d16_hi
     constexpr bool F16 = std::is_same<TexT, f16_t>::value;     // fp16: the loaded half is the value's fp16 pattern -- converted inside the FMA (v_fma_mix_f32)
 
     // `smem` is the ONLY __shared__ object of this kernel, i.e. it starts at LDS offset 0, and the staging buffers lead it: the [0,1] test below folds
@@ -476,15 +479,9 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
         float dots[PPT];
 #pragma unroll
         for (int q = 0; q < PPT; ++q) dots[q] = STRICT ? ray_dot(q) : 0.0f;  // (default mode applies the dot product once, at the end)
-        // ---- per wave: exec masks / pass count of the box of the plane last issued (recomputed when the box shape changes: a handful of
-        //      times per band).  (`three` of plane t is latched before plane t + 1 is issued: the range check of plane t reads it.) ----
-        uint64_t m_cur[kNP];
-        int dims_cur = 0;
-        bool three = false;  // the box of the plane last issued needs the LAST pass (the kNP-th: the third as shipped)
-        int np_cur = kNP - 1;  // kNP == 5: its number of passes (3, 4 or 5)
-#pragma unroll
-        for (int r = 0; r < kNP; ++r) m_cur[r] = 0;
-
+        // ---- the DMA of a plane: the exec masks of its passes are formed from the box shape by scalar arithmetic (gmpi_band_masks.hpp), for every plane
+        //      anew -- a sub-block's box changes its shape on every second plane step (profiles/band_masks.txt), and with nothing kept from plane to
+        //      plane every wave of the workgroup does the same work in front of its DMA, whatever its box does ----
         auto issue = [&](const uint4& rl, uint32_t g_off, auto ub) {  // DMA of the plane with record part L = rl into buffer U (this wave's part of its sub-block's box)
             constexpr int U = decltype(ub)::value;
             const int dims = static_cast<int>(rl.z);
@@ -494,46 +491,58 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
             const u32x4 rsrc = {static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(rl.x))),
                                 static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(rl.y))), 0x80000000u, 0x00020000u};
             if (dims >= 0) {  // the box lies inside the texture: lanes of the box load, the others are switched off
-                if (dims != dims_cur) {
-                    const int nq = dims & 31, rows = dims >> 5;
-                    dims_cur = dims;
-                    three = rows > (kNP - 1) * kRPP;
-                    np_cur = max((rows + kRPP - 1) / kRPP, 3);
-                    int l_col, l_line, l_row;
-                    bool l_on;
-                    loader_pos(l_col, l_line, l_row, l_on);
-#pragma unroll
-                    for (int r = 0; r < kNP; ++r) {
-                        m_cur[r] = __ballot(l_on && l_col < nq && l_row + r * kRPP < rows);
-                        if (abl_noload) m_cur[r] = 0;
-                    }
-                }
+                const int nq = dims & 31, rows = dims >> 5;
+                const bool three = rows > (kNP - 1) * kRPP;  // the box needs the LAST pass (the kNP-th: the third as shipped)
+                // passes 0 ... last: the ones below the last move whole passes of rows (mask `cols`), the last one what is left (`part`); `last` is a literal
+                // on every path, so a path forms its masks in under 30 scalar instructions, whatever kNP (a row run per PASS cost fp32 volumes 3-5 %)
+                auto masks = [&](auto lc) {
+                    typename Masks::Passes mk = Masks::passes(nq, rows, wj, decltype(lc)::value);
+                    if (abl_noload) mk.cols = mk.part = 0;
+                    return mk;
+                };
+                const uint64_t none = 0;
                 if constexpr (kNP == 3) {
-                    if (three) dma16x3<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, rsrc, wave_dst, m_cur[0], m_cur[1], m_cur[2]);
-                    else dma16x2<U * kBufBytes, kPassItems * 16>(g_off, pass_off, rsrc, wave_dst, m_cur[0], m_cur[1]);
+                    if (three) {
+                        const auto mk = masks(ic<2>{});
+                        dma16x3<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, rsrc, wave_dst, mk.cols, mk.cols, mk.part);
+                    } else if (rows > kRPP) {
+                        const auto mk = masks(ic<1>{});
+                        dma16x2<U * kBufBytes, kPassItems * 16>(g_off, pass_off, rsrc, wave_dst, mk.cols, mk.part);
+                    } else {
+                        const auto mk = masks(ic<0>{});
+                        dma16x2<U * kBufBytes, kPassItems * 16>(g_off, pass_off, rsrc, wave_dst, mk.part, none);
+                    }
                 } else {  // (a pass whose mask is empty still takes its turn on the CU's vector-memory issue path: issue what the box needs)
-                    if (np_cur == 5) dma16x5<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, pass_off3, pass_off4, rsrc, wave_dst, m_cur[0], m_cur[1], m_cur[2], m_cur[3], m_cur[4]);
-                    else if (np_cur == 4) dma16x4<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, pass_off3, rsrc, wave_dst, m_cur[0], m_cur[1], m_cur[2], m_cur[3]);
-                    else dma16x3<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, rsrc, wave_dst, m_cur[0], m_cur[1], m_cur[2]);
+                    const int np_cur = max((rows + kRPP - 1) / kRPP, 3);  // its number of passes (3, 4 or 5)
+                    if (np_cur == 5) {
+                        const auto mk = masks(ic<4>{});
+                        dma16x5<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, pass_off3, pass_off4, rsrc, wave_dst, mk.cols, mk.cols, mk.cols, mk.cols, mk.part);
+                    } else if (np_cur == 4) {
+                        const auto mk = masks(ic<3>{});
+                        dma16x4<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, pass_off3, rsrc, wave_dst, mk.cols, mk.cols, mk.cols, mk.part);
+                    } else if (rows > 2 * kRPP) {
+                        const auto mk = masks(ic<2>{});
+                        dma16x3<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, rsrc, wave_dst, mk.cols, mk.cols, mk.part);
+                    } else {  // (one or two passes of rows: rare, the third pass moves nothing)
+                        typename Masks::Passes mk = Masks::passes(nq, rows, wj);
+                        if (abl_noload) mk.cols = mk.part = 0;
+                        dma16x3<U * kBufBytes, kPassItems * 16>(g_off, pass_off, pass_off2, rsrc, wave_dst, mk[0], mk[1], none);
+                    }
                 }
             } else {  // zeros padding: every lane of the box rows is active, lanes outside the texture get the out-of-range offset
                 const Shape h = shape_unpack(static_cast<uint32_t>(dims));
                 const int rows = h.rows;
                 const uint32_t clo = h.clo, ncol = h.ncol, llo = 4 * h.rlo, nline = 4 * h.nrow;
-                dims_cur = dims;
-                three = rows > (kNP - 1) * kRPP;
                 const int npk = (rows + kRPP - 1) / kRPP;
-                np_cur = max(npk, 3);
                 int l_col, l_line, l_row;
                 bool l_on;
                 loader_pos(l_col, l_line, l_row, l_on);
 #pragma unroll
                 for (int r = 0; r < kNP; ++r) {
-                    m_cur[r] = __ballot(l_on && l_row + r * kRPP < rows);
-                    if (abl_noload) m_cur[r] = 0;
                     if (r < npk) {
+                        const uint64_t m = abl_noload ? 0 : Masks::rowmask(rows - r * kRPP, wj);
                         const bool ok = (static_cast<uint32_t>(l_col) - clo < ncol) & (static_cast<uint32_t>(l_line + 4 * r * kRPP) - llo < nline);
-                        dma16(ok ? g_off : 0x80000000u, r * pass_off, rsrc, wave_dst + static_cast<uint32_t>(U * kBufBytes + r * (kPassItems * 16)), m_cur[r]);
+                        dma16(ok ? g_off : 0x80000000u, r * pass_off, rsrc, wave_dst + static_cast<uint32_t>(U * kBufBytes + r * (kPassItems * 16)), m);
                     }
                 }
             }
