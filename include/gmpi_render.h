@@ -209,8 +209,8 @@ int gmpi_mpi_render_launch(const GmpiRenderParams *params, void *stream);
  *   WAVE, BAND, DMA and unknown values: GMPI_E_VARIANT.
  * GMPI_DTYPE_U8 with these strides is forwarded to gmpi_mpi_render_launch (the interleaved uint8 layout above: same kernels, same bits).
  * gmpi_mpi_render_launch and every other entry but gmpi_mpi_render_layers_backward_launch (below) keep refusing the layout for the float types
- * (GMPI_E_STRIDE).  Not built for the layout: the atomics-free backward pair, geometry gradients, the chunked, shaded, shared-colour and depth-alpha
- * forms, the strip and band kernels, texel strides other than 4.  gmpi_query(42) == 1 says the two entries are built in.
+ * (GMPI_E_STRIDE); the geometry gradients have an entry of their own, gmpi_mpi_render_layers_geometry_backward_launch.  Not built for the layout: the
+ * atomics-free backward pair, the chunked, shaded, shared-colour and depth-alpha forms, the strip and band kernels, texel strides other than 4.  gmpi_query(42) == 1 says the two entries are built in.
  */
 int gmpi_mpi_render_layers_launch(const GmpiRenderParams *params, void *stream);
 
@@ -365,6 +365,35 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams *params, 
                                                 float *grad_z_dir, float *grad_dhw, void *stream);
 /* Bytes of workspace gmpi_mpi_render_geometry_backward_launch needs for the eye / z_dir sums, and with want_dhw != 0 the plane sums too. */
 uint64_t gmpi_render_geometry_backward_workspace_bytes(const GmpiRenderParams *params, int want_dhw);
+
+/*
+ * gmpi_mpi_render_geometry_backward_ex_launch over the volume in the formats it is STORED in, read in place: the same four gradients, the same
+ * tiles, slabs and fixed-order sums (no atomics: bit-reproducible), nothing the size of a volume is allocated, copied or written.  For equal values
+ * the outputs have the bits of the volume entry over the planar float volume (GMPI_FLAG_STRICT_ORDER or not: the pass is one text over tap sources).
+ *   gmpi_mpi_render_u8_geometry_backward_launch      params as gmpi_mpi_render_launch takes a GMPI_DTYPE_U8 volume -- planar codes, or channels-last
+ *       texels (rgba_stride[2] == 1 and rgba_stride[4] == 4: one 4-byte load per tap, a base pointer at any byte): told by the strides, as the forward
+ *       tells them.  Every tap is the correctly rounded c / 255, the value the forward reads.  Any other rgba_dtype: GMPI_E_DTYPE.  Without
+ *       GMPI_FLAG_STRICT_ORDER, where the staged 8-bit forward may have written transmittance_out (variant not GATHER, tensors it can stage), that value
+ *       is not read: the forward sums the CODES and scales once, and under exactly opaque texels (four taps of 255) its 1 - alpha differs from the
+ *       sweep's by orders of magnitude; every pixel walks the alpha texels with the sweep's own arithmetic instead (one more pass over the taps).
+ *   gmpi_mpi_render_layers_geometry_backward_launch  params as gmpi_mpi_render_layers_backward_launch takes them: channels-last float layers,
+ *       rgba_stride [s_M, s_D, 1, s_row, 4], F32 / BF16 / F16 (one 16- / 8-byte load per tap at the element's alignment).  Planar or any other strides:
+ *       GMPI_E_STRIDE; GMPI_DTYPE_U8: GMPI_E_DTYPE (the entry above takes channels-last codes).
+ * Both: rgb_out, depth_out and status may be NULL; transmittance_out as for the volume entry (the sweep starts from it, or re-walks the alpha texels
+ * where it has underflowed: runs of exactly opaque codes); grad_transmittance may be NULL.  A NULL grad_rgb is GMPI_E_NULL; with no output wanted
+ * GMPI_OK and nothing is launched; N == 0 is GMPI_OK at once; N or M > 65535: GMPI_E_SHAPE.  The per-view and per-plane sums need
+ * gmpi_render_geometry_inplace_workspace_bytes(params, grad_dhw != NULL) bytes in params->workspace (256-byte aligned; otherwise GMPI_E_WORKSPACE).
+ * Nothing is written on any refusal.  No status bits are set.  gmpi_query(48) == 1 says the three entries are built in.
+ */
+int gmpi_mpi_render_u8_geometry_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                                const float *grad_transmittance /* or NULL */, float *grad_ray_dir, float *grad_eye_pos,
+                                                float *grad_z_dir, float *grad_dhw, void *stream);
+int gmpi_mpi_render_layers_geometry_backward_launch(const GmpiRenderParams *params, const float *grad_rgb, const float *grad_depth,
+                                                    const float *grad_transmittance /* or NULL */, float *grad_ray_dir, float *grad_eye_pos,
+                                                    float *grad_z_dir, float *grad_dhw, void *stream);
+/* gmpi_render_geometry_backward_workspace_bytes for the params of the two entries above (that query keeps answering 0 for GMPI_DTYPE_U8 and for the
+ * layers' strides): the same size -- it depends on N, H, W and D only --, also for a planar float volume.  0 for params neither entry would take. */
+uint64_t gmpi_render_geometry_inplace_workspace_bytes(const GmpiRenderParams *params, int want_dhw);
 
 /*
  * Shared-colour layout: what GMPI's generator produces before it concatenates (networks_cond_on_pos_enc.py:950-975 with gmpi.yml:137-145) -- ONE
@@ -858,7 +887,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in; 43 is unused (-1); 44 whether their in-place backward
  * (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in; 45 is unused (-1); 46 whether the backward of the shading augmentation's image-sized middle and
  * the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch,
- * gmpi_light_shade_images_backward_launch) are built in.  Unknown -> -1.  */
+ * gmpi_light_shade_images_backward_launch) are built in; 47 is unused (-1); 48 whether the geometry backward over 8-bit volumes and float layers in place
+ * (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in.
+ * Unknown -> -1.  */
 int gmpi_query(int32_t what);
 
 const char *gmpi_version_string(void);

@@ -14,7 +14,7 @@ _LIB = None
 
 ABI_VERSION = 2
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
-DTYPE_U8 = 3   # 8 bits per channel, code c = c / 255: the forward render only (every other entry returns GMPI_E_DTYPE for it)
+DTYPE_U8 = 3   # 8 bits per channel, code c = c / 255: the forward render and gmpi_mpi_render_u8_geometry_backward_launch (every other entry returns GMPI_E_DTYPE for it)
 FLAG_ALIGN_CORNERS, FLAG_OUT_PM1, FLAG_CHECK_LAST_PLANE, FLAG_CHECK_RANGE, FLAG_STRICT_ORDER, FLAG_HINT_FRONTAL, FLAG_HINT_TILTED = 1, 2, 4, 8, 16, 32, 64
 FLAG_HINT_OBLIQUE = 256     # advisory: some camera axis more than 0.35 rad off the MPI normal (views that share an MPI then stay on the tile kernel)
 FLAG_GRAD_OVERWRITE = 128   # backward only: grad_rgba's content is not needed (with the backward's workspace every element is written: no zero-fill)
@@ -32,6 +32,9 @@ EXPORTS = (
     "gmpi_mpi_render_geometry_backward_launch",
     "gmpi_mpi_render_backward_ex_launch",
     "gmpi_mpi_render_geometry_backward_ex_launch",
+    "gmpi_mpi_render_u8_geometry_backward_launch",
+    "gmpi_mpi_render_layers_geometry_backward_launch",
+    "gmpi_render_geometry_inplace_workspace_bytes",
     "gmpi_mpi_render_chunk_launch",
     "gmpi_mpi_render_chunk_backward_launch",
     "gmpi_mpi_render_layers_launch",
@@ -243,6 +246,13 @@ def load_library():
                                                        ctypes.POINTER(ctypes.c_int64), vp]
     lib.gmpi_mpi_render_geometry_backward_ex_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    # the geometry backward over 8-bit volumes (planar or channels-last) and float layers in place (gmpi_query(48)): the _ex signature, and their workspace query
+    lib.gmpi_mpi_render_u8_geometry_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_u8_geometry_backward_launch.argtypes = list(lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes)
+    lib.gmpi_mpi_render_layers_geometry_backward_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_layers_geometry_backward_launch.argtypes = list(lib.gmpi_mpi_render_geometry_backward_ex_launch.argtypes)
+    lib.gmpi_render_geometry_inplace_workspace_bytes.restype = ctypes.c_uint64
+    lib.gmpi_render_geometry_inplace_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.c_int]
     lib.gmpi_mpi_render_chunk_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_chunk_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiCarry), vp]
     lib.gmpi_mpi_render_chunk_backward_launch.restype = ctypes.c_int

@@ -69,6 +69,8 @@ hipError_t launch_backward_layers(const KParams& p, int dtype, const float* g_rg
 bool backward_layers_tile_supports(const KParams& p, int dtype, const int64_t* gstride);   // render_backward.hip
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
+hipError_t launch_backward_geometry_inplace(const KParams& p, int dtype, bool layers, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray,
+                                            float* g_eye, float* g_z, float* g_dhw, hipStream_t stream);   // render_backward_geometry.hip
 hipError_t launch_backward_geometry_layout(const KParams& p, int dtype, const SharedK& sh, const DepthK* dk, const float* g_rgb, const float* g_depth,
                                            const float* g_T, float* g_ray, float* g_eye, float* g_z, float* g_dhw, float* g_pz, hipStream_t stream);   // render_backward_geometry.hip
 
@@ -680,6 +682,65 @@ int gmpi_mpi_render_geometry_backward_ex_launch(const GmpiRenderParams* params, 
                                            static_cast<hipStream_t>(stream)));
 }
 
+// ---- the geometry backward over the volume as STORED, read in place: 8-bit codes (planar, or channels-last: told by the strides, as the forward tells
+// them) and channels-last float layers.  Entries of their own: the two above keep refusing GMPI_DTYPE_U8 and the layers' strides.  The argument checks
+// after the struct are geometry_backward_args'; the workspace is the volume entry's size (N, H, W, D only), asked for through the query below.
+int gmpi_mpi_render_u8_geometry_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, const float* grad_transmittance,
+                                                float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir, float* grad_dhw, void* stream) {
+    if (params == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    if (params->N == 0) return GMPI_OK;  // no views
+    if (params->rgba_dtype != GMPI_DTYPE_U8) return GMPI_E_DTYPE;   // (the float types: gmpi_mpi_render_geometry_backward_ex_launch)
+    KParams p;
+    int rc = to_kparams(params, p, false, true, true);
+    if (rc != GMPI_OK) return rc;
+    bool launch;
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    if (!launch) return rc;
+    // The sweep divides the transmittance it starts from by ITS alpha samples (per tap c / 255, then the fma chain).  Without GMPI_FLAG_STRICT_ORDER the
+    // staged 8-bit forward (render_u8.hip) samples the CODES and scales the sum by RN(1 / 255): where all four taps are 255 -- exactly opaque texels, the
+    // common case of a stored MPI -- its om = (1 - a) + 1e-10 and the sweep's differ in the last bits of a, i.e. by orders of magnitude in om (1e-10
+    // against 6e-8), and so would every T in front of that plane.  Where that kernel may have written transmittance_out (the forward's own routing: not
+    // GATHER, tensors it can stage; some of its planes fall back to per-tap sampling, which cannot be told from here) the value is NOT used: every pixel
+    // walks the alpha texels with the sweep's arithmetic, as it does where the forward's value has underflowed.  The strict-order forwards and the gather
+    // kernel sample per tap: their value is the sweep's own product and is used.
+    if ((p.flags & GMPI_FLAG_STRICT_ORDER) == 0 && params->variant != GMPI_VARIANT_GATHER && u8_variant_supports(p)) p.T_out = nullptr;
+    return hip_rc(launch_backward_geometry_inplace(p, GMPI_DTYPE_U8, false, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos, grad_z_dir,
+                                                   grad_dhw, static_cast<hipStream_t>(stream)));
+}
+
+int gmpi_mpi_render_layers_geometry_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth,
+                                                    const float* grad_transmittance, float* grad_ray_dir, float* grad_eye_pos, float* grad_z_dir,
+                                                    float* grad_dhw, void* stream) {
+    if (params == nullptr) return GMPI_E_NULL;
+    if (params->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    if (params->N == 0) return GMPI_OK;  // no views
+    const int rs = layers_strides_ok(params);   // (the order of layers_backward_args: the strides, the type, every other field)
+    if (rs != GMPI_OK) return rs;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) return GMPI_E_DTYPE;   // (codes: gmpi_mpi_render_u8_geometry_backward_launch)
+    KParams p;
+    int rc = to_kparams_layers(params, p, true);
+    if (rc != GMPI_OK) return rc;
+    bool launch;
+    rc = geometry_backward_args(p, grad_rgb, grad_ray_dir, grad_eye_pos, grad_z_dir, grad_dhw, &launch);
+    if (!launch) return rc;
+    return hip_rc(launch_backward_geometry_inplace(p, params->rgba_dtype, true, grad_rgb, grad_depth, grad_transmittance, grad_ray_dir, grad_eye_pos, grad_z_dir,
+                                                   grad_dhw, static_cast<hipStream_t>(stream)));
+}
+
+// gmpi_render_geometry_backward_workspace_bytes for the params of the two entries above (that query answers 0 for GMPI_DTYPE_U8 and for the layers'
+// strides, and stays so): the same size -- it depends on N, H, W and D only -- for 8-bit volumes in either order, float layers, and planar float volumes.
+uint64_t gmpi_render_geometry_inplace_workspace_bytes(const GmpiRenderParams* params, int want_dhw) {
+    if (params == nullptr || params->struct_size != sizeof(GmpiRenderParams)) return 0;
+    KParams p;
+    int rc;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) rc = to_kparams(params, p, false, true, true);
+    else if (layers_strides_ok(params) == GMPI_OK) rc = to_kparams_layers(params, p, true);
+    else rc = to_kparams(params, p, false, true);
+    if (rc != GMPI_OK || p.N == 0) return 0;
+    return geometry_backward_workspace_bytes(p, want_dhw != 0);
+}
+
 // shared-colour entries: params->rgba = the alpha planes (rgba_stride[2] ignored); checks of to_kparams + the GmpiSharedColor struct.
 // forward: the forward launch and its support query, which know GMPI_VARIANT_LDS; the backward knows AUTO and GATHER only.
 static int to_shared(const GmpiRenderParams* params, const GmpiSharedColor* shared, bool forward, KParams& p, SharedK& sh) {
@@ -1182,6 +1243,7 @@ int gmpi_query(int32_t what) {
         case 42: return 1;  // channels-last float layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports) are built in  (41: unused)
         case 44: return 1;  // the in-place backward of channels-last float layers (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in  (43: unused)
         case 46: return 1;  // the backward of the shading augmentation's image-sized middle and the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch, gmpi_light_shade_images_backward_launch) are built in  (45: unused)
+        case 48: return 1;  // the geometry backward over 8-bit volumes and float layers in place (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in  (47: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

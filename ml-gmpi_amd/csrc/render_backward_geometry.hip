@@ -16,12 +16,16 @@
 // written to this tile's slot of a slab in the caller's workspace; geometry_reduce_kernel then sums the slabs in a fixed order.  No atomics: every
 // output is bit-reproducible from run to run.  Any view_to_mpi, any ray field (each pixel gathers its own taps), 64-bit volume offsets.
 //
-// ONE frame (geometry_pixel_kernel), three TAP SOURCES, selected by the layout structs the kernel is instantiated with (SourceOf).  The frame
+// ONE frame (geometry_pixel_kernel), four TAP SOURCES, selected by the storage type and the layout structs the kernel is instantiated with (SourceOf).  The frame
 // depends on the input layout in two places only: where the 4 x 4 tap values
 // t[c][nw, ne, sw, se] of a plane come from, and where the sweep's starting transmittance comes from.  A source is a small struct with
 //   start(bp, ...)            the per-pixel setup (bwd_pixel_setup / bwd_pixel_setup_with, gmpi_backward.hpp) with the layout's transmittance walk
 //   taps<STRICT>(k, ix, iy, q)   the 16 tap values of plane k and the fractions; false = the plane is the identity of this pixel's sweep: skipped
-//   VolumeSource   the RGBA volume (no layout struct): four channels of one plane; never skips
+//   VolumeSource   the RGBA volume (no layout struct): four channels of one plane; never skips.  float / bf16_t / f16_t, and u8_t: planar 8-bit codes read
+//                  in place, every tap through to_f32(u8_t), the correctly rounded c / 255 the forward reads
+//   TexelSource    the RGBA volume stored as whole texels, read in place (no layout struct; selected by the storage type): rgba8_t, channels-last
+//                  8-bit codes, one 4-byte load per tap; rgba32f_t / rgba16h_t / rgba16b_t, channels-last float layers, one 16- / 8-byte load per
+//                  tap at the element's alignment.  VolumeSource's values, padding and start: for equal values the volume entry's bits
 //   SharedSource   the shared-colour layout (SharedK): channels 0-2 from rgb[m] (background[m] on plane D - 1 when one is
 //                  given: uniform per plane), channel 3 from alpha[m, k]; the start is the volume's (KParams carries the alpha planes with s_chan = 0)
 //   DepthSource    the depth-alpha layout (SharedK, DepthK): channel 3's taps are the RAMP of each depth tap (depth_ramp: the forward's
@@ -127,6 +131,43 @@ struct VolumeSource {
     }
 };
 
+// The RGBA volume stored as whole texels, read in place: rgba8_t (channels-last 8-bit codes: one 4-byte load per tap, then texel_code + unorm8_to_f32
+// per channel -- to_f32(u8_t)'s value, the one the forward reads) and rgba32f_t / rgba16h_t / rgba16b_t (channels-last float layers: one 16- / 8-byte
+// load per tap at the element's alignment).  KParams' strides count BYTES, s_chan is unused; offsets are 64-bit.  The padding is VolumeSource's
+// (tap_pos / pad_taps: address clamped, value masked) and so is every value: the frame's results are, bit for bit, those of the planar fp32 /
+// 16-bit volume of the same values.  The start is the volume's (total_transmittance walks the texels through gather_sample's texel forms).
+template <typename TexT>
+struct TexelSource {
+    static constexpr bool kSkips = false;
+    static constexpr bool kPlaneZ = false;
+    static constexpr bool kForwardAlpha = false;
+    const TexT* __restrict__ vol;
+    __device__ __forceinline__ TexelSource(const KParams& p, const BwdView& vw)
+        : vol(tex_offset(static_cast<const TexT*>(p.rgba), static_cast<int64_t>(vw.m) * p.s_mpi)) {}
+    template <bool AC, bool STRICT>
+    __device__ __forceinline__ void start(BwdPixel& bp, const KParams& p, const BwdView& vw, const BwdParams& b, int n, int px, int py, bool active) const {
+        bwd_pixel_setup<TexT, AC, true>(bp, p, vw, n, px, py, active, b.g_rgb, b.g_depth, b.g_T, vol);
+    }
+    __device__ __forceinline__ static float chan(uint32_t t, int c) { return unorm8_to_f32(texel_code(t, c)); }
+    template <typename T>
+    __device__ __forceinline__ static float chan(const T& t, int c) { return to_f32(t.c[c]); }
+    template <bool STRICT>
+    __device__ __forceinline__ bool taps(const KParams& p, int k, int Ht, int Wt, float ix, float iy, Taps& q) const {
+        constexpr int64_t kTexel = sizeof(TexT);
+        const TexT* __restrict__ pl = tex_offset(vol, static_cast<int64_t>(k) * p.s_plane);
+        const TapPos tp = tap_pos(Ht, Wt, ix, iy, q);
+        const int64_t oa = static_cast<int64_t>(tp.ya) * p.s_row, ob = static_cast<int64_t>(tp.yb) * p.s_row;
+        const auto t_nw = load_texel(pl, oa + kTexel * tp.xa), t_ne = load_texel(pl, oa + kTexel * tp.xb);
+        const auto t_sw = load_texel(pl, ob + kTexel * tp.xa), t_se = load_texel(pl, ob + kTexel * tp.xb);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float v[4] = {chan(t_nw, c), chan(t_ne, c), chan(t_sw, c), chan(t_se, c)};
+            pad_taps(tp, v, q.t[c]);
+        }
+        return true;
+    }
+};
+
 // the colour image of plane k of MPI m: rgb, or the background on the last plane (uniform per plane)
 template <typename TexT>
 struct ColourImages {
@@ -224,7 +265,11 @@ struct DepthSource {
 };
 
 template <typename TexT, typename... Extra> struct SourceOf;
-template <typename TexT> struct SourceOf<TexT> { using type = VolumeSource<TexT>; };
+template <typename TexT> struct SourceOf<TexT> { using type = VolumeSource<TexT>; };   // (u8_t too: planar codes, every tap through to_f32(u8_t))
+template <> struct SourceOf<rgba8_t> { using type = TexelSource<rgba8_t>; };
+template <> struct SourceOf<rgba32f_t> { using type = TexelSource<rgba32f_t>; };
+template <> struct SourceOf<rgba16h_t> { using type = TexelSource<rgba16h_t>; };
+template <> struct SourceOf<rgba16b_t> { using type = TexelSource<rgba16b_t>; };
 template <typename TexT> struct SourceOf<TexT, SharedK> { using type = SharedSource<TexT>; };
 template <typename TexT> struct SourceOf<TexT, SharedK, DepthK> { using type = DepthSource<TexT>; };
 template <typename TexT> struct SourceOf<TexT, SharedK, DepthK, PlaneZGrad> { using type = DepthSource<TexT, true>; };
@@ -460,9 +505,10 @@ uint64_t geometry_backward_workspace_bytes(const KParams& p, bool want_dhw, bool
 // g_dhw != nullptr, pz != nullptr) bytes when any of g_eye, g_z, g_dhw, the plane_z gradient is wanted (checked by the caller).  pixel(type, AC,
 // STRICT, DHW, grid, b, slab, tiles_x, n_tiles) launches the layout's pixel kernel; the slab reducer is the same for all.  pz: the depth-alpha
 // layout's DepthK when the gradient w.r.t. plane_z is wanted (g_pz [M,D], or [D] for one table: overwritten; `pixel` launches a PZ instance).
-template <typename Pixel>
-static hipError_t launch_geometry_passes(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_eye, float* g_z,
-                                         float* g_dhw, hipStream_t stream, Pixel&& pixel, const DepthK* pz = nullptr, float* g_pz = nullptr) {
+// types(f): calls f(TypeTag<storage type>{}) for the launch's storage type -- dispatch_dtype for the planar float volumes, the storage formats read in place below.
+template <typename Types, typename Pixel>
+static hipError_t launch_geometry_passes_over(const KParams& p, Types&& types, const float* g_rgb, const float* g_depth, const float* g_T, float* g_eye, float* g_z,
+                                              float* g_dhw, hipStream_t stream, Pixel&& pixel, const DepthK* pz = nullptr, float* g_pz = nullptr) {
     using namespace bwgeo;
     BwdParams b{};
     b.g_rgb = g_rgb, b.g_depth = g_depth, b.g_T = g_T;
@@ -470,7 +516,7 @@ static hipError_t launch_geometry_passes(const KParams& p, int dtype, const floa
     float* slab = (g_eye || g_z || g_dhw || g_pz) ? static_cast<float*>(p.ws) : nullptr;
     const int tx = tiles_x_of(p), nt = tiles_of(p);
     const dim3 grid(xcd_grid_per_group(nt, nt), p.N);
-    dispatch_dtype(dtype, [&](auto t) {
+    types([&](auto t) {
         dispatch_bool(p.flags & GMPI_FLAG_ALIGN_CORNERS, [&](auto AC) {
             dispatch_bool(p.flags & GMPI_FLAG_STRICT_ORDER, [&](auto STRICT) {
                 dispatch_bool(want_dhw, [&](auto DHW) { pixel(t, AC, STRICT, DHW, grid, b, slab, tx, nt); });
@@ -488,12 +534,34 @@ static hipError_t launch_geometry_passes(const KParams& p, int dtype, const floa
     }
     return hipGetLastError();
 }
+template <typename Pixel>
+static hipError_t launch_geometry_passes(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_eye, float* g_z,
+                                         float* g_dhw, hipStream_t stream, Pixel&& pixel, const DepthK* pz = nullptr, float* g_pz = nullptr) {
+    return launch_geometry_passes_over(p, [&](auto&& f) { dispatch_dtype(dtype, f); }, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream, pixel, pz, g_pz);
+}
 #define GMPI_GEOMETRY_INSTANCE(kernel, ...) kernel<typename decltype(t)::type, decltype(AC)::value, decltype(STRICT)::value, decltype(DHW)::value, ##__VA_ARGS__>
 
 hipError_t launch_backward_geometry(const KParams& p, int dtype, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray, float* g_eye,
                                     float* g_z, float* g_dhw, hipStream_t stream) {
     return launch_geometry_passes(p, dtype, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream,
                                   [&](auto t, auto AC, auto STRICT, auto DHW, dim3 grid, const BwdParams& b, float* slab, int tx, int nt) {
+        hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt);
+    });
+}
+
+// The same passes over the RGBA volume in the formats it is STORED in, read in place: dtype GMPI_DTYPE_U8 -- planar codes (u8_t: VolumeSource) or, when
+// to_kparams marked the strides channels-last (u8_interleaved), packed texels (rgba8_t) -- or, layers: channels-last float layers (rgba32f_t /
+// rgba16h_t / rgba16b_t; p's strides in bytes, as to_kparams_layers leaves them).  The frame, the tiles, the slabs and the reducer are the volume's.
+hipError_t launch_backward_geometry_inplace(const KParams& p, int dtype, bool layers, const float* g_rgb, const float* g_depth, const float* g_T, float* g_ray,
+                                            float* g_eye, float* g_z, float* g_dhw, hipStream_t stream) {
+    if (layers ? (dtype != GMPI_DTYPE_F32 && dtype != GMPI_DTYPE_F16 && dtype != GMPI_DTYPE_BF16) : dtype != GMPI_DTYPE_U8) return hipErrorInvalidValue;
+    auto types = [&](auto&& f) {
+        if (!layers) return u8_interleaved(p) ? f(TypeTag<rgba8_t>{}) : f(TypeTag<u8_t>{});
+        if (dtype == GMPI_DTYPE_F32) return f(TypeTag<rgba32f_t>{});
+        return dtype == GMPI_DTYPE_F16 ? f(TypeTag<rgba16h_t>{}) : f(TypeTag<rgba16b_t>{});
+    };
+    return launch_geometry_passes_over(p, types, g_rgb, g_depth, g_T, g_eye, g_z, g_dhw, stream,
+                                       [&](auto t, auto AC, auto STRICT, auto DHW, dim3 grid, const BwdParams& b, float* slab, int tx, int nt) {
         hipLaunchKernelGGL((GMPI_GEOMETRY_INSTANCE(bwgeo::geometry_pixel_kernel)), grid, dim3(bwgeo::kGT), 0, stream, p, b, g_ray, slab, tx, nt);
     });
 }

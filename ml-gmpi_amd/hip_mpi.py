@@ -32,7 +32,7 @@ _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch
 
 
 def _refuse_uint8(what: str, *tensors) -> None:
-    """uint8 storage (code c = c / 255, quantized.py) is read by the forward render of an RGBA volume alone.  Everything else refuses it here,
+    """uint8 storage (code c = c / 255, quantized.py) is read by the render of an RGBA volume alone (forward, and the geometry backward in place).  Everything else refuses it here,
     before any launch, instead of casting the codes 0..255 to values."""
     for t in tensors:
         if t is not None and t.dtype is torch.uint8:
@@ -388,6 +388,10 @@ _Kind = collections.namedtuple("_Kind", "name expand first geometry_entry")
 _SHARED_COLOUR = _Kind("shared-colour", "expand_shared_color", "alpha", "gmpi_mpi_render_shared_geometry_backward_launch")
 _DEPTH_ALPHA = _Kind("depth-alpha", "expand_depth_alpha", "depth", "gmpi_mpi_render_depth_geometry_backward_launch")
 # ... of the depth-alpha geometry backward when plane_z needs a gradient (grad_plane_z before the stream), and its workspace query
+# the geometry backward over the volume as stored, read in place (geometry_grad="all"): 8-bit codes on render_views, float layers on render_views_layers;
+# grad_transmittance is always an argument (NULL: unused), and the workspace has a query of its own
+_U8_GEOMETRY_ENTRY, _LAYERS_GEOMETRY_ENTRY = "gmpi_mpi_render_u8_geometry_backward_launch", "gmpi_mpi_render_layers_geometry_backward_launch"
+_INPLACE_GEOMETRY_QUERY = "gmpi_render_geometry_inplace_workspace_bytes"
 _DEPTH_PZ_ENTRY, _DEPTH_PZ_QUERY = "gmpi_mpi_render_depth_geometry_backward_pz_launch", "gmpi_render_depth_geometry_backward_workspace_bytes"
 # render_views_depth(depth_backward=...): the C entry of the backward (same signature, same structs)
 _DEPTH_BACKWARD_ENTRIES = {"pixel": "gmpi_mpi_render_depth_backward_launch", "tile": "gmpi_mpi_render_depth_backward_tile_launch",
@@ -711,7 +715,11 @@ class MPI(nn.Module):
                      an extension, the reference builds its grid under torch.no_grad(), mpi.py:65) on the volume entry, `render_views`; the
                      two layout entries raise NotImplementedError for such tensors | "all": everything True gives, and the gradient reaches the
                      four tensors on `render_views_shared` and `render_views_depth` too (gmpi_mpi_render_shared_geometry_backward_launch /
-                     gmpi_mpi_render_depth_geometry_backward_launch: the same pass with the layout's taps, nothing is expanded).  Any other
+                     gmpi_mpi_render_depth_geometry_backward_launch: the same pass with the layout's taps, nothing is expanded), and THROUGH a volume
+                     as stored, read in place: a uint8 volume, planar or channels-last, on `render_views` (gmpi_mpi_render_u8_geometry_backward_launch:
+                     the node saves the codes and its backward is that one launch -- no volume backward, no zero-fill, nothing the size of a volume)
+                     and float layers on `render_views_layers` (gmpi_mpi_render_layers_geometry_backward_launch: one more launch after the layers
+                     backward, over the saved layers); with True both raise NotImplementedError, as before.  Any other
                      string: ValueError.  `mpi.geometry_grad` stays a bool; `mpi.geometry_grad_layouts` says whether the layouts are included.
 
     The transmittance output T (want_transmittance=True) is differentiable like colour and depth: a loss on it (`color + T * bg`, a coverage
@@ -841,7 +849,8 @@ class MPI(nn.Module):
         camera axis lies more than 0.35 rad off the normal (GMPI_FLAG_HINT_OBLIQUE: views that share an MPI then go to the tile kernel at once).
 
         rgba [M,D,4,Ht,Wt] (f32/bf16/f16, or uint8 codes c that stand for c / 255 -- quantized.py; any outer strides, innermost contiguous;
-        a uint8 volume is read as it is: no cast, no copy, no gradient, no exhaustive range pass -- every code is in [0, 1]; so is a channels-last
+        a uint8 volume is read as it is: no cast, no copy, no gradient w.r.t. the codes (with geometry_grad="all" the gradient w.r.t. the camera
+        tensors and dhw flows through them in place), no exhaustive range pass -- every code is in [0, 1]; so is a channels-last
         uint8 volume, `layers_as_volume(layers)` of [M,D,Ht,Wt,4] layers: channel stride 1, texel stride 4), dhw [M,D,3],
         ray_dir [N,3,H,W], eye_pos [N,3], z_dir [N,3].  View n samples MPI `view_to_mpi[n]`; without it,
         `views_per_mpi` (an int or one count per MPI) gives the reference's grouping.
@@ -854,7 +863,8 @@ class MPI(nn.Module):
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
         if torch.is_grad_enabled() and not _in_autograd_fn:
-            if rgba.dtype is torch.uint8 and self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
+            if (rgba.dtype is torch.uint8 and self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir))
+                    and not (self.geometry_grad_layouts and _layout is None and _shading is None)):   # ("all": the codes are differentiated through in place)
                 raise NotImplementedError("no gradient flows through a uint8 volume, w.r.t. the plane geometry and the camera tensors included "
                                           "(geometry_grad=True): render dequantize_volume(q) (ml_gmpi_amd.quantized) for that, or detach the "
                                           "camera and dhw tensors")
@@ -990,11 +1000,13 @@ class MPI(nn.Module):
         return None
 
     def _layers_bridge(self, layers, dhw, ray_dir, eye_pos, z_dir):
-        """`_autograd_bridge` for float layers: the gradient reaches the layers, never the geometry."""
-        if self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)):
+        """`_autograd_bridge` for float layers: the gradient reaches the layers and, with geometry_grad="all", the geometry (one more launch over the
+        saved layers in place); geometry_grad=True raises as ever."""
+        geometry = self.geometry_grad and any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir))
+        if geometry and not self.geometry_grad_layouts:
             raise NotImplementedError("the render of float layers has no gradient w.r.t. the plane geometry or the camera tensors: render the planar "
                                       "volume layers.permute(0, 1, 4, 2, 3) with render_views for that, or detach the camera and dhw tensors")
-        return (_LayersRenderFunction, (layers,)) if layers.requires_grad else None
+        return (_LayersRenderFunction, (layers,)) if layers.requires_grad or geometry else None
 
     def _shaded_bridge(self, rgba, shading, dhw, ray_dir, eye_pos, z_dir):
         """`_autograd_bridge` for the shaded render: the gradient reaches the volume and the shading image, never the geometry."""
@@ -1051,8 +1063,11 @@ class MPI(nn.Module):
         the tile kernel cannot take (Wt = 1, more than 65535 views, in-plane offsets past 2^31) run the one-pixel kernel: `layers_backward_fallbacks`,
         one RuntimeWarning per process.  Layers that had to be copied (`layers_copies`) take the same path over the copy.  Anything else is a
         ValueError.  Either way the atomic kernels run, whatever the module's `backward` (MPI(backward="gather") included: the atomics-free pair has
-        no form for the layout), and the gradient comes back in the layers' shape and dtype.  geometry_grad with a camera or dhw tensor that requires
-        grad raises NotImplementedError.  Measured, not routed: profiles/float_layers_backward.txt."""
+        no form for the layout), and the gradient comes back in the layers' shape and dtype.  A camera or dhw tensor that requires grad: with
+        geometry_grad="all" its gradient comes from one more launch after the layers backward (gmpi_mpi_render_layers_geometry_backward_launch),
+        which reads the SAVED layers in place under either `layers_backward` -- never the planar copy --; the layers backward is skipped when the
+        layers need no gradient; with geometry_grad=True it raises NotImplementedError.  Measured, not routed: profiles/float_layers_backward.txt,
+        profiles/geometry_backward_inplace.txt."""
         if layers.ndim != 5 or layers.shape[4] != 4:
             raise ValueError(f"render_views_layers takes layers of shape [M, D, Ht, Wt, 4], got {tuple(layers.shape)}")
         unknown = set(kwargs) - self._LAYERS_KEYWORDS
@@ -1279,14 +1294,18 @@ def _upstream(ctx, dev, g_color, g_depth, g_T):
     return g_color, g_depth, g_T
 
 
-def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream, plane_z=None):
+def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream, plane_z=None, query="gmpi_render_geometry_backward_workspace_bytes",
+                   layers=False):
     """The gradient w.r.t. the sample positions (render_backward_geometry.hip) for the inputs (dhw, ray_dir, eye_pos, z_dir) flagged in `want`, in
     each input's own dtype and device (ctx.geo_meta): every output overwritten, NULL = not wanted; the per-view and per-plane sums go through
     slabs in a workspace lent for this call (no atomics: bit-reproducible).  entry: the C entry; structs: what it takes between the parameter
     struct and the upstream gradients (the layout's structs).  plane_z (depth-alpha: the table the kernels read, when ITS gradient is wanted): the
     pass is then the _pz entry behind its own workspace query, once, whatever else is wanted, and a fifth gradient -- fp32, plane_z's shape -- is
-    returned behind the four."""
+    returned behind the four.  query: the entry's workspace query (the in-place entries have their own); layers: keep.rgba is a stack of float layers, described
+    to the entry as the volume it is a view of."""
     p = _render_params(ctx.scalars, keep, T=T)   # the forward's launch, rebuilt from the saved tensors
+    if layers:
+        p.rgba_stride[:] = layer_strides(keep.rgba)   # [s_M, s_D, 1, s_row, 4]
     shapes = [(p.M, p.D, 3), (p.N, 3, p.H, p.W), (p.N, 3), (p.N, 3)]
     out = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
     ws = None   # (held until this call returns: the launch that uses it is on the stream by then)
@@ -1298,7 +1317,7 @@ def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream, pl
         _call(_DEPTH_PZ_ENTRY, dev, ctypes.byref(p), *structs, *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), _ptr(g_pz), stream=stream)
         return [t.to(device=d, dtype=dt) if t is not None else None for t, (dt, d) in zip(out, ctx.geo_meta)] + [g_pz]
     if want[0] or want[2] or want[3]:
-        need = int(_lib.load_library().gmpi_render_geometry_backward_workspace_bytes(ctypes.byref(p), int(want[0])))
+        need = int(getattr(_lib.load_library(), query)(ctypes.byref(p), int(want[0])))
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         _lend(p, ws)
     _call(entry, dev, ctypes.byref(p), *structs, *upstream, _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[0]), stream=stream)
@@ -1308,7 +1327,8 @@ def _geometry_pass(ctx, keep, T, dev, stream, want, entry, structs, upstream, pl
 class _RenderFunction(torch.autograd.Function):
     """autograd bridge: forward = gmpi_mpi_render_launch, backward = gmpi_mpi_render_backward_launch (d/d rgba) and, for an MPI with
     geometry_grad=True, gmpi_mpi_render_geometry_backward_launch (d/d dhw, ray_dir, eye_pos, z_dir); their _ex forms when the loss
-    reaches the transmittance output.
+    reaches the transmittance output.  A uint8 volume (geometry_grad="all"): the saved tensor is the codes, and the backward is
+    gmpi_mpi_render_u8_geometry_backward_launch alone.
 
     Everything the backward reads is kept through `save_for_backward` (so an in-place update of the volume between
     forward and backward raises instead of producing gradients of overwritten memory), the parameter struct is rebuilt
@@ -1362,8 +1382,12 @@ class _RenderFunction(torch.autograd.Function):
         geo = [None] * 4   # dhw, ray_dir, eye_pos, z_dir
         want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
         if any(want):
-            entry = "gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch"
-            geo = _geometry_pass(ctx, keep, T, dev, stream, want, entry, (), upstream)
+            if keep.rgba.dtype is torch.uint8:   # the saved codes, in place: this launch alone (a uint8 volume never needs a gradient)
+                geo = _geometry_pass(ctx, keep, T, dev, stream, want, _U8_GEOMETRY_ENTRY, (), (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T)),
+                                     query=_INPLACE_GEOMETRY_QUERY)
+            else:
+                entry = "gmpi_mpi_render_geometry_backward_launch" if g_T is None else "gmpi_mpi_render_geometry_backward_ex_launch"
+                geo = _geometry_pass(ctx, keep, T, dev, stream, want, entry, (), upstream)
         return grad, None, geo[0], geo[1], geo[2], geo[3], None
 
 
@@ -1372,7 +1396,8 @@ class _LayersRenderFunction(torch.autograd.Function):
     planar copy.  backward, layers_backward="planar" (the default) = gmpi_mpi_render_backward_launch (its _ex form when the loss reaches T) over the
     planar copy of the saved layers, made then and freed with the call, into a zero-filled planar fp32 gradient that goes back in the layers' order,
     shape and dtype; layers_backward="texel" = gmpi_mpi_render_layers_backward_launch over the saved layers themselves into ONE zero-filled fp32
-    tensor of the layers' shape and order.  backward="gather" is not built for the layout (the atomic kernels run either way)."""
+    tensor of the layers' shape and order.  backward="gather" is not built for the layout (the atomic kernels run either way).  geometry_grad="all":
+    then gmpi_mpi_render_layers_geometry_backward_launch over the saved layers (d/d dhw, ray_dir, eye_pos, z_dir); alone when the layers need no gradient."""
 
     @staticmethod
     def forward(ctx, layers, mpi, dhw, ray_dir, eye_pos, z_dir, kwargs):
@@ -1381,6 +1406,8 @@ class _LayersRenderFunction(torch.autograd.Function):
         ctx.save_for_backward(*keep[:5], res["T"], *([keep.view_to_mpi] if ctx.has_v2m else []))
         ctx.in_dtype = layers.dtype
         ctx.texel, ctx.mpi = kwargs.get("_layers_backward", "planar") == "texel", mpi
+        ctx.geometry = mpi.geometry_grad_layouts
+        ctx.geo_meta = [(t.dtype, t.device) for t in (dhw, ray_dir, eye_pos, z_dir)]   # (the gradients go back in each input's own dtype and device)
         return res["color"], res["depth"], res["T"], res["status"]
 
     @staticmethod
@@ -1406,9 +1433,29 @@ class _LayersRenderFunction(torch.autograd.Function):
         return grad.to(ctx.in_dtype)   # (fp32 layers: the filled tensor itself)
 
     @staticmethod
+    def _backward_geometry(ctx, g_color, g_depth, g_T):
+        """geometry_grad="all": d/d (dhw, ray_dir, eye_pos, z_dir) over the SAVED LAYERS in place, whatever layers_backward says: one more launch."""
+        want = [ctx.geometry and ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
+        if not any(want):
+            return [None] * 4
+        saved = ctx.saved_tensors
+        keep, T = _Keep(*saved[:5], saved[6] if ctx.has_v2m else None), saved[5]
+        dev = keep.rgba.device
+        g_color, g_depth, g_T = _upstream(ctx, dev, g_color, g_depth, g_T)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        return _geometry_pass(ctx, keep, T, dev, stream, want, _LAYERS_GEOMETRY_ENTRY, (), (g_color.data_ptr(), _ptr(g_depth), _ptr(g_T)),
+                              query=_INPLACE_GEOMETRY_QUERY, layers=True)
+
+    @staticmethod
     def backward(ctx, g_color, g_depth, g_T, g_status):
-        if ctx.texel:
-            return _LayersRenderFunction._backward_texel(ctx, g_color, g_depth, g_T), None, None, None, None, None, None
+        grad = None
+        if ctx.needs_input_grad[0]:   # (layers that need no gradient: the geometry launch alone)
+            grad = (_LayersRenderFunction._backward_texel if ctx.texel else _LayersRenderFunction._backward_planar)(ctx, g_color, g_depth, g_T)
+        geo = _LayersRenderFunction._backward_geometry(ctx, g_color, g_depth, g_T)
+        return grad, None, geo[0], geo[1], geo[2], geo[3], None
+
+    @staticmethod
+    def _backward_planar(ctx, g_color, g_depth, g_T):
         saved = ctx.saved_tensors
         planar = saved[0].permute(0, 1, 4, 2, 3).contiguous()   # the transient planar copy [M,D,4,Ht,Wt]
         keep, T = _Keep(planar, *saved[1:5], saved[6] if ctx.has_v2m else None), saved[5]
@@ -1421,7 +1468,7 @@ class _LayersRenderFunction(torch.autograd.Function):
         _call("gmpi_mpi_render_backward_launch" if g_T is None else "gmpi_mpi_render_backward_ex_launch", dev,
               ctypes.byref(p), *upstream, grad.data_ptr(), (ctypes.c_int64 * 5)(*grad.stride()), stream=stream)
         del planar, keep
-        return grad.permute(0, 1, 3, 4, 2).to(ctx.in_dtype, memory_format=torch.contiguous_format), None, None, None, None, None, None
+        return grad.permute(0, 1, 3, 4, 2).to(ctx.in_dtype, memory_format=torch.contiguous_format)
 
 
 class _ShadedRenderFunction(torch.autograd.Function):

@@ -524,7 +524,8 @@ class MPIRenderer:
         consumption of the torch RNG are `render`'s: a seeded call returns the c2w and angles `render` returns for the planar volume.  `variant`:
         "auto", "gather", "lds" or None = the renderer's own, as in `MPI.render_views_layers`.  `layers_backward`: "planar" (the default: the backward
         over a transient planar copy) or "texel" (the backward that reads the saved layers and writes their gradient in place), as in
-        `MPI.render_views_layers`; anything else is a ValueError."""
+        `MPI.render_views_layers`; anything else is a ValueError.  Camera tensors that require grad (`given_cam_infos` from `rays_from_c2w`) are
+        handed through: a renderer built with geometry_grad="all" gives c2w.grad over the layers in place."""
         if layers.ndim != 5 or layers.shape[4] != 4:
             raise ValueError(f"render_layers takes layers of shape [B, D, Ht, Wt, 4], got {tuple(layers.shape)}")
         if layers_backward not in ("planar", "texel"):
@@ -606,5 +607,6 @@ class _RaysFromC2W(torch.autograd.Function):
 def rays_from_c2w(renderer: MPIRenderer, c2w: torch.Tensor):
     """Differentiable rays of the renderer's camera for camera-to-world matrices c2w [B,4,4] on the device:
     (ray_dir [B,3,H,W], eye_pos [B,3], z_dir [B,3]), the same bits as the renderer's own rays; the gradient reaches c2w (pose refinement):
-    feed them to `render(..., given_cam_infos=...)` of a renderer built with geometry_grad=True."""
+    feed them to `render(..., given_cam_infos=...)` of a renderer built with geometry_grad=True -- or, built with geometry_grad="all", to
+    `render` of a uint8 volume as stored, to `render_layers`, `render_shared` and `render_depth`, which hand the tensors through likewise."""
     return _RaysFromC2W.apply(c2w, renderer)
