@@ -22,7 +22,32 @@ Margins: a wrong 32-bit byte offset reaches at most 2 GiB below a plane's first 
 starts LEAD = 2 GiB before its first window element and ends TAIL = 4 GiB behind its LAST window element, all of it NaN (uint8: 255, an opaque
 white texel).  A truncated offset lands on the fill inside the allocation -- a failed assertion, never an access outside it.  Do not shrink them.
 One buffer lives at a time (`Window` is a context manager; peak about 18 GiB for the fp32 outer layout), and a case skips when the device has
-less than NEED_FREE = 24 GiB free -- which no MI355X does."""
+less than NEED_FREE = 24 GiB free -- which no MI355X does.
+
+Channels-last float layers [M, D, HT, WT, 4] (texel stride 4, channel stride 1; `layer_strides`: (s_mpi, s_plane, s_row) in elements), for the
+kernels that read whole texels in place (render_layers.hip, the texel instances of render_backward.hip and render_backward_geometry.hip):
+  L-outer  s_row = 4 PITCH (dense rows), s_plane = S_PLANE, s_mpi = S_MPI: the large strides are the 64-bit ones.
+  L-rowA/T/B/C   [HT, M, D, PITCH, 4] storage permuted to [M, D, HT, WT, 4]; the row stride in whole 64-byte steps.
+           A: the largest the staged forward takes -- (32 + 1) s_row es + 16 * 64 + 128 < 2^31, the bound of layers_variant_supports --, which the
+              tile backward takes too; T: the smallest with 33 s_row es >= 2^31: the staged forward refuses it, the tile backward, whose bound is
+              (32 s_row + 4 WT) es < 2^31, takes it; B, C: 31 s_row es = 2^31 + 2^24 and 2^32 + 2^24, rounded up as rowB / rowC are: both refuse.
+           The two bounds are restated here to FIND the strides; tests/test_big_strides_cpu.py asks the library on which side each one lies.
+Their fp32 gradient [M, D, HT, WT, 4] (`grad_strides`), the same storage order, gs_row in dwords:
+  G-byte   31 gs_row 4 bytes = 2^32 + 2^24 (rounded up): every dword offset of a plane is below 2^31, so the tile backward takes the launch -- and
+           the bytes behind them are past 2^32: right only if nothing scales a dword offset by 4 in 32 bits.
+  G-past   the first gs_row with HT gs_row + 4 WT >= 2^31, which layers_offsets_fit_32(gs_row, HT, WT, 1) refuses: the one-pixel kernel.
+The shading image [M, 1, HT, WT] of the shaded render, fp32 (`shading_strides`: (s_mpi, s_row)):
+  S-outer  s_mpi = S_MPI, rows of PITCH.
+  S-rowA/B [HT, M, PITCH] storage permuted; s_row the largest / the smallest multiple of 16 elements with HT s_row + WT < / >= 2^31 / 4, the third
+           guard of the shaded tile backward (plane_offsets_fit_32(0, s_row, HT, WT, 4)): the tile twin / the one-pixel twin.
+
+Margins of the layouts above, by the unit the kernel counts an offset in.  Layers and the shading image are addressed at 32-bit BYTE offsets (l_off
+and pass_off of the staged forward, s_row_b of the pair loads): a mistake reaches 2^31 bytes below or 2^32 bytes above -- LEAD and TAIL as they are.
+The gradient of the texel tile backward is addressed at 32-bit DWORD offsets (row gs_row + column, counted in floats): a sign-extended offset
+reaches 2^31 dwords = 8 GiB below the box origin, a wrapped one less than 2^32 dwords = 16 GiB above it; a dword offset scaled to bytes in 32 bits
+loses multiples of 4 GiB and lands below the true cell, never below the origin.  So a gradient window has GRAD_LEAD = 4 LEAD in front of its first
+element and GRAD_TAIL = 4 TAIL behind its last: 8 + 4 + 16 = 28 GiB for G-byte, 8 + 8 + 16 = 32 GiB for G-past.  Both are more than NEED_FREE:
+`Window(need=...)` states the case's own need (the buffer, the contiguous copy and 2 GiB of room) and skips below it."""
 import gc
 
 HT, PITCH = 32, 40
@@ -34,7 +59,14 @@ CHAN_BYTES = {"chanA": 2 ** 31 - 2 ** 24, "chanB": 2 ** 31 + 2 ** 24, "chanC": 2
 ROW_BYTES = {"rowB": 2 ** 31 + 2 ** 24, "rowC": 2 ** 32 + 2 ** 24}                                  # 31 s_row es
 FLOAT_LAYOUTS = ("outer", "chanA", "chanB", "chanC", "rowB", "rowC")
 FITS_32 = ("outer", "chanA")      # every in-plane byte offset is below 2^31: all staged kernels and the atomics-free backward pair take these
-PLANES = {"outer": 2}             # D; every other layout has 3
+PLANES = {"outer": 2, "L-outer": 2}   # D; every other layout has 3
+GRAD_LEAD, GRAD_TAIL = 4 * LEAD, 4 * TAIL                # bytes: offsets counted in dwords
+LAYER_LAYOUTS = ("L-outer", "L-rowA", "L-rowT", "L-rowB", "L-rowC")
+LAYERS_STAGED = ("L-outer", "L-rowA")                    # the staged forward takes these (gmpi_render_layers_supports) ...
+LAYERS_TILE = ("L-outer", "L-rowA", "L-rowT")            # ... the tile backward these (gmpi_render_layers_backward_supports)
+GRAD_LAYOUTS = ("G-byte", "G-past")
+SHADING_LAYOUTS = ("S-outer", "S-rowA", "S-rowB")
+SHADING_TILE = ("S-outer", "S-rowA")                     # inside the shaded tile backward's third guard
 
 
 def wt_of(es):
@@ -81,6 +113,40 @@ def image_strides(layout, es, C=3):
     raise KeyError(layout)
 
 
+def layer_row_stride(layout, es):
+    """s_row of a row layout of float layers, in elements (the module docstring has the four bounds)."""
+    if layout == "L-rowA":
+        return _step((2 ** 31 - 16 * 64 - 128 - 1) // 33, es, up=False)
+    if layout == "L-rowT":
+        return _step(-(-2 ** 31 // 33), es, up=True)
+    return row_stride({"L-rowB": "rowB", "L-rowC": "rowC"}[layout], es)
+
+
+def layer_strides(layout, es, D=None):
+    """(s_mpi, s_plane, s_row) of layers [M, D, HT, WT, 4] in `layout`, in elements; the texel stride is 4, the channel stride 1."""
+    D = planes_of(layout) if D is None else D
+    if layout == "L-outer":
+        return (S_MPI, S_PLANE, 4 * PITCH)
+    return (D * 4 * PITCH, 4 * PITCH, layer_row_stride(layout, es))
+
+
+def grad_strides(layout, wt, D=3):
+    """(gs_mpi, gs_plane, gs_row) of the fp32 gradient [M, D, HT, wt, 4] of float layers, in dwords."""
+    gs_row = row_stride("rowC", 4) if layout == "G-byte" else -(-(2 ** 31 - 4 * wt) // HT)
+    assert layout in GRAD_LAYOUTS
+    return (D * 4 * PITCH, 4 * PITCH, gs_row)
+
+
+def shading_strides(layout, wt):
+    """(s_mpi, s_row) of the fp32 shading image [M, 1, HT, wt], in elements."""
+    if layout == "S-outer":
+        return (S_MPI, PITCH)
+    lim = 2 ** 31 // 4
+    s_row = (lim - wt - 1) // HT // 16 * 16 if layout == "S-rowA" else -(-(lim - wt) // (HT * 16)) * 16
+    assert layout in SHADING_LAYOUTS
+    return (PITCH, s_row)
+
+
 def span(shape, stride):
     """Offset of the last element of a view, in elements."""
     return sum((n - 1) * s for n, s in zip(shape, stride))
@@ -98,13 +164,13 @@ def release():
     torch.cuda.empty_cache()
 
 
-def need_memory():
+def need_memory(need=NEED_FREE):
     import pytest
     import torch
     release()
     free, _ = torch.cuda.mem_get_info()
-    if free < NEED_FREE:
-        pytest.skip(f"needs {NEED_FREE >> 30} GiB of free device memory for the NaN margins, {free >> 30} GiB are free")
+    if free < need:
+        pytest.skip(f"needs {need / 2 ** 30:.0f} GiB of free device memory for the margins, {free >> 30} GiB are free")
 
 
 class Window:
@@ -114,20 +180,23 @@ class Window:
             ...
 
     The buffer never leaves the device and is released on exit (keep no reference to `w.view`: let tensors made from it die with the block's
-    helper functions)."""
+    helper functions).  lead, tail: the margins in bytes (the module docstring derives them from the unit the kernel counts offsets in); need: the
+    free device memory below which the case skips -- NEED_FREE, or the case's own need where its buffer is larger than that allows."""
 
-    def __init__(self, values, stride, fill=float("nan"), device="cuda:0"):
+    def __init__(self, values, stride, fill=float("nan"), device="cuda:0", lead=LEAD, tail=TAIL, need=None):
         self.values, self.stride, self.fill, self.device = values, tuple(stride), fill, device
+        self.lead_bytes, self.tail_bytes = lead, tail
         es = values.element_size()
-        assert LEAD % es == 0 and len(self.stride) == values.dim()
+        assert lead >= LEAD and tail >= TAIL and lead % es == 0 and len(self.stride) == values.dim()
         dims = sorted((s, n) for n, s in zip(values.shape, self.stride) if n > 1)
         assert all(s > 0 for s, _ in dims) and all(b[0] >= a[0] * a[1] for a, b in zip(dims, dims[1:])), "the window's elements must not overlap"
-        self.lead = LEAD // es
-        self.numel = self.lead + span(values.shape, self.stride) + 1 + TAIL // es
+        self.lead = lead // es
+        self.numel = self.lead + span(values.shape, self.stride) + 1 + tail // es
+        self.need = max(NEED_FREE, self.numel * es + values.numel() * es + 2 ** 31) if need is None else need
 
     def __enter__(self):
         import torch
-        need_memory()
+        need_memory(self.need)
         torch.cuda.reset_peak_memory_stats()   # (the tests print max_memory_allocated: each its own)
         buf = torch.empty((self.numel,), dtype=self.values.dtype, device=self.device)
         buf.fill_(self.fill)
@@ -138,7 +207,7 @@ class Window:
         # the margins, from the addresses: 2 GiB of fill below the first element, 4 GiB behind the last one, inside the allocation
         es = buf.element_size()
         first, last = self.view.data_ptr(), self.view.data_ptr() + span(self.values.shape, self.stride) * es
-        assert first - buf.data_ptr() >= LEAD and buf.data_ptr() + buf.numel() * es - last > TAIL
+        assert first - buf.data_ptr() >= self.lead_bytes and buf.data_ptr() + buf.numel() * es - last > self.tail_bytes
         del buf
         return self
 

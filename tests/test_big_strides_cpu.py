@@ -11,6 +11,7 @@ import _big_strides as big
 DTYPES = {"f32": (0, 4), "bf16": (1, 2), "f16": (2, 2)}
 H, W = 19, 130
 E_VARIANT = -6
+QUERY_SF_ROWS = 14   # gmpi_query: kSFRows, the box rows of the staged shared-colour and shaded forwards (shared_forward_query, render_shared_forward.hip)
 
 
 @pytest.fixture(scope="module")
@@ -24,7 +25,7 @@ def env():
 
 def _params(env, dtype, stride, *, wt=None, variant=None, D=3, flags=None):
     L, lib, fake, _ = env
-    code, es = DTYPES[dtype]
+    code, es = DTYPES[dtype] if dtype != "u8" else (L.DTYPE_U8, 1)
     p = L.GmpiRenderParams()
     p.struct_size = ctypes.sizeof(L.GmpiRenderParams)
     p.flags = L.FLAG_ALIGN_CORNERS if flags is None else flags
@@ -54,6 +55,142 @@ def test_layout_strides_are_where_the_docstring_says():
     # the fp32 outer layout is the largest buffer: about 18 GiB
     top = big.LEAD + (big.span((2, 2, 4, big.HT, 36), big.strides("outer", 4) + (1,)) + 1) * 4 + big.TAIL
     assert 18 * 2 ** 30 <= top < 18.01 * 2 ** 30 < big.NEED_FREE
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_the_cameras_of_the_gpu_modules_reach_the_first_and_last_texel_row(dtype):
+    """The row layouts put the row whose offset passes 2^31 or 2^32 last (31 s_row), so the cameras of tests/test_hip_big_strides.py (`_geo`) must
+    put weight on it: with the oracle, halving texel row 0, row HT - 1 or column WT - 1 of the front plane changes the image, for both
+    image sizes and both plane counts -- and no ray leaves the stack (T < 1 everywhere), so the planes' borders lie inside the image."""
+    import oracle
+    import test_hip_big_strides as G
+    for D in (2, 3):
+        v = G._volume(dtype, D).float().numpy()
+        geo = G._geo(dtype, D)
+        base = oracle.render(v, *geo, align_corners=True)
+        assert base["status"] == 0 and float(base["T"].max()) < 1
+        for axis, index in ((3, 0), (3, big.HT - 1), (4, v.shape[-1] - 1)):
+            w = v.copy()
+            cut = [slice(None)] * 5
+            cut[1], cut[axis] = 0, index
+            w[tuple(cut)] *= 0.5
+            seen = int((oracle.render(w, *geo, align_corners=True)["color"] != base["color"]).any(1).sum())
+            assert seen >= 8, (dtype, D, axis, index, seen)
+
+
+def _layer_params(env, dtype, stride3, *, D=3, backward=False):
+    """Float layers [2, D, HT, WT, 4] with (s_mpi, s_plane, s_row) = stride3, as `render_views_layers` hands them to the layers entries."""
+    L, _, fake, _ = env
+    s_mpi, s_plane, s_row = stride3
+    p = _params(env, dtype, (s_mpi, s_plane, 1, s_row), D=D)
+    p.rgba_stride[:] = [s_mpi, s_plane, 1, s_row, 4]
+    if backward:   # (a backward: the forward's T, no outputs)
+        p.rgb_out = p.depth_out = None
+        p.transmittance_out = fake
+    return p
+
+
+def _dense_layers(D, wt):
+    return (D * big.HT * 4 * wt, big.HT * 4 * wt, 4 * wt)
+
+
+def _i64(v):
+    return (ctypes.c_int64 * len(v))(*v)
+
+
+def test_layer_gradient_and_shading_strides_are_where_the_docstring_says():
+    for dtype, (_, es) in DTYPES.items():
+        wt = big.wt_of(es)
+        for layout in big.LAYER_LAYOUTS:
+            s_mpi, s_plane, s_row = big.layer_strides(layout, es)
+            D = big.planes_of(layout)
+            assert s_row * es % 64 == 0 and s_plane * es % 64 == 0 and s_mpi * es % 64 == 0, (layout, dtype)
+            dims = sorted([(4, wt), (s_row, big.HT), (s_plane, D), (s_mpi, 2)])
+            assert all(b[0] >= a[0] * a[1] for a, b in zip(dims, dims[1:])), (layout, dtype, "the window's texels must not overlap")
+        a, t, b, c = (big.layer_row_stride(k, es) * es for k in ("L-rowA", "L-rowT", "L-rowB", "L-rowC"))
+        assert 33 * a + 16 * 64 + 128 < 2 ** 31 <= 33 * (a + 64) + 16 * 64 + 128
+        assert 33 * (t - 64) < 2 ** 31 <= 33 * t and 32 * t + 4 * wt * es < 2 ** 31
+        assert 2 ** 31 + 2 ** 24 <= 31 * b < 2 ** 31 + 2 ** 25 and 2 ** 32 + 2 ** 24 <= 31 * c < 2 ** 32 + 2 ** 25
+        _, _, g_byte = big.grad_strides("G-byte", wt)
+        _, _, g_past = big.grad_strides("G-past", wt)
+        assert big.HT * g_byte + 4 * wt < 2 ** 31 and 31 * g_byte * 4 >= 2 ** 32 + 2 ** 24
+        assert big.HT * (g_past - 1) + 4 * wt < 2 ** 31 <= big.HT * g_past + 4 * wt
+        (_, ra), (_, rb) = big.shading_strides("S-rowA", wt), big.shading_strides("S-rowB", wt)
+        assert rb - ra == 16 and big.HT * ra + wt < 2 ** 29 <= big.HT * rb + wt
+        # SHADING_TILE: the layouts inside the shaded tile backward's third guard, plane_offsets_fit_32(0, s_row, HT, WT, 4) -- no query of the
+        # library answers for that guard, so the list is held to the guard's arithmetic here
+        for layout in big.SHADING_LAYOUTS:
+            assert (big.HT * big.shading_strides(layout, wt)[1] + wt < 2 ** 29) == (layout in big.SHADING_TILE), (layout, dtype)
+    # the dword margins are four times the byte margins; the largest buffers: 28 GiB (G-byte) and 32 GiB (G-past)
+    assert (big.GRAD_LEAD, big.GRAD_TAIL) == (4 * big.LEAD, 4 * big.TAIL)
+    for layout, lo in (("G-byte", 28), ("G-past", 31.7)):
+        gs = big.grad_strides(layout, 36)
+        top = big.GRAD_LEAD + (big.span((2, 3, big.HT, 36, 4), gs + (4, 1)) + 1) * 4 + big.GRAD_TAIL
+        assert lo * 2 ** 30 <= top < (lo + 0.1) * 2 ** 30, (layout, top / 2 ** 30)
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_layer_layouts_lie_on_the_side_of_each_guard_the_table_claims(env, dtype):
+    """gmpi_render_layers_supports (the staged forward of render_layers.hip) and gmpi_render_layers_backward_supports (the texel tile backward), as
+    compiled: outer and A are taken by both, T by the backward alone, B and C by neither; one 64-byte step above A the forward refuses."""
+    _, lib, _, _ = env
+    _, es = DTYPES[dtype]
+    wt = big.wt_of(es)
+    fwd = lambda p: int(lib.gmpi_render_layers_supports(ctypes.byref(p)))
+    bwd = lambda p, gs: int(lib.gmpi_render_layers_backward_supports(ctypes.byref(p), _i64([gs[0], gs[1], 1, gs[2], 4])))
+    for layout in big.LAYER_LAYOUTS:
+        D = big.planes_of(layout)
+        st = big.layer_strides(layout, es)
+        assert fwd(_layer_params(env, dtype, st, D=D)) == (1 if layout in big.LAYERS_STAGED else 0), (layout, dtype)
+        assert bwd(_layer_params(env, dtype, st, D=D, backward=True), _dense_layers(D, wt)) == (1 if layout in big.LAYERS_TILE else 0), (layout, dtype)
+    s_mpi, s_plane, a = big.layer_strides("L-rowA", es)
+    assert fwd(_layer_params(env, dtype, (s_mpi, s_plane, a + 64 // es))) == 0                       # A is the LARGEST the staged forward takes
+    assert bwd(_layer_params(env, dtype, (s_mpi, s_plane, a + 64 // es), backward=True), _dense_layers(3, wt)) == 1
+    # the gradient's layouts over dense layers: G-byte is taken, G-past is the FIRST row stride refused
+    dense = _layer_params(env, dtype, _dense_layers(3, wt), backward=True)
+    g_mpi, g_plane, g_past = big.grad_strides("G-past", wt)
+    assert bwd(dense, big.grad_strides("G-byte", wt)) == 1
+    assert bwd(dense, (g_mpi, g_plane, g_past)) == 0 and bwd(dense, (g_mpi, g_plane, g_past - 1)) == 1
+
+
+def test_channels_last_codes_outer_is_staged_and_the_row_layout_is_not(env):
+    """u8_variant_supports through gmpi_render_layers_supports: it decides which forward renders channels-last codes and, in default mode, whether
+    the in-place geometry backward uses the forward's transmittance (gmpi_abi.hip).  `outer` is taken; rows of row_stride("rowC", 1) bytes are not."""
+    L, lib, _, _ = env
+    ask = lambda st, D: int(lib.gmpi_render_layers_supports(ctypes.byref(_layer_params(env, "u8", st, D=D))))
+    assert ask((big.U8_S_MPI, big.U8_S_PLANE, 4 * big.PITCH), 2) == 1
+    assert ask((3 * 4 * big.PITCH, 4 * big.PITCH, big.row_stride("rowC", 1)), 3) == 0
+    assert (big.HT - 1) * big.row_stride("rowC", 1) >= 2 ** 32 + 2 ** 24
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_shaded_forward_takes_every_layout_of_the_shaded_cases(env, dtype):
+    """gmpi_render_shaded_supports: the staged shaded forward gives every channel image a 64-bit base and keeps only row offsets in 32 bits, at
+    (27 + 1) rows of the volume and of the shading image: it takes the volume on `outer` and on `chanB`, and the shading image on all three of its
+    layouts -- rows of 2^24 floats are inside ITS bound.  (S-rowA and S-rowB straddle the third guard of the shaded tile BACKWARD, for which the
+    library has no query: test_layer_gradient_and_shading_strides_are_where_the_docstring_says holds them to that guard's arithmetic.)  A shading
+    row stride past the forward's own bound is refused."""
+    L, lib, fake, _ = env
+    _, es = DTYPES[dtype]
+    wt = big.wt_of(es)
+    rows = lib.gmpi_query(QUERY_SF_ROWS)
+    assert rows > 0
+
+    def ask(vol_stride, D, sh_stride):
+        p = _params(env, dtype, vol_stride, D=D, variant=L.VARIANT_LDS)
+        sh = L.GmpiShading()
+        sh.struct_size = ctypes.sizeof(L.GmpiShading)
+        sh.shading = fake
+        sh.shading_stride[:] = list(sh_stride)
+        return int(lib.gmpi_render_shaded_supports(ctypes.byref(p), ctypes.byref(sh)))
+
+    dense_sh = (big.HT * wt, wt)
+    for layout in ("outer", "chanB"):
+        assert ask(big.strides(layout, es), big.planes_of(layout), dense_sh) == 1, (layout, dtype)
+    for layout in big.SHADING_LAYOUTS:
+        assert ask(_contiguous(3, wt), 3, big.shading_strides(layout, wt)) == 1, (layout, dtype)
+    first_bad = -(-(2 ** 29 - 128) // ((rows + 1) * 4)) * 4
+    assert ask(_contiguous(3, wt), 3, (big.PITCH, first_bad)) == 0 and ask(_contiguous(3, wt), 3, (big.PITCH, first_bad - 4)) == 1
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -114,7 +251,7 @@ def test_explicit_staged_variants_refuse_strides_they_cannot_address(env, dtype)
 
 def test_shared_forward_supports_answers_zero_for_a_row_stride_over_its_bound(env):
     L, lib, fake, _ = env
-    rows = lib.gmpi_query(14)   # kSFRows: box rows of the staged shared-colour forward
+    rows = lib.gmpi_query(QUERY_SF_ROWS)
     assert rows > 0
 
     def ask(dtype, s_row, rgb_row=big.PITCH, bg_row=big.PITCH):

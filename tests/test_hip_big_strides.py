@@ -48,10 +48,15 @@ def _es(name):
 
 @functools.lru_cache(maxsize=None)
 def _geo(name, D):
-    """(dhw, ray, eye, zd) as numpy: cameras of test_hip_backward.py (tilt 0.3), one view per MPI.  Shared, never written to."""
+    """(dhw, ray, eye, zd) as numpy: cameras of test_hip_backward.py (tilt 0.3), one view per MPI, over planes 0.9 times the size of `_dhw`'s.
+    Under `_dhw`'s own planes these cameras sample texel rows 1 .. HT - 2 only, and the row layouts put the row whose offset passes 2^31 or 2^32 LAST
+    (31 s_row): a one-pixel kernel never formed that offset.  At 0.9 the front planes' rows 0 and HT - 1 and first and last columns carry weight
+    (tests/test_big_strides_cpu.py shows it with the oracle), and no ray leaves the last plane.  Shared, never written to."""
     H, W = SIZES[name]
     ray, eye, zd = _cam(N, H, W, seed=6, tilt=0.3)
-    return _dhw(M, D), ray, eye, zd
+    dhw = _dhw(M, D)
+    dhw[..., 1:] *= np.float32(0.9)
+    return dhw, ray, eye, zd
 
 
 @functools.lru_cache(maxsize=None)
