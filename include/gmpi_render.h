@@ -305,8 +305,8 @@ uint64_t gmpi_render_backward_workspace_bytes(const GmpiRenderParams *params);
  * OR-accumulate as ever (GMPI_STATUS_CAMERA_BEHIND_PLANE looks at the chunk's planes).
  * Kernels: GMPI_VARIANT_GATHER and GMPI_VARIANT_LDS for fp32 / bf16 / fp16 and for GMPI_DTYPE_U8, planar and channels-last (the kernels and conditions of
  * gmpi_mpi_render_launch, in instances of their own); GMPI_VARIANT_AUTO is LDS where the tile kernel takes the tensors, else GATHER, whatever the launch
- * size and the camera hints; WAVE and BAND are GMPI_E_VARIANT (the strip kernel splits the plane axis itself; the band kernel has no carry yet).  No
- * workspace is read.  With GMPI_FLAG_STRICT_ORDER the chunked render has the bits of the one-shot render of the concatenation with the same variant, however
+ * size and the camera hints; WAVE and BAND are GMPI_E_VARIANT (the strip kernel splits the plane axis itself; the band kernel's carry instances have an
+ * entry of their own, gmpi_mpi_render_chunk_band_launch below, because they want a workspace).  No workspace is read.  With GMPI_FLAG_STRICT_ORDER the chunked render has the bits of the one-shot render of the concatenation with the same variant, however
  * the stack is cut; without it too, as long as the tile kernel stages the same planes.  gmpi_query(36) == 1 says the entries are built in.
  */
 typedef struct GmpiCarry {
@@ -316,6 +316,32 @@ typedef struct GmpiCarry {
     float *state_out;        /* [N,5,H,W] fp32 or NULL: not wanted (the last chunk) */
 } GmpiCarry;
 int gmpi_mpi_render_chunk_launch(const GmpiRenderParams *params, const GmpiCarry *carry, void *stream);
+
+/*
+ * One chunk through the BAND kernel's carry instances (fp32 / bf16 / fp16 volumes; 256 x 8 / 128 x 8 pixel bands, LDS-DMA loader: what GMPI_VARIANT_AUTO of
+ * gmpi_mpi_render_launch means for large launches).  `params` and `carry` are those of gmpi_mpi_render_chunk_launch in every respect: the state's layout and
+ * format, the NULL rules, GMPI_FLAG_OUT_PM1 / GMPI_FLAG_CHECK_LAST_PLANE on the last chunk only, status bits OR-accumulated, state_in == state_out allowed (every
+ * band is rendered exactly once; a lane outside the image may read a pixel that is being rewritten, and stores nothing).  The state is ONE format: a stack may be
+ * carried from a chunk of gmpi_mpi_render_chunk_launch into a chunk of this entry and back, in the mode (GMPI_FLAG_STRICT_ORDER or not) that produced it.
+ * params->workspace must hold gmpi_render_chunk_band_workspace_bytes(params) bytes, 256-byte aligned: the band table of the chunk's own D planes, rebuilt by
+ * every launch (what it held before does not matter); missing, too small or misaligned: GMPI_E_WORKSPACE.
+ *   GMPI_VARIANT_BAND  the band carry kernel renders every view; a band with a texel box that does not fit its staging buffers takes the direct gather inside
+ *                      the kernel, with the same state.
+ *   GMPI_VARIANT_AUTO  the pair of gmpi_mpi_render_launch's band path: views with a box that does not fit are handed, through a gate word per view in the
+ *                      workspace, to the tile kernel's carry instances (a second launch); every view's state passes through exactly one of the two kernels.
+ *                      No size threshold and no camera hints: the caller opted in by calling this entry.
+ *   any other variant: GMPI_E_VARIANT.  GMPI_DTYPE_U8, and tensors the band kernel (for AUTO: the tile kernel too) cannot take -- the alignment rules of
+ *   GMPI_VARIANT_BAND / GMPI_VARIANT_LDS above, Ht or Wt above 8192 --: GMPI_E_VARIANT; gmpi_render_chunk_band_supports() says so beforehand.
+ * N == 0: GMPI_OK.  Every other error as at gmpi_mpi_render_chunk_launch.  With GMPI_FLAG_STRICT_ORDER the chunked render has the bits of the oracle and of the
+ * one-shot GMPI_VARIANT_BAND render however the stack is cut; without it too wherever every box fits (the per-plane arithmetic does not know the chunk).
+ * gmpi_query(50) == 1 says the three entries are built in.
+ */
+int gmpi_mpi_render_chunk_band_launch(const GmpiRenderParams *params, const GmpiCarry *carry, void *stream);
+/* Bytes of workspace the launch above wants: gmpi_render_workspace_bytes of the same struct with variant = GMPI_VARIANT_BAND; 0 where it answers GMPI_E_VARIANT
+ * or a struct error, and for N == 0. */
+uint64_t gmpi_render_chunk_band_workspace_bytes(const GmpiRenderParams *params);
+/* 1: gmpi_mpi_render_chunk_band_launch takes these parameters given its workspace, 0: it answers GMPI_E_VARIANT; a negative struct error as the launch. */
+int gmpi_render_chunk_band_supports(const GmpiRenderParams *params);
 
 /*
  * Gradient of a chunked render w.r.t. ONE chunk; chunks are swept from the last to the first.  `params` are the chunk's forward parameters;
@@ -888,7 +914,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in; 45 is unused (-1); 46 whether the backward of the shading augmentation's image-sized middle and
  * the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch,
  * gmpi_light_shade_images_backward_launch) are built in; 47 is unused (-1); 48 whether the geometry backward over 8-bit volumes and float layers in place
- * (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in.
+ * (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in;
+ * 49 is unused (-1); 50 whether the plane-chunked render through the band kernel (gmpi_mpi_render_chunk_band_launch, gmpi_render_chunk_band_workspace_bytes,
+ * gmpi_render_chunk_band_supports) is built in.
  * Unknown -> -1.  */
 int gmpi_query(int32_t what);
 

@@ -37,6 +37,9 @@ EXPORTS = (
     "gmpi_render_geometry_inplace_workspace_bytes",
     "gmpi_mpi_render_chunk_launch",
     "gmpi_mpi_render_chunk_backward_launch",
+    "gmpi_mpi_render_chunk_band_launch",
+    "gmpi_render_chunk_band_workspace_bytes",
+    "gmpi_render_chunk_band_supports",
     "gmpi_mpi_render_layers_launch",
     "gmpi_render_layers_supports",
     "gmpi_mpi_render_layers_backward_launch",
@@ -258,6 +261,13 @@ def load_library():
     lib.gmpi_mpi_render_chunk_backward_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_chunk_backward_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp, vp, vp, vp, vp, vp,
                                                           ctypes.POINTER(ctypes.c_int64), vp]
+    # the plane-chunked render through the band kernel's carry instances (gmpi_query(50)): the launch, the bytes of workspace it wants, whether it takes the tensors
+    lib.gmpi_mpi_render_chunk_band_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_chunk_band_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiCarry), vp]
+    lib.gmpi_render_chunk_band_workspace_bytes.restype = ctypes.c_uint64
+    lib.gmpi_render_chunk_band_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams)]
+    lib.gmpi_render_chunk_band_supports.restype = ctypes.c_int
+    lib.gmpi_render_chunk_band_supports.argtypes = [ctypes.POINTER(GmpiRenderParams)]
     # channels-last float layers [M,D,Ht,Wt,4] in place (rgba_stride [s_M, s_D, 1, s_row, 4]; gmpi_query(42)): the launch, and whether its staged kernel takes the tensors
     lib.gmpi_mpi_render_layers_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_layers_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp]

@@ -25,6 +25,9 @@ hipError_t launch_wave(const KParams& p, int dtype, int tune, hipStream_t stream
 bool wave_variant_supports(const KParams& p, int dtype);                    // render_wave.hip
 hipError_t launch_band(const KParams& p, int dtype, int tune, hipStream_t stream);  // render_band.hip
 bool band_variant_supports(const KParams& p, int dtype);                    // render_band.hip
+hipError_t launch_band_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream);   // render_band.hip
+bool band_takes_tensors(const KParams& p, int dtype);                       // render_band.hip (band_variant_supports without its workspace clause)
+bool band_workspace_ok(const KParams& p, int dtype);                        // render_band.hip
 uint64_t band_workspace_bytes(const KParams& p, int dtype);                 // render_band.hip
 uint32_t* band_gate_words(const KParams& p, int dtype);                     // render_band.hip
 int band_pixels_wide(int dtype);                                            // render_band.hip
@@ -369,6 +372,12 @@ static bool auto_takes_band(const KParams& p, int dtype) {
     return band_count(p, dtype) >= need;
 }
 
+// The generation of a two-kernel launch's view gate (KParams::gate_gen): one counter for every entry that stamps gate words into a workspace.
+static uint32_t next_gate_gen() {
+    static std::atomic<uint32_t> gate_counter{0x6d2b79f5u};
+    return gate_counter.fetch_add(1u, std::memory_order_relaxed);
+}
+
 static int hip_rc(hipError_t e) { return e == hipSuccess ? GMPI_OK : GMPI_E_LAUNCH - static_cast<int>(e); }
 
 // Channels-last layers (gmpi_mpi_render_layers_launch, gmpi_render_layers_supports): rgba_stride = [s_M, s_D, 1, s_row, 4] in elements, s_row >= 4 Wt, s_M and
@@ -471,8 +480,7 @@ int gmpi_mpi_render_launch(const GmpiRenderParams* params, void* stream) {
         // lets the band kernel's table kernel share out the views through a gate word per view (KParams::gate): views with a box that does
         // not fit fall to the tile kernel, the others' tile workgroups exit at once (an empty second launch costs a few microseconds).
         if (band_path) {
-            static std::atomic<uint32_t> gate_counter{0x6d2b79f5u};
-            uint32_t gen = gate_counter.fetch_add(1u, std::memory_order_relaxed);
+            const uint32_t gen = next_gate_gen();
             KParams pb = p;
             pb.gate = band_gate_words(p, params->rgba_dtype), pb.gate_gen = gen, pb.gate_sense = 0u;
             const hipError_t e = launch_band(pb, params->rgba_dtype, 0, st);
@@ -608,7 +616,7 @@ int gmpi_mpi_render_chunk_launch(const GmpiRenderParams* params, const GmpiCarry
     if (carry == nullptr) return GMPI_E_NULL;
     if (carry->struct_size != sizeof(GmpiCarry)) return GMPI_E_ABI;
     int variant = params->variant;
-    if (variant == GMPI_VARIANT_WAVE || variant == GMPI_VARIANT_BAND) return GMPI_E_VARIANT;   // (the strip kernel splits the plane axis itself; the band kernel: a follow-up)
+    if (variant == GMPI_VARIANT_WAVE || variant == GMPI_VARIANT_BAND) return GMPI_E_VARIANT;   // (the strip kernel splits the plane axis itself; the band kernel: gmpi_mpi_render_chunk_band_launch)
     if (variant != GMPI_VARIANT_AUTO && variant != GMPI_VARIANT_GATHER && variant != GMPI_VARIANT_LDS) return GMPI_E_VARIANT;
     if (carry->state_out == nullptr && p.rgb_out == nullptr && p.depth_out == nullptr && p.T_out == nullptr) return GMPI_E_NULL;   // nothing to write
     const CarryK ck{carry->state_in, carry->state_out};
@@ -623,6 +631,53 @@ int gmpi_mpi_render_chunk_launch(const GmpiRenderParams* params, const GmpiCarry
     }
     if (!staged) return GMPI_E_VARIANT;   // LDS: these tensors are not aligned for its loader
     return hip_rc(u8 ? launch_u8_chunk(p, ck, st) : launch_lds_chunk(p, ck, params->rgba_dtype, st));
+}
+
+// ---- ... through the band kernel's carry instances.  What the three entries ask alike once the struct is read: the variant (BAND, or AUTO = BAND and the tile
+// kernel's carry instances behind the view gate), a float storage type, tensors the band kernel -- for AUTO the tile kernel too -- can take.  The workspace is the
+// launch's own question.
+static bool chunk_band_takes(const KParams& p, const GmpiRenderParams* params) {
+    if (params->variant != GMPI_VARIANT_BAND && params->variant != GMPI_VARIANT_AUTO) return false;
+    if (params->rgba_dtype == GMPI_DTYPE_U8) return false;   // (the band kernel is not built for the type)
+    if (!band_takes_tensors(p, params->rgba_dtype)) return false;
+    return params->variant == GMPI_VARIANT_BAND || lds_variant_supports(p, params->rgba_dtype);
+}
+
+int gmpi_render_chunk_band_supports(const GmpiRenderParams* params) {
+    KParams p;
+    const int rc = to_kparams(params, p, false, true, true);
+    return rc != GMPI_OK ? rc : (chunk_band_takes(p, params) ? 1 : 0);
+}
+
+uint64_t gmpi_render_chunk_band_workspace_bytes(const GmpiRenderParams* params) {
+    KParams p;
+    if (to_kparams(params, p, false, true, true) != GMPI_OK || p.N == 0 || !chunk_band_takes(p, params)) return 0;
+    return band_workspace_bytes(p, params->rgba_dtype);   // the table of the chunk's own D planes
+}
+
+int gmpi_mpi_render_chunk_band_launch(const GmpiRenderParams* params, const GmpiCarry* carry, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;  // no views
+    KParams p;
+    const int rc = to_kparams(params, p, false, true, true);
+    if (rc != GMPI_OK) return rc;
+    if (carry == nullptr) return GMPI_E_NULL;
+    if (carry->struct_size != sizeof(GmpiCarry)) return GMPI_E_ABI;
+    if (params->variant != GMPI_VARIANT_BAND && params->variant != GMPI_VARIANT_AUTO) return GMPI_E_VARIANT;
+    if (carry->state_out == nullptr && p.rgb_out == nullptr && p.depth_out == nullptr && p.T_out == nullptr) return GMPI_E_NULL;   // nothing to write
+    if (!chunk_band_takes(p, params)) return GMPI_E_VARIANT;
+    if (!band_workspace_ok(p, params->rgba_dtype)) return GMPI_E_WORKSPACE;
+    const CarryK ck{carry->state_in, carry->state_out};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (params->variant == GMPI_VARIANT_BAND) return hip_rc(launch_band_chunk(p, ck, params->rgba_dtype, st));   // bands whose boxes do not fit: the in-kernel direct gather
+    // AUTO: the pair of gmpi_mpi_render_launch's band path -- the table kernel stamps the gate word of every view with a box that does not fit, the band carry kernel
+    // renders the others, the tile kernel's carry instances render the stamped ones: every view's state passes through exactly one of the two.  No size threshold and
+    // no camera hints: the caller opted in.
+    KParams pb = p;
+    pb.gate = band_gate_words(p, params->rgba_dtype), pb.gate_gen = next_gate_gen(), pb.gate_sense = 0u;
+    const hipError_t e = launch_band_chunk(pb, ck, params->rgba_dtype, st);
+    if (e != hipSuccess) return hip_rc(e);
+    pb.gate_sense = 1u;
+    return hip_rc(launch_lds_chunk(pb, ck, params->rgba_dtype, st));
 }
 
 int gmpi_mpi_render_chunk_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, const float* grad_transmittance,
@@ -1244,6 +1299,7 @@ int gmpi_query(int32_t what) {
         case 44: return 1;  // the in-place backward of channels-last float layers (gmpi_mpi_render_layers_backward_launch, gmpi_render_layers_backward_supports) is built in  (43: unused)
         case 46: return 1;  // the backward of the shading augmentation's image-sized middle and the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch, gmpi_light_shade_images_backward_launch) are built in  (45: unused)
         case 48: return 1;  // the geometry backward over 8-bit volumes and float layers in place (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in  (47: unused)
+        case 50: return 1;  // the plane-chunked render through the band kernel (gmpi_mpi_render_chunk_band_launch, gmpi_render_chunk_band_workspace_bytes, gmpi_render_chunk_band_supports) is built in  (49: unused)
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -312,9 +312,15 @@ __global__ __launch_bounds__(1024) void band_table_kernel(const KParams p, const
     }
 }
 
-template <typename TexT, bool AC, bool STRICT, bool CHECK>
-__global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void render_band_kernel(const KParams p, const int bands_x, const int bands_y, const int n_bands, const float cx, const float cy,
-                                                         const uint4* __restrict__ recs, const uint4* __restrict__ pl, const uint32_t* __restrict__ hdr, uint32_t* __restrict__ tickets) {
+// The kernel body.  Carry = CarryK: the instances of a plane-chunked render (gmpi_mpi_render_chunk_band_launch): the Accum of every pixel enters from
+// state_in in place of the zero start and leaves to state_out, through the epilogue the tile kernel's carry instances share (store_pixel).  The table, the
+// XCD order, the tickets and the DMA know nothing of it: a chunk launch is a band launch over the chunk's own D planes and dhw rows.  state_in == state_out
+// is fine: every band is drawn exactly once -- the ticketed ones too --, so an ACTIVE lane reads and writes its own pixel only; a lane outside the image
+// shadows the last row / column, i.e. it may load a pixel that the lane owning it (of this or another workgroup) is rewriting, and its result is never stored.
+template <typename TexT, bool AC, bool STRICT, bool CHECK, typename Carry = NoCarry>
+__device__ __forceinline__ void render_band_body(const KParams& p, const int bands_x, const int bands_y, const int n_bands, const float cx, const float cy,
+                                                 const uint4* __restrict__ recs, const uint4* __restrict__ pl, const uint32_t* __restrict__ hdr, uint32_t* __restrict__ tickets,
+                                                 const Carry& carry = Carry{}) {
     using G = Geo<TexT>;
     constexpr int kES = G::kES, kTPI = G::kTPI, kCols = G::kCols, kNP = G::kNP;
     constexpr int NSB = G::NSB, PPT = G::PPT, WPS = G::WPS, kSubLanes = G::kSubLanes;
@@ -420,6 +426,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
         const int64_t pix = static_cast<int64_t>(min(py0 + WPS * q, H - 1)) * W + pxc;
         rx[q] = rdv[pix], ry[q] = rdv[HW + pix], rz[q] = rdv[2 * HW + pix];
         rcp_rz[q] = 1.0f / rz[q];  // correctly rounded; hoisted out of the plane loop (div_by_recip)
+        if constexpr (std::is_same_v<Carry, CarryK>) A[q] = load_carry(carry, n, HW, pix);  // (the clamped index: a lane outside the image reads valid memory)
     }
     auto ray_dot = [&](int q) { return gmpi::ray_dot(vw, rx[q], ry[q], rz[q]); };
 
@@ -883,7 +890,7 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
     for (int q = 0; q < PPT; ++q) {
         const int py = byi * SBH + wj + WPS * q;
         if (leaves_last_plane<AC>(vw, lp, rx[q], ry[q], rz[q])) bad |= GMPI_STATUS_OUT_OF_LAST_PLANE;
-        store_pixel<STRICT>(p, n, HW, static_cast<int64_t>(py) * W + px_e, A[q], ray_dot(q), px_e < W && py < H);
+        store_pixel<STRICT>(p, n, HW, static_cast<int64_t>(py) * W + px_e, A[q], ray_dot(q), px_e < W && py < H, carry);
     }
     report_status(p.status, bad);
 #ifdef GMPI_TUNE
@@ -904,6 +911,20 @@ __global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void
 #endif
 }
 
+template <typename TexT, bool AC, bool STRICT, bool CHECK>
+__global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void render_band_kernel(const KParams p, const int bands_x, const int bands_y, const int n_bands, const float cx, const float cy,
+                                                         const uint4* __restrict__ recs, const uint4* __restrict__ pl, const uint32_t* __restrict__ hdr, uint32_t* __restrict__ tickets) {
+    render_band_body<TexT, AC, STRICT, CHECK>(p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets, NoCarry{});
+}
+// (the carry instances: the state's five loads per pixel lie in front of the plane loop, its stores behind it; same bounds as their one-shot twins.  The carry is a kernel
+//  argument of its own -- as two more members of KParams the pointers moved band instances into scratch, gmpi_device.hpp)
+template <typename TexT, bool AC, bool STRICT, bool CHECK>
+__global__ __launch_bounds__(Geo<TexT>::kThreads, Geo<TexT>::kWavesPerSimd) void render_band_chunk_kernel(const KParams p, const CarryK carry, const int bands_x, const int bands_y, const int n_bands,
+                                                         const float cx, const float cy, const uint4* __restrict__ recs, const uint4* __restrict__ pl, const uint32_t* __restrict__ hdr,
+                                                         uint32_t* __restrict__ tickets) {
+    render_band_body<TexT, AC, STRICT, CHECK>(p, bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets, carry);
+}
+
 static int nsb_of(int dtype) { return dtype != 0 ? Geo<bf16_t>::NSB : Geo<float>::NSB; }  // (bf16 and fp16 share the 16-bit geometry)
 static void band_grid(const KParams& p, int nsb, int& bands_x, int& bands_y, int& n_bands) {
     bands_x = (p.W + nsb * SBW - 1) / (nsb * SBW), bands_y = (p.H + SBH - 1) / SBH;
@@ -919,8 +940,9 @@ static uint64_t ws_bytes(const KParams& p, int nsb) {
     return ws_hdr_bytes(nb, p.N) + ws_pl_bytes(p) + (static_cast<uint64_t>(nb) * p.D + 2) * nsb * 16;
 }
 
+// carry: nullptr = the one-shot kernels, else their carry instances
 template <typename TexT>
-static hipError_t launch_t(const KParams& p, hipStream_t stream) {
+static hipError_t launch_t(const KParams& p, const CarryK* carry, hipStream_t stream) {
     constexpr int NSB = Geo<TexT>::NSB;
     int bands_x, bands_y, n_bands;
     band_grid(p, NSB, bands_x, bands_y, n_bands);
@@ -942,8 +964,12 @@ static hipError_t launch_t(const KParams& p, hipStream_t stream) {
     // 2. the render
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
         dispatch_bool(p.flags & GMPI_FLAG_CHECK_RANGE, [&](auto CHECK) {
-            hipLaunchKernelGGL((render_band_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, decltype(CHECK)::value>), grid, block, 0, stream, p, bands_x,
-                               bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
+            if (carry != nullptr)
+                hipLaunchKernelGGL((render_band_chunk_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, decltype(CHECK)::value>), grid, block, 0, stream, p, *carry,
+                                   bands_x, bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
+            else
+                hipLaunchKernelGGL((render_band_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, decltype(CHECK)::value>), grid, block, 0, stream, p, bands_x,
+                                   bands_y, n_bands, cx, cy, recs, pl, hdr, tickets);
         });
     });
     return hipGetLastError();
@@ -961,11 +987,11 @@ uint32_t* band_gate_words(const KParams& p, int dtype) {
     return static_cast<uint32_t*>(p.ws) + nb;
 }
 
-bool band_variant_supports(const KParams& p, int dtype) {
+// What the band kernel asks of the tensors (everything but the workspace: gmpi_render_chunk_band_supports, whose launch answers a missing workspace with an error of its own).
+bool band_takes_tensors(const KParams& p, int dtype) {
     // fp32, bf16 and (round 4) fp16 volumes: a d16_hi load of a bf16 texel IS its fp32 value; an fp16 texel is converted inside the bilinear FMAs.
     if (dtype < 0 || dtype > 2) return false;
     const int nsb = band::nsb_of(dtype), bw = nsb * band::SBW;
-    if (p.ws == nullptr || p.ws_bytes < band::ws_bytes(p, nsb) || reinterpret_cast<uintptr_t>(p.ws) % 256 != 0) return false;  // needs the caller's workspace
     if (static_cast<int64_t>(p.N) * p.D * ((p.W + bw - 1) / bw) * ((p.H + 7) / 8) > (int64_t(1) << 28)) return false;  // record indices stay in 32 bits
     const int es = dtype == 0 ? 4 : 2;
     if (!volume_stages_in_items(p, dtype)) return false;
@@ -974,8 +1000,13 @@ bool band_variant_supports(const KParams& p, int dtype) {
     if (span >= (int64_t(1) << 31) / es) return false;
     return true;
 }
+bool band_workspace_ok(const KParams& p, int dtype) {
+    if (dtype < 0 || dtype > 2) return false;
+    return p.ws != nullptr && p.ws_bytes >= band::ws_bytes(p, band::nsb_of(dtype)) && reinterpret_cast<uintptr_t>(p.ws) % 256 == 0;  // the caller's workspace
+}
+bool band_variant_supports(const KParams& p, int dtype) { return band_workspace_ok(p, dtype) && band_takes_tensors(p, dtype); }
 
-hipError_t launch_band(const KParams& p0, int dtype, int tune, hipStream_t stream) {
+static hipError_t launch_band_any(const KParams& p0, const CarryK* carry, int dtype, int tune, hipStream_t stream) {
     KParams p = p0;
     p.band_cols = dtype != 0 ? band::kWindowCols16 : p.D > band::kDeepPlanes ? band::kWindowCols32Deep : band::kWindowCols32;
     p.band_rot = band::kViewRotation, p.band_split = band::kRunPieces, p.band_tail = band::kTicketTail;
@@ -993,7 +1024,10 @@ hipError_t launch_band(const KParams& p0, int dtype, int tune, hipStream_t strea
     (void)tune;
 #endif
     if (dtype < 0 || dtype > 2) return hipErrorInvalidValue;
-    return dispatch_dtype(dtype, [&](auto t) { return band::launch_t<typename decltype(t)::type>(p, stream); });
+    return dispatch_dtype(dtype, [&](auto t) { return band::launch_t<typename decltype(t)::type>(p, carry, stream); });
 }
+hipError_t launch_band(const KParams& p, int dtype, int tune, hipStream_t stream) { return launch_band_any(p, nullptr, dtype, tune, stream); }
+// One chunk of a plane-chunked render: the table kernel over the chunk's planes, then the carry instances.
+hipError_t launch_band_chunk(const KParams& p, const CarryK& carry, int dtype, hipStream_t stream) { return launch_band_any(p, &carry, dtype, 0, stream); }
 
 }  // namespace gmpi

@@ -677,7 +677,9 @@ hipError_t launch_lds(const KParams& p0, int dtype, int tune, hipStream_t stream
     });
 }
 
-// The carry instances: the shipped tile shape and layouts of launch_lds, never gated (a chunk launch is one kernel).  fp32: 6 waves per SIMD as the
+// The carry instances: the shipped tile shape and layouts of launch_lds.  gmpi_mpi_render_chunk_launch never gates them (its launch is one kernel);
+// gmpi_mpi_render_chunk_band_launch's AUTO does (KParams::gate: the views the band carry kernel leaves) -- render_lds_tile reads the gate words themselves when
+// no cached bits come with the call, in the per-group tile order a gated launch has.  fp32: 6 waves per SIMD as the
 // one-shot kernel.  16-bit volumes: the one-shot instances sit at the 64 VGPRs of 8 waves per SIMD (store_pixel's comment), and with the state's
 // pointers and its optional outputs every one of the eight instances went 8 to 28 bytes into scratch there; asked for 7 they take 68-72 VGPRs, none.
 constexpr int kChunkMinWaves16 = 7;
@@ -685,7 +687,7 @@ template <typename TexT, int TW, int MINW, int PF, int LAYOUT>
 static hipError_t launch_lds_chunk_t(const KParams& p, const CarryK& carry, hipStream_t stream) {
     constexpr int TH = kNT / TW;
     const FwdTileGrid tg = fwd_tile_grid<TW, TH>(p);
-    const unsigned grid_x = sizeof(TexT) == 4 ? tg.grid.x : static_cast<unsigned>(((tg.n_tiles + 7) / 8) * 8);  // (16-bit: one run per XCD, as launch_lds_t)
+    const unsigned grid_x = (p.gate != nullptr || sizeof(TexT) == 4) ? tg.grid.x : static_cast<unsigned>(((tg.n_tiles + 7) / 8) * 8);  // (16-bit: one run per XCD, as launch_lds_t)
     dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
         hipLaunchKernelGGL((render_lds_chunk_kernel<TexT, decltype(AC)::value, decltype(STRICT)::value, TW, MINW, PF, LAYOUT>), dim3(grid_x), dim3(kNT), 0, stream, p,
                            carry, tg.tiles_x, tg.tiles_y, tg.n_tiles);
@@ -694,8 +696,7 @@ static hipError_t launch_lds_chunk_t(const KParams& p, const CarryK& carry, hipS
 }
 hipError_t launch_lds_chunk(const KParams& p0, const CarryK& carry, int dtype, hipStream_t stream) {
     KParams p = p0;
-    p.band_rot = kTileViewRotation, p.band_split = kTileRunPieces;
-    p.gate = nullptr;
+    p.band_rot = kTileViewRotation, p.band_split = kTileRunPieces;   // (p.gate: nullptr from gmpi_mpi_render_chunk_launch)
     return dispatch_dtype(dtype, [&](auto t) {
         using TexT = typename decltype(t)::type;
         constexpr bool k16 = sizeof(TexT) == 2;

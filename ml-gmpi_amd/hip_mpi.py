@@ -561,6 +561,7 @@ def _warn_window_fallback() -> None:
 
 _GATHER_FALLBACK_WARNED = False
 _CHUNK_VARIANT_WARNED = False
+_CHUNK_BAND_WARNED = False
 _SHADED_BACKWARD_WARNED = False
 
 
@@ -595,9 +596,24 @@ def _warn_chunk_variant(name: str) -> None:
     global _CHUNK_VARIANT_WARNED
     if not _CHUNK_VARIANT_WARNED:
         _CHUNK_VARIANT_WARNED = True
-        warnings.warn(f'plane-chunked render: variant="{name}" has no kernel that takes a carried state (the strip kernel splits the plane axis '
-                      "itself, the band kernel is not built for it); the chunks render with the library's own choice, the tile kernel where it "
-                      "can take the tensors (counted in MPI.chunk_variant_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
+        warnings.warn(f'plane-chunked render: variant="{name}" selects no kernel of a chunk launch (the strip kernel splits the plane axis itself; the '
+                      'band kernel\'s carry instances are asked for per render, chunk_kernel="band" or "band+tile"); the chunks render with the '
+                      "library's own choice, the tile kernel where it can take the tensors (counted in MPI.chunk_variant_fallbacks; this warning is "
+                      "given once)", RuntimeWarning, stacklevel=4)
+
+
+CHUNK_KERNELS = {None: None, "band": _lib.VARIANT_BAND, "band+tile": _lib.VARIANT_AUTO}   # ChunkedRender.chunk_kernel -> the variant gmpi_mpi_render_chunk_band_launch gets
+
+
+def _warn_chunk_band(name: str) -> None:
+    """Once per process: a chunk asked for through the band kernel (chunk_kernel="band" / "band+tile") that the band entry cannot take (every such
+    launch is counted in `MPI.chunk_band_fallbacks`)."""
+    global _CHUNK_BAND_WARNED
+    if not _CHUNK_BAND_WARNED:
+        _CHUNK_BAND_WARNED = True
+        warnings.warn(f'plane-chunked render: chunk_kernel="{name}" cannot take these tensors (the band kernel reads fp32 / bf16 / fp16 volumes whose base '
+                      "pointer and outer strides are multiples of 16 bytes, textures of at most 8192 x 8192); the chunk renders as with chunk_kernel=None, "
+                      "the tile kernel where it can take the tensors (counted in MPI.chunk_band_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=4)
 
 
 def _warn_gather_fallback(kind: _Kind) -> None:
@@ -753,6 +769,7 @@ class MPI(nn.Module):
         self.depth_window_fallbacks = 0  # depth-alpha launches that asked for depth_forward="window" and ran the one-pixel kernel instead
         self.layout_gather_fallbacks = 0   # shared-colour / depth-alpha backwards that asked for "gather" and ran the atomic kernels instead
         self.chunk_variant_fallbacks = 0   # chunk launches of a module built with variant "band" / "wave", which ran AUTO's chunk kernel instead
+        self.chunk_band_fallbacks = 0      # chunk launches asked for with chunk_kernel="band" / "band+tile" that the band entry could not take: today's path ran
         self.shaded_lds_fallbacks = 0    # shaded launches of a module built with variant "lds" that ran the one-pixel kernel instead
         self.shaded_backward_fallbacks = 0   # shaded backwards of a module built with backward="gather", which ran the default backward instead
         self.layers_copies = 0           # render_views_layers calls whose layers were not read in place: a contiguous copy of the layers was rendered
@@ -1184,7 +1201,10 @@ class MPI(nn.Module):
         the next Dc planes [M, Dc, 4, Ht, Wt] -- the next Dc rows of dhw [M, D, 3] -- and launches at once, `.finish()` returns `render_views`' dict.
         Between the launches only a per-pixel state [N, 5, H, W] lives on the device: the stack [M, D, 4, Ht, Wt] never exists as one tensor.  kwargs:
         `render_views`' views_per_mpi, view_to_mpi, check_last_plane, out_pm1, want_transmittance, status, defer_status, out (and c2w_mat, sphere_c
-        for the diagnostics of a ray that leaves the last plane).  The no-gradient path: see `render_views_chunks` for chunks that require grad."""
+        for the diagnostics of a ray that leaves the last plane), and chunk_kernel: None (default) = gmpi_mpi_render_chunk_launch with this module's
+        variant, "band" = the band kernel's carry instances (gmpi_mpi_render_chunk_band_launch with GMPI_VARIANT_BAND), "band+tile" = the same with
+        GMPI_VARIANT_AUTO, views whose texel boxes do not fit the band kernel handed to the tile kernel's carry instances -- `ChunkedRender.chunk_kernel`,
+        read at every `add`.  The no-gradient path: see `render_views_chunks` for chunks that require grad."""
         return ChunkedRender(self, dhw, ray_dir, eye_pos, z_dir, **kwargs)
 
     def render_views_chunks(self, chunks, dhw: torch.Tensor, ray_dir: torch.Tensor, eye_pos: torch.Tensor, z_dir: torch.Tensor, **kwargs):
@@ -1196,7 +1216,8 @@ class MPI(nn.Module):
         in place (gmpi_mpi_render_chunk_backward_launch), and every chunk gets a gradient of ITS size in its dtype: no [M, D, ...] gradient volume.
         (An iterator whose chunks require grad is refused by `ChunkedRender.add`: the backward needs every chunk again.)  `MPI(backward="gather")`
         takes the atomic kernels here -- the atomics-free pair has no chunk form --, `MPI(variant="gather")` the one-pixel-per-lane kernels.  No
-        gradient reaches the camera tensors or dhw: with geometry_grad such tensors raise NotImplementedError."""
+        gradient reaches the camera tensors or dhw: with geometry_grad such tensors raise NotImplementedError.  chunk_kernel ("band" / "band+tile":
+        `chunked_render`) selects the forward launches, under autograd too; the chunk backward is the same either way."""
         if torch.is_grad_enabled():
             if any(t.requires_grad for t in (dhw, ray_dir, eye_pos, z_dir)) and (self.geometry_grad or dhw.requires_grad):
                 raise NotImplementedError("the plane-chunked render has no gradient w.r.t. the plane geometry or the camera tensors: use render_views "
@@ -1516,16 +1537,21 @@ class _ShadedRenderFunction(torch.autograd.Function):
 
 
 class ChunkedRender:
-    """`MPI.chunked_render`: the volume of a `render_views` call, a few planes at a time.  Every `add` is one gmpi_mpi_render_chunk_launch whose state
+    """`MPI.chunked_render`: the volume of a `render_views` call, a few planes at a time.  Every `add` is one gmpi_mpi_render_chunk_launch -- or, with
+    `chunk_kernel` "band" / "band+tile", one gmpi_mpi_render_chunk_band_launch over the stream's lent workspace -- whose state
     is read and written in place; the LAST chunk -- the one that reaches dhw's D planes -- alone carries GMPI_FLAG_CHECK_LAST_PLANE and
     GMPI_FLAG_OUT_PM1 and alone gets output pointers.  No reference to a chunk is kept.  One status word serves the whole stack -- words of this
     object's own unless the caller passes `status` -- and is settled once, in `finish()` (defer_status=True: not at all; "lag" reads back at once:
     the ring's entries keep the tensors of ONE launch).  range_check="full" runs the exhaustive pass on every chunk (never cached).  Peak memory
-    above the inputs: one chunk, the state (five images per view) and the outputs."""
+    above the inputs: one chunk, the state (five images per view) and the outputs.
+    `chunk_kernel` is a public attribute, read at every `add`: it may change between two chunks -- the state is one format, whichever kernel wrote it.  A
+    chunk the band entry cannot take (uint8, an unaligned view, Ht or Wt above 8192) renders as with None: counted in `MPI.chunk_band_fallbacks`."""
 
     def __init__(self, mpi, dhw, ray_dir, eye_pos, z_dir, views_per_mpi=1, view_to_mpi=None, check_last_plane=False, out_pm1=False,
-                 want_transmittance=False, status=None, defer_status=False, out=None, c2w_mat=None, sphere_c=None):
+                 want_transmittance=False, status=None, defer_status=False, out=None, c2w_mat=None, sphere_c=None, chunk_kernel=None):
         assert dhw.ndim == 3 and dhw.shape[2] == 3, dhw.shape
+        assert chunk_kernel in CHUNK_KERNELS, f"chunk_kernel is one of {list(CHUNK_KERNELS)}, got {chunk_kernel!r}"
+        self.chunk_kernel = chunk_kernel
         self.mpi, self.geometry = mpi, (dhw, ray_dir, eye_pos, z_dir)
         self.views = (views_per_mpi, view_to_mpi)
         self.check_last_plane, self.out_pm1, self.want_T = check_last_plane, out_pm1, want_transmittance
@@ -1551,9 +1577,8 @@ class ChunkedRender:
         if self.status is None:   # (never the stream's shared words: another render may settle -- and clear -- them between two chunks)
             self.status = torch.zeros(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
         variant = mpi.variant
-        if variant in ("band", "wave"):
+        if variant in ("band", "wave"):   # (warned of where such a launch runs: `add`)
             variant = "auto"
-            _warn_chunk_variant(mpi.variant)
         self._fallback, self._variant = variant != mpi.variant, _lib.VARIANTS[variant]
 
     def add(self, chunk: torch.Tensor, _T: Optional[torch.Tensor] = None):
@@ -1607,9 +1632,31 @@ class ChunkedRender:
             carry.state_out = None if last else self.state.data_ptr()
             if mpi.range_check == "full" and chunk.dtype is not torch.uint8:
                 _range_pass((chunk,), p, dev, stream)
-            _call("gmpi_mpi_render_chunk_launch", dev, ctypes.byref(p), ctypes.byref(carry), stream=stream)
-        if self._fallback:
-            mpi.chunk_variant_fallbacks += 1
+            assert self.chunk_kernel in CHUNK_KERNELS, f"chunk_kernel is one of {list(CHUNK_KERNELS)}, got {self.chunk_kernel!r}"
+            band = self.chunk_kernel is not None
+            if band:   # the band entry, where it takes this chunk: its own variant, the stream's workspace for the chunk's table
+                lib = _lib.load_library()
+                p.variant = CHUNK_KERNELS[self.chunk_kernel]
+                takes = lib.gmpi_render_chunk_band_supports(ctypes.byref(p))
+                if takes < 0:
+                    _lib.check(takes, "gmpi_render_chunk_band_supports")
+                if takes == 1:
+                    need = int(lib.gmpi_render_chunk_band_workspace_bytes(ctypes.byref(p)))
+                    if not on_device:   # (a records-only library: nothing reads the bytes, the pointer stays valid as long as this object)
+                        self._host_ws = torch.empty(need, dtype=torch.uint8)
+                    _lend(p, _workspace(dev, stream, need) if on_device else self._host_ws)
+                    _call("gmpi_mpi_render_chunk_band_launch", dev, ctypes.byref(p), ctypes.byref(carry), stream=stream)
+                    # (the struct goes on to the autograd node's backward and to the diagnostics as today's: the chunk backward is the same either way)
+                    p.variant, p.workspace, p.workspace_bytes = self._variant, None, 0
+                else:   # today's path, call for call
+                    band, p.variant = False, self._variant
+                    mpi.chunk_band_fallbacks += 1
+                    _warn_chunk_band(self.chunk_kernel)
+            if not band:
+                _call("gmpi_mpi_render_chunk_launch", dev, ctypes.byref(p), ctypes.byref(carry), stream=stream)
+                if self._fallback:
+                    mpi.chunk_variant_fallbacks += 1
+                    _warn_chunk_variant(mpi.variant)
         self.planes, self.n_chunks = k0 + Dc, self.n_chunks + 1
         if last:
             # (what a tripped assertion's diagnostics read: the last chunk's struct and camera tensors -- not the chunk, which is not kept)

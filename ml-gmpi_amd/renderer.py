@@ -429,6 +429,8 @@ class MPIRenderer:
         shading = ext.pop("_shading", None)   # render_shaded: the shading image [B,1,Ht,Wt] of the shaded render
         layers_variant = ext.pop("_layers", None)   # render_layers: batch_mpi_rgbas is then the stack of layers [B,D,Ht,Wt,4]; (variant, layers_backward)
         chunks = ext.pop("_chunks", None)   # render_chunks: the stack's chunks (batch_mpi_rgbas is then the first of them, looked at for its shape alone)
+        chunk_kernel = ext.pop("chunk_kernel", None)   # render_chunks: None | "band" | "band+tile" (MPI.chunked_render)
+        assert chunk_kernel is None or chunks is not None, "chunk_kernel is render_chunks' keyword"
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -472,7 +474,7 @@ class MPIRenderer:
         if chunks is not None:   # (no camera hints: a chunk launch has one kernel per variant, whatever the pose)
             res = self.mpi.render_views_chunks(
                 chunks, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi, check_last_plane=assert_not_out_of_last_plane, out_pm1=True,
-                want_transmittance=want_T, c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer)
+                want_transmittance=want_T, c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, chunk_kernel=chunk_kernel)
         elif layers_variant is not None:   # (the camera hints are accepted and ignored by the layout's entry: not passed)
             res = self.mpi.render_views_layers(
                 batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, variant=layers_variant[0], layers_backward=layers_variant[1], views_per_mpi=views_per_mpi,
@@ -502,7 +504,8 @@ class MPIRenderer:
         generates `chunk_n_planes` planes at a time, without its torch.cat.  An iterator is consumed lazily, one chunk alive at a time (no
         gradients); a list or tuple whose chunks require grad is recorded by one autograd node.  Keyword arguments and the return tuple are
         `render`'s (T fifth under want_transmittance=True); the poses are sampled once, before the first chunk is rendered, exactly as `render`
-        samples them: a seeded call returns `render`'s c2w and angles.  A status check that lags ("lag") is read back at once here."""
+        samples them: a seeded call returns `render`'s c2w and angles.  A status check that lags ("lag") is read back at once here.
+        chunk_kernel (None | "band" | "band+tile") is passed through to `MPI.render_views_chunks`: the band kernel's carry instances."""
         if isinstance(chunks, (list, tuple)):
             assert len(chunks) > 0, "no chunks"
             return self.render(chunks[0], render_h, render_w, _chunks=chunks, **kwargs)

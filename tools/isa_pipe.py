@@ -53,6 +53,21 @@ def check(body, name):
     return bad
 
 
+def counted_waits(body):
+    """How many waits of the listing leave LDS operations in flight (`lgkmcnt(N)`, N > 0): what tells a software-pipelined plane step from one that
+    drains the counter behind every batch."""
+    return sum(1 for l in body if re.search(r"s_waitcnt lgkmcnt\([1-9]\d*\)", l))
+
+
+def kernel_bodies(asm, key):
+    """{mangled name: listing lines} of every kernel of the -save-temps listing `asm` whose name contains `key`."""
+    out = {}
+    for name in sorted(set(n for n in re.findall(r"^(_Z\w+):", asm, flags=re.M) if key in n)):
+        a = asm.index("\n" + name + ":") + 1
+        out[name] = asm[a:asm.index(".Lfunc_end", a)].split("\n")
+    return out
+
+
 def main():
     s = open(sys.argv[1]).read()
     key = sys.argv[2] if len(sys.argv) > 2 else "render_band_kernel"
@@ -62,7 +77,7 @@ def main():
         a = s.index(name + ":")
         body = s[a:s.index(".Lfunc_end", a)].split("\n")
         bad = check(body, name)
-        n_counted = sum(1 for l in body if re.search(r"s_waitcnt lgkmcnt\([1-9]\d*\)", l))
+        n_counted = counted_waits(body)
         print(f"{name}: {n_counted} counted LDS waits, {len(bad)} uses of in-flight LDS destinations")
         for ln, txt, regs in bad[:10]:
             print(f"   line {ln}: {txt}   <- v{regs}")

@@ -4,12 +4,14 @@ forward + backward at the 32-plane G-step shapes (256^2 x 8, 512^2 x 4, 1024^2 x
 tensor (it has to exist for the one-shot columns): what is timed is the launches, not a generator.
 
   chunked        render_views_chunks over the chunks, variant "lds" (what "auto" means for a chunk launch wherever the tile kernel takes the tensors)
+  chunked_band   the same through the band kernel's carry instances (chunk_kernel="band": gmpi_mpi_render_chunk_band_launch, a table kernel per chunk)
+  chunked_band_tile  chunk_kernel="band+tile": the band carry kernel and the gated tile carry kernel behind it, per chunk
   one_lds        the one-shot render_views of the whole volume with the same variant
   one_auto       the one-shot render_views with variant "auto" (the band kernel at these sizes, with its workspace)
   emulated       what the parent commit allows: per chunk render_views(..., want_transmittance=True) -- "auto" --, combined with image-sized torch ops
                  (C += T C_c, Z += T Z_c, T *= T_c: three passes per chunk); not bit-identical to the one-shot render
   *_peak_mb      peak device memory of one call above the inputs (volume, camera tensors): outputs, state, workspace
-  err_*          max |colour difference| of `chunked` and `emulated` against one_lds (chunked: 0 is expected and asserted in strict order by the tests;
+  err_*          max |colour difference| of `chunked`, `chunked_band` (against one_auto: the band kernel's own one-shot render) and `emulated` against one_lds (chunked: 0 is expected and asserted in strict order by the tests;
                  here the default mode runs)
   G-step rows    fwd+bwd of render_views (tile backward, zero-fill included) against render_views_chunks under autograd (one zero-filled buffer per chunk)
 
@@ -83,6 +85,7 @@ def one(S, B, D, dtype_name, with_backward, reps, sizes):
             one_lds = lambda: r_lds.mpi.render_views(vol, dhw, ray, eye, zd, **kw)
             one_auto = lambda: r_auto.mpi.render_views(vol, dhw, ray, eye, zd, **kw)
             ref = one_lds()["color"].clone()
+            ref_auto = one_auto()["color"].clone()
             row["one_lds"], row["one_auto"] = timed(one_lds), timed(one_auto)
             row["one_lds_peak_mb"], row["one_auto_peak_mb"] = peak(one_lds), peak(one_auto)
             for Dc in sizes:
@@ -91,6 +94,11 @@ def one(S, B, D, dtype_name, with_backward, reps, sizes):
                 row[f"chunked_{Dc}"], row[f"emulated_{Dc}"] = timed(chunked), timed(lambda: emulated(Dc))
                 row[f"chunked_{Dc}_peak_mb"], row[f"emulated_{Dc}_peak_mb"] = peak(chunked), peak(lambda: emulated(Dc))
                 row[f"err_chunked_{Dc}"] = float((chunked()["color"] - ref).abs().max())
+                for name, kernel in (("chunked_band", "band"), ("chunked_band_tile", "band+tile")):
+                    banded = lambda: r_lds.mpi.render_views_chunks(chunks, dhw, ray, eye, zd, chunk_kernel=kernel, **kw)
+                    row[f"{name}_{Dc}"], row[f"{name}_{Dc}_peak_mb"] = timed(banded), peak(banded)
+                    row[f"err_{name}_{Dc}"] = float((banded()["color"] - ref_auto).abs().max())
+                assert r_lds.mpi.chunk_band_fallbacks == 0
                 row[f"err_emulated_{Dc}"] = float((emulated(Dc)[0] - ref).abs().max())
     else:
         gc = torch.randn((B, 3, S, S), device=dev, generator=g)
