@@ -344,6 +344,42 @@ uint64_t gmpi_render_chunk_band_workspace_bytes(const GmpiRenderParams *params);
 int gmpi_render_chunk_band_supports(const GmpiRenderParams *params);
 
 /*
+ * Sparse GMPI_DTYPE_U8 volumes: the staged uint8 kernel (GMPI_VARIANT_LDS above) skipping every (tile, plane) whose texel box holds alpha code 0 alone.
+ *
+ * Stored MPIs are mostly empty, and at 8 bits "empty" is the exact code 0.  An alpha sample of exactly 0 changes nothing: w = 0 T, C += 0 rgb,
+ * Z += 0 depth, T (1 - 0 + 1e-10) = T 1.0f.  So such a pair needs no loads, no LDS store, no taps, no conversions and no bilerps -- and skipping them
+ * moves no output bit and no status bit (codes cannot be out of range: GMPI_FLAG_CHECK_RANGE has nothing to miss).  The bits are those of
+ * gmpi_mpi_render_launch with GMPI_VARIANT_LDS on the same parameters, in both modes and for both layouts, whatever the ray field: an empty plane still
+ * computes each pixel's coordinates and its box test, a pixel whose footprint lies outside its tile's box takes the direct gather as ever, every other
+ * pixel is blended with the all-zero sample and its own s and dot (so a non-finite s does to the depth what it did before).
+ *
+ * The occupancy map: uint8 map[M, D, ceil(Ht / B), ceil(Wt / B)], contiguous, B = gmpi_query(53) = 16; an entry is the largest alpha code among the texels
+ * of its B x B block that exist (border blocks are partial).  gmpi_u8_occupancy_launch builds it from a planar or channels-last GMPI_DTYPE_U8 volume with
+ * any outer strides (the stride rules of gmpi_mpi_render_launch; no alignment is asked for), reading the alpha bytes only; it uses nothing of *params but
+ * the volume description: rgba, rgba_dtype, rgba_stride, M, D, Ht, Wt and struct_size.  gmpi_u8_occupancy_bytes is the map's size (0 for a struct the launch refuses).
+ * A map describes the codes it was built from: after a write to the volume it must be rebuilt (a stale zero skips texels that are no longer empty).
+ *
+ * gmpi_mpi_render_u8_sparse_launch: params as gmpi_mpi_render_launch takes a GMPI_DTYPE_U8 volume, variant AUTO or LDS; occ->map the volume's map, occ->block =
+ * gmpi_query(53); occ->stats NULL or two uint32 counters on the device, to which every workgroup adds (atomically) [0] the (tile, plane) pairs it skipped and
+ * [1] those it staged -- a pair whose box does not fit the staging buffer takes the direct gather and is neither.  Per tile the thread that fills a plane's row of
+ * the box table tests the box, clipped to the texture (outside is zero padding), against the at most 5 x 3 blocks it overlaps.
+ * Refusals, nothing written: a struct error as gmpi_mpi_render_launch; another dtype: GMPI_E_DTYPE; occ or occ->map NULL: GMPI_E_NULL; occ->block !=
+ * gmpi_query(53): GMPI_E_SHAPE; any other variant, or tensors the staged kernel cannot take (the alignment rules above): GMPI_E_VARIANT --
+ * gmpi_render_u8_sparse_supports says 1 / 0 (GMPI_E_VARIANT) / a negative error beforehand.  N == 0: GMPI_OK.
+ * Stream-ordered, allocate nothing, never synchronise.  Not built: float volumes, the carry instances of the chunked render, thresholds above code 0 (not
+ * exact), early termination behind opaque planes; GMPI_VARIANT_AUTO of gmpi_mpi_render_launch never comes here.  gmpi_query(52) == 1 says the four entries are built in.
+ */
+typedef struct GmpiOccupancy {
+    const uint8_t *map;   /* [M, D, ceil(Ht / block), ceil(Wt / block)], device memory                         */
+    int32_t block;        /* gmpi_query(53)                                                                    */
+    uint32_t *stats;      /* NULL, or uint32[2] on the device: [0] += pairs skipped, [1] += pairs staged       */
+} GmpiOccupancy;
+uint64_t gmpi_u8_occupancy_bytes(const GmpiRenderParams *params);
+int gmpi_u8_occupancy_launch(const GmpiRenderParams *params, uint8_t *map, void *stream);
+int gmpi_mpi_render_u8_sparse_launch(const GmpiRenderParams *params, const GmpiOccupancy *occ, void *stream);
+int gmpi_render_u8_sparse_supports(const GmpiRenderParams *params, const GmpiOccupancy *occ);
+
+/*
  * Gradient of a chunked render w.r.t. ONE chunk; chunks are swept from the last to the first.  `params` are the chunk's forward parameters;
  * params->transmittance_out is T BEHIND the chunk as the forward launch wrote it (NULL: rebuilt from T_in by a walk of the chunk's alpha).  grad_rgb,
  * grad_depth, grad_transmittance are the gradients w.r.t. the FINAL images (grad_depth NULL or given to every chunk; grad_transmittance to the LAST chunk
@@ -916,7 +952,9 @@ int gmpi_stream_probe_launch(const void *buf, uint64_t bytes, uint32_t *sink, vo
  * gmpi_light_shade_images_backward_launch) are built in; 47 is unused (-1); 48 whether the geometry backward over 8-bit volumes and float layers in place
  * (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in;
  * 49 is unused (-1); 50 whether the plane-chunked render through the band kernel (gmpi_mpi_render_chunk_band_launch, gmpi_render_chunk_band_workspace_bytes,
- * gmpi_render_chunk_band_supports) is built in.
+ * gmpi_render_chunk_band_supports) is built in; 51 is unused (-1); 52 whether the occupancy map and the sparse render of GMPI_DTYPE_U8 volumes
+ * (gmpi_u8_occupancy_bytes, gmpi_u8_occupancy_launch, gmpi_mpi_render_u8_sparse_launch, gmpi_render_u8_sparse_supports) are built in; 53 the side of a block of
+ * that map in texels (16).
  * Unknown -> -1.  */
 int gmpi_query(int32_t what);
 

@@ -10,6 +10,7 @@ from .shaded import apply_shading
 from .depth_alpha import depth_alpha_bounds, depth_alpha_planes, expand_depth_alpha
 from .quantized import quantize_volume, dequantize_volume, layers_as_volume, volume_as_layers
 from .layers import is_float_layers
+from .occupancy import Occupancy, build_occupancy, occupancy_reference
 
 __all__ = [
     "GmpiError", "build_extension", "library_path", "load_library",
@@ -20,4 +21,5 @@ __all__ = [
     "depth_alpha_bounds", "depth_alpha_planes", "expand_depth_alpha",
     "quantize_volume", "dequantize_volume", "layers_as_volume", "volume_as_layers",
     "is_float_layers",
+    "Occupancy", "build_occupancy", "occupancy_reference",
 ]

@@ -40,6 +40,10 @@ EXPORTS = (
     "gmpi_mpi_render_chunk_band_launch",
     "gmpi_render_chunk_band_workspace_bytes",
     "gmpi_render_chunk_band_supports",
+    "gmpi_u8_occupancy_bytes",
+    "gmpi_u8_occupancy_launch",
+    "gmpi_mpi_render_u8_sparse_launch",
+    "gmpi_render_u8_sparse_supports",
     "gmpi_mpi_render_layers_launch",
     "gmpi_render_layers_supports",
     "gmpi_mpi_render_layers_backward_launch",
@@ -126,6 +130,11 @@ class GmpiCarry(ctypes.Structure):
         ("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
         ("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p),
     ]
+
+
+class GmpiOccupancy(ctypes.Structure):
+    """Field-for-field mirror of `struct GmpiOccupancy` in include/gmpi_render.h: the occupancy map of a uint8 volume, as the sparse render reads it."""
+    _fields_ = [("map", ctypes.c_void_p), ("block", ctypes.c_int32), ("stats", ctypes.c_void_p)]
 
 
 class GmpiSharedColor(ctypes.Structure):
@@ -268,6 +277,15 @@ def load_library():
     lib.gmpi_render_chunk_band_workspace_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams)]
     lib.gmpi_render_chunk_band_supports.restype = ctypes.c_int
     lib.gmpi_render_chunk_band_supports.argtypes = [ctypes.POINTER(GmpiRenderParams)]
+    # the occupancy map of a uint8 volume and the sparse render that reads it (gmpi_query(52); block side gmpi_query(53))
+    lib.gmpi_u8_occupancy_bytes.restype = ctypes.c_uint64
+    lib.gmpi_u8_occupancy_bytes.argtypes = [ctypes.POINTER(GmpiRenderParams)]
+    lib.gmpi_u8_occupancy_launch.restype = ctypes.c_int
+    lib.gmpi_u8_occupancy_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp, vp]
+    lib.gmpi_mpi_render_u8_sparse_launch.restype = ctypes.c_int
+    lib.gmpi_mpi_render_u8_sparse_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiOccupancy), vp]
+    lib.gmpi_render_u8_sparse_supports.restype = ctypes.c_int
+    lib.gmpi_render_u8_sparse_supports.argtypes = [ctypes.POINTER(GmpiRenderParams), ctypes.POINTER(GmpiOccupancy)]
     # channels-last float layers [M,D,Ht,Wt,4] in place (rgba_stride [s_M, s_D, 1, s_row, 4]; gmpi_query(42)): the launch, and whether its staged kernel takes the tensors
     lib.gmpi_mpi_render_layers_launch.restype = ctypes.c_int
     lib.gmpi_mpi_render_layers_launch.argtypes = [ctypes.POINTER(GmpiRenderParams), vp]

@@ -64,6 +64,10 @@ int depth_window_query(int what);                                           // r
 hipError_t launch_u8(const KParams& p, hipStream_t stream);                 // render_u8.hip
 bool u8_variant_supports(const KParams& p);                                 // render_u8.hip
 int u8_variant_query(int what);                                             // render_u8.hip
+hipError_t launch_u8_sparse(const KParams& p, const uint8_t* map, uint32_t* stats, hipStream_t stream);   // render_u8.hip
+uint64_t u8_occupancy_bytes(int M, int D, int Ht, int Wt);                   // render_u8.hip
+hipError_t launch_u8_occupancy(const void* vol, int64_t s_mpi, int64_t s_plane, int64_t s_row, int64_t a_off, int xs, int M, int D, int Ht, int Wt, uint8_t* map,
+                               hipStream_t stream);                         // render_u8.hip
 hipError_t launch_gather_layers(const KParams& p, int dtype, hipStream_t stream);   // render_gather.hip
 hipError_t launch_layers(const KParams& p, int dtype, hipStream_t stream);  // render_layers.hip
 bool layers_variant_supports(const KParams& p, int dtype);                  // render_layers.hip
@@ -678,6 +682,65 @@ int gmpi_mpi_render_chunk_band_launch(const GmpiRenderParams* params, const Gmpi
     if (e != hipSuccess) return hip_rc(e);
     pb.gate_sense = 1u;
     return hip_rc(launch_lds_chunk(pb, ck, params->rgba_dtype, st));
+}
+
+// ---- sparse 8-bit volumes (render_u8.hip): the occupancy map of a volume, and the staged uint8 kernel's instances that skip the boxes it says are empty.
+// The map entries read the volume description alone: the strides by the rules of to_kparams, nothing of the views.  On GMPI_OK: the alpha channel's byte
+// offset inside a plane and the bytes from one texel of a row to the next.
+static int occupancy_volume(const GmpiRenderParams* q, int64_t& a_off, int& xs) {
+    if (q == nullptr) return GMPI_E_NULL;
+    if (q->struct_size != sizeof(GmpiRenderParams)) return GMPI_E_ABI;
+    if (q->M <= 0 || q->D <= 0 || q->Ht <= 0 || q->Wt <= 0) return GMPI_E_SHAPE;
+    if (q->rgba == nullptr) return GMPI_E_NULL;
+    if (q->rgba_dtype != GMPI_DTYPE_U8) return GMPI_E_DTYPE;
+    const bool interleaved = q->rgba_stride[4] == 4 && q->rgba_stride[2] == 1;
+    if (q->rgba_stride[4] != 1 && !interleaved) return GMPI_E_STRIDE;
+    for (int i = 0; i < 4; ++i)
+        if (q->rgba_stride[i] < 0) return GMPI_E_STRIDE;
+    if (q->rgba_stride[3] < (interleaved ? 4 : 1) * static_cast<int64_t>(q->Wt) || q->rgba_stride[2] == 0 || q->rgba_stride[1] == 0) return GMPI_E_STRIDE;
+    a_off = 3 * q->rgba_stride[2], xs = interleaved ? 4 : 1;
+    return GMPI_OK;
+}
+
+uint64_t gmpi_u8_occupancy_bytes(const GmpiRenderParams* params) {
+    int64_t a_off;
+    int xs;
+    return occupancy_volume(params, a_off, xs) == GMPI_OK ? u8_occupancy_bytes(params->M, params->D, params->Ht, params->Wt) : 0;
+}
+
+int gmpi_u8_occupancy_launch(const GmpiRenderParams* params, uint8_t* map, void* stream) {
+    int64_t a_off;
+    int xs;
+    const int rc = occupancy_volume(params, a_off, xs);
+    if (rc != GMPI_OK) return rc;
+    if (map == nullptr) return GMPI_E_NULL;
+    return hip_rc(launch_u8_occupancy(params->rgba, params->rgba_stride[0], params->rgba_stride[1], params->rgba_stride[3], a_off, xs, params->M, params->D,
+                                      params->Ht, params->Wt, map, static_cast<hipStream_t>(stream)));
+}
+
+// What the sparse launch and its query check alike, in this order: the struct, the type, the map, its block size, then the variant and the tensors.
+static int u8_sparse_args(const GmpiRenderParams* params, const GmpiOccupancy* occ, KParams& p) {
+    const int rc = to_kparams(params, p, true, false, true);
+    if (rc != GMPI_OK) return rc;
+    if (params->rgba_dtype != GMPI_DTYPE_U8) return GMPI_E_DTYPE;
+    if (occ == nullptr || occ->map == nullptr) return GMPI_E_NULL;
+    if (occ->block != u8_variant_query(53)) return GMPI_E_SHAPE;
+    if (params->variant != GMPI_VARIANT_AUTO && params->variant != GMPI_VARIANT_LDS) return GMPI_E_VARIANT;
+    return u8_variant_supports(p) ? GMPI_OK : GMPI_E_VARIANT;
+}
+
+int gmpi_render_u8_sparse_supports(const GmpiRenderParams* params, const GmpiOccupancy* occ) {
+    KParams p;
+    const int rc = u8_sparse_args(params, occ, p);
+    return rc == GMPI_OK ? 1 : rc == GMPI_E_VARIANT ? 0 : rc;
+}
+
+int gmpi_mpi_render_u8_sparse_launch(const GmpiRenderParams* params, const GmpiOccupancy* occ, void* stream) {
+    if (params != nullptr && params->struct_size == sizeof(GmpiRenderParams) && params->N == 0) return GMPI_OK;  // no views
+    KParams p;
+    const int rc = u8_sparse_args(params, occ, p);
+    if (rc != GMPI_OK) return rc;
+    return hip_rc(launch_u8_sparse(p, occ->map, occ->stats, static_cast<hipStream_t>(stream)));
 }
 
 int gmpi_mpi_render_chunk_backward_launch(const GmpiRenderParams* params, const float* grad_rgb, const float* grad_depth, const float* grad_transmittance,
@@ -1300,6 +1363,8 @@ int gmpi_query(int32_t what) {
         case 46: return 1;  // the backward of the shading augmentation's image-sized middle and the shade-images pair (gmpi_light_shading_backward_launch, gmpi_light_blur_backward_launch, gmpi_light_shade_images_launch, gmpi_light_shade_images_backward_launch) are built in  (45: unused)
         case 48: return 1;  // the geometry backward over 8-bit volumes and float layers in place (gmpi_mpi_render_u8_geometry_backward_launch, gmpi_mpi_render_layers_geometry_backward_launch, gmpi_render_geometry_inplace_workspace_bytes) is built in  (47: unused)
         case 50: return 1;  // the plane-chunked render through the band kernel (gmpi_mpi_render_chunk_band_launch, gmpi_render_chunk_band_workspace_bytes, gmpi_render_chunk_band_supports) is built in  (49: unused)
+        case 52: return 1;  // the occupancy map and the sparse render of 8-bit volumes (gmpi_u8_occupancy_bytes, gmpi_u8_occupancy_launch, gmpi_mpi_render_u8_sparse_launch, gmpi_render_u8_sparse_supports) are built in  (51: unused)
+        case 53: return u8_variant_query(what);  // the side of a block of that map, in texels
         case 36: return 1;  // the plane-chunked render (gmpi_mpi_render_chunk_launch, gmpi_mpi_render_chunk_backward_launch) is built in  (35: unused)
         default: return -1;
     }

@@ -29,6 +29,11 @@
 // a single pixel whose footprint lies outside its tile's box (a ray field that is no pinhole camera's).  Weights of taps outside the texture are
 // zeroed as gather_sample zeroes them, so in strict-order mode a pixel's bits do not depend on the path; in default mode gather_plane converts per
 // tap, which differs from the staged sample by the 2e-7 above.  GMPI_FLAG_CHECK_RANGE has nothing to test: every code is in [0, 1].
+//
+// Sparse volumes (opt-in: gmpi_mpi_render_u8_sparse_launch).  A stored MPI is mostly empty, and at 8 bits "empty" is the exact alpha code 0, whose composite
+// changes nothing: w = 0 T, C += 0 rgb, Z += 0 depth, T (1 - 0 + 1e-10) = T 1.0f.  u8_occupancy_kernel reduces a volume's alpha bytes to the largest code per
+// 16 x 16 texel block; the Occ = OccK instances of the body below look a plane's box up in that map while they fill the plane table and, where it holds code 0
+// alone, neither load nor stage nor sample it -- the same bits, for any ray field (composite's EMPTY branch has the argument).  Occ = NoOcc is the dense text.
 #include "gmpi_device.hpp"
 
 namespace gmpi {
@@ -47,11 +52,42 @@ static_assert(2 * kUBufWords * 4 + kUChunk * 48 <= 40 * 1024, "4 workgroups per 
 // run of 16 bytes per item.  The item's dword alignment is what u8_variant_supports asks for.  Everything behind the LDS image is the same code:
 // the kernel body is this one function, the two kernels below are its instances (the planar one keeps its name and its template arguments).
 // Carry = CarryK: the instances of a plane-chunked render (gmpi_mpi_render_chunk_launch): the Accum enters from state_in and leaves to state_out.
-template <typename TexT, bool AC, bool STRICT, typename Carry = NoCarry>
-__device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles, const Carry& carry = Carry{}) {
+// Occ = OccK: the sparse instances (gmpi_mpi_render_u8_sparse_launch; "the occupancy map" below): a (tile, plane) whose texel box holds alpha code 0
+// alone is neither loaded nor staged nor sampled.  Occ = NoOcc (the default) is the text as it was: the one-shot and carry kernels do not change.
+struct OccK {
+    const uint8_t* map;   // [M, D, ceil(Ht / 16), ceil(Wt / 16)]: the largest alpha code of each 16 x 16 texel block
+    uint32_t* stats;      // nullable: [0] += (tile, plane) pairs skipped, [1] += pairs staged
+};
+struct NoOcc {};
+constexpr int kOccBlock = 16, kOccShift = 4;   // texels per side of a block of the map
+
+// Does the box (x0 = bb.x, y0 = bb.y, bb.z items of kUTPI texels, bb.w rows) of plane k of MPI m hold alpha code 0 alone?  Texels outside the texture are
+// the zero padding: only the part inside is looked up, in the blocks it overlaps -- at most 5 x 3 of them (64 texels from a multiple of 4, 32 rows).
+__device__ __forceinline__ bool box_is_empty(const uint8_t* __restrict__ map, int m, int k, int D, const int4& bb, int Ht, int Wt) {
+    const int x0 = max(bb.x, 0), x1 = min(bb.x + kUTPI * bb.z, Wt) - 1, y0 = max(bb.y, 0), y1 = min(bb.y + bb.w, Ht) - 1;   // (inclusive)
+    if (x0 > x1 || y0 > y1) return true;
+    const int nbx = (Wt + kOccBlock - 1) >> kOccShift, nby = (Ht + kOccBlock - 1) >> kOccShift;
+    const uint8_t* __restrict__ mp = map + (static_cast<int64_t>(m) * D + k) * nby * nbx;
+    // (5 x 3 loads whatever the box, the indices clamped into its blocks: fifteen independent loads and one wait -- a loop over the blocks that exist waits for
+    //  every byte in turn, with the whole workgroup at the barrier behind the table)
+    static_assert(kUPitch + kOccBlock - kUTPI <= 5 * kOccBlock && kURows + kOccBlock - 1 <= 3 * kOccBlock, "a staged box overlaps at most 5 x 3 blocks");
+    const int bx0 = x0 >> kOccShift, bx1 = x1 >> kOccShift, by0 = y0 >> kOccShift, by1 = y1 >> kOccShift;
+    uint32_t any = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) any |= mp[min(by0 + j, by1) * nbx + min(bx0 + i, bx1)];
+    return any == 0;
+}
+
+template <typename TexT, bool AC, bool STRICT, typename Carry = NoCarry, typename Occ = NoOcc>
+__device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles_x, const int tiles_y, const int n_tiles, const Carry& carry = Carry{},
+                                               const Occ& occ = Occ{}) {
+    constexpr bool kSparse = std::is_same_v<Occ, OccK>;
     // Per plane of the chunk, written once by one thread so that the 8 waves do not repeat the address arithmetic on their scalar units:
     //   box:  qx0 (a multiple of 4), by0, items per row (0: not staged), rows
-    //   org:  byte address of the box origin (texel row by0, column qx0 of channel 0) = words 0, 1 of the plane's buffer descriptor, RN(1 / hh).
+    //   org:  byte address of the box origin (texel row by0, column qx0 of channel 0) = words 0, 1 of the plane's buffer descriptor, RN(1 / hh);
+    //         the sparse instances: 1 where the staged box holds alpha code 0 alone (box_is_empty), else 0.
     //         The origin may lie before the image: only lanes inside the texture pass the range test.
     //   geo:  zdiff = d - eye_z, hw = w / 2, hh = h / 2, RN(1 / hw)
     __shared__ int4 box[kUChunk];
@@ -88,6 +124,7 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
     const uint32_t l_off = static_cast<uint32_t>(lrow) * static_cast<uint32_t>(p.s_row) + kTexelBytes * kUTPI * lcol;
     const int chan_bytes = __builtin_amdgcn_readfirstlane(static_cast<int>(p.s_chan));   // (planar only)
 
+    [[maybe_unused]] int n_skipped = 0, n_staged = 0;   // (the sparse instances: this tile's planes of either kind)
     for (int kc = 0; kc < D; kc += kUChunk) {
         const int kn = min(kUChunk, D - kc);
         __syncthreads();   // the previous chunk's table and buffers are no longer read
@@ -100,7 +137,9 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
             box[t] = bb;
             const float hw = pw * 0.5f, hh = ph * 0.5f;   // exact halves: (2x) / w == x / (w / 2)
             const int2 o = origin_words(reinterpret_cast<uint64_t>(vol) + static_cast<uint64_t>(static_cast<int64_t>(k) * p.s_plane + bb.y * p.s_row + kTexelBytes * bb.x));
-            org[t] = make_int4(o.x, o.y, __float_as_int(1.0f / hh), 0);
+            int empty = 0;
+            if constexpr (kSparse) empty = (bb.z > 0 && box_is_empty(occ.map, vw.m, k, D, bb, Ht, Wt)) ? 1 : 0;
+            org[t] = make_int4(o.x, o.y, __float_as_int(1.0f / hh), empty);
             geo[t] = make_float4(zdiff, hw, hh, 1.0f / hw);
         }
         __syncthreads();   // table published
@@ -148,7 +187,9 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
             }
             if ((lcol < nq) & (lrow < nrows)) *reinterpret_cast<u32x4*>(buf + lrow * kUPitch + kUTPI * lcol) = o;
         };
-        auto composite = [&](int t, const uint32_t* __restrict__ buf) {
+        // EMPTY (the sparse instances, a staged box of alpha code 0 alone): the same coordinates and the same box test, no tap is read -- every alpha tap is
+        // code 0 and every weight is finite (footprint), so the alpha sample is +0 and w = 0 T: the colour taps do not reach the Accum.
+        auto composite = [&](int t, const uint32_t* __restrict__ buf, auto EMPTY) {
             const int k = kc + t;
             const int4 bb = box[t];
             const int qx0 = __builtin_amdgcn_readfirstlane(bb.x), by0 = __builtin_amdgcn_readfirstlane(bb.y);
@@ -180,6 +221,10 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
                 gather_plane<TexT, AC, STRICT>(p, vw, vol, k, g.x, g.z + g.z, g.y + g.y, rx, ry, rz, dot, false, bad, A);
                 return;
             }
+            if constexpr (decltype(EMPTY)::value) {
+                blend<STRICT>(A, 0.0f, 0.0f, 0.0f, 0.0f, s, dot);
+                return;
+            }
             // a footprint outside the box with every weight zero (the sentinel corner of NaN / far-off coordinates) reads texel (0, 0) of the box
             const uint32_t idx = inb ? static_cast<uint32_t>(ly * kUPitch + lx) : 0u;
             const uint32_t t_nw = buf[idx], t_ne = buf[idx + 1], t_sw = buf[idx + kUPitch], t_se = buf[idx + kUPitch + 1];   // two ds_read2_b32
@@ -195,13 +240,47 @@ __device__ __forceinline__ void render_u8_tile(const KParams& p, const int tiles
         };
 
         uint32_t L[4];
-        issue_loads(0, L);
-        for (int t = 0; t < kn; ++t) {
-            uint32_t* buf = stage[t & 1];
-            store_box(t, buf, L);
-            __syncthreads();          // box t visible; everybody is done reading box t - 1 (the other buffer)
-            issue_loads(t + 1, L);    // in flight while plane t is composited
-            composite(t, buf);
+        if constexpr (kSparse) {
+            // The chunk's empty planes as one wave-uniform 64-bit mask (lane l of every wave reads row l of the table).  Empty planes pass no barrier and
+            // take no buffer: the two buffers alternate over the other planes alone (ns), and the prefetch goes to the next of THOSE, so that a store
+            // still lands in the buffer that every wave has left at the barrier before.
+            static_assert(kUChunk <= 64, "one bit per plane of the chunk");
+            const int ln = tid & 63;
+            const bool l_empty = ln < kn && org[min(ln, kn - 1)].w != 0;
+            const uint64_t empty = __ballot(l_empty);
+            const uint64_t staged = __ballot(ln < kn && !l_empty && box[min(ln, kn - 1)].z > 0);
+            const uint64_t live = ~empty & (kn >= 64 ? ~uint64_t(0) : (uint64_t(1) << kn) - 1);
+            n_skipped += __popcll(empty), n_staged += __popcll(staged);
+            int ns = 0;
+            issue_loads(live ? __ffsll(static_cast<unsigned long long>(live)) - 1 : kn, L);
+            for (int t = 0; t < kn; ++t) {
+                if ((empty >> t) & 1) {   // uniform
+                    composite(t, nullptr, std::true_type{});
+                    continue;
+                }
+                uint32_t* buf = stage[ns & 1];
+                ++ns;
+                store_box(t, buf, L);
+                __syncthreads();          // this box visible; everybody is done reading the box staged before it (the other buffer)
+                const uint64_t rest = t >= 63 ? uint64_t(0) : (live >> (t + 1)) << (t + 1);
+                issue_loads(rest ? __ffsll(static_cast<unsigned long long>(rest)) - 1 : kn, L);   // in flight while plane t is composited
+                composite(t, buf, std::false_type{});
+            }
+        } else {
+            issue_loads(0, L);
+            for (int t = 0; t < kn; ++t) {
+                uint32_t* buf = stage[t & 1];
+                store_box(t, buf, L);
+                __syncthreads();          // box t visible; everybody is done reading box t - 1 (the other buffer)
+                issue_loads(t + 1, L);    // in flight while plane t is composited
+                composite(t, buf, std::false_type{});
+            }
+        }
+    }
+    if constexpr (kSparse) {
+        if (occ.stats != nullptr && tid == 0) {
+            atomicAdd(occ.stats, static_cast<uint32_t>(n_skipped));
+            atomicAdd(occ.stats + 1, static_cast<uint32_t>(n_staged));
         }
     }
     const LastPlane lp = last_plane(p, vw);
@@ -232,6 +311,46 @@ __global__ __launch_bounds__(kUThreads, STRICT ? 7 : 8) void render_rgba8_chunk_
     render_u8_tile<rgba8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles, carry);
 }
 
+// (the sparse instances: the bounds of their dense twins)
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 6 : 8) void render_u8_sparse_kernel(const KParams p, const OccK occ, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<u8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles, NoCarry{}, occ);
+}
+template <bool AC, bool STRICT>
+__global__ __launch_bounds__(kUThreads, STRICT ? 7 : 8) void render_rgba8_sparse_kernel(const KParams p, const OccK occ, const int tiles_x, const int tiles_y, const int n_tiles) {
+    render_u8_tile<rgba8_t, AC, STRICT>(p, tiles_x, tiles_y, n_tiles, NoCarry{}, occ);
+}
+
+// ---- the occupancy map: map[m, k, by, bx] = the largest alpha code among the texels of block (by, bx) of plane k of MPI m that exist (border blocks are
+//      partial).  One lane per texel column, 16 rows each, a maximum over 16 lanes; 256 columns per workgroup.  Only the alpha bytes are read: `a_off` is the
+//      alpha channel's byte offset inside a plane (3 s_chan; 3 for channels-last texels), `xs` the bytes from one texel of a row to the next (1 / 4). ------
+constexpr int kOccThreads = 256;
+__global__ __launch_bounds__(kOccThreads) void u8_occupancy_kernel(const uint8_t* __restrict__ vol, const int64_t s_mpi, const int64_t s_plane, const int64_t s_row,
+                                                                   const int64_t a_off, const int xs, const int D, const int Ht, const int Wt, const int gx,
+                                                                   uint8_t* __restrict__ map) {
+    const int nbx = (Wt + kOccBlock - 1) >> kOccShift, nby = (Ht + kOccBlock - 1) >> kOccShift;
+    int64_t b = blockIdx.x;
+    const int cx = static_cast<int>(b % gx);
+    b /= gx;
+    const int by = static_cast<int>(b % nby);
+    b /= nby;
+    const int k = static_cast<int>(b % D);
+    const int64_t m = b / D;
+    const int x = cx * kOccThreads + static_cast<int>(threadIdx.x);
+    uint32_t v = 0;
+    if (x < Wt) {
+        const uint8_t* __restrict__ col = vol + m * s_mpi + k * s_plane + a_off + static_cast<int64_t>(x) * xs;
+        for (int r = 0; r < kOccBlock; ++r) {
+            const int y = by * kOccBlock + r;
+            if (y < Ht) v = max(v, static_cast<uint32_t>(col[y * s_row]));
+        }
+    }
+#pragma unroll
+    for (int o = kOccBlock / 2; o > 0; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));   // (every lane is here: no early exit above)
+    const int bx = x >> kOccShift;
+    if ((threadIdx.x & (kOccBlock - 1)) == 0 && bx < nbx) map[((m * D + k) * nby + by) * nbx + bx] = static_cast<uint8_t>(v);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 // The analogue of volume_stages_in_items for one-byte texels and 4-texel items: an item of a box that touches the border does not straddle it
 // (Wt % 4), every item is a naturally aligned dword (base pointer and strides in BYTES), and the in-box byte offsets are kept in 32 bits.
@@ -252,6 +371,7 @@ int u8_variant_query(int what) {
         case 17: return kUPitch;
         case 18: return kURows;
         case 20: return 1;   // the channels-last instances (rgba8_t) are built in
+        case 53: return kOccBlock;   // texels per side of a block of the occupancy map
         default: return -1;
     }
 }
@@ -264,6 +384,30 @@ hipError_t launch_u8(const KParams& p, hipStream_t stream) {
         if (packed) hipLaunchKernelGGL((render_rgba8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
         else hipLaunchKernelGGL((render_u8_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, tg.tiles_x, tg.tiles_y, tg.n_tiles);
     });
+    return hipGetLastError();
+}
+hipError_t launch_u8_sparse(const KParams& p, const uint8_t* map, uint32_t* stats, hipStream_t stream) {
+    const FwdTileGrid tg = fwd_tile_grid<kUW, kUH>(p);
+    const dim3 block(kUThreads);
+    const bool packed = u8_interleaved(p);
+    const OccK occ{map, stats};
+    dispatch_ac_strict(p.flags, [&](auto AC, auto STRICT) {
+        if (packed) hipLaunchKernelGGL((render_rgba8_sparse_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, occ, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+        else hipLaunchKernelGGL((render_u8_sparse_kernel<decltype(AC)::value, decltype(STRICT)::value>), tg.grid, block, 0, stream, p, occ, tg.tiles_x, tg.tiles_y, tg.n_tiles);
+    });
+    return hipGetLastError();
+}
+// The map of a volume of M x D planes of Ht x Wt texels: its bytes, and the launch that fills it (byte strides of the alpha channel, see the kernel).
+uint64_t u8_occupancy_bytes(int M, int D, int Ht, int Wt) {
+    return static_cast<uint64_t>(M) * D * ((Ht + kOccBlock - 1) / kOccBlock) * ((Wt + kOccBlock - 1) / kOccBlock);
+}
+hipError_t launch_u8_occupancy(const void* vol, int64_t s_mpi, int64_t s_plane, int64_t s_row, int64_t a_off, int xs, int M, int D, int Ht, int Wt, uint8_t* map,
+                               hipStream_t stream) {
+    const int gx = (Wt + kOccThreads - 1) / kOccThreads;
+    const int64_t groups = static_cast<int64_t>(M) * D * ((Ht + kOccBlock - 1) / kOccBlock) * gx;
+    if (groups > 0x7fffffff) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(u8_occupancy_kernel, dim3(static_cast<uint32_t>(groups)), dim3(kOccThreads), 0, stream, static_cast<const uint8_t*>(vol), s_mpi, s_plane, s_row,
+                       a_off, xs, D, Ht, Wt, gx, map);
     return hipGetLastError();
 }
 hipError_t launch_u8_chunk(const KParams& p, const CarryK& carry, hipStream_t stream) {

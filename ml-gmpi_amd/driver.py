@@ -20,6 +20,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .hip_mpi import _call, _ptr
+from .occupancy import build_occupancy
 
 
 def shard_views(n_views: int, rank: int, world_size: int, mode: str = "strided") -> List[int]:
@@ -171,7 +172,7 @@ class ViewBatchDriver:
     @torch.no_grad()
     def render_path(self, mpi_rgbas: torch.Tensor, render_size: int, yaws: Sequence[float],
                     pitches: Sequence[float], indices: Optional[Sequence[int]] = None, to_uint8: bool = False,
-                    depth_range=None, want_transmittance: bool = False, to_host: bool = False):
+                    depth_range=None, want_transmittance: bool = False, to_host: bool = False, occupancy=None):
         """Views `indices` (default all) of ONE MPI [1,D,4,Ht,Wt] along (yaws[i], pitches[i]) -- the loop of
         render_video.py:95-130 (h_mean/v_mean = angle, std 0) as batched launches.
 
@@ -179,12 +180,15 @@ class ViewBatchDriver:
         `to_host=True` (with `to_uint8`; round 6): the uint8 epilogue runs per batch and every batch's frames travel to PINNED host buffers on a second
         HIP stream while the next batch renders -- the copy of the whole path (64 frames of 512^2: 67 MB) then hides behind the render launches instead
         of following them; adds `img8_host`, `dep8_host` (buffers of the driver, reused by the next call of the same shape: consume or copy them).
+        `occupancy` (a uint8 MPI): None, `build_occupancy(mpi_rgbas)`, or True = build the map once for this call; every batch then takes the sparse launch
+        of `MPI.render_views` -- the same frames.
         """
         assert mpi_rgbas.shape[0] == 1, "render_path draws many views of one MPI"
         r = self.renderer
+        occ = {} if occupancy is None else {"occupancy": build_occupancy(mpi_rgbas) if occupancy is True else occupancy}
 
         def launch(dhw, ray, eye, zd, **kw):
-            r.mpi.render_views(mpi_rgbas, dhw, ray, eye, zd, **kw)
+            r.mpi.render_views(mpi_rgbas, dhw, ray, eye, zd, **occ, **kw)
         return self._render_path(launch, mpi_rgbas.device, render_size, yaws, pitches, indices, to_uint8, depth_range, want_transmittance, to_host)
 
     @torch.no_grad()
@@ -306,11 +310,17 @@ class ViewBatchDriver:
         return res
 
     @torch.no_grad()
-    def render_seeds(self, mpi_rgbas: torch.Tensor, render_size: int, views_per_mpi: int = 1, **render_kwargs):
+    def render_seeds(self, mpi_rgbas: torch.Tensor, render_size: int, views_per_mpi: int = 1, occupancy=None, **render_kwargs):
         """Random-pose renders of a stack of MPIs [B,D,4,Ht,Wt] (prepare_fake_data.py:58-66 /
-        fid_evaluation.py:116 pattern), `batch` MPIs per launch.  Returns the renderer's 4-tuple, concatenated."""
+        fid_evaluation.py:116 pattern), `batch` MPIs per launch.  Returns the renderer's 4-tuple, concatenated.
+        `occupancy` (a uint8 stack): None, `build_occupancy(mpi_rgbas)` of the whole stack, or True = build it once for this call; every launch gets the
+        map of its own MPIs and takes the sparse launch of `MPI.render_views` -- the same frames."""
+        if occupancy is True:
+            occupancy = build_occupancy(mpi_rgbas)
+
         def render(s):
-            return self.renderer.render(mpi_rgbas[s:s + self.batch], render_size, render_size, views_per_mpi=views_per_mpi, **render_kwargs)
+            occ = {} if occupancy is None else {"occupancy": occupancy.of_mpis(mpi_rgbas, s, s + self.batch)}
+            return self.renderer.render(mpi_rgbas[s:s + self.batch], render_size, render_size, views_per_mpi=views_per_mpi, **occ, **render_kwargs)
         return self._render_seeds(render, mpi_rgbas.shape[0], render_kwargs)
 
     @torch.no_grad()

@@ -632,6 +632,19 @@ _LAYERS_LDS_WARNED = False
 _LAYERS_BACKWARD_WARNED = False
 
 
+_OCCUPANCY_FALLBACK_WARNED = False
+
+
+def _warn_occupancy_fallback() -> None:
+    """Once per process: a render was given occupancy= and ran the plain launch (every such launch is counted in `MPI.occupancy_fallbacks`)."""
+    global _OCCUPANCY_FALLBACK_WARNED
+    if not _OCCUPANCY_FALLBACK_WARNED:
+        _OCCUPANCY_FALLBACK_WARNED = True
+        warnings.warn('uint8 render: occupancy= is read by the staged kernel alone, which does not run this launch (variant "gather", or a volume whose width, '
+                      "base pointer or outer strides are no multiples of 4 bytes); the plain launch runs instead, with the same result (counted in "
+                      "MPI.occupancy_fallbacks; this warning is given once)", RuntimeWarning, stacklevel=3)
+
+
 def _warn_layers_copy() -> None:
     """Once per process: `render_views_layers` was handed layers it cannot read in place (every such call is counted in `MPI.layers_copies`)."""
     global _LAYERS_COPY_WARNED
@@ -773,6 +786,7 @@ class MPI(nn.Module):
         self.shaded_lds_fallbacks = 0    # shaded launches of a module built with variant "lds" that ran the one-pixel kernel instead
         self.shaded_backward_fallbacks = 0   # shaded backwards of a module built with backward="gather", which ran the default backward instead
         self.layers_copies = 0           # render_views_layers calls whose layers were not read in place: a contiguous copy of the layers was rendered
+        self.occupancy_fallbacks = 0     # uint8 launches given occupancy= that the staged kernel would not have run: the plain launch ran
         self.layers_lds_fallbacks = 0    # float-layer launches that asked for "lds" and ran the one-pixel kernel instead
         self.layers_backward_fallbacks = 0   # layers_backward="texel" backward launches whose tensors the tile kernel could not take: the one-pixel kernel ran
 
@@ -859,7 +873,7 @@ class MPI(nn.Module):
                      status: Optional[torch.Tensor] = None, defer_status: bool = False, out: Optional[dict] = None,
                      _in_autograd_fn: bool = False, frontal_hint: bool = False, tilted_hint: bool = False, oblique_hint: bool = False,
                      _layout: Optional[_Layout] = None, _shading: Optional[torch.Tensor] = None, _layers: Optional[str] = None,
-                     _layers_backward: str = "planar"):
+                     _layers_backward: str = "planar", occupancy=None):
         """Renders N views in one launch.  `frontal_hint`: the caller knows every camera axis to lie within 0.2 rad of the MPI normal
         (GMPI_FLAG_HINT_FRONTAL: advisory, only the kernel choice of small launches depends on it, never a result); `tilted_hint`: some
         camera axis lies more than 0.53 rad off the normal (GMPI_FLAG_HINT_TILTED: keeps such launches off the strip kernel); `oblique_hint`: some
@@ -875,7 +889,17 @@ class MPI(nn.Module):
         (no host sync); call `raise_on_status` later.  `defer_status="lag"`: the call neither blocks nor leaves the check to the caller --
         its status travels to pinned host memory behind the kernel and is looked at by a later call on the same stream, by
         `flush_status()` or at interpreter exit (see `_StatusRing`).
+
+        `occupancy`: None, or `build_occupancy(rgba)` of a uint8 volume (occupancy.py): the staged uint8 kernel then skips every (tile, plane) whose texel
+        box holds alpha code 0 alone (gmpi_mpi_render_u8_sparse_launch) -- the same bits, in both modes and for both layouts.  A float volume: TypeError;
+        a map of another volume, or of one written in place since the build: ValueError, before anything is launched.  Where the staged kernel would not
+        run (variant "gather", tensors it cannot take such as Wt = 6) the plain launch runs: counted in `occupancy_fallbacks`, one RuntimeWarning per
+        process.  Opt-in: without the keyword every launch is today's.
         """
+        if occupancy is not None:
+            if _layout is not None or _shading is not None or _layers is not None:
+                raise TypeError("occupancy= belongs to the render of a uint8 RGBA volume (render_views): layers, layouts and the shaded render do not take it")
+            occupancy.check(rgba)
         if torch.is_grad_enabled() and dhw.requires_grad and not self.geometry_grad:
             raise NotImplementedError("no gradient flows to the plane geometry (the reference computes the grid under "
                                       "torch.no_grad(), mpi.py:65); MPI(geometry_grad=True) provides one")
@@ -895,6 +919,8 @@ class MPI(nn.Module):
                               out_pm1=out_pm1, want_transmittance=want_transmittance, c2w_mat=c2w_mat, sphere_c=sphere_c,
                               status=status, defer_status=defer_status, out=out, frontal_hint=frontal_hint, tilted_hint=tilted_hint, oblique_hint=oblique_hint,
                               _layout=_layout, _shading=_shading)
+                if occupancy is not None:
+                    kwargs["occupancy"] = occupancy
                 if _layers is not None:
                     kwargs["_layers"], kwargs["_layers_backward"] = _layers, _layers_backward
                 color, depth, T, st = bridge[0].apply(*bridge[1], self, dhw, ray_dir, eye_pos, z_dir, kwargs)
@@ -984,7 +1010,20 @@ class MPI(nn.Module):
                 if self.range_check == "full" and rgba.dtype is not torch.uint8 and self._full_check_needed(rgba_in):
                     _range_pass((rgba,), p, dev, stream)
                     fully_checked = rgba_in
-                _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
+                sparse = None
+                if occupancy is not None and on_device:   # the sparse instances of the staged uint8 kernel, where that kernel would run
+                    sparse = occupancy.struct()
+                    rc = _lib.load_library().gmpi_render_u8_sparse_supports(ctypes.byref(p), ctypes.byref(sparse))
+                    if rc < 0:
+                        _lib.check(rc, "gmpi_render_u8_sparse_supports")
+                    if rc == 0:
+                        sparse = None
+                        self.occupancy_fallbacks += 1
+                        _warn_occupancy_fallback()
+                if sparse is not None:
+                    _call("gmpi_mpi_render_u8_sparse_launch", dev, ctypes.byref(p), ctypes.byref(sparse), stream=stream)
+                else:
+                    _call("gmpi_mpi_render_launch", dev, ctypes.byref(p), stream=stream)
             else:
                 _layout.launch(self, p, rgba, images, dev, stream)
             res = dict(color=color, depth=depth, T=T, status=status)

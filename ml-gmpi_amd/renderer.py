@@ -417,7 +417,9 @@ class MPIRenderer:
         AssertionError); "lag" -- the asserts of this call are looked at by a later call, by `ml_gmpi_amd.flush_status()` or at exit, without
         blocking the host on the kernel; True -- not at all;
         `views_per_mpi=k` renders k consecutive views per MPI without replicating the volume
-        (the reference's n_view_per_z expand, prepare_fake_data.py:58-63, batch = B*k views).
+        (the reference's n_view_per_z expand, prepare_fake_data.py:58-63, batch = B*k views);
+        `occupancy=build_occupancy(batch_mpi_rgbas)` (a uint8 volume): the sparse launch of `MPI.render_views` -- the same bits; this entry alone takes it
+        (`render_layers`, `render_shared`, `render_depth`, `render_shaded` and `render_chunks` raise TypeError).
         """
         horizontal_mean = self.horizontal_mean if horizontal_mean is None else horizontal_mean
         horizontal_std = self.horizontal_std if horizontal_std is None else horizontal_std
@@ -431,6 +433,9 @@ class MPIRenderer:
         chunks = ext.pop("_chunks", None)   # render_chunks: the stack's chunks (batch_mpi_rgbas is then the first of them, looked at for its shape alone)
         chunk_kernel = ext.pop("chunk_kernel", None)   # render_chunks: None | "band" | "band+tile" (MPI.chunked_render)
         assert chunk_kernel is None or chunks is not None, "chunk_kernel is render_chunks' keyword"
+        occupancy = ext.pop("occupancy", None)   # the occupancy map of a uint8 volume (occupancy.py): the plain render alone
+        if occupancy is not None and not (layout is None and shading is None and layers_variant is None and chunks is None):
+            raise TypeError("occupancy= belongs to the render of a uint8 RGBA volume (render): layers, layouts, the shaded and the chunked render do not take it")
         defer = ext.pop("defer_status", self.status_mode)   # False (default: read back at once) | "lag" | True (the caller's status tensor / no check)
         assert not ext, f"unknown arguments {list(ext)}"
 
@@ -490,7 +495,7 @@ class MPIRenderer:
                 batch_mpi_rgbas, dhw, ray_t, eye_t, zd_t, views_per_mpi=views_per_mpi,
                 check_last_plane=assert_not_out_of_last_plane, out_pm1=True, want_transmittance=want_T,
                 c2w_mat=c2w, sphere_c=self.sphere_center, defer_status=defer, frontal_hint=frontal, tilted_hint=tilted, oblique_hint=oblique,
-                _layout=layout)
+                _layout=layout, **({} if occupancy is None else {"occupancy": occupancy}))
         if cam_angles is None:
             cam_angles = torch.cat([pitches, yaws], -1).to(self.device)
         if want_T:
